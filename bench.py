@@ -19,6 +19,11 @@ random legal moves (agz_arena_random_moves, deterministic per slot)
 is the measured 19x19 moves/s in `extra`), and the next move's tree is grown to Budget - warmup - steps/2 simulations, so the
 timed steps run on deep trees and straddle a move boundary: end_move (bestMove, example record, Apply, Ended) and begin_move
 (tree re-root, prepareRoot) of all games are inside the timed region.
+
+A plain run does only that: set up, pre-grow, warm up, time --steps steps, print the line.  --full adds everything else the line
+used to carry (per-kernel breakdown and roofline, the other compute modes, the N > 1 exchange leg, the other configurations' legs,
+the trainer step, the CPU baseline).  --dump-outputs DIR writes what the last timed step left the caller (game states, root
+statistics, examples) as DIR/*.npy, so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -642,6 +647,78 @@ def aggregate_over_ranks(dt, sims, evals, iters, rank, world, device=None):
     return {"t_max": t_max, "sims": sums[0], "evals": sums[1], "iters": sums[2], "per_rank_sims": sums[3:], "world_size": world}
 
 
+def dtype_label(compute, wtm):
+    """the line's `dtype` for a compute mode (wtm: the Winograd tile size of wino_h2 on this board)"""
+    return {"f32": "f32",
+            "bf16x3": "f32 (bf16x3 split: each fp32 operand = 3 exact bf16 pieces, 6 bf16 MFMAs per product, fp32 accumulate)",
+            "fp16x2": "f32 (fp16x2 split: power-of-two range scaling, 2 fp16 pieces = 23 significand bits, 3 fp16 MFMAs per product, fp32 accumulate)",
+            "wino": "f32 (Winograd F(4x4,3x3): fp32 transforms; transform-domain products as bf16x3 = 3 exact bf16 pieces per fp32 operand, 6 bf16 MFMAs per product, fp32 accumulate)",
+            "wino_h2": "f32 (Winograd F(%dx%d,3x3): fp32 transforms; transform-domain products as fp16x2 = each fp32 operand scaled by a power of two and split into 2 fp16 pieces (22-23 significand bits, absolute error <= 2^-38 of the tensor range), 3 fp16 MFMAs per product, fp32 accumulate)" % (wtm, wtm)}[compute]
+
+
+def config_fields(args, S, K, L, G, Aspace, full_move, hbm_per_rank, two_queues):
+    """the line's `config` object"""
+    return {"workload": "19x19 Go (wq) self-play: K=%d, %d dual-branch blocks, FC=%d, A=%d, WQEncoder F=18, "
+                        "%d concurrent games/GPU, %d sims/move, leaf batch=%d, one net for both agents=%s"
+                        % (K, L, 2 * K, Aspace, G, args.budget, G, str(not args.two_nets)),
+            "board": S, "K": K, "blocks": L, "games_per_gpu": G, "sims_per_move": args.budget,
+            "weights": "random-init seed 1337: GlorotU conv, GlorotN FC as the reference (ermahagerdmonards.go:39,80); DEVIATION from the "
+                       "reference initialiser: BatchNorm gamma=1, beta=0 with IDENTITY statistics instead of GlorotN gamma/beta under "
+                       "the degenerate-eps reading (x316 per layer saturates softmax/tanh and every search tree degenerates); "
+                       "FLOPs and bytes per evaluation are identical",
+            "priors_note": "with gamma = 1 / beta = 0 and identity statistics the random-init policy is near uniform: the search runs on WIDE trees "
+                           "(~250 children per visited node, paths ~3 nodes: extra.mcts) — the MCTS share of the step is measured on that shape",
+            "parallelism": "games sharded %d/GPU, no data-path collective" % G,
+            "whole_move_sims_per_s": (full_move or {}).get("sims_per_s"),
+            "hbm_used_bytes_per_rank": hbm_per_rank,
+            "tower_queues": 2 if two_queues else 1}
+
+
+MAX_DUMP_GAMES = 1024      # --dump-outputs: more games than this -> a fixed, seeded sample of them
+MAX_DUMP_EXAMPLES = 4096   # ... and of the recorded example rows
+
+
+def dump_outputs(out_dir, arena, S, rank, world):
+    """--dump-outputs: what the timed path hands its caller after the last timed step, as float32 .npy files — every game's state
+    (board, to_move / move number / passes / ended / winner / a_is_black / last move / scores, the moves played so far), the root
+    statistics of both agents' trees (children as agz_arena_root_children returns them: move, visits, blackScores, prior; padded with
+    -1 / 0), and the self-play examples recorded so far (policy, value, game index; by game, each game's rows in ply order).  Inputs
+    are seeded, so the same arguments give the same arrays on every run; two builds can be compared file for file.  At most MAX_DUMP_GAMES games and MAX_DUMP_EXAMPLES example rows (a fixed,
+    seeded sample beyond that): well under 64 MB."""
+    os.makedirs(out_dir, exist_ok=True)
+    G, cap = arena.n_games, S * S + 2
+    games = np.arange(G) if G <= MAX_DUMP_GAMES else np.sort(np.random.default_rng(1337).choice(G, MAX_DUMP_GAMES, replace=False))
+    n = len(games)
+    boards = np.zeros((n, S * S), np.float32)
+    state = np.zeros((n, 9), np.float32)
+    hists = []
+    root = {k: np.full((n, 2, cap), -1.0 if k == "moves" else 0.0, np.float32) for k in ("moves", "visits", "black_scores", "priors")}
+    for i, g in enumerate(games):
+        board, st = arena.game(int(g))
+        boards[i] = board
+        state[i] = [st[f] for f in ("to_move", "move_number", "passes", "ended", "winner", "a_is_black", "last_move", "score_black", "score_white")]
+        hists.append(arena.history(int(g)))
+        for agent in (0, 1):
+            for k, a in zip(("moves", "visits", "black_scores", "priors"), arena.root_children(int(g), agent)):
+                root[k][i, agent, :len(a)] = a
+    history = np.full((n, max([len(h) for h in hists] + [1])), -1.0, np.float32)
+    for i, h in enumerate(hists):
+        history[i, :len(h)] = h
+    _, policy, value, gidx = arena.examples()
+    # one end_move appends the games' rows in no fixed order; each game's own rows are in ply order: a stable sort by game is canonical
+    order = np.argsort(gidx, kind="stable")
+    policy, value, gidx = policy[order], value[order], gidx[order]
+    if len(value) > MAX_DUMP_EXAMPLES:
+        rows = np.sort(np.random.default_rng(1337).choice(len(value), MAX_DUMP_EXAMPLES, replace=False))
+        policy, value, gidx = policy[rows], value[rows], gidx[rows]
+    arrays = {"games": games, "board": boards, "game_state": state, "history": history,
+              "root_moves": root["moves"], "root_visits": root["visits"], "root_black_scores": root["black_scores"], "root_priors": root["priors"],
+              "example_policy": policy, "example_value": value, "example_game": gidx}
+    suffix = "_rank%d" % rank if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def headline_fields(agg, gpus, steps, warmup):
     """metric / value / n_gpus / ms_per_step of the line from the aggregate; refuses to print a line whose n_gpus is not the
     --gpus it was asked for, or whose per-rank counters do not add up to the aggregate."""
@@ -696,7 +773,17 @@ def main():
     ap.add_argument("--shared-gpu", action="store_true",
                     help="debug: all ranks use GPU 0 and gloo collectives (exercises the N>1 code path on a 1-GPU box)")
     ap.add_argument("--print-launch", action="store_true", help="print the re-launch command for --gpus N (JSON list) and exit")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: per-kernel breakdown and roofline (one-queue steps after the timed region), the "
+                         "other compute modes, the example all-gather (N > 1), the configs[0]/[1]/[2]/[4] legs, complete games, deep trees, "
+                         "the trainer step and the CPU baseline (the --no-* switches turn single legs off).  Without it the run sets up, warms "
+                         "up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the timed path computed in its last step to DIR/<name>.npy (float32; game "
+                         "states, both agents' root statistics, recorded examples)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     t_process = time.perf_counter()
 
     # `python bench.py --gpus N` (N > 1) outside a launcher: become the N-rank job (one process per GPU over RCCL)
@@ -815,6 +902,50 @@ def main():
     st1 = arena.stats()
     dom_n, dom_ms = ctx.prof_read(dom)
     move_n, _ = ctx.prof_read(capi.PROF_MOVE)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, arena, S, rank, world)
+    sims = st1["sims_nonnull"] - st0["sims_nonnull"]
+    sims_all = st1["sims_total"] - st0["sims_total"]
+    evals = st1["nn_evals"] - st0["nn_evals"]
+    timed_region = {"moves_finished": st1["moves_played"] - st0["moves_played"],
+                    "move_boundaries": move_n // 2,
+                    "mean_path_nodes": (st1["path_nodes"] - st0["path_nodes"]) / max(1, sims_all),
+                    "mean_children_per_select": (st1["children_read"] - st0["children_read"]) / max(1, (st1["path_nodes"] - st0["path_nodes"]) - sims_all),
+                    "opening_moves_mean": float(n_open.mean()), "opening_moves_max": int(n_open.max()),
+                    "tree_sims_before_timing": (0 if args.no_pregrow else max(0, args.budget - args.warmup - args.steps // 2)) + args.warmup,
+                    "note": "every game on its own random opening; trees pre-grown so the timed steps cross a move "
+                            "boundary (end_move + begin_move of all games inside the timed region)"}
+    if not args.full:
+        # a plain run: the headline and what the steps above measured on the way, nothing that takes runs of its own (--full)
+        agg = aggregate_over_ranks(dt, sims, evals, sims_all, rank, world, device="cuda" if world > 1 else None)
+        hbm_per_rank = [int(hbm_total - hbm_free)]
+        if world > 1:
+            per = [0.0] * world
+            per[rank] = float(hbm_total - hbm_free)
+            hbm_per_rank = [int(x) for x in adist.reduce_step_timing(0.0, per, device="cuda")[1]]
+        if rank == 0:
+            wtm = capi.wino_h2_tile(S, S) if args.compute == "wino_h2" else 4
+            out = headline_fields(agg, args.gpus, args.steps, args.warmup) | {
+                "dtype": dtype_label(args.compute, wtm),
+                "data": "synthetic",
+                "config": config_fields(args, S, K, L, G, Aspace, full_move, hbm_per_rank, two_queues),
+                "full_move_sims_per_s": (full_move or {}).get("sims_per_s"),
+                "per_rank_sims": agg["per_rank_sims"], "world_size": world,
+                "extra": {"nn_evals_per_s": agg["evals"] / agg["t_max"], "iterations_per_s": agg["iters"] / agg["t_max"],
+                          "per_rank_sims": agg["per_rank_sims"], "world_size": world, "timed_region": timed_region,
+                          "full_move_19x19": full_move, "compute": args.compute, "tree_full": st1["tree_full"],
+                          "full": "plain run: `bench.py --full` adds the per-kernel breakdown and roofline, the other compute modes, the "
+                                  "exchange leg, the configs[0]/[1]/[2]/[4] legs, complete games, deep trees, the trainer step and the CPU baseline",
+                          "bench_wall_seconds": time.perf_counter() - t_process}}
+            sys.stdout.flush()
+            os.write(json_fd, (json.dumps(out) + "\n").encode())
+        if world > 1:
+            dist.destroy_process_group()
+        arena.close()
+        for n_ in nets:
+            n_.close()
+        ctx.close()
+        return
     ctx.prof_set_stride(dom, 1)
     if two_queues:
         for n_ in nets:
@@ -832,9 +963,6 @@ def main():
             n_.set_tower_queues(args.tower_queues)
 
     max_path_main = arena.max_path_nodes()
-    sims = st1["sims_nonnull"] - st0["sims_nonnull"]
-    sims_all = st1["sims_total"] - st0["sims_total"]
-    evals = st1["nn_evals"] - st0["nn_evals"]
     # MAX of the wall time, SUM of the counters over ranks; the per-rank sims travel along so that the line is self-checking
     agg = aggregate_over_ranks(dt, sims, evals, sims_all, rank, world, device="cuda" if world > 1 else None)
     t_max, sims_sum, evals_sum, iters_sum, per_rank_sims = agg["t_max"], agg["sims"], agg["evals"], agg["iters"], agg["per_rank_sims"]
@@ -1049,11 +1177,6 @@ def main():
                 else:
                     leg["frac_of_its_roofline"] = leg["conv_dual_tflops"] / peaks[mode]
                     leg["roofline_peak_tflops"] = peaks[mode]
-        dtypes = {"f32": "f32",
-                  "bf16x3": "f32 (bf16x3 split: each fp32 operand = 3 exact bf16 pieces, 6 bf16 MFMAs per product, fp32 accumulate)",
-                  "fp16x2": "f32 (fp16x2 split: power-of-two range scaling, 2 fp16 pieces = 23 significand bits, 3 fp16 MFMAs per product, fp32 accumulate)",
-                  "wino": "f32 (Winograd F(4x4,3x3): fp32 transforms; transform-domain products as bf16x3 = 3 exact bf16 pieces per fp32 operand, 6 bf16 MFMAs per product, fp32 accumulate)",
-                  "wino_h2": "f32 (Winograd F(%dx%d,3x3): fp32 transforms; transform-domain products as fp16x2 = each fp32 operand scaled by a power of two and split into 2 fp16 pieces (22-23 significand bits, absolute error <= 2^-38 of the tensor range), 3 fp16 MFMAs per product, fp32 accumulate)" % (wtm, wtm)}
         kernels = {"f32": "conv3x3_mfma_kernel<2,2,2,DUAL> (fused dual-branch block)",
                    "bf16x3": "conv3x3_x3_kernel<DUAL> (fused dual-branch block, bf16x3)",
                    "fp16x2": "conv3x3_h2w_kernel (fused dual-branch block, fp16x2, 128x256 tile)",
@@ -1075,22 +1198,9 @@ def main():
                              % ((flops_launch / 1e9, wino_detail["wino_gemm"]["algorithmic_bytes"] / 1e9,
                                  3 * flops_launch / wino_detail["wino_gemm"]["algorithmic_bytes"]) if wino_detail else (0, 0, 0)))}
         out = headline_fields(agg, args.gpus, args.steps, args.warmup) | {
-            "dtype": dtypes[args.compute],
+            "dtype": dtype_label(args.compute, wtm),
             "data": "synthetic",
-            "config": {"workload": "19x19 Go (wq) self-play: K=%d, %d dual-branch blocks, FC=%d, A=%d, WQEncoder F=18, "
-                                   "%d concurrent games/GPU, %d sims/move, leaf batch=%d, one net for both agents=%s"
-                                   % (K, L, 2 * K, Aspace, G, args.budget, G, str(not args.two_nets)),
-                       "board": S, "K": K, "blocks": L, "games_per_gpu": G, "sims_per_move": args.budget,
-                       "weights": "random-init seed 1337: GlorotU conv, GlorotN FC as the reference (ermahagerdmonards.go:39,80); DEVIATION from the "
-                                  "reference initialiser: BatchNorm gamma=1, beta=0 with IDENTITY statistics instead of GlorotN gamma/beta under "
-                                  "the degenerate-eps reading (x316 per layer saturates softmax/tanh and every search tree degenerates); "
-                                  "FLOPs and bytes per evaluation are identical",
-                       "priors_note": "with gamma = 1 / beta = 0 and identity statistics the random-init policy is near uniform: the search runs on WIDE trees "
-                                      "(~250 children per visited node, paths ~3 nodes: extra.mcts) — the MCTS share of the step is measured on that shape",
-                       "parallelism": "games sharded %d/GPU, no data-path collective" % G,
-                       "whole_move_sims_per_s": (full_move or {}).get("sims_per_s"),
-                       "hbm_used_bytes_per_rank": hbm_per_rank,
-                       "tower_queues": 2 if two_queues else 1},
+            "config": config_fields(args, S, K, L, G, Aspace, full_move, hbm_per_rank, two_queues),
             "roofline": ({"bound": "hbm", "achieved": wino_detail["wino_gemm"]["achieved_GBs"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
                           "frac": wino_detail["wino_gemm"]["achieved_GBs"] / HBM_PEAK_GBS, "traffic": traffic,
                           "traffic_source": (traffic_source + " (separate rocprofv3 --pmc passes over this kernel on this shape, scripts/r5_pmc_tower.sh: FETCH_SIZE x 2 (gfx950) + WRITE_SIZE; QUOTED from the committed pass, not collected in this run)") if traffic_source else None,
@@ -1147,14 +1257,7 @@ def main():
                            else "MISMATCH: rows_gathered is not the sum of rows_per_rank"),
             "extra": {"nn_evals_per_s": evals_sum / t_max, "iterations_per_s": iters_sum / t_max,
                       "per_rank_sims": per_rank_sims, "world_size": world,
-                      "timed_region": {"moves_finished": st1["moves_played"] - st0["moves_played"],
-                                       "move_boundaries": move_n // 2,
-                                       "mean_path_nodes": (st1["path_nodes"] - st0["path_nodes"]) / max(1, sims_all),
-                                       "mean_children_per_select": (st1["children_read"] - st0["children_read"]) / max(1, (st1["path_nodes"] - st0["path_nodes"]) - sims_all),
-                                       "opening_moves_mean": float(n_open.mean()), "opening_moves_max": int(n_open.max()),
-                                       "tree_sims_before_timing": (0 if args.no_pregrow else max(0, args.budget - args.warmup - args.steps // 2)) + args.warmup,
-                                       "note": "every game on its own random opening; trees pre-grown so the timed steps cross a move "
-                                               "boundary (end_move + begin_move of all games inside the timed region)"},
+                      "timed_region": timed_region,
                       "full_move_19x19": full_move,
                       "mcts": mcts_detail,
                       # (replaced below by moves/s / the MEASURED mean game length when the complete-games leg runs)

@@ -234,7 +234,7 @@ def test_bench_two_ranks_end_to_end_through_the_self_relaunch(tmp_path):
     env = dict(os.environ, AGZ_RCCL_LIB=FAKE, MASTER_ADDR="127.0.0.1")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--shared-gpu", "--games", "32", "--budget", "16", "--steps", "2",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--shared-gpu", "--games", "32", "--budget", "16", "--steps", "2",
            "--warmup", "1", "--L", "4", "--cpu-threads", "8", "--cpu-baseline-seconds", "2", "--no-games-leg", "--no-go9-leg", "--no-latency-leg",
            "--no-train-leg", "--no-f32-leg"]
     pr = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
@@ -274,7 +274,7 @@ def test_bench_eight_ranks_rehearsal_on_one_gpu(tmp_path):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR"):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", "8", "--shared-gpu", "--games", "16", "--budget", "8", "--steps", "2", "--warmup", "1", "--L", "2",
+           os.path.join(ROOT, "bench.py"), "--full", "--gpus", "8", "--shared-gpu", "--games", "16", "--budget", "8", "--steps", "2", "--warmup", "1", "--L", "2",
            "--no-cpu-baseline", "--no-games-leg", "--no-go9-leg", "--no-latency-leg", "--no-train-leg", "--no-f32-leg"]
     pr = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert pr.returncode == 0, pr.stderr.decode(errors="replace")[-3000:]

@@ -3,15 +3,15 @@
 go/agzhip cannot meet a Go compiler in this image, so nothing type-checks `*agzhip.MCTS` against the interface INTEGRATION.md section 2 puts on
 `Agent.MCTS`, or `*agzhip.Inferencer` against `agogo.Inferer`.  This test parses the method declarations on both sides with a small
 signature parser (receiver, name, parameter TYPES, result TYPES — names dropped) and asserts that every method the reference calls on its
-tree / requires of an inferer exists in the shim with the same types.  The reference half is skipped where /root/reference is absent (the
-GPU box); the shim-only checks (gofmt's import order, no leaked handle on NewMCTS's error paths) always run."""
+tree / requires of an inferer exists in the shim with the same types.  The reference half reads the reference's side from
+tests/golden/reference_go_signatures.json (written by tests/golden/make_go_signatures.py from a checkout of the reference, with the parser
+below); the shim-only checks (gofmt's import order, no leaked handle on NewMCTS's error paths) read the shim itself."""
+import json
 import os
 import re
 
-import pytest
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
+REF = os.path.join(ROOT, "tests", "golden", "reference_go_signatures.json")
 SHIM = os.path.join(ROOT, "go", "agzhip", "agzhip.go")
 
 
@@ -101,21 +101,20 @@ def test_shim_source_hygiene():
     assert "func timeoutMs(" in src and "return 1" in src[src.index("func timeoutMs("):src.index("func (t *MCTS) SetTimeout")]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference sources are not on this box")
 def test_mcts_and_inferer_method_sets_match_the_reference():
     shim = open(SHIM).read()
-    tree = "".join(open(os.path.join(REF, "mcts", f)).read() for f in ("tree.go", "search.go", "graph.go", "release.go"))
-    ref = methods(tree, ("*MCTS", "lumberjack"))
+    golden = json.load(open(REF))
+    ref = {k: tuple(v) for k, v in golden["mcts_methods"].items()}
     got = methods(shim, ("*MCTS",))
     # what agent.go:78-79 and arena.go:107,140-141,200-202 call on Agent.MCTS (INTEGRATION.md's `searcher`), plus the tree's read-outs
     for name in ("SetGame", "Search", "Policies", "Reset", "Log", "Nodes", "ToDot"):
         assert name in ref, "the reference has no %s" % name
         assert name in got, "go/agzhip's MCTS lacks %s" % name
         assert got[name] == ref[name], "%s: shim %r, reference %r" % (name, got[name], ref[name])
-    # the uses themselves are still there (a reference update that changes them must be seen here)
-    agent, arena = open(os.path.join(REF, "agent.go")).read(), open(os.path.join(REF, "arena.go")).read()
-    assert re.search(r"MCTS\s+\*mcts\.MCTS", agent) and "a.MCTS.SetGame(g)" in agent and "a.MCTS.Search(a.Player)" in agent
-    assert arena.count("mcts.New(") == 4 and ".MCTS.Policies(a.game)" in arena and "a.A.MCTS.Reset()" in arena and "a.A.MCTS.Log()" in arena
+    # the uses themselves are there (a reference update that changes them must be seen here when the fixture is re-made)
+    agent, arena = golden["agent_go"], golden["arena_go"]
+    assert agent["field MCTS *mcts.MCTS"] and agent["a.MCTS.SetGame(g)"] and agent["a.MCTS.Search(a.Player)"]
+    assert arena["mcts.New("] == 4 and arena[".MCTS.Policies(a.game)"] and arena["a.A.MCTS.Reset()"] and arena["a.A.MCTS.Log()"]
     # INTEGRATION.md's interface = exactly those five, with the reference's types
     doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     want = iface(doc.replace("  \t", "\t").replace("\n  ", "\n"), "searcher")
@@ -123,12 +122,12 @@ def test_mcts_and_inferer_method_sets_match_the_reference():
     for name, sig in want.items():
         assert sig == ref[name], "INTEGRATION.md searcher.%s: %r, reference %r" % (name, sig, ref[name])
     # agogo.Inferer (datatypes.go:56-59) = Infer + io.Closer;  *agzhip.Inferencer must satisfy it
-    inf = iface(open(os.path.join(REF, "datatypes.go")).read(), "Inferer")
+    inf = {k: tuple(v) for k, v in golden["inferer"].items()}
     assert inf == {"Infer": (["[]float32"], ["[]float32", "float32", "error"])}, inf     # (io.Closer is embedded: Close() error)
     gi = methods(shim, ("*Inferencer",))
     assert gi["Infer"] == inf["Infer"] and gi["Close"] == ([], ["error"])
     # mcts.New's parameter list (tree.go:80) is what NewMCTS mirrors after the device-side arguments
-    assert re.search(r"func New\(game game\.State, conf Config, nn Inferencer\) \*MCTS", tree)
+    assert golden["mcts_new"] == [["game.State", "Config", "Inferencer"], ["*MCTS"]]
     assert re.search(r"func NewMCTS\(ctx \*Ctx, kind GameKind, g game\.State, .*conf mcts\.Config, nn \*Net, seed uint64\) \(\*MCTS, error\)", shim)
 
 
