@@ -256,6 +256,9 @@ def lib():
     sig("agz_trainer_forward_backward_allreduce", i32, vp, vp, pf, pf, pf, pf)
     sig("agz_trainer_forward_backward_allreduce_dev", i32, vp, vp, vp, vp, vp, pf)
     sig("agz_comm_debug_fail_slice", i32, vp, i32)
+    sig("agz_trainer_create_sharded", i32, vp, C.POINTER(NetConf), pvp)
+    sig("agz_trainer_shard", i32, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32))
+    sig("agz_comm_debug_fail_layer", i32, vp, i32)
     _LIB = L
     return L
 
@@ -454,6 +457,25 @@ class Trainer:
         self.h = C.c_void_p()
         _check(lib().agz_trainer_create(ctx.h, C.byref(self.conf), C.byref(self.h)), "agz_trainer_create")
         ctx._adopt(self)
+
+    @classmethod
+    def sharded(cls, ctx, comm, K, SharedLayers, FC, Width, Height, Features, ActionSpace, BatchSize, bn_eps=1e-5):
+        """dual.Train at the GLOBAL batch BatchSize split over the ranks of `comm` (agz_trainer_create_sharded): this rank holds rows
+        shard() of every batch-shaped learnable; forward_backward / batch / train / train_dev / export / save are collective"""
+        assert comm.ctx is ctx, "the communicator belongs to another context"
+        self = cls.__new__(cls)
+        self.ctx, self.comm = ctx, comm
+        self.conf = NetConf(K, SharedLayers, FC, BatchSize, Width, Height, Features, ActionSpace, 0, bn_eps)
+        self.h = C.c_void_p()
+        _check(lib().agz_trainer_create_sharded(comm.h, C.byref(self.conf), C.byref(self.h)), "agz_trainer_create_sharded")
+        ctx._adopt(self)
+        return self
+
+    def shard(self):
+        """(row0, rows, n_ranks): this rank's rows [row0, row0 + rows) of the global batch; a plain trainer: (0, BatchSize, 1)"""
+        r0, n, nr = C.c_int(0), C.c_int(0), C.c_int(0)
+        _check(lib().agz_trainer_shard(self.h, C.byref(r0), C.byref(n), C.byref(nr)), "agz_trainer_shard")
+        return r0.value, n.value, nr.value
 
     def close(self):
         if self.h and self.ctx.h:
@@ -927,6 +949,10 @@ class Comm:
     def debug_fail_slice(self, k):
         """agz_debug.h: this rank's next data-parallel step fails right before slice k (failure injection for the N > 1 tests)"""
         _check(lib().agz_comm_debug_fail_slice(self.h, int(k)), "agz_comm_debug_fail_slice")
+
+    def debug_fail_layer(self, layer):
+        """agz_debug.h: this rank's next sharded-trainer step fails right before layer `layer`'s first exchange (L + 1: the heads)"""
+        _check(lib().agz_comm_debug_fail_layer(self.h, int(layer)), "agz_comm_debug_fail_layer")
 
     def forward_backward_allreduce_dev(self, trainer, planes_ptr, pi_ptr, v_ptr, want_cost=True):
         c = C.c_float(0)

@@ -120,7 +120,8 @@ void agz_comm_destroy(agz_comm* c) {
   const Rccl* R = rccl();
   if (R && c->comm) { hipSetDevice(c->ctx->device); hipStreamSynchronize(c->ctx->stream); R->CommDestroy(c->comm); }
   if (c->d_words) { hipSetDevice(c->ctx->device); hipFree(c->d_words); }
-  if (c->ar_stream) { hipSetDevice(c->ctx->device); hipStreamSynchronize(c->ar_stream); hipStreamDestroy(c->ar_stream); hipEventDestroy(c->ev_ready); hipEventDestroy(c->ev_done); if (c->h_status) hipHostFree(c->h_status); }
+  if (c->ar_stream) { hipSetDevice(c->ctx->device); hipStreamSynchronize(c->ar_stream); hipStreamDestroy(c->ar_stream); hipEventDestroy(c->ev_ready); hipEventDestroy(c->ev_done); }
+  if (c->h_status) hipHostFree(c->h_status);
   delete c;
 }
 
@@ -129,6 +130,7 @@ int agz_comm_size(const agz_comm* c) { return c ? c->size : 0; }
 
 int agz_trainer_allreduce(agz_comm* c, agz_trainer* t) {
   AGZ_REQUIRE(c && t, AGZ_E_INVALID, "agz_trainer_allreduce: NULL argument");
+  AGZ_REQUIRE(!agz_trainer_is_sharded(t), AGZ_E_STATE, "agz_trainer_allreduce: a sharded trainer sums its shared gradients inside its own step (agz_trainer_create_sharded)");
   // the gradients are produced on the trainer's ctx stream and reduced on the communicator's: they must be the same queue
   AGZ_REQUIRE(agz_trainer_ctx(t) == c->ctx, AGZ_E_INVALID, "agz_trainer_allreduce: the communicator and the trainer belong to different contexts");
   const Rccl* R = rccl();
@@ -154,8 +156,8 @@ static int dp_begin(agz_comm* c, agz_trainer* t, const Rccl* R) {
     AGZ_HIP_TRY(hipStreamCreateWithFlags(&c->ar_stream, hipStreamNonBlocking));
     AGZ_HIP_TRY(hipEventCreateWithFlags(&c->ev_ready, hipEventDisableTiming));
     AGZ_HIP_TRY(hipEventCreateWithFlags(&c->ev_done, hipEventDisableTiming));
-    AGZ_HIP_TRY(hipHostMalloc((void**)&c->h_status, 16, hipHostMallocDefault));
   }
+  if (!c->h_status) AGZ_HIP_TRY(hipHostMalloc((void**)&c->h_status, 16, hipHostMallocDefault));
   float* g = nullptr;
   size_t n_all = 0;
   int r = agz_trainer_grads_dev(t, &g, &n_all);
@@ -214,6 +216,7 @@ int agz_comm_debug_fail_slice(agz_comm* c, int k) {
 
 int agz_trainer_forward_backward_allreduce(agz_comm* c, agz_trainer* t, const float* planes, const float* pi, const float* v, float* cost) {
   AGZ_REQUIRE(c && t && planes && pi && v, AGZ_E_INVALID, "agz_trainer_forward_backward_allreduce: NULL argument");
+  AGZ_REQUIRE(!agz_trainer_is_sharded(t), AGZ_E_STATE, "agz_trainer_forward_backward_allreduce: not for a sharded trainer (its own step is collective)");
   AGZ_REQUIRE(agz_trainer_ctx(t) == c->ctx, AGZ_E_INVALID, "agz_trainer_forward_backward_allreduce: the communicator and the trainer belong to different contexts");
   const Rccl* R = rccl();
   if (!R) return AGZ_E_UNSUPPORTED;
@@ -225,6 +228,7 @@ int agz_trainer_forward_backward_allreduce(agz_comm* c, agz_trainer* t, const fl
 
 int agz_trainer_forward_backward_allreduce_dev(agz_comm* c, agz_trainer* t, const float* planes_dev, const float* pi_dev, const float* v_dev, float* cost) {
   AGZ_REQUIRE(c && t && planes_dev && pi_dev && v_dev, AGZ_E_INVALID, "agz_trainer_forward_backward_allreduce_dev: NULL argument");
+  AGZ_REQUIRE(!agz_trainer_is_sharded(t), AGZ_E_STATE, "agz_trainer_forward_backward_allreduce_dev: not for a sharded trainer (its own step is collective)");
   AGZ_REQUIRE(agz_trainer_ctx(t) == c->ctx, AGZ_E_INVALID, "agz_trainer_forward_backward_allreduce_dev: the communicator and the trainer belong to different contexts");
   const Rccl* R = rccl();
   if (!R) return AGZ_E_UNSUPPORTED;
@@ -232,6 +236,110 @@ int agz_trainer_forward_backward_allreduce_dev(agz_comm* c, agz_trainer* t, cons
   int r = dp_begin(c, t, R);
   if (r != AGZ_OK) return r;
   return dp_end(c, t, R, agz_trainer_forward_backward_dev(t, planes_dev, pi_dev, v_dev, cost));
+}
+
+// ---- sharded trainer: dual.Train at the global batch (agz_trainer_create_sharded) ------------------------------------------------------
+// Rank r owns rows [r * B, (r + 1) * B) of the global batch: the batch-shaped gamma / beta and FC biases — 98 % of the learnables — and their
+// gradients stay on their rank.  Per step: one all-gather of the partial BatchNorm sums per statistic (forward: every tower layer and the
+// head BatchNorm, once or twice; backward: the same layers once; the cost), one grouped all-reduce of the shared tensors' gradients (filters,
+// the heads' 1x1 convolution, Wp / W1 / W2: ~96 MB at G19 against the 7.7 GB of the averaged step) and the status word — all on the ctx
+// stream, in the same order on every rank.
+
+// the status word of a collective call on the ctx stream: the number of ranks that failed.  r != AGZ_OK keeps this rank's own error
+static int sh_agree(agz_comm* c, const Rccl* R, int r, const char* what) {
+  const std::string first = r != AGZ_OK ? agz_last_error() : "";
+  hipStream_t s = c->ctx->stream;
+  c->h_status[0] = r != AGZ_OK ? 1ull : 0ull;
+  c->h_status[1] = 0;
+  unsigned long long* dw = c->d_words + c->size + 2;
+  const bool ok = hipMemcpyAsync(dw, &c->h_status[0], 8, hipMemcpyHostToDevice, s) == hipSuccess &&
+                  R->AllReduce(dw, dw, 1, ncclUint64, ncclSum, c->comm, s) == ncclSuccess &&
+                  hipMemcpyAsync(&c->h_status[1], dw, 8, hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+  if (r != AGZ_OK) { set_error("%s failed on this rank (its peers are told): %s", what, first.c_str()); return r; }
+  if (!ok) { set_error("%s: the status exchange failed (fatal for the process group)", what); return AGZ_E_HIP; }
+  if (c->h_status[1] != 0) { set_error("%s: another rank failed in this call; its results are undefined", what); return AGZ_E_PEER; }
+  return AGZ_OK;
+}
+
+// End of a sharded step, whatever happened on this rank: the gathers the forward / backward pass did not reach are entered (a collective one
+// rank never enters is a hang for its peers), then the shared gradients are summed and the status word is exchanged.
+static int sh_step(agz_comm* c, agz_trainer* t, const Rccl* R, const std::function<int()>& body) {
+  agz_trainer_exchange_plan(t, c->sh_plan);
+  c->sh_issued = 0;
+  int r = body();
+  if (r == AGZ_OK && c->sh_issued != c->sh_plan.size()) {
+    set_error("sharded step: %zu of the %zu exchanges of the plan were issued", c->sh_issued, c->sh_plan.size());
+    r = AGZ_E_STATE;
+  }
+  const std::string first = r != AGZ_OK ? agz_last_error() : "";
+  hipStream_t s = c->ctx->stream;
+  double* xg = agz_trainer_gather_buf(t);
+  bool coll = true;
+  for (; c->sh_issued < c->sh_plan.size(); c->sh_issued++) {   // only ever non-empty after a local failure (in place, contents undefined)
+    const size_t cnt = c->sh_plan[c->sh_issued];
+    coll = R->AllGather(xg + (size_t)c->rank * cnt, xg, cnt, ncclFloat64, c->comm, s) == ncclSuccess && coll;
+  }
+  c->sh_plan.clear();
+  float* g = nullptr;
+  size_t n_all = 0;
+  std::vector<std::pair<size_t, size_t>> shared;
+  agz_trainer_grads_dev(t, &g, &n_all);
+  agz_trainer_shared_ranges(t, shared);
+  coll = R->GroupStart() == ncclSuccess && coll;
+  for (const auto& sr : shared) coll = R->AllReduce(g + sr.first, g + sr.first, sr.second, ncclFloat32, ncclSum, c->comm, s) == ncclSuccess && coll;
+  coll = R->GroupEnd() == ncclSuccess && coll;
+  if (r != AGZ_OK) set_error("%s", first.c_str());
+  else if (!coll) { set_error("sharded step: a collective failed (fatal for the process group)"); r = AGZ_E_HIP; }
+  return sh_agree(c, R, r, "sharded training step");
+}
+
+int agz_trainer_create_sharded(agz_comm* c, const agz_net_conf* conf, agz_trainer** out) {
+  AGZ_REQUIRE(c && conf && out, AGZ_E_INVALID, "agz_trainer_create_sharded: NULL argument");
+  AGZ_REQUIRE(conf->BatchSize >= 1 && conf->BatchSize % c->size == 0, AGZ_E_INVALID,
+              "agz_trainer_create_sharded: the global BatchSize %d is not a multiple of the %d ranks", conf->BatchSize, c->size);
+  const Rccl* R = rccl();
+  if (!R) return AGZ_E_UNSUPPORTED;
+  AGZ_HIP_TRY(hipSetDevice(c->ctx->device));
+  if (!c->h_status) AGZ_HIP_TRY(hipHostMalloc((void**)&c->h_status, 16, hipHostMallocDefault));
+  agz_net_conf local = *conf;
+  local.BatchSize = conf->BatchSize / c->size;
+  agz_trainer* t = nullptr;
+  int r = agz_trainer_create(c->ctx, &local, &t);
+  if (r != AGZ_OK) return r;
+  agz_shard_hooks h;
+  h.gather = [c, R](int site, const double* send, double* recv, size_t count) -> int {
+    AGZ_REQUIRE(c->sh_issued < c->sh_plan.size() && c->sh_plan[c->sh_issued] == count, AGZ_E_STATE,
+                "sharded step: exchange %zu (%zu values) is not the one the plan announces", c->sh_issued, count);
+    if (c->debug_fail_layer == site) {
+      c->debug_fail_layer = -1;
+      set_error("injected failure before the exchange of layer %d (agz_comm_debug_fail_layer)", site);
+      return AGZ_E_STATE;
+    }
+    AGZ_NCCL_TRY(R->AllGather(send, recv, count, ncclFloat64, c->comm, c->ctx->stream));
+    c->sh_issued++;
+    return AGZ_OK;
+  };
+  h.step = [c, t, R](const std::function<int()>& body) -> int { return sh_step(c, t, R, body); };
+  h.allgather_bytes = [c, R](const void* send, void* recv, size_t bytes) -> int {
+    AGZ_NCCL_TRY(R->AllGather(send, recv, bytes, ncclUint8, c->comm, c->ctx->stream));
+    AGZ_HIP_TRY(hipStreamSynchronize(c->ctx->stream));
+    return AGZ_OK;
+  };
+  h.bcast0 = [c, R](void* buf, size_t bytes) -> int {
+    AGZ_NCCL_TRY(R->Broadcast(buf, buf, bytes, ncclUint8, 0, c->comm, c->ctx->stream));
+    AGZ_HIP_TRY(hipStreamSynchronize(c->ctx->stream));
+    return AGZ_OK;
+  };
+  h.agree = [c, R](int rc) -> int { return sh_agree(c, R, rc, "sharded trainer call"); };
+  if ((r = agz_trainer_bind_shard(t, c->rank, c->size, std::move(h))) != AGZ_OK) { agz_trainer_destroy(t); return r; }
+  *out = t;
+  return AGZ_OK;
+}
+
+int agz_comm_debug_fail_layer(agz_comm* c, int layer) {
+  AGZ_REQUIRE(c, AGZ_E_INVALID, "agz_comm_debug_fail_layer: NULL communicator");
+  c->debug_fail_layer = layer;
+  return AGZ_OK;
 }
 
 }  // extern "C"

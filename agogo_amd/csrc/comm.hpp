@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "shard.hpp"
 
 namespace agz {
 struct Rccl {
@@ -51,6 +52,11 @@ struct agz_comm {
   size_t dp_issued = 0;
   unsigned long long* h_status = nullptr;   // pinned
   int debug_fail_slice = -1;                // agz_comm_debug_fail_slice (agz_debug.h)
+  // one step of a sharded trainer (agz_trainer_create_sharded): the gathers it issues (agz_trainer_exchange_plan) and how many of them
+  // this rank has entered
+  std::vector<size_t> sh_plan;
+  size_t sh_issued = 0;
+  int debug_fail_layer = -1;                // agz_comm_debug_fail_layer (agz_debug.h)
 };
 
 #define AGZ_NCCL_TRY(expr)                                                                                   \

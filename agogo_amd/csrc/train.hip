@@ -24,7 +24,8 @@
 // reference's batch-shaped gamma / beta fix their bytes); the heads run as wave-per-row reductions and LDS-tiled FC kernels (second form,
 // 0.35 ms per step); the batch-shaped gamma / beta take their SGD step inside k_bn_bwd1 on single-process steps; the weight gradient
 // runs on its own stream; a data-parallel step reduces every layer's slice of the flat gradient buffer under the backward pass
-// (on_slice, comm.hip).
+// (on_slice, comm.hip).  A sharded trainer (agz_trainer_create_sharded) holds its rank's rows of the global batch and
+// exchanges the BatchNorm statistics' partial sums through the hooks of shard.hpp (comm.hip), summing them in rank order.
 #include <cmath>
 #include <cstring>
 #include <thread>
@@ -33,6 +34,7 @@
 
 #include "net.hpp"
 #include "conv_maps.hpp"
+#include "shard.hpp"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -125,6 +127,40 @@ __global__ void k_bn_fin2(double* acc, int C, double m, float eps, float* mean, 
   mean[c] = (float)mu;
   inv[c] = 1.0f / sqrtf((float)var + eps);
   acc[c] = 0; acc[1024 + c] = 0;
+}
+
+// ---- sharded trainer (agz_trainer_create_sharded): the per-channel sums of the n ranks, gathered as n partial vectors --------------
+// xg [n][stride] holds every rank's partial sums (an all-gather of each rank's acc), summed here in RANK order: every rank computes the
+// same bits, run after run, whatever the collective's own reduction algorithm.  mode 2: the single-pass statistics (sums at [0, C), sums
+// of squares at [1024, 1024 + C)) -> mean, inv as k_bn_fin2; mode 0 / 1: the two passes of k_bn_fin.  m = rows of the GLOBAL batch.
+// With n = 1 the expressions are those of k_bn_fin2 / k_bn_fin on the same values.  Clears this rank's acc.
+__global__ void k_bn_fin_ranks(const double* __restrict__ xg, int n, int stride, double* __restrict__ acc, int C, double m, float eps,
+                               float* __restrict__ mean, float* __restrict__ inv, int mode) {
+  int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  double s = xg[c];
+  for (int r = 1; r < n; r++) s += xg[(size_t)r * stride + c];
+  if (mode == 2) {
+    double q = xg[1024 + c];
+    for (int r = 1; r < n; r++) q += xg[(size_t)r * stride + 1024 + c];
+    const double mu = s / m;
+    double var = q / m - mu * mu;
+    var = var > 0 ? var : 0;
+    mean[c] = (float)mu;
+    inv[c] = 1.0f / sqrtf((float)var + eps);
+    acc[c] = 0; acc[1024 + c] = 0;
+  } else {
+    if (mode == 0) mean[c] = (float)(s / m); else inv[c] = 1.0f / sqrtf((float)(s / m) + eps);
+    acc[c] = 0;
+  }
+}
+// out[lo + i] = sum over ranks r (in rank order) of xg[r][lo + i], i < cnt: the head statistics, the cost and the backward BatchNorm sums
+__global__ void k_sum_ranks(const double* __restrict__ xg, int n, int stride, double* __restrict__ out, int lo, int cnt) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= cnt) return;
+  double s = xg[lo + i];
+  for (int r = 1; r < n; r++) s += xg[(size_t)r * stride + lo + i];
+  out[lo + i] = s;
 }
 
 // ---- tower BN apply (+ReLU, + dual add + ReLU).  z [pix][nbr*Kp]; gamma/beta [M][nbr*Kp]; out [pix][Kp] --------
@@ -280,15 +316,14 @@ __global__ void k_bn_bwd1(TGeo g, const float* __restrict__ z, float* gamma, flo
     atomicAdd(&s2[cc], a2);
   }
 }
-// step 2: dz = inv * (dxhat - s1/m - xhat*s2/m)
+// step 2: dz = inv * (dxhat - s1/m - xhat*s2/m); m = the rows the sums run over (g.M, or the global batch's rows of a sharded trainer)
 __global__ void k_bn_bwd2(TGeo g, const float* __restrict__ z, const float* __restrict__ mean, const float* __restrict__ inv,
-                          float* __restrict__ dz, const double* __restrict__ s1, const double* __restrict__ s2, int C) {
+                          float* __restrict__ dz, const double* __restrict__ s1, const double* __restrict__ s2, int C, float m) {
   size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (size_t)g.M * C) return;
   int r = (int)(idx / C), cc = (int)(idx - (size_t)r * C);
   size_t po = pix_off(g, r);
   float xh = (z[po * C + cc] - mean[cc]) * inv[cc];
-  float m = (float)g.M;
   dz[po * C + cc] = inv[cc] * (dz[po * C + cc] - (float)s1[cc] / m - xh * ((float)s2[cc] / m));
 }
 
@@ -297,10 +332,9 @@ __global__ void k_bn_bwd2(TGeo g, const float* __restrict__ z, const float* __re
 __global__ __launch_bounds__(256) void k_bn_bwd2_v(TGeo g, const float* __restrict__ z, const float* __restrict__ mean,
                                                    const float* __restrict__ inv, float* __restrict__ dz, const double* __restrict__ s1,
                                                    const double* __restrict__ s2, int C, int rows_per_block, unsigned* __restrict__ amax_bits,
-                                                   unsigned* __restrict__ board_bits) {
+                                                   unsigned* __restrict__ board_bits, float m) {
   const int q = C >> 2, tpr = 256 / q, cq = threadIdx.x % q, rs = threadIdx.x / q;
   const int r0 = blockIdx.x * rows_per_block, r1 = min(r0 + rows_per_block, g.M);
-  const float m = (float)g.M;
   float mv[4], nv[4], a1[4], a2[4];
 #pragma unroll
   for (int k = 0; k < 4; k++) {
@@ -1016,6 +1050,7 @@ __global__ void k_head_apply(TGeo g, const float* __restrict__ zh, const float* 
 }
 struct HeadT {
   int B, HW, A, FC;
+  int Bn;           // the batch the loss is normalised by: B, or the GLOBAL batch of a sharded trainer (B is the loop bound: this rank's rows)
   const float* yh;  // [B][3][HW]
   const float *Wp, *bp, *W1, *b1, *W2, *b2;
   const float *Pi, *V;
@@ -1054,18 +1089,18 @@ __global__ void k_cost(HeadT h) {  // single block
   for (int i = threadIdx.x; i < h.B * h.A; i += 256) s += -(double)(h.Pi[i] * h.logits[i] + (1.f - h.Pi[i]) * (1.f - h.logits[i]));
   red[threadIdx.x] = s; __syncthreads();
   for (int o = 128; o > 0; o >>= 1) { if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
-  if (threadIdx.x == 0) h.cost[0] = (float)(red[0] / ((double)h.B * h.A));
+  if (threadIdx.x == 0) h.cost[0] = (float)(red[0] / ((double)h.Bn * h.A));
   __syncthreads();
   s = 0;
   for (int b = threadIdx.x; b < h.B; b += 256) { double d = h.o[b] - h.V[b]; s += d * d; }
   red[threadIdx.x] = s; __syncthreads();
   for (int o = 128; o > 0; o >>= 1) { if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
-  if (threadIdx.x == 0) h.cost[1] = (float)(red[0] / h.B);
+  if (threadIdx.x == 0) h.cost[1] = (float)(red[0] / h.Bn);
 }
 // backward of the FC parts.  One thread per gradient element (sums over the batch inside).
 __global__ void k_fc_bwd(HeadT h) {
   int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  const float sc = 1.0f / ((float)h.B * (float)h.A);
+  const float sc = 1.0f / ((float)h.Bn * (float)h.A);
   int n_wp = 2 * h.HW * h.A, n_bp = h.B * h.A, n_w1 = h.HW * h.FC, n_b1 = h.B * h.FC, n_w2 = h.FC, n_b2 = h.B;
   int n_dy = h.B * 3 * h.HW;
   if (idx < n_wp) {  // dWp[i][j] = sum_b yp[b][i] * dl[b][j]
@@ -1082,7 +1117,7 @@ __global__ void k_fc_bwd(HeadT h) {
     int i = idx / h.FC, j = idx - i * h.FC;
     float s = 0.f;
     for (int b = 0; b < h.B; b++) {
-      float dob = 2.f * (h.o[b] - h.V[b]) / (float)h.B;
+      float dob = 2.f * (h.o[b] - h.V[b]) / (float)h.Bn;
       float dh = h.hpre[(size_t)b * h.FC + j] > 0.f ? dob * h.W2[j] : 0.f;
       s += h.yh[((size_t)b * 3 + 2) * h.HW + i] * dh;
     }
@@ -1092,19 +1127,19 @@ __global__ void k_fc_bwd(HeadT h) {
   idx -= n_w1;
   if (idx < n_b1) {
     int b = idx / h.FC, j = idx - b * h.FC;
-    float dob = 2.f * (h.o[b] - h.V[b]) / (float)h.B;
+    float dob = 2.f * (h.o[b] - h.V[b]) / (float)h.Bn;
     h.db1[idx] = h.hpre[idx] > 0.f ? dob * h.W2[j] : 0.f;
     return;
   }
   idx -= n_b1;
   if (idx < n_w2) {
     float s = 0.f;
-    for (int b = 0; b < h.B; b++) { float hv = h.hpre[(size_t)b * h.FC + idx]; s += (2.f * (h.o[b] - h.V[b]) / (float)h.B) * (hv > 0.f ? hv : 0.f); }
+    for (int b = 0; b < h.B; b++) { float hv = h.hpre[(size_t)b * h.FC + idx]; s += (2.f * (h.o[b] - h.V[b]) / (float)h.Bn) * (hv > 0.f ? hv : 0.f); }
     h.dW2[idx] = s;
     return;
   }
   idx -= n_w2;
-  if (idx < n_b2) { h.db2[idx] = 2.f * (h.o[idx] - h.V[idx]) / (float)h.B; return; }
+  if (idx < n_b2) { h.db2[idx] = 2.f * (h.o[idx] - h.V[idx]) / (float)h.Bn; return; }
   idx -= n_b2;
   if (idx < n_dy) {  // d(yh)[b][j][p]
     int b = idx / (3 * h.HW), q = idx - b * 3 * h.HW;
@@ -1113,7 +1148,7 @@ __global__ void k_fc_bwd(HeadT h) {
       for (int j = 0; j < h.A; j++) s += ((1.f - 2.f * h.Pi[(size_t)b * h.A + j]) * sc) * h.Wp[(size_t)q * h.A + j];
     } else {
       int i = q - 2 * h.HW;
-      float dob = 2.f * (h.o[b] - h.V[b]) / (float)h.B;
+      float dob = 2.f * (h.o[b] - h.V[b]) / (float)h.Bn;
       for (int j = 0; j < h.FC; j++) if (h.hpre[(size_t)b * h.FC + j] > 0.f) s += dob * h.W2[j] * h.W1[(size_t)i * h.FC + j];
     }
     h.dyh[idx] = s;
@@ -1206,11 +1241,11 @@ __global__ __launch_bounds__(256) void k_head_stats_part(TGeo g, const float* __
   __syncthreads();
   if (threadIdx.x < 6) atomicAdd(&hacc[threadIdx.x], red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3]);
 }
-__global__ void k_head_stats_fin(TGeo g, const double* __restrict__ hacc, float eps, float* __restrict__ mean, float* __restrict__ inv) {
+__global__ void k_head_stats_fin(TGeo g, const double* __restrict__ hacc, float eps, float* __restrict__ mean, float* __restrict__ inv, double m) {
   const int j = threadIdx.x;
   if (j >= 3) return;
-  const double mu = hacc[j] / g.M;
-  double var = hacc[3 + j] / g.M - mu * mu;
+  const double mu = hacc[j] / m;
+  double var = hacc[3 + j] / m - mu * mu;
   if (var < 0) var = 0;
   mean[j] = (float)mu;
   inv[j] = 1.0f / sqrtf((float)var + eps);
@@ -1266,7 +1301,7 @@ __global__ __launch_bounds__(256) void k_cost_part(HeadT h, double* __restrict__
   if (threadIdx.x < 2) atomicAdd(&hacc[6 + threadIdx.x], red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3]);
 }
 __global__ void k_cost_fin(HeadT h, const double* __restrict__ hacc) {
-  if (threadIdx.x == 0) { h.cost[0] = (float)(hacc[6] / ((double)h.B * h.A)); h.cost[1] = (float)(hacc[7] / h.B); }
+  if (threadIdx.x == 0) { h.cost[0] = (float)(hacc[6] / ((double)h.Bn * h.A)); h.cost[1] = (float)(hacc[7] / h.Bn); }
 }
 // dW[i][j] = sum_b y[b][i] * d[b][j], eight rows i per block: grid (ceil(N / 256), ceil(K / 8), 2); z = 0: dWp (d = the xent gradient),
 // z = 1: dW1 (d = the value head's hidden-layer gradient).  The b loop is the old kernel's.
@@ -1282,12 +1317,12 @@ __global__ __launch_bounds__(256) void k_fc_bwd_w(HeadT h) {
   }
   __syncthreads();
   if (j >= N) return;
-  const float sc = 1.0f / ((float)h.B * (float)h.A);
+  const float sc = 1.0f / ((float)h.Bn * (float)h.A);
   float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   for (int b = 0; b < h.B; b++) {
     float d;
     if (pol) d = (1.f - 2.f * h.Pi[(size_t)b * h.A + j]) * sc;
-    else { const float dob = 2.f * (h.o[b] - h.V[b]) / (float)h.B; d = h.hpre[(size_t)b * h.FC + j] > 0.f ? dob * h.W2[j] : 0.f; }
+    else { const float dob = 2.f * (h.o[b] - h.V[b]) / (float)h.Bn; d = h.hpre[(size_t)b * h.FC + j] > 0.f ? dob * h.W2[j] : 0.f; }
 #pragma unroll
     for (int t = 0; t < 8; t++) acc[t] += ys[b * 8 + t] * d;
   }
@@ -1298,25 +1333,25 @@ __global__ __launch_bounds__(256) void k_fc_bwd_w(HeadT h) {
 // the elementwise / small parts of the FC backward: dbp, db1, dW2, db2
 __global__ void k_fc_bwd_small(HeadT h) {
   int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  const float sc = 1.0f / ((float)h.B * (float)h.A);
+  const float sc = 1.0f / ((float)h.Bn * (float)h.A);
   const int n_bp = h.B * h.A, n_b1 = h.B * h.FC, n_w2 = h.FC, n_b2 = h.B;
   if (idx < n_bp) { h.dbp[idx] = (1.f - 2.f * h.Pi[idx]) * sc; return; }
   idx -= n_bp;
   if (idx < n_b1) {
     const int b = idx / h.FC, j = idx - b * h.FC;
-    const float dob = 2.f * (h.o[b] - h.V[b]) / (float)h.B;
+    const float dob = 2.f * (h.o[b] - h.V[b]) / (float)h.Bn;
     h.db1[idx] = h.hpre[idx] > 0.f ? dob * h.W2[j] : 0.f;
     return;
   }
   idx -= n_b1;
   if (idx < n_w2) {
     float s = 0.f;
-    for (int b = 0; b < h.B; b++) { const float hv = h.hpre[(size_t)b * h.FC + idx]; s += (2.f * (h.o[b] - h.V[b]) / (float)h.B) * (hv > 0.f ? hv : 0.f); }
+    for (int b = 0; b < h.B; b++) { const float hv = h.hpre[(size_t)b * h.FC + idx]; s += (2.f * (h.o[b] - h.V[b]) / (float)h.Bn) * (hv > 0.f ? hv : 0.f); }
     h.dW2[idx] = s;
     return;
   }
   idx -= n_w2;
-  if (idx < n_b2) h.db2[idx] = 2.f * (h.o[idx] - h.V[idx]) / (float)h.B;
+  if (idx < n_b2) h.db2[idx] = 2.f * (h.o[idx] - h.V[idx]) / (float)h.Bn;
 }
 // d(yh)[b][q] for eight batch rows per block: grid (ceil(Q / 256), ceil(B / 8), 2); z = 0: q < 2 HW (sum over the A logits), z = 1: the value
 // channel (sum over the FC hidden units).  The j loop is the old kernel's; the per-(b, j) factor comes from an LDS tile.
@@ -1326,13 +1361,13 @@ __global__ __launch_bounds__(256) void k_fc_bwd_y(HeadT h) {
   const int J = pol ? h.A : h.FC, Q = pol ? 2 * h.HW : h.HW;
   const int q = blockIdx.x * 256 + threadIdx.x, b0 = blockIdx.y * 8;
   if (blockIdx.x * 256 >= Q) return;
-  const float sc = 1.0f / ((float)h.B * (float)h.A);
+  const float sc = 1.0f / ((float)h.Bn * (float)h.A);
   for (int e = threadIdx.x; e < 8 * J; e += 256) {
     const int t = e / J, j = e - t * J, b = b0 + t;
     float d = 0.f;
     if (b < h.B) {
       if (pol) d = (1.f - 2.f * h.Pi[(size_t)b * h.A + j]) * sc;
-      else { const float dob = 2.f * (h.o[b] - h.V[b]) / (float)h.B; d = h.hpre[(size_t)b * h.FC + j] > 0.f ? dob * h.W2[j] : 0.f; }
+      else { const float dob = 2.f * (h.o[b] - h.V[b]) / (float)h.Bn; d = h.hpre[(size_t)b * h.FC + j] > 0.f ? dob * h.W2[j] : 0.f; }
     }
     ds[e] = d;
   }
@@ -1380,11 +1415,11 @@ __global__ __launch_bounds__(256) void k_head_bn_bwd_a(TGeo g, const float* __re
   if (threadIdx.x < 6) atomicAdd(&hacc[8 + threadIdx.x], red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3]);
 }
 __global__ __launch_bounds__(256) void k_head_bn_bwd_b(TGeo g, const float* __restrict__ zh, const float* __restrict__ mean, const float* __restrict__ inv,
-                                                       float* __restrict__ dzh, const double* __restrict__ hacc) {
+                                                       float* __restrict__ dzh, const double* __restrict__ hacc, float m) {
   const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (idx >= (size_t)g.M * 3) return;
   const int j = (int)(idx % 3);
-  const float s1 = (float)hacc[8 + j], s2 = (float)hacc[11 + j], m = (float)g.M;
+  const float s1 = (float)hacc[8 + j], s2 = (float)hacc[11 + j];
   const float xh = (zh[idx] - mean[j]) * inv[j];
   dzh[idx] = inv[j] * (dzh[idx] - s1 / m - xh * (s2 / m));
 }
@@ -1833,6 +1868,17 @@ struct agz_trainer {
   int prep_weights();
   float fuse_lr = 0.f;      // != 0 during a fused step: k_bn_bwd1 updates gamma / beta in place, apply() skips them
   bool fused_done = false;  // the backward that just ran took the fused path
+  // sharded trainer (agz_trainer_create_sharded): this rank's rows [rank * B, (rank + 1) * B) of a global batch of n_ranks * B rows.
+  // B, g, P, G and every work buffer are this rank's; the BatchNorm statistics, the loss normalisation and the shared tensors' gradients
+  // are the global batch's (the exchanges go through `shard`, comm.hip)
+  bool sharded = false;
+  int rank = 0, n_ranks = 1;
+  agz_shard_hooks shard;
+  double* xg = nullptr;     // [n_ranks][2048] the partial sums of one exchange, rank-major
+  int m_glob() const { return g.M * n_ranks; }
+  int exchange(int site, const double* send, size_t count) { return shard.gather(site, send, xg, count); }
+  bool bn_single_pass(int C) const { return C % 4 == 0 && C <= 1024 && g.M >= 4096; }
+  int step(const float* planes, const float* pi, const float* v);   // forward_backward_dev, collective on a sharded trainer
 };
 
 static inline int nblk(size_t n, int bs = 256) { return (int)((n + bs - 1) / bs); }
@@ -1948,14 +1994,23 @@ int agz_trainer::forward_backward_dev(const float* planes, const float* pi, cons
     }
     if (r != AGZ_OK) return r;
     int C = ly.Cout_p;
-    if (C % 4 == 0 && C <= 1024 && g.M >= 4096) {   // (small problems keep the two-pass form: nothing to gain, and it is the oracle's order)
+    // (sharded: this rank's partial sums are gathered from every rank and k_bn_fin_ranks sums them in rank order over the global rows)
+    if (bn_single_pass(C)) {   // (small problems keep the two-pass form: nothing to gain, and it is the oracle's order)
       hipLaunchKernelGGL(k_bn_stats, dim3(nblk(g.M, 128)), dim3(256), 0, s, g, ly.z, C, acc, 128);   // (256 / 128 / 64 / 32 rows: 46 / 37 / 46 / 71 us at G19)
-      hipLaunchKernelGGL(k_bn_fin2, dim3(nblk(C)), dim3(256), 0, s, acc, C, (double)g.M, conf.bn_eps, ly.mean, ly.inv);
+      if (sharded) {
+        if ((r = exchange(l, acc, 2048)) != AGZ_OK) return r;
+        hipLaunchKernelGGL(k_bn_fin_ranks, dim3(nblk(C)), dim3(256), 0, s, xg, n_ranks, 2048, acc, C, (double)m_glob(), conf.bn_eps, ly.mean, ly.inv, 2);
+      } else
+        hipLaunchKernelGGL(k_bn_fin2, dim3(nblk(C)), dim3(256), 0, s, acc, C, (double)g.M, conf.bn_eps, ly.mean, ly.inv);
     } else {
-      hipLaunchKernelGGL(k_bn_sum, dim3(nblk(g.M, RPB)), dim3(std::min(C, 512)), 0, s, g, ly.z, C, (const float*)nullptr, acc, RPB);
-      hipLaunchKernelGGL(k_bn_fin, dim3(nblk(C)), dim3(256), 0, s, acc, C, (double)g.M, conf.bn_eps, ly.mean, ly.inv, 0);
-      hipLaunchKernelGGL(k_bn_sum, dim3(nblk(g.M, RPB)), dim3(std::min(C, 512)), 0, s, g, ly.z, C, (const float*)ly.mean, acc, RPB);
-      hipLaunchKernelGGL(k_bn_fin, dim3(nblk(C)), dim3(256), 0, s, acc, C, (double)g.M, conf.bn_eps, ly.mean, ly.inv, 1);
+      for (int pass = 0; pass < 2; pass++) {   // the mean over the global rows first, then the centred sums around it (the oracle's order)
+        hipLaunchKernelGGL(k_bn_sum, dim3(nblk(g.M, RPB)), dim3(std::min(C, 512)), 0, s, g, ly.z, C, pass ? (const float*)ly.mean : (const float*)nullptr, acc, RPB);
+        if (sharded) {
+          if ((r = exchange(l, acc, 1024)) != AGZ_OK) return r;
+          hipLaunchKernelGGL(k_bn_fin_ranks, dim3(nblk(C)), dim3(256), 0, s, xg, n_ranks, 1024, acc, C, (double)m_glob(), conf.bn_eps, ly.mean, ly.inv, pass);
+        } else
+          hipLaunchKernelGGL(k_bn_fin, dim3(nblk(C)), dim3(256), 0, s, acc, C, (double)g.M, conf.bn_eps, ly.mean, ly.inv, pass);
+      }
     }
     x_amax_ready[l + 1] = 0; xb_ready[l + 1] = 0;
     if (wino && Kp % 4 == 0 && Kp / 4 <= 256 && 256 % (Kp / 4) == 0 && ly.nbr <= 2) {
@@ -1984,21 +2039,31 @@ int agz_trainer::forward_backward_dev(const float* planes, const float* pi, cons
   }
   // ---- heads forward
   HeadT h{};
-  h.B = B; h.HW = g.HW; h.A = A; h.FC = FC; h.yh = yh; h.Wp = P + o_Wp; h.bp = P + o_bp; h.W1 = P + o_W1; h.b1 = P + o_b1;
+  h.B = B; h.Bn = B * n_ranks; h.HW = g.HW; h.A = A; h.FC = FC; h.yh = yh; h.Wp = P + o_Wp; h.bp = P + o_bp; h.W1 = P + o_W1; h.b1 = P + o_b1;
   h.W2 = P + o_W2; h.b2 = P + o_b2; h.Pi = pi; h.V = v; h.logits = logits; h.hpre = hpre; h.o = o;
   h.dWp = G + o_Wp; h.dbp = G + o_bp; h.dW1 = G + o_W1; h.db1 = G + o_b1; h.dW2 = G + o_W2; h.db2 = G + o_b2; h.dyh = dyh; h.cost = cost;
   // (second form of the head kernels: see k_head_conv2 ... above; fast_heads = 0, agz_debug.h, keeps the first form for A/B)
   const int fcK = 2 * g.HW > FC ? 2 * g.HW : FC, fcJ = A > FC ? A : FC;
-  const bool fh = fast_heads && (size_t)8 * (2 * g.HW) * 4 <= 60000 && (size_t)B * 8 * 4 <= 60000 && (size_t)8 * fcJ * 4 <= 60000 && fcK > 0;
+  const bool fh = (fast_heads || sharded) && (size_t)8 * (2 * g.HW) * 4 <= 60000 && (size_t)B * 8 * 4 <= 60000 && (size_t)8 * fcJ * 4 <= 60000 && fcK > 0;
   if (fh) {
     AGZ_HIP_TRY(hipMemsetAsync(head_acc, 0, 16 * sizeof(double), s));
     hipLaunchKernelGGL(k_head_conv2, dim3(std::min(nblk(g.M, 4), ctx->num_cus * 16)), dim3(256), 0, s, g, cur, P + o_hc, zh, Kp);
     hipLaunchKernelGGL(k_head_stats_part, dim3(std::min(nblk(g.M), ctx->num_cus)), dim3(256), 0, s, g, zh, head_acc);
-    hipLaunchKernelGGL(k_head_stats_fin, dim3(1), dim3(64), 0, s, g, head_acc, conf.bn_eps, hmean, hinv);
+    if (sharded) {   // (head_acc [16] is gathered whole; each exchange sums the ranks' part it concerns into this rank's head_acc)
+      int r = exchange(L + 1, head_acc, 16);
+      if (r != AGZ_OK) return r;
+      hipLaunchKernelGGL(k_sum_ranks, dim3(1), dim3(64), 0, s, xg, n_ranks, 16, head_acc, 0, 6);
+    }
+    hipLaunchKernelGGL(k_head_stats_fin, dim3(1), dim3(64), 0, s, g, head_acc, conf.bn_eps, hmean, hinv, (double)m_glob());
     hipLaunchKernelGGL(k_head_apply, dim3(nblk((size_t)g.M * 3)), dim3(256), 0, s, g, zh, P + o_hg, P + o_hb, hmean, hinv, yh);
     hipLaunchKernelGGL(k_fc_fwd2, dim3(nblk(std::max(A, FC)), nblk(B, 8), 2), dim3(256), (size_t)8 * 2 * g.HW * sizeof(float), s, h);
     hipLaunchKernelGGL(k_value_out2, dim3(B), dim3(64), 0, s, h);
     hipLaunchKernelGGL(k_cost_part, dim3(std::min(nblk((size_t)B * A), 64)), dim3(256), 0, s, h, head_acc);
+    if (sharded) {
+      int r = exchange(L + 1, head_acc, 16);
+      if (r != AGZ_OK) return r;
+      hipLaunchKernelGGL(k_sum_ranks, dim3(1), dim3(64), 0, s, xg, n_ranks, 16, head_acc, 6, 2);
+    }
     hipLaunchKernelGGL(k_cost_fin, dim3(1), dim3(64), 0, s, h, head_acc);
   } else {
   hipLaunchKernelGGL(k_head_conv, dim3(nblk((size_t)g.M * 3)), dim3(256), 0, s, g, cur, P + o_hc, zh, Kp);
@@ -2015,7 +2080,12 @@ int agz_trainer::forward_backward_dev(const float* planes, const float* pi, cons
     hipLaunchKernelGGL(k_fc_bwd_small, dim3(nblk((size_t)B * A + (size_t)B * FC + FC + B)), dim3(256), 0, s, h);
     hipLaunchKernelGGL(k_fc_bwd_y, dim3(nblk(2 * g.HW), nblk(B, 8), 2), dim3(256), (size_t)8 * fcJ * sizeof(float), s, h);
     hipLaunchKernelGGL(k_head_bn_bwd_a, dim3(std::min(nblk(g.M), ctx->num_cus)), dim3(256), 0, s, g, zh, yh, dyh, P + o_hg, hmean, hinv, G + o_hg, G + o_hb, dzh, head_acc);
-    hipLaunchKernelGGL(k_head_bn_bwd_b, dim3(nblk((size_t)g.M * 3)), dim3(256), 0, s, g, zh, hmean, hinv, dzh, head_acc);
+    if (sharded) {
+      int r = exchange(L + 1, head_acc, 16);
+      if (r != AGZ_OK) return r;
+      hipLaunchKernelGGL(k_sum_ranks, dim3(1), dim3(64), 0, s, xg, n_ranks, 16, head_acc, 8, 6);
+    }
+    hipLaunchKernelGGL(k_head_bn_bwd_b, dim3(nblk((size_t)g.M * 3)), dim3(256), 0, s, g, zh, hmean, hinv, dzh, head_acc, (float)m_glob());
     hipLaunchKernelGGL(k_head_conv_bwd_w2, dim3(nblk(g.M, RPB)), dim3(256), 0, s, g, cur, dzh, G + o_hc, Kp, RPB);
   } else {
   hipLaunchKernelGGL(k_fc_bwd, dim3(nblk(n_fc)), dim3(256), 0, s, h);
@@ -2052,15 +2122,20 @@ int agz_trainer::forward_backward_dev(const float* planes, const float* pi, cons
     if (sw != s && l < L) AGZ_HIP_TRY(hipStreamWaitEvent(s, ev_split, 0));   // the previous layer's weight gradient has taken its copy of dz
     hipLaunchKernelGGL(k_bn_bwd1, dim3(nblk(g.M, RPB)), dim3(std::min(C, 512)), 0, s, g, ly.z, P + ly.o_gamma, P + ly.o_beta, ly.mean, ly.inv,
                        ly.out, dcur, G + ly.o_gamma, G + ly.o_beta, dz, s1, s2, Kp, ly.nbr, RPB, fuse_lr);
+    if (sharded) {   // the two channel sums over the global batch (in place: acc_b of this layer holds the ranks' sum afterwards)
+      int r = exchange(l, s1, 2048);
+      if (r != AGZ_OK) return r;
+      hipLaunchKernelGGL(k_sum_ranks, dim3(nblk(2048)), dim3(256), 0, s, xg, n_ranks, 2048, s1, 0, 2048);
+    }
     bool dz_amax_ready = false, dzb_ready = false;
     if (wino && C % 4 == 0 && C / 4 <= 256 && 256 % (C / 4) == 0) {
       const int tpr = 256 / (C / 4), rpb = round_up(std::max(tpr, ceil_div(g.M, 2048)), tpr);
       dzb_ready = rpb <= g.HW;
       hipLaunchKernelGGL(k_bn_bwd2_v, dim3(nblk(g.M, rpb)), dim3(256), 0, s, g, ly.z, ly.mean, ly.inv, dz, s1, s2, C, rpb, wg_amax,
-                         dzb_ready ? board_words + (size_t)(L + 2 + l) * B : nullptr);
+                         dzb_ready ? board_words + (size_t)(L + 2 + l) * B : nullptr, (float)m_glob());
       dz_amax_ready = true;
     } else
-      hipLaunchKernelGGL(k_bn_bwd2, dim3(nblk((size_t)g.M * C)), dim3(256), 0, s, g, ly.z, ly.mean, ly.inv, dz, s1, s2, C);
+      hipLaunchKernelGGL(k_bn_bwd2, dim3(nblk((size_t)g.M * C)), dim3(256), 0, s, g, ly.z, ly.mean, ly.inv, dz, s1, s2, C, (float)m_glob());
     // weight gradient (on its own stream from here)
     if (sw != s) { AGZ_HIP_TRY(hipEventRecord(ev_dz, s)); AGZ_HIP_TRY(hipStreamWaitEvent(sw, ev_dz, 0)); }
     bool split_recorded = false;
@@ -2146,7 +2221,69 @@ void agz_trainer_slices(const agz_trainer* t, std::vector<std::pair<size_t, size
   for (int l = L; l >= 0; l--) out.emplace_back(t->layers[l].o_wf, (l < L ? t->layers[l + 1].o_wf : t->o_hc) - t->layers[l].o_wf);
 }
 
+// one training step's forward / backward; on a sharded trainer a COLLECTIVE step (the communicator enters whatever exchanges a failure
+// skipped, sums the shared tensors' gradients and agrees on the status: comm.hip)
+int agz_trainer::step(const float* planes, const float* pi, const float* v) {
+  if (!sharded) return forward_backward_dev(planes, pi, v);
+  return shard.step([&]() -> int {
+    const int r = forward_backward_dev(planes, pi, v);
+    if (r != AGZ_OK) {
+      // a step that failed part-way may have left work on the side stream: join it, so that the next step starts on a quiet trainer; and
+      // the forward statistics' sums of the layer it stopped at were never finalized (which clears them): clear them here
+      if (wg_stream && hipEventRecord(ev_join, wg_stream) == hipSuccess) hipStreamWaitEvent(ctx->stream, ev_join, 0);
+      hipMemsetAsync(acc, 0, 2048 * sizeof(double), ctx->stream);
+    }
+    return r;
+  });
+}
+
+int agz_trainer_bind_shard(agz_trainer* t, int rank, int n, agz_shard_hooks hooks) {
+  AGZ_REQUIRE(t && n >= 1 && rank >= 0 && rank < n, AGZ_E_INVALID, "agz_trainer_bind_shard: rank %d of %d", rank, n);
+  // the sharded step exchanges the partial sums of the second form of the head kernels (forward_backward_dev: fh)
+  const int fcJ = std::max(t->A, t->FC);
+  AGZ_REQUIRE((size_t)8 * (2 * t->g.HW) * 4 <= 60000 && (size_t)t->B * 8 * 4 <= 60000 && (size_t)8 * fcJ * 4 <= 60000, AGZ_E_UNSUPPORTED,
+              "sharded trainer: board, batch or action space too large for the head kernels it runs");
+  AGZ_HIP_TRY(hipSetDevice(t->ctx->device));
+  int r = t->alloc(&t->xg, (size_t)n * 2048);
+  if (r != AGZ_OK) return r;
+  AGZ_HIP_TRY(hipStreamSynchronize(t->ctx->stream));
+  t->sharded = true; t->rank = rank; t->n_ranks = n; t->shard = std::move(hooks);
+  return AGZ_OK;
+}
+bool agz_trainer_is_sharded(const agz_trainer* t) { return t && t->sharded; }
+// the gathers of forward_backward_dev in issue order: per tower layer 0 .. L one (single-pass statistics) or two (two-pass), the heads'
+// statistics, cost and BatchNorm backward, then the backward BatchNorm sums of layer L .. 0
+void agz_trainer_exchange_plan(const agz_trainer* t, std::vector<size_t>& out) {
+  out.clear();
+  for (const auto& ly : t->layers) {
+    if (t->bn_single_pass(ly.Cout_p)) out.push_back(2048);
+    else { out.push_back(1024); out.push_back(1024); }
+  }
+  for (int k = 0; k < 3; k++) out.push_back(16);
+  for (size_t l = 0; l < t->layers.size(); l++) out.push_back(2048);
+}
+double* agz_trainer_gather_buf(agz_trainer* t) { return t->xg; }
+void agz_trainer_shared_ranges(const agz_trainer* t, std::vector<std::pair<size_t, size_t>>& out) {
+  out.clear();
+  for (const auto& ly : t->layers) out.emplace_back(ly.o_wf, (size_t)9 * ly.Cout_p * ly.Cin_p);
+  out.emplace_back(t->o_hc, (size_t)3 * t->Kp);
+  out.emplace_back(t->o_Wp, (size_t)2 * t->g.HW * t->A);
+  out.emplace_back(t->o_W1, (size_t)t->g.HW * t->FC);
+  out.emplace_back(t->o_W2, (size_t)t->FC);
+}
+
+// batch-shaped learnables (gamma / beta of every BatchNorm, the FC biases): dimension 0 is the batch, a sharded trainer holds its rows
+static bool pref_batch_shaped(const TParamRef& p) { return p.kind == 1 || p.kind == 3; }
+
 extern "C" {
+
+int agz_trainer_shard(const agz_trainer* t, int* row0, int* rows, int* n_ranks) {
+  AGZ_REQUIRE(t, AGZ_E_INVALID, "agz_trainer_shard: NULL trainer");
+  if (row0) *row0 = t->rank * t->B;
+  if (rows) *rows = t->B;
+  if (n_ranks) *n_ranks = t->n_ranks;
+  return AGZ_OK;
+}
 
 int agz_trainer_create(agz_ctx* ctx, const agz_net_conf* c, agz_trainer** out) {
   AGZ_REQUIRE(ctx && c && out, AGZ_E_INVALID, "agz_trainer_create: NULL argument");
@@ -2364,6 +2501,8 @@ int agz_trainer_get_grad(const agz_trainer* t, int i, float* host, size_t n) {
   return xfer_param(t, t->G, i, host, 1);
 }
 
+// A sharded trainer draws its rows' slice of the GLOBAL tensors: the stream position of its first element, the Glorot deviation of the
+// global shape — bit for bit those rows of a plain trainer's init_random(seed) at the global batch.
 int agz_trainer_init_random(agz_trainer* t, uint64_t seed) {  // same recipe as agz_net_init_random over the FULL shapes
   AGZ_REQUIRE(t, AGZ_E_INVALID, "trainer is NULL");
   // SplitMix64 is counter based (state_n = seed + n * golden), so the sequential stream of the oracle's initialiser can be
@@ -2374,17 +2513,18 @@ int agz_trainer_init_random(agz_trainer* t, uint64_t seed) {  // same recipe as 
   for (int i = 0; i < (int)t->prefs.size(); i++) {
     const TParamRef& p = t->prefs[i];
     std::vector<float> v(pref_size(p));
+    const int nr = pref_batch_shaped(p) ? t->n_ranks : 1;   // this rank's slice: elements [g0, g0 + v.size()) of a tensor of n elements
     double field = 1; for (size_t k = 2; k < p.shape.size(); k++) field *= p.shape[k];
-    const double stdev = std::sqrt(2.0 / ((double)(p.shape[0] + p.shape[1]) * field));
-    const size_t n = v.size();
+    const double stdev = std::sqrt(2.0 / ((double)(p.shape[0] * nr + p.shape[1]) * field));
+    const size_t n = v.size() * nr, g0 = v.size() * (nr > 1 ? t->rank : 0);
     const uint64_t d0 = draws;
     if (p.kind == 0) {           // GlorotU: one draw per element
       const double lim = stdev * std::sqrt(3.0);
       auto work = [&](size_t lo, size_t hi) {
-        SplitMix64 r(seed + (d0 + lo) * GOLD);
+        SplitMix64 r(seed + (d0 + g0 + lo) * GOLD);
         for (size_t k = lo; k < hi; k++) v[k] = (float)((r.float64() * 2.0 - 1.0) * lim);
       };
-      if (n < (1u << 16)) work(0, n);
+      if (n < (1u << 16)) work(0, n);   // (filters are shared: n = v.size())
       else {
         std::vector<std::thread> th;
         size_t per = (n + nthr - 1) / nthr;
@@ -2393,21 +2533,23 @@ int agz_trainer_init_random(agz_trainer* t, uint64_t seed) {  // same recipe as 
       }
       draws += n;
     } else if (p.kind == 1 || p.kind == 2) {   // GlorotN by Box-Muller: two draws per PAIR of elements
-      const size_t pairs = (n + 1) / 2;
-      auto work = [&](size_t lo, size_t hi) {   // pair indices
-        SplitMix64 r(seed + (d0 + 2 * lo) * GOLD);
-        for (size_t q = lo; q < hi; q++) {
+      const size_t pairs = (n + 1) / 2, e1 = g0 + v.size();
+      const size_t p0 = g0 / 2, p1 = (e1 + 1) / 2;   // the pairs this rank's elements fall in (a slice may start or end mid-pair)
+      auto work = [&](size_t lo, size_t hi) {   // pair indices, relative to p0
+        SplitMix64 r(seed + (d0 + 2 * (p0 + lo)) * GOLD);
+        for (size_t q = p0 + lo; q < p0 + hi; q++) {
           double u1 = 1.0 - r.float64(), u2 = r.float64();
           double rad = std::sqrt(-2.0 * std::log(u1)), th = 6.283185307179586476925 * u2;
-          v[2 * q] = (float)(rad * std::cos(th) * stdev);
-          if (2 * q + 1 < n) v[2 * q + 1] = (float)(rad * std::sin(th) * stdev);
+          if (2 * q >= g0) v[2 * q - g0] = (float)(rad * std::cos(th) * stdev);
+          if (2 * q + 1 < e1) v[2 * q + 1 - g0] = (float)(rad * std::sin(th) * stdev);
         }
       };
-      if (pairs < (1u << 15)) work(0, pairs);
+      const size_t np = p1 - p0;
+      if (np < (1u << 15)) work(0, np);
       else {
         std::vector<std::thread> th;
-        size_t per = (pairs + nthr - 1) / nthr;
-        for (unsigned q = 0; q < nthr; q++) { size_t lo = q * per, hi = std::min(pairs, lo + per); if (lo < hi) th.emplace_back(work, lo, hi); }
+        size_t per = (np + nthr - 1) / nthr;
+        for (unsigned q = 0; q < nthr; q++) { size_t lo = q * per, hi = std::min(np, lo + per); if (lo < hi) th.emplace_back(work, lo, hi); }
         for (auto& x : th) x.join();
       }
       draws += 2 * pairs;
@@ -2425,7 +2567,7 @@ int agz_trainer_forward_backward(agz_trainer* t, const float* planes, const floa
   AGZ_HIP_TRY(hipMemcpyAsync(t->d_planes, planes, (size_t)t->B * t->F * t->g.HW * 4, hipMemcpyHostToDevice, s));
   AGZ_HIP_TRY(hipMemcpyAsync(t->d_pi, pi, (size_t)t->B * t->A * 4, hipMemcpyHostToDevice, s));
   AGZ_HIP_TRY(hipMemcpyAsync(t->d_v, v, (size_t)t->B * 4, hipMemcpyHostToDevice, s));
-  int r = t->forward_backward_dev(t->d_planes, t->d_pi, t->d_v);
+  int r = t->step(t->d_planes, t->d_pi, t->d_v);
   if (r != AGZ_OK) return r;
   float c[2] = {0, 0};
   AGZ_HIP_TRY(hipMemcpyAsync(c, t->cost, 8, hipMemcpyDeviceToHost, s));
@@ -2438,7 +2580,7 @@ int agz_trainer_forward_backward(agz_trainer* t, const float* planes, const floa
 int agz_trainer_forward_backward_dev(agz_trainer* t, const float* planes_dev, const float* pi_dev, const float* v_dev, float* cost) {
   AGZ_REQUIRE(t && planes_dev && pi_dev && v_dev, AGZ_E_INVALID, "agz_trainer_forward_backward_dev: NULL argument");
   AGZ_HIP_TRY(hipSetDevice(t->ctx->device));
-  int r = t->forward_backward_dev(planes_dev, pi_dev, v_dev);
+  int r = t->step(planes_dev, pi_dev, v_dev);
   if (r != AGZ_OK) return r;
   if (cost) {
     float c[2] = {0, 0};
@@ -2531,14 +2673,16 @@ static constexpr float DUAL_TRAIN_LR = 0.1f;
 // like the reference does.
 int agz_train(agz_trainer* t, float* Xs, float* policies, float* values, int batches, int iterations, uint64_t seed, float* last_cost) {
   AGZ_REQUIRE(t && Xs && policies && values && batches >= 1 && iterations >= 0, AGZ_E_INVALID, "agz_train: bad argument");
-  const size_t xs = (size_t)t->F * t->g.HW, ps = (size_t)t->A;
-  const size_t n = (size_t)batches * t->B;
+  // (sharded: the tensors are the GLOBAL examples, the same on every rank; batch b is rows [b * Bg, (b + 1) * Bg), this rank trains its
+  // own rows of it, and every rank shuffles the whole set with the same stream)
+  const size_t xs = (size_t)t->F * t->g.HW, ps = (size_t)t->A, Bg = (size_t)t->B * t->n_ranks;
+  const size_t n = (size_t)batches * Bg;
   SplitMix64 rng(seed);
   std::vector<float> tmp(std::max(xs, ps));
   float c = 0;
   for (int it = 0; it < iterations; it++) {
     for (int b = 0; b < batches; b++) {
-      size_t s0 = (size_t)b * t->B;
+      size_t s0 = (size_t)b * Bg + (size_t)t->rank * t->B;
       int r = agz_trainer_batch(t, Xs + s0 * xs, policies + s0 * ps, values + s0, DUAL_TRAIN_LR, &c);
       if (r != AGZ_OK) return r;
     }
@@ -2563,12 +2707,18 @@ int agz_train_dev(agz_trainer* t, const float* Xs_dev, const float* policies_dev
   AGZ_REQUIRE(t && Xs_dev && policies_dev && values_dev && batches >= 1 && iterations >= 0, AGZ_E_INVALID, "agz_train_dev: bad argument");
   AGZ_HIP_TRY(hipSetDevice(t->ctx->device));
   hipStream_t s = t->ctx->stream;
-  const size_t xs = (size_t)t->F * t->g.HW, ps = (size_t)t->A;
-  const size_t n = (size_t)batches * t->B;
+  const size_t xs = (size_t)t->F * t->g.HW, ps = (size_t)t->A, Bg = (size_t)t->B * t->n_ranks;   // (sharded: as agz_train)
+  const size_t n = (size_t)batches * Bg;
   std::vector<int32_t> perm(n);
   for (size_t i = 0; i < n; i++) perm[i] = (int32_t)i;
   int32_t* d_perm = nullptr;
-  AGZ_HIP_TRY(hipMalloc(&d_perm, n * 4));
+  const hipError_t em = hipMalloc(&d_perm, n * 4);
+  if (t->sharded) {   // (every rank agrees before the first collective step: none may stay out of a step its peers enter)
+    if (em != hipSuccess) agz::set_error("agz_train_dev: %s", hipGetErrorString(em));
+    const int a = t->shard.agree(em == hipSuccess ? AGZ_OK : AGZ_E_NOMEM);
+    if (a != AGZ_OK) { if (em == hipSuccess) hipFree(d_perm); return a; }
+  } else
+    AGZ_HIP_TRY(em);
   SplitMix64 rng(seed);
   int rc = AGZ_OK;
   for (int it = 0; it < iterations && rc == AGZ_OK; it++) {
@@ -2576,12 +2726,12 @@ int agz_train_dev(agz_trainer* t, const float* Xs_dev, const float* policies_dev
     if (e == hipSuccess) e = hipStreamSynchronize(s);   // perm is reshuffled on the host below
     if (e != hipSuccess) { agz::set_error("agz_train_dev: %s", hipGetErrorString(e)); rc = AGZ_E_HIP; break; }
     for (int b = 0; b < batches && rc == AGZ_OK; b++) {
-      const int32_t* ib = d_perm + (size_t)b * t->B;
+      const int32_t* ib = d_perm + (size_t)b * Bg + (size_t)t->rank * t->B;
       hipLaunchKernelGGL(k_gather_rows_t, dim3(nblk((size_t)t->B * xs)), dim3(256), 0, s, Xs_dev, ib, t->d_planes, (int)xs, (size_t)t->B * xs);
       hipLaunchKernelGGL(k_gather_rows_t, dim3(nblk((size_t)t->B * ps)), dim3(256), 0, s, policies_dev, ib, t->d_pi, (int)ps, (size_t)t->B * ps);
       hipLaunchKernelGGL(k_gather_rows_t, dim3(nblk((size_t)t->B)), dim3(256), 0, s, values_dev, ib, t->d_v, 1, (size_t)t->B);
       t->fuse_lr = DUAL_TRAIN_LR;
-      rc = t->forward_backward_dev(t->d_planes, t->d_pi, t->d_v);
+      rc = t->step(t->d_planes, t->d_pi, t->d_v);
       t->fused_done = rc == AGZ_OK;
       t->fuse_lr = 0.f;
       if (rc == AGZ_OK) rc = agz_trainer_apply(t, DUAL_TRAIN_LR, 1.0f);
@@ -2601,10 +2751,87 @@ int agz_train_dev(agz_trainer* t, const float* Xs_dev, const float* policies_dev
   return AGZ_OK;
 }
 
+// the configuration a checkpoint of this trainer carries: BatchSize is the GLOBAL batch of a sharded trainer
+static agz_net_conf global_conf(const agz_trainer* t) {
+  agz_net_conf c = t->conf;
+  c.BatchSize = t->B * t->n_ranks;
+  return c;
+}
+
+// Sharded save (collective): rank 0 writes the plain trainer's file at the global batch.  Tensor by tensor, batch-shaped ones are gathered
+// from every rank (rows in rank order = the global tensor) through one device buffer of n slices; nothing larger than one global tensor is
+// ever staged on the host.  Every rank enters every gather whatever failed locally, and the call ends with the status exchange.
+static int save_sharded(const agz_trainer* t, const char* path) {
+  const int n = t->n_ranks;
+  int rc = AGZ_OK;
+  FILE* f = nullptr;
+  if (t->rank == 0 && !(f = fopen(path, "wb"))) { agz::set_error("agz_trainer_save: cannot open %s", path); rc = AGZ_E_INVALID; }
+  size_t mx = 0;
+  for (const auto& p : t->prefs) if (pref_batch_shaped(p)) mx = std::max(mx, pref_size(p));
+  float* d = nullptr;   // [n][mx] gathered slices, then this rank's slice
+  if (hipMalloc(&d, (size_t)(n + 1) * mx * 4) != hipSuccess) { d = nullptr; if (rc == AGZ_OK) { agz::set_error("agz_trainer_save: out of device memory for the gather"); rc = AGZ_E_NOMEM; } }
+  int a = t->shard.agree(rc);
+  if (a != AGZ_OK) { if (f) fclose(f); if (d) hipFree(d); return a; }
+  const agz_net_conf gc = global_conf(t);
+  const uint64_t np = t->prefs.size();
+  bool ok = f == nullptr || (fwrite("AGZTRN01", 1, 8, f) == 8 && fwrite(&gc, sizeof(gc), 1, f) == 1 && fwrite(&np, 8, 1, f) == 1);
+  std::vector<float> v, all;
+  for (int i = 0; i < (int)t->prefs.size(); i++) {
+    const TParamRef& p = t->prefs[i];
+    v.assign(pref_size(p), 0.f);
+    if (agz_trainer_get_param(t, i, v.data(), v.size()) != AGZ_OK && rc == AGZ_OK) rc = AGZ_E_HIP;
+    const float* out = v.data();
+    uint64_t cnt = v.size();
+    if (pref_batch_shaped(p)) {
+      float* mine = d + (size_t)n * mx;
+      if (hipMemcpy(mine, v.data(), v.size() * 4, hipMemcpyHostToDevice) != hipSuccess && rc == AGZ_OK) rc = AGZ_E_HIP;
+      int r = t->shard.allgather_bytes(mine, d, v.size() * 4);
+      if (r != AGZ_OK && rc == AGZ_OK) rc = r;
+      if (f) {
+        all.resize(v.size() * n);
+        if (hipMemcpy(all.data(), d, all.size() * 4, hipMemcpyDeviceToHost) != hipSuccess && rc == AGZ_OK) rc = AGZ_E_HIP;
+        out = all.data(); cnt = all.size();
+      }
+    }
+    if (f && ok) ok = fwrite(&cnt, 8, 1, f) == 1 && fwrite(out, 4, cnt, f) == cnt;
+  }
+  if (f) ok = (fclose(f) == 0) && ok;
+  hipFree(d);
+  if (!ok && rc == AGZ_OK) { agz::set_error("agz_trainer_save: write to %s failed", path); rc = AGZ_E_INVALID; }
+  return t->shard.agree(rc);
+}
+
+// Sharded load (local): a checkpoint of the GLOBAL configuration; this rank reads its rows of every batch-shaped tensor
+static int load_sharded(agz_trainer* t, const char* path) {
+  FILE* f = fopen(path, "rb");
+  AGZ_REQUIRE(f, AGZ_E_INVALID, "agz_trainer_load: cannot open %s", path);
+  char magic[8];
+  agz_net_conf c;
+  uint64_t np = 0;
+  const agz_net_conf gc = global_conf(t);
+  bool ok = fread(magic, 1, 8, f) == 8 && memcmp(magic, "AGZTRN01", 8) == 0 && fread(&c, sizeof(c), 1, f) == 1 && fread(&np, 8, 1, f) == 1;
+  if (ok) ok = memcmp(&c, &gc, sizeof(c)) == 0 && np == t->prefs.size();
+  if (!ok) { fclose(f); agz::set_error("agz_trainer_load: %s is not a checkpoint of this trainer configuration (global batch %d)", path, gc.BatchSize); return AGZ_E_INVALID; }
+  for (int i = 0; ok && i < (int)t->prefs.size(); i++) {
+    const TParamRef& p = t->prefs[i];
+    const bool bs = pref_batch_shaped(p);
+    std::vector<float> v(pref_size(p));
+    const uint64_t want = v.size() * (bs ? t->n_ranks : 1), skip = bs ? (uint64_t)v.size() * t->rank : 0;
+    uint64_t cnt = 0;
+    ok = fread(&cnt, 8, 1, f) == 1 && cnt == want && fseek(f, (long)(skip * 4), SEEK_CUR) == 0 && fread(v.data(), 4, v.size(), f) == v.size() &&
+         fseek(f, (long)((want - skip - v.size()) * 4), SEEK_CUR) == 0;
+    if (ok && agz_trainer_set_param(t, i, v.data(), v.size()) != AGZ_OK) { fclose(f); return AGZ_E_HIP; }
+  }
+  fclose(f);
+  AGZ_REQUIRE(ok, AGZ_E_INVALID, "agz_trainer_load: %s is truncated or mismatched", path);
+  return AGZ_OK;
+}
+
 // Checkpoint of the TRAINABLE network (AZ.Save / AZ.Load, agogo.go:175-209, for the side that keeps learning): every
 // learnable in its full batch-shaped form.  File: "AGZTRN01", agz_net_conf, count, then per tensor {n, n floats}.
 int agz_trainer_save(const agz_trainer* t, const char* path) {
   AGZ_REQUIRE(t && path, AGZ_E_INVALID, "agz_trainer_save: NULL argument");
+  if (t->sharded) return save_sharded(t, path);
   FILE* f = fopen(path, "wb");
   AGZ_REQUIRE(f, AGZ_E_INVALID, "agz_trainer_save: cannot open %s", path);
   bool ok = fwrite("AGZTRN01", 1, 8, f) == 8 && fwrite(&t->conf, sizeof(t->conf), 1, f) == 1;
@@ -2623,6 +2850,7 @@ int agz_trainer_save(const agz_trainer* t, const char* path) {
 
 int agz_trainer_load(agz_trainer* t, const char* path) {
   AGZ_REQUIRE(t && path, AGZ_E_INVALID, "agz_trainer_load: NULL argument");
+  if (t->sharded) return load_sharded(t, path);
   FILE* f = fopen(path, "rb");
   AGZ_REQUIRE(f, AGZ_E_INVALID, "agz_trainer_load: cannot open %s", path);
   char magic[8];
@@ -2642,12 +2870,49 @@ int agz_trainer_load(agz_trainer* t, const char* path) {
   return AGZ_OK;
 }
 
+// row 0 of every learnable as rank 0 holds it (a plain trainer's export), broadcast to every rank: the nets are bit-identical everywhere
+static int export_sharded(const agz_trainer* t, agz_net* net) {
+  int rc = AGZ_OK;
+  size_t mx = 0;
+  for (int i = 0; i < (int)t->prefs.size(); i++) {
+    size_t want = 0;
+    if (agz_net_param_info(net, i, nullptr, 0, &want) != AGZ_OK || want > pref_size(t->prefs[i])) { rc = AGZ_E_INVALID; want = 0; }
+    mx = std::max(mx, want);
+  }
+  if (rc != AGZ_OK) agz::set_error("agz_trainer_export: network shapes differ");
+  float* d = nullptr;
+  if (hipMalloc(&d, std::max<size_t>(mx, 1) * 4) != hipSuccess) { d = nullptr; if (rc == AGZ_OK) { agz::set_error("agz_trainer_export: out of device memory"); rc = AGZ_E_NOMEM; } }
+  int a = t->shard.agree(rc);
+  if (a != AGZ_OK) { if (d) hipFree(d); return a; }
+  std::vector<float> v;
+  for (int i = 0; i < (int)t->prefs.size(); i++) {
+    size_t want = 0;
+    agz_net_param_info(net, i, nullptr, 0, &want);
+    const TParamRef& p = t->prefs[i];
+    const bool conv_bn = p.layer >= 0 && (p.sub % 10) != 0;   // as agz_trainer_export: row 0 only of the tower's gamma / beta
+    if (t->rank == 0) {
+      v.assign(conv_bn ? want : pref_size(p), 0.f);
+      if (xfer_param(t, t->P, i, v.data(), 1, conv_bn ? 1 : 0) != AGZ_OK && rc == AGZ_OK) rc = AGZ_E_HIP;
+      if (hipMemcpy(d, v.data(), want * 4, hipMemcpyHostToDevice) != hipSuccess && rc == AGZ_OK) rc = AGZ_E_HIP;
+    }
+    int r = t->shard.bcast0(d, want * 4);
+    if (r != AGZ_OK && rc == AGZ_OK) rc = r;
+    v.assign(want, 0.f);
+    if (hipMemcpy(v.data(), d, want * 4, hipMemcpyDeviceToHost) != hipSuccess && rc == AGZ_OK) rc = AGZ_E_HIP;
+    if (rc == AGZ_OK && (r = agz_net_set_param(net, i, v.data(), want)) != AGZ_OK) rc = r;
+  }
+  hipFree(d);
+  rc = t->shard.agree(rc);
+  return rc == AGZ_OK ? agz_net_commit(net) : rc;
+}
+
 // the copy loop of dual.Infer (meta.go:141-146): row 0 of every learnable -> the inference net, then commit
 int agz_trainer_export(const agz_trainer* t, agz_net* net) {
   AGZ_REQUIRE(t && net, AGZ_E_INVALID, "NULL argument");
   AGZ_REQUIRE((int)t->prefs.size() == agz_net_num_params(net), AGZ_E_INVALID, "agz_trainer_export: network shapes differ");
   AGZ_HIP_TRY(hipSetDevice(t->ctx->device));
   AGZ_HIP_TRY(hipStreamSynchronize(t->ctx->stream));
+  if (t->sharded) return export_sharded(t, net);
   for (int i = 0; i < (int)t->prefs.size(); i++) {
     size_t want = 0;
     int r = agz_net_param_info(net, i, nullptr, 0, &want);

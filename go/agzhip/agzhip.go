@@ -775,6 +775,9 @@ func NewTrainer(ctx *Ctx, d *dual.Dual) (*Trainer, error) {
 // into d.Model() so the rest of AZ.Learn (SwitchToInference, Save) sees the trained network.  Xs [rows, F, H, W], policies
 // [rows, ActionSpace], values [rows] as flat float32 slices (tensor.Dense.Data()).
 func (t *Trainer) Train(Xs, policies, values []float32, batches, iterations int, seed uint64) error {
+	if t.d == nil {
+		return fmt.Errorf("agzhip: Train: a sharded trainer has no dual.Dual to copy back into: use TrainDev")
+	}
 	rows := batches * t.d.BatchSize
 	if batches < 1 || len(Xs) < rows*t.d.Features*t.d.Height*t.d.Width || len(policies) < rows*t.d.ActionSpace || len(values) < rows {
 		return fmt.Errorf("agzhip: Train: %d batches of %d rows need %d / %d / %d values, got %d / %d / %d", batches, t.d.BatchSize,
@@ -888,6 +891,42 @@ func (c *Comm) BatchStep(t *Trainer, planes, pi, v []float32, lr float32) (cost 
 }
 
 func (c *Comm) Close() error { defer c.ctx.enter()(); C.agz_comm_destroy(c.h); c.h = nil; return nil }
+
+// NewShardedTrainer is dual.Train at the GLOBAL batch conf.BatchSize split over the ranks of comm (agz_trainer_create_sharded): this rank
+// holds rows Shard() of the batch-shaped BatchNorm gamma / beta and FC biases (dualnet/dual.go:105-132), the shared tensors whole; the
+// BatchNorm statistics and the loss are the global batch's, so the run IS dual.Train (dualnet/meta.go:16-54) at conf.BatchSize.
+// conf.BatchSize must be a multiple of the ranks.  Start the learnables with InitRandom (every rank draws its rows of the global stream,
+// the same seed everywhere).  TrainDev (on the tensors of an Examples set gathered and prepared with the
+// global batch and a shared seed) and Export are collective: every rank calls them, concurrently, in the same order; Train is not
+// available (there is no dual.Dual to copy back into).
+func NewShardedTrainer(comm *Comm, conf dual.Config) (*Trainer, error) {
+	defer comm.ctx.enter()()
+	cc := C.agz_net_conf{
+		K: C.int32_t(conf.K), SharedLayers: C.int32_t(conf.SharedLayers), FC: C.int32_t(conf.FC), BatchSize: C.int32_t(conf.BatchSize),
+		Width: C.int32_t(conf.Width), Height: C.int32_t(conf.Height), Features: C.int32_t(conf.Features),
+		ActionSpace: C.int32_t(conf.ActionSpace), bn_mode: C.AGZ_BN_DEGENERATE_EPS, bn_eps: 1e-5,
+	}
+	t := &Trainer{ctx: comm.ctx}
+	if err := lastErr(C.agz_trainer_create_sharded(comm.h, &cc, &t.h)); err != nil {
+		return nil, err
+	}
+	return t, nil
+}
+
+// InitRandom fills the learnables from the library's initialiser (agz_trainer_init_random); a sharded trainer draws its rows of the
+// global tensors.
+func (t *Trainer) InitRandom(seed uint64) error {
+	defer t.ctx.enter()()
+	return lastErr(C.agz_trainer_init_random(t.h, C.uint64_t(seed)))
+}
+
+// Shard reports this rank's rows [row0, row0+rows) of a global batch of nRanks*rows; a plain trainer: 0, BatchSize, 1.
+func (t *Trainer) Shard() (row0, rows, nRanks int, err error) {
+	defer t.ctx.enter()()
+	var r0, n, nr C.int
+	err = lastErr(C.agz_trainer_shard(t.h, &r0, &n, &nr))
+	return int(r0), int(n), int(nr), err
+}
 
 var _ = game.Pass // keep the import: game.Single values cross the ABI as int32 (-1 pass, -2 resign)
 

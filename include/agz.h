@@ -565,6 +565,30 @@ int agz_trainer_allreduce(agz_comm* comm, agz_trainer* t);
  * process group (destroy the communicator).  dualnet/meta.go:16-54. */
 int agz_trainer_forward_backward_allreduce(agz_comm* comm, agz_trainer* t, const float* planes, const float* pi, const float* v, float* cost);
 int agz_trainer_forward_backward_allreduce_dev(agz_comm* comm, agz_trainer* t, const float* planes_dev, const float* pi_dev, const float* v_dev, float* cost);
+/* Sharded training: dual.Train (dualnet/meta.go:16-54) at the GLOBAL batch conf->BatchSize, split over the ranks of the communicator.
+ * The reference's BatchNorm gamma / beta [BatchSize,C,H,W] and FC biases [BatchSize,units] (dualnet/dual.go:105-132) give every batch row
+ * its own parameters: rank r of n owns rows [r*B, (r+1)*B), B = BatchSize / n, and holds only those rows of them (and of their gradients).
+ * The shared tensors (filters, the heads' 1x1 convolutions, the FC weights) are replicated and their gradients summed over the ranks;
+ * BatchNorm takes its statistics over all BatchSize rows (the ranks' partial sums are gathered and summed in rank order: the same bits on
+ * every rank) and the loss is normalised by the global batch.  The result is dual.Train at BatchSize, not an average of n smaller runs.
+ * BatchSize must be a multiple of agz_comm_size(comm) (else AGZ_E_INVALID); the trainer lives on the communicator's ctx, which must
+ * outlive it together with the communicator.  On such a handle:
+ *   forward_backward(_dev), batch, train, train_dev, export, save are COLLECTIVE: every rank calls them for the same step, in the same
+ *     order.  planes / pi / v of forward_backward and batch are this rank's B rows; *cost is the GLOBAL cost, bit-identical on every
+ *     rank; the shared tensors' gradients come back summed.  train / train_dev take the GLOBAL tensors (the same on every rank, e.g.
+ *     agz_examples_tensors_dev after agz_examples_allgather and agz_examples_prepare with the global BatchSize and a shared seed) and the
+ *     single-process shuffle stream; each rank trains its rows of every global batch.  export gives every rank's net rank 0's row 0
+ *     (broadcast); save has rank 0 write the file of a plain trainer with the global conf (gathered tensor by tensor).
+ *   apply, init_random, load, param_info / get_param / set_param / get_grad are local: batch-shaped tensors are this rank's row slice
+ *     (n_elems reports the slice), shared tensors are whole; apply takes no 1/n (the loss is already the global batch's); init_random(seed)
+ *     draws exactly those rows of a plain trainer's init_random(seed) at the global batch; load reads a global checkpoint's rows.
+ *   agz_trainer_allreduce and agz_trainer_forward_backward_allreduce(_dev) return AGZ_E_STATE.
+ * Errors of a collective call: a rank that fails part-way still enters every remaining collective and all ranks exchange a status word —
+ * the call fails on EVERY rank (AGZ_E_PEER on the ranks that were fine), nobody hangs, and the next call is an ordinary one.  After a
+ * failed step the learnables are undefined (see agz_trainer_batch). */
+int agz_trainer_create_sharded(agz_comm* comm, const agz_net_conf* conf, agz_trainer** out);
+/* this rank's rows of the global batch: [*row0, *row0 + *rows) of *n_ranks * *rows; a plain trainer reports 0, BatchSize, 1 */
+int agz_trainer_shard(const agz_trainer* t, int* row0, int* rows, int* n_ranks);
 
 #ifdef __cplusplus
 }

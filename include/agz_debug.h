@@ -97,6 +97,12 @@ int agz_arena_pool_capacity(agz_arena* arena, int* nodes_per_pool, int* grows);
  * healthy ones), nobody hangs, and the next step is a normal one. */
 int agz_comm_debug_fail_slice(agz_comm* comm, int k);
 
+/* Failure injection (tests): the next collective step of a sharded trainer on this communicator (agz_trainer_create_sharded) returns an
+ * error on THIS rank right before the first exchange of tower layer `layer` (0 .. SharedLayers; SharedLayers + 1 = the heads; < 0: off) —
+ * an error return, nothing on the device.  One shot.  What the test checks: the failing rank still enters every remaining collective of
+ * the step, every rank's call fails (AGZ_E_PEER on the healthy ones), nobody hangs, and the next step is a normal one. */
+int agz_comm_debug_fail_layer(agz_comm* comm, int layer);
+
 #ifdef __cplusplus
 }
 #endif
