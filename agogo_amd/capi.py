@@ -35,6 +35,11 @@ class NetConf(C.Structure):
                 ("bn_mode", C.c_int32), ("bn_eps", C.c_float)]
 
 
+class SolverConf(C.Structure):
+    """agz_solver_conf: the options of gorgonia's solver constructor (dualnet/meta.go:20) — momentum, WithL2Reg, WithClip; all 0 = vanilla."""
+    _fields_ = [("momentum", C.c_float), ("l2reg", C.c_float), ("clip", C.c_float), ("reserved", C.c_int32)]
+
+
 class GameConf(C.Structure):
     _fields_ = [("kind", C.c_int32), ("m", C.c_int32), ("n", C.c_int32), ("k", C.c_int32), ("komi", C.c_float),
                 ("max_moves", C.c_int32), ("encoder", C.c_int32)]
@@ -173,6 +178,11 @@ def lib():
     sig("agz_trainer_forward_backward_dev", i32, vp, vp, vp, vp, pf)
     sig("agz_trainer_apply", i32, vp, C.c_float, C.c_float)
     sig("agz_trainer_grads_dev", i32, vp, pvp, C.POINTER(C.c_size_t))
+    sig("agz_trainer_set_solver", i32, vp, C.POINTER(SolverConf))
+    sig("agz_trainer_get_solver", i32, vp, C.POINTER(SolverConf))
+    sig("agz_trainer_get_velocity", i32, vp, i32, pf, C.c_size_t)
+    sig("agz_trainer_set_velocity", i32, vp, i32, pf, C.c_size_t)
+    sig("agz_trainer_reset_solver", i32, vp)
     sig("agz_trainer_set_compute_mode", i32, vp, i32)
     sig("agz_train", i32, vp, pf, pf, pf, i32, i32, u64, pf)
     sig("agz_trainer_export", i32, vp, vp)
@@ -538,6 +548,30 @@ class Trainer:
 
     def apply(self, lr=0.1, grad_scale=1.0):
         _check(lib().agz_trainer_apply(self.h, lr, grad_scale), "agz_trainer_apply")
+
+    def set_solver(self, momentum=0.0, l2reg=0.0, clip=0.0, reserved=0):
+        """gorgonia's solver options (agz_trainer_set_solver): L2, then clip, then v = momentum * v - lr * g, w += v; all 0 = vanilla SGD"""
+        sc = SolverConf(momentum, l2reg, clip, reserved)
+        _check(lib().agz_trainer_set_solver(self.h, C.byref(sc)), "agz_trainer_set_solver")
+
+    def get_solver(self):
+        sc = SolverConf()
+        _check(lib().agz_trainer_get_solver(self.h, C.byref(sc)), "agz_trainer_get_solver")
+        return {"momentum": sc.momentum, "l2reg": sc.l2reg, "clip": sc.clip}
+
+    def get_velocity(self, i):
+        """the momentum state of learnable i, shaped and indexed like get_param(i); zeros while the momentum is 0"""
+        a = np.zeros(self.param_info(i)[1], np.float32)
+        _check(lib().agz_trainer_get_velocity(self.h, i, _pf(a), a.size), "agz_trainer_get_velocity")
+        return a
+
+    def set_velocity(self, i, v):
+        a = np.ascontiguousarray(v, dtype=np.float32).ravel()
+        _check(lib().agz_trainer_set_velocity(self.h, i, _pf(a), a.size), "agz_trainer_set_velocity")
+
+    def reset_solver(self):
+        """velocity := 0, the options kept"""
+        _check(lib().agz_trainer_reset_solver(self.h), "agz_trainer_reset_solver")
 
     def set_compute_mode(self, mode):
         _check(lib().agz_trainer_set_compute_mode(self.h, int(mode)), "agz_trainer_set_compute_mode")

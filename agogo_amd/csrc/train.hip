@@ -282,11 +282,27 @@ __global__ __launch_bounds__(256) void k_bn_apply_v(TGeo g, const float* __restr
 // agz_trainer_apply sweep parameters and gradients again: 23 GB less traffic per step.  Same arithmetic (one fp32 multiply-subtract per
 // element, as k_axpy); the gradients of these tensors are then not materialised (agz_trainer_forward_backward keeps them: the
 // data-parallel path reduces them before its apply).
+//
+// SOLVER (agz_trainer_set_solver with any option != 0, fused steps only): the same in-place step through solver_step below — L2 with the
+// gm / bt already in registers, the clamp, and with MOM the velocity of gamma / beta read and written at the same (r * C + cc) index of the
+// flat velocity buffer.  A template parameter, not a run-time branch: the <false, false> instantiation is the code above, instruction for
+// instruction (SolverDev is then an unused kernel argument).
+struct SolverDev { float mu, l2, clip; float* vgamma; float* vbeta; };
+// One element of the solver step (gorgonia's VanillaSolver / Momentum as documented: L2, then clip, then the update), fp32:
+//   g2 = g + l2 * w (l2 != 0);  g3 = clamp(g2, -clip, clip) (clip > 0);  MOM: v = mu * v + (-lr) * g3, w += v;  else w += (-lr) * g3
+template <bool MOM>
+__device__ __forceinline__ void solver_step(float& w, float& v, float gr, float lr, float mu, float l2, float clip) {
+  if (l2 != 0.f) gr = gr + l2 * w;
+  if (clip > 0.f) gr = fminf(fmaxf(gr, -clip), clip);
+  if (MOM) { v = mu * v + (-lr) * gr; w = w + v; }
+  else w = w + (-lr) * gr;
+}
+template <bool SOLVER, bool MOM>
 __global__ void k_bn_bwd1(TGeo g, const float* __restrict__ z, float* gamma, float* beta,
                           const float* __restrict__ mean, const float* __restrict__ inv, const float* __restrict__ out,
                           const float* __restrict__ dout, float* __restrict__ dgamma, float* __restrict__ dbeta,
                           float* __restrict__ dz, double* __restrict__ s1, double* __restrict__ s2, int Kp, int nbr,
-                          int rows_per_block, float fuse_lr) {
+                          int rows_per_block, float fuse_lr, SolverDev sv) {
   int C = nbr * Kp;
   int r0 = blockIdx.x * rows_per_block, r1 = min(r0 + rows_per_block, g.M);
   for (int cc = threadIdx.x; cc < C; cc += blockDim.x) {
@@ -301,7 +317,15 @@ __global__ void k_bn_bwd1(TGeo g, const float* __restrict__ z, float* gamma, flo
       float bt = beta[(size_t)r * C + cc];
       float y = gm * xh + bt;
       float gg = y > 0.f ? g0 : 0.f;
-      if (fuse_lr != 0.f) {   // (uniform) p += alpha * g with alpha = -lr, exactly k_axpy's expression
+      if (SOLVER) {           // (fused steps only: fuse_lr != 0)
+        float wg = gm, wb = bt, vg = 0.f, vb = 0.f;
+        if (MOM) { vg = sv.vgamma[(size_t)r * C + cc]; vb = sv.vbeta[(size_t)r * C + cc]; }
+        solver_step<MOM>(wg, vg, gg * xh, fuse_lr, sv.mu, sv.l2, sv.clip);
+        solver_step<MOM>(wb, vb, gg, fuse_lr, sv.mu, sv.l2, sv.clip);
+        if (MOM) { sv.vgamma[(size_t)r * C + cc] = vg; sv.vbeta[(size_t)r * C + cc] = vb; }
+        gamma[(size_t)r * C + cc] = wg;
+        beta[(size_t)r * C + cc] = wb;
+      } else if (fuse_lr != 0.f) {   // (uniform) p += alpha * g with alpha = -lr, exactly k_axpy's expression
         gamma[(size_t)r * C + cc] = gm + (-fuse_lr) * (gg * xh);
         beta[(size_t)r * C + cc] = bt + (-fuse_lr) * gg;
       } else {
@@ -1005,6 +1029,24 @@ __global__ void k_gather_rows_t(const float* __restrict__ src, const int32_t* __
 __global__ void k_axpy(float* __restrict__ p, const float* __restrict__ g, float alpha, size_t n) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) p[i] += alpha * g[i];
+}
+// The solver form of the same sweep (agz_trainer_set_solver): solver_step over n4 float4 of p / g (/ v with MOM), g scaled by gs first
+// (grad_scale of the two-pass and data-parallel paths).  Grid-stride, the grid sized by the CU count: it streams p, g, v -> p, v.
+template <bool MOM>
+__global__ __launch_bounds__(256) void k_solver_sweep(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ v, size_t n4,
+                                                      float lr, float gs, float mu, float l2, float clip) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+    const float4 gg = reinterpret_cast<const float4*>(g)[i];
+    float4 w = reinterpret_cast<float4*>(p)[i];
+    float4 vv = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (MOM) vv = reinterpret_cast<float4*>(v)[i];
+    solver_step<MOM>(w.x, vv.x, gs * gg.x, lr, mu, l2, clip);
+    solver_step<MOM>(w.y, vv.y, gs * gg.y, lr, mu, l2, clip);
+    solver_step<MOM>(w.z, vv.z, gs * gg.z, lr, mu, l2, clip);
+    solver_step<MOM>(w.w, vv.w, gs * gg.w, lr, mu, l2, clip);
+    if (MOM) reinterpret_cast<float4*>(v)[i] = vv;
+    reinterpret_cast<float4*>(p)[i] = w;
+  }
 }
 
 // ---- heads (small; one thread per output element, plain loops) --------------------------------------------------
@@ -1866,6 +1908,12 @@ struct agz_trainer {
   hipEvent_t ev_w0 = nullptr, ev_bw = nullptr;
   int side_stream();
   int prep_weights();
+  // solver options (agz_trainer_set_solver; all 0 = the vanilla step, which then runs the kernels it always ran) and the first-order state:
+  // V, one flat buffer laid out exactly like P / G, exists only while momentum != 0 (allocated and zeroed when it is first set, released
+  // when it is set back to 0): a trainer that never asks for momentum allocates nothing more
+  agz_solver_conf solver{0.f, 0.f, 0.f, 0};
+  float* V = nullptr;
+  bool solver_on() const { return solver.momentum != 0.f || solver.l2reg != 0.f || solver.clip != 0.f; }
   float fuse_lr = 0.f;      // != 0 during a fused step: k_bn_bwd1 updates gamma / beta in place, apply() skips them
   bool fused_done = false;  // the backward that just ran took the fused path
   // sharded trainer (agz_trainer_create_sharded): this rank's rows [rank * B, (rank + 1) * B) of a global batch of n_ranks * B rows.
@@ -2120,8 +2168,14 @@ int agz_trainer::forward_backward_dev(const float* planes, const float* pi, cons
     unsigned* wg_amax = amax_words + 2 * l;
     float* dz = l == 0 ? this->dz0 : this->dz;  // (different pixel strides: keep the [pix][2Kp] buffer's zero halo intact)
     if (sw != s && l < L) AGZ_HIP_TRY(hipStreamWaitEvent(s, ev_split, 0));   // the previous layer's weight gradient has taken its copy of dz
-    hipLaunchKernelGGL(k_bn_bwd1, dim3(nblk(g.M, RPB)), dim3(std::min(C, 512)), 0, s, g, ly.z, P + ly.o_gamma, P + ly.o_beta, ly.mean, ly.inv,
-                       ly.out, dcur, G + ly.o_gamma, G + ly.o_beta, dz, s1, s2, Kp, ly.nbr, RPB, fuse_lr);
+    {
+      // (the solver variants only on a fused step with an option set: everything else launches the instantiation without them)
+      const bool sv_on = fuse_lr != 0.f && solver_on(), sv_mom = sv_on && solver.momentum != 0.f;
+      const SolverDev sd{solver.momentum, solver.l2reg, solver.clip, sv_mom ? V + ly.o_gamma : nullptr, sv_mom ? V + ly.o_beta : nullptr};
+      auto* bwd1 = sv_mom ? k_bn_bwd1<true, true> : sv_on ? k_bn_bwd1<true, false> : k_bn_bwd1<false, false>;
+      hipLaunchKernelGGL(bwd1, dim3(nblk(g.M, RPB)), dim3(std::min(C, 512)), 0, s, g, ly.z, P + ly.o_gamma, P + ly.o_beta, ly.mean, ly.inv,
+                         ly.out, dcur, G + ly.o_gamma, G + ly.o_beta, dz, s1, s2, Kp, ly.nbr, RPB, fuse_lr, sd);
+    }
     if (sharded) {   // the two channel sums over the global batch (in place: acc_b of this layer holds the ranks' sum afterwards)
       int r = exchange(l, s1, 2048);
       if (r != AGZ_OK) return r;
@@ -2372,6 +2426,7 @@ void agz_trainer_destroy(agz_trainer* t) {
   wino_raw_scratch_free(&t->wsc);
   if (t->dz_h2) hipFree(t->dz_h2);
   if (t->x_h2) hipFree(t->x_h2);
+  if (t->V) hipFree(t->V);
   delete t;
 }
 
@@ -2501,6 +2556,69 @@ int agz_trainer_get_grad(const agz_trainer* t, int i, float* host, size_t n) {
   return xfer_param(t, t->G, i, host, 1);
 }
 
+// ---- solver options (gorgonia's solver constructor options, dualnet/meta.go:20) ---------------------------------------------------------
+static bool solver_conf_valid(const agz_solver_conf* c) {
+  return std::isfinite(c->momentum) && std::isfinite(c->l2reg) && std::isfinite(c->clip) && c->momentum >= 0.f && c->momentum < 1.f &&
+         c->l2reg >= 0.f && c->clip >= 0.f && c->reserved == 0;
+}
+// momentum != 0 for the first time: the velocity buffer, zeroed; momentum back to 0: released (v has no meaning without it).  The options
+// change only if the call succeeds.  (Sharded: a local call; every rank sets the same options, as every rank passes the same lr.)
+int agz_trainer_set_solver(agz_trainer* t, const agz_solver_conf* c) {
+  AGZ_REQUIRE(t && c, AGZ_E_INVALID, "agz_trainer_set_solver: NULL argument");
+  AGZ_REQUIRE(solver_conf_valid(c), AGZ_E_INVALID,
+              "agz_trainer_set_solver: need 0 <= momentum < 1, l2reg >= 0, clip >= 0, all finite, reserved = 0 (got %g, %g, %g, %d)",
+              (double)c->momentum, (double)c->l2reg, (double)c->clip, (int)c->reserved);
+  AGZ_HIP_TRY(hipSetDevice(t->ctx->device));
+  AGZ_HIP_TRY(hipStreamSynchronize(t->ctx->stream));
+  if (c->momentum != 0.f && !t->V) {
+    float* v = nullptr;
+    if (hipMalloc(&v, t->n_flat * sizeof(float)) != hipSuccess) {
+      (void)hipGetLastError();
+      agz::set_error("agz_trainer_set_solver: out of device memory for the velocity (%zu bytes)", t->n_flat * sizeof(float));
+      return AGZ_E_NOMEM;
+    }
+    if (hipMemsetAsync(v, 0, t->n_flat * sizeof(float), t->ctx->stream) != hipSuccess || hipStreamSynchronize(t->ctx->stream) != hipSuccess) {
+      hipFree(v);
+      agz::set_error("agz_trainer_set_solver: clearing the velocity failed");
+      return AGZ_E_HIP;
+    }
+    t->V = v;
+  } else if (c->momentum == 0.f && t->V) {
+    AGZ_HIP_TRY(hipFree(t->V));
+    t->V = nullptr;
+  }
+  t->solver = *c;
+  return AGZ_OK;
+}
+int agz_trainer_get_solver(const agz_trainer* t, agz_solver_conf* out) {
+  AGZ_REQUIRE(t && out, AGZ_E_INVALID, "agz_trainer_get_solver: NULL argument");
+  *out = t->solver;
+  return AGZ_OK;
+}
+int agz_trainer_get_velocity(const agz_trainer* t, int i, float* host, size_t n) {
+  AGZ_REQUIRE(t && host && i >= 0 && i < (int)t->prefs.size() && n >= pref_size(t->prefs[i]), AGZ_E_INVALID, "agz_trainer_get_velocity: bad argument");
+  if (!t->V) { std::fill(host, host + pref_size(t->prefs[i]), 0.f); return AGZ_OK; }   // (no momentum: no velocity)
+  AGZ_HIP_TRY(hipSetDevice(t->ctx->device));
+  AGZ_HIP_TRY(hipStreamSynchronize(t->ctx->stream));
+  return xfer_param(t, t->V, i, host, 1);
+}
+int agz_trainer_set_velocity(agz_trainer* t, int i, const float* host, size_t n) {
+  AGZ_REQUIRE(t && host && i >= 0 && i < (int)t->prefs.size(), AGZ_E_INVALID, "agz_trainer_set_velocity: bad argument");
+  AGZ_REQUIRE(n == pref_size(t->prefs[i]), AGZ_E_INVALID, "agz_trainer_set_velocity(%s): need %zu floats, got %zu", t->prefs[i].name.c_str(), pref_size(t->prefs[i]), n);
+  AGZ_REQUIRE(t->V, AGZ_E_STATE, "agz_trainer_set_velocity: the trainer has no velocity (set a momentum != 0 first: agz_trainer_set_solver)");
+  AGZ_HIP_TRY(hipSetDevice(t->ctx->device));
+  AGZ_HIP_TRY(hipStreamSynchronize(t->ctx->stream));
+  return xfer_param(t, t->V, i, const_cast<float*>(host), 0);
+}
+int agz_trainer_reset_solver(agz_trainer* t) {
+  AGZ_REQUIRE(t, AGZ_E_INVALID, "agz_trainer_reset_solver: NULL trainer");
+  if (!t->V) return AGZ_OK;
+  AGZ_HIP_TRY(hipSetDevice(t->ctx->device));
+  AGZ_HIP_TRY(hipMemsetAsync(t->V, 0, t->n_flat * sizeof(float), t->ctx->stream));
+  AGZ_HIP_TRY(hipStreamSynchronize(t->ctx->stream));
+  return AGZ_OK;
+}
+
 // A sharded trainer draws its rows' slice of the GLOBAL tensors: the stream position of its first element, the Glorot deviation of the
 // global shape — bit for bit those rows of a plain trainer's init_random(seed) at the global batch.
 int agz_trainer_init_random(agz_trainer* t, uint64_t seed) {  // same recipe as agz_net_init_random over the FULL shapes
@@ -2591,9 +2709,32 @@ int agz_trainer_forward_backward_dev(agz_trainer* t, const float* planes_dev, co
   return AGZ_OK;
 }
 
+// solver.Step with options (agz_trainer_set_solver): the regions the vanilla step sweeps with k_axpy, through k_solver_sweep
+static int apply_solver(agz_trainer* t, float lr, float grad_scale) {
+  const agz_solver_conf& sc = t->solver;
+  const bool mom = sc.momentum != 0.f;
+  hipStream_t s = t->ctx->stream;
+  auto sweep = [&](size_t off, size_t n) {   // (every region starts and ends on a multiple of four floats: take() in agz_trainer_create)
+    const size_t n4 = n / 4;
+    const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>(nblk(n4), (size_t)t->ctx->num_cus * 8));
+    if (mom) hipLaunchKernelGGL(k_solver_sweep<true>, dim3(grid), dim3(256), 0, s, t->P + off, t->G + off, t->V + off, n4, lr, grad_scale, sc.momentum, sc.l2reg, sc.clip);
+    else hipLaunchKernelGGL(k_solver_sweep<false>, dim3(grid), dim3(256), 0, s, t->P + off, t->G + off, (float*)nullptr, n4, lr, grad_scale, sc.momentum, sc.l2reg, sc.clip);
+  };
+  if (t->fused_done) {   // k_bn_bwd1<true, .> stepped the tower's gamma / beta and their velocity: the filters and the head region remain
+    AGZ_REQUIRE(grad_scale == 1.0f, AGZ_E_STATE, "agz_trainer_apply: a fused step takes no gradient scale");
+    for (const auto& ly : t->layers) sweep(ly.o_wf, (size_t)9 * ly.Cout_p * ly.Cin_p);
+    sweep(t->o_hc, t->n_flat - t->o_hc);
+    t->fused_done = false;
+  } else
+    sweep(0, t->n_flat);
+  AGZ_HIP_TRY(hipGetLastError());
+  return AGZ_OK;
+}
+
 int agz_trainer_apply(agz_trainer* t, float lr, float grad_scale) {  // solver.Step (meta.go:40): w -= lr * grad
   AGZ_REQUIRE(t, AGZ_E_INVALID, "trainer is NULL");
   AGZ_HIP_TRY(hipSetDevice(t->ctx->device));
+  if (t->solver_on()) return apply_solver(t, lr, grad_scale);
   if (t->fused_done) {
     // the backward that just ran stepped the tower's gamma / beta itself (k_bn_bwd1): the filters of every layer and the head region remain
     AGZ_REQUIRE(grad_scale == 1.0f, AGZ_E_STATE, "agz_trainer_apply: a fused step takes no gradient scale");
@@ -2758,6 +2899,16 @@ static agz_net_conf global_conf(const agz_trainer* t) {
   return c;
 }
 
+// An AGZTRN02 file is checked for its full length BEFORE anything of it is loaded (the header has been read; the position is restored):
+// a truncated file is rejected with the trainer's parameters, options and velocity untouched.  nr: ranks the global tensors are split over.
+static bool checkpoint_complete(FILE* f, const agz_trainer* t, int nr) {
+  const long at = ftell(f);
+  uint64_t need = (uint64_t)at + sizeof(agz_solver_conf);
+  for (const auto& p : t->prefs) need += 2 * (8 + 4 * (uint64_t)pref_size(p) * (pref_batch_shaped(p) ? nr : 1));
+  const bool ok = at >= 0 && fseek(f, 0, SEEK_END) == 0 && (uint64_t)ftell(f) == need;
+  return fseek(f, at, SEEK_SET) == 0 && ok;
+}
+
 // Sharded save (collective): rank 0 writes the plain trainer's file at the global batch.  Tensor by tensor, batch-shaped ones are gathered
 // from every rank (rows in rank order = the global tensor) through one device buffer of n slices; nothing larger than one global tensor is
 // ever staged on the host.  Every rank enters every gather whatever failed locally, and the call ends with the status exchange.
@@ -2774,12 +2925,16 @@ static int save_sharded(const agz_trainer* t, const char* path) {
   if (a != AGZ_OK) { if (f) fclose(f); if (d) hipFree(d); return a; }
   const agz_net_conf gc = global_conf(t);
   const uint64_t np = t->prefs.size();
-  bool ok = f == nullptr || (fwrite("AGZTRN01", 1, 8, f) == 8 && fwrite(&gc, sizeof(gc), 1, f) == 1 && fwrite(&np, 8, 1, f) == 1);
+  // (AGZTRN02 when this trainer has a velocity — the same on every rank, like the options themselves: agz_trainer_save)
+  bool ok = f == nullptr || (fwrite(t->V ? "AGZTRN02" : "AGZTRN01", 1, 8, f) == 8 && fwrite(&gc, sizeof(gc), 1, f) == 1 && fwrite(&np, 8, 1, f) == 1);
   std::vector<float> v, all;
-  for (int i = 0; i < (int)t->prefs.size(); i++) {
+  const int np_i = (int)t->prefs.size();
+  for (int k = 0; k < (t->V ? 2 * np_i : np_i); k++) {   // the learnables, then (02) the options and every tensor's velocity
+    const int i = k % np_i;
+    if (k == np_i && f && ok) ok = fwrite(&t->solver, sizeof(t->solver), 1, f) == 1;
     const TParamRef& p = t->prefs[i];
     v.assign(pref_size(p), 0.f);
-    if (agz_trainer_get_param(t, i, v.data(), v.size()) != AGZ_OK && rc == AGZ_OK) rc = AGZ_E_HIP;
+    if ((k < np_i ? agz_trainer_get_param(t, i, v.data(), v.size()) : agz_trainer_get_velocity(t, i, v.data(), v.size())) != AGZ_OK && rc == AGZ_OK) rc = AGZ_E_HIP;
     const float* out = v.data();
     uint64_t cnt = v.size();
     if (pref_batch_shaped(p)) {
@@ -2809,10 +2964,20 @@ static int load_sharded(agz_trainer* t, const char* path) {
   agz_net_conf c;
   uint64_t np = 0;
   const agz_net_conf gc = global_conf(t);
-  bool ok = fread(magic, 1, 8, f) == 8 && memcmp(magic, "AGZTRN01", 8) == 0 && fread(&c, sizeof(c), 1, f) == 1 && fread(&np, 8, 1, f) == 1;
+  bool ok = fread(magic, 1, 8, f) == 8 && (memcmp(magic, "AGZTRN01", 8) == 0 || memcmp(magic, "AGZTRN02", 8) == 0) && fread(&c, sizeof(c), 1, f) == 1 && fread(&np, 8, 1, f) == 1;
   if (ok) ok = memcmp(&c, &gc, sizeof(c)) == 0 && np == t->prefs.size();
   if (!ok) { fclose(f); agz::set_error("agz_trainer_load: %s is not a checkpoint of this trainer configuration (global batch %d)", path, gc.BatchSize); return AGZ_E_INVALID; }
-  for (int i = 0; ok && i < (int)t->prefs.size(); i++) {
+  const bool v2 = magic[7] == '2';
+  if (v2 && !checkpoint_complete(f, t, t->n_ranks)) { fclose(f); agz::set_error("agz_trainer_load: %s is truncated or mismatched", path); return AGZ_E_INVALID; }
+  const int np_i = (int)t->prefs.size();
+  for (int k = 0; ok && k < (v2 ? 2 * np_i : np_i); k++) {
+    const int i = k % np_i;
+    if (k == np_i) {   // (02) the options, then every tensor's velocity
+      agz_solver_conf sc;
+      ok = fread(&sc, sizeof(sc), 1, f) == 1 && solver_conf_valid(&sc) && sc.momentum != 0.f;
+      if (ok && agz_trainer_set_solver(t, &sc) != AGZ_OK) { fclose(f); return AGZ_E_HIP; }
+      if (!ok) break;
+    }
     const TParamRef& p = t->prefs[i];
     const bool bs = pref_batch_shaped(p);
     std::vector<float> v(pref_size(p));
@@ -2820,21 +2985,26 @@ static int load_sharded(agz_trainer* t, const char* path) {
     uint64_t cnt = 0;
     ok = fread(&cnt, 8, 1, f) == 1 && cnt == want && fseek(f, (long)(skip * 4), SEEK_CUR) == 0 && fread(v.data(), 4, v.size(), f) == v.size() &&
          fseek(f, (long)((want - skip - v.size()) * 4), SEEK_CUR) == 0;
-    if (ok && agz_trainer_set_param(t, i, v.data(), v.size()) != AGZ_OK) { fclose(f); return AGZ_E_HIP; }
+    if (ok && (k < np_i ? agz_trainer_set_param(t, i, v.data(), v.size()) : agz_trainer_set_velocity(t, i, v.data(), v.size())) != AGZ_OK) { fclose(f); return AGZ_E_HIP; }
   }
   fclose(f);
   AGZ_REQUIRE(ok, AGZ_E_INVALID, "agz_trainer_load: %s is truncated or mismatched", path);
+  if (!v2) return agz_trainer_reset_solver(t);   // a file without velocity: v := 0, the options stay
   return AGZ_OK;
 }
 
 // Checkpoint of the TRAINABLE network (AZ.Save / AZ.Load, agogo.go:175-209, for the side that keeps learning): every
 // learnable in its full batch-shaped form.  File: "AGZTRN01", agz_net_conf, count, then per tensor {n, n floats}.
+// A trainer that holds a velocity (momentum != 0, agz_trainer_set_solver) writes "AGZTRN02": the same payload, then agz_solver_conf
+// (16 bytes), then per tensor {n, n floats} of velocity in the same order and layout.  Without a velocity the file is AGZTRN01, byte for
+// byte what it always was (l2reg / clip alone are not stored: they are the caller's configuration, like lr).  Load reads both: an 02 file
+// sets the options it carries and the velocity, an 01 file zeroes the velocity and keeps the trainer's options.
 int agz_trainer_save(const agz_trainer* t, const char* path) {
   AGZ_REQUIRE(t && path, AGZ_E_INVALID, "agz_trainer_save: NULL argument");
   if (t->sharded) return save_sharded(t, path);
   FILE* f = fopen(path, "wb");
   AGZ_REQUIRE(f, AGZ_E_INVALID, "agz_trainer_save: cannot open %s", path);
-  bool ok = fwrite("AGZTRN01", 1, 8, f) == 8 && fwrite(&t->conf, sizeof(t->conf), 1, f) == 1;
+  bool ok = fwrite(t->V ? "AGZTRN02" : "AGZTRN01", 1, 8, f) == 8 && fwrite(&t->conf, sizeof(t->conf), 1, f) == 1;
   uint64_t np = t->prefs.size();
   ok = ok && fwrite(&np, 8, 1, f) == 1;
   for (int i = 0; ok && i < (int)t->prefs.size(); i++) {
@@ -2842,6 +3012,15 @@ int agz_trainer_save(const agz_trainer* t, const char* path) {
     if (agz_trainer_get_param(t, i, v.data(), v.size()) != AGZ_OK) { fclose(f); return AGZ_E_HIP; }
     uint64_t cnt = v.size();
     ok = fwrite(&cnt, 8, 1, f) == 1 && fwrite(v.data(), 4, cnt, f) == cnt;
+  }
+  if (t->V) {
+    ok = ok && fwrite(&t->solver, sizeof(t->solver), 1, f) == 1;
+    for (int i = 0; ok && i < (int)t->prefs.size(); i++) {
+      std::vector<float> v(pref_size(t->prefs[i]));
+      if (agz_trainer_get_velocity(t, i, v.data(), v.size()) != AGZ_OK) { fclose(f); return AGZ_E_HIP; }
+      uint64_t cnt = v.size();
+      ok = fwrite(&cnt, 8, 1, f) == 1 && fwrite(v.data(), 4, cnt, f) == cnt;
+    }
   }
   ok = (fclose(f) == 0) && ok;
   AGZ_REQUIRE(ok, AGZ_E_INVALID, "agz_trainer_save: write to %s failed", path);
@@ -2856,17 +3035,31 @@ int agz_trainer_load(agz_trainer* t, const char* path) {
   char magic[8];
   agz_net_conf c;
   uint64_t np = 0;
-  bool ok = fread(magic, 1, 8, f) == 8 && memcmp(magic, "AGZTRN01", 8) == 0 && fread(&c, sizeof(c), 1, f) == 1 && fread(&np, 8, 1, f) == 1;
+  bool ok = fread(magic, 1, 8, f) == 8 && (memcmp(magic, "AGZTRN01", 8) == 0 || memcmp(magic, "AGZTRN02", 8) == 0) && fread(&c, sizeof(c), 1, f) == 1 && fread(&np, 8, 1, f) == 1;
   if (ok) ok = memcmp(&c, &t->conf, sizeof(c)) == 0 && np == t->prefs.size();
   if (!ok) { fclose(f); agz::set_error("agz_trainer_load: %s is not a checkpoint of this trainer configuration", path); return AGZ_E_INVALID; }
+  const bool v2 = magic[7] == '2';
+  if (v2 && !checkpoint_complete(f, t, 1)) { fclose(f); agz::set_error("agz_trainer_load: %s is truncated or mismatched", path); return AGZ_E_INVALID; }
   for (int i = 0; ok && i < (int)t->prefs.size(); i++) {
     uint64_t cnt = 0;
     std::vector<float> v(pref_size(t->prefs[i]));
     ok = fread(&cnt, 8, 1, f) == 1 && cnt == v.size() && fread(v.data(), 4, cnt, f) == cnt;
     if (ok && agz_trainer_set_param(t, i, v.data(), v.size()) != AGZ_OK) { fclose(f); return AGZ_E_HIP; }
   }
+  if (ok && v2) {
+    agz_solver_conf sc;
+    ok = fread(&sc, sizeof(sc), 1, f) == 1 && solver_conf_valid(&sc) && sc.momentum != 0.f;
+    if (ok && agz_trainer_set_solver(t, &sc) != AGZ_OK) { fclose(f); return AGZ_E_HIP; }
+    for (int i = 0; ok && i < (int)t->prefs.size(); i++) {
+      uint64_t cnt = 0;
+      std::vector<float> v(pref_size(t->prefs[i]));
+      ok = fread(&cnt, 8, 1, f) == 1 && cnt == v.size() && fread(v.data(), 4, cnt, f) == cnt;
+      if (ok && agz_trainer_set_velocity(t, i, v.data(), v.size()) != AGZ_OK) { fclose(f); return AGZ_E_HIP; }
+    }
+  }
   fclose(f);
   AGZ_REQUIRE(ok, AGZ_E_INVALID, "agz_trainer_load: %s is truncated or mismatched", path);
+  if (!v2) return agz_trainer_reset_solver(t);   // a file without velocity: v := 0, the options stay
   return AGZ_OK;
 }
 

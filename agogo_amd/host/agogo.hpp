@@ -87,6 +87,13 @@ struct Trainable {
   Trainable& operator=(const Trainable&) = delete;
   void Init(uint64_t seed) { agz::check(agz_trainer_init_random(h, seed), "Dual.Init"); }
   void SetComputeMode(int mode) { agz::check(agz_trainer_set_compute_mode(h, mode), "compute mode"); }  // AGZ_COMPUTE_BF16X3: faster fwd/dgrad
+  // the options of the solver dual.Train constructs (meta.go:20: NewVanillaSolver -> WithL2Reg / WithClip / NewMomentum); all 0 = vanilla
+  void SetSolver(float momentum, float l2reg = 0.f, float clip = 0.f) {
+    agz_solver_conf sc{momentum, l2reg, clip, 0};
+    agz::check(agz_trainer_set_solver(h, &sc), "solver options");
+  }
+  agz_solver_conf Solver() const { agz_solver_conf sc{}; agz::check(agz_trainer_get_solver(h, &sc), "solver options"); return sc; }
+  void ResetSolver() { agz::check(agz_trainer_reset_solver(h), "solver reset"); }   // velocity := 0
   // dual.Infer (meta.go:125-162): copy row 0 of every learnable into an inference net
   void SwitchToInference(Dual& inf) const { agz::check(agz_trainer_export(h, inf.h), "SwitchToInference"); }
   // AZ.Save / AZ.Load (agogo.go:175-209) of the learning side, full batch-shaped learnables
@@ -210,6 +217,9 @@ struct Config {
   // (default), AGZ_COMPUTE_BF16X3, AGZ_COMPUTE_WINO (training then uses BF16X3), AGZ_COMPUTE_WINO_H2 / AGZ_COMPUTE_AUTO (the measured mode;
   // training takes the trainer's AGZ_COMPUTE_WINO_H2)
   int ComputeMode = AGZ_COMPUTE_F32_MFMA;
+  // build extension: the options of the solver dual.Train builds (agz_trainer_set_solver); all 0 (default) = the reference's vanilla solver.
+  // Applied to A, B and every newB.
+  agz_solver_conf Solver = {0.f, 0.f, 0.f, 0};
   // test hooks (not in the reference): inferencers of the self-play games once the dummy is no longer in use, and of the evaluation
   // games — AGZ_INF_NET plays the networks as the reference does; the synthetic kinds make an epoch's games independent of fp32 rounding
   // in a network evaluation (tests/test_learn_parity_gpu.py compares the epoch log with oracle/learn.hpp)
@@ -246,9 +256,12 @@ struct AZ {
   AZ(agz::Ctx& c, GameSpec g, const Config& cf, uint64_t seed_ = 1337) : ctx(c), game(g), conf(cf), seed(seed_) {  // agogo.go:41-72
     if (!cf.NNConf.IsValid()) throw agz::Error("NNConf is not valid. Unable to proceed");
     if (!cf.MCTSConf.IsValid()) throw agz::Error("MCTSConf is not valid. Unable to proceed");
-    A.reset(new dual::Trainable(ctx, cf.NNConf)); A->Init(seed * 3 + 1);
-    B.reset(new dual::Trainable(ctx, cf.NNConf)); B->Init(seed * 3 + 2);
+    A.reset(new dual::Trainable(ctx, cf.NNConf)); A->Init(seed * 3 + 1); applySolver(*A);
+    B.reset(new dual::Trainable(ctx, cf.NNConf)); B->Init(seed * 3 + 2); applySolver(*B);
     infA.reset(new dual::Dual(ctx, cf.NNConf)); infB.reset(new dual::Dual(ctx, cf.NNConf));
+  }
+  void applySolver(dual::Trainable& t) const {   // (the default options leave the trainer untouched: no call)
+    if (conf.Solver.momentum != 0.f || conf.Solver.l2reg != 0.f || conf.Solver.clip != 0.f) t.SetSolver(conf.Solver.momentum, conf.Solver.l2reg, conf.Solver.clip);
   }
   // AZ.Learn (agogo.go:100-172)
   void Learn(int iters, int episodes, int nniters, int arenaGames) {
@@ -297,6 +310,7 @@ struct AZ {
       b_id = next_id++;
       B.reset(new dual::Trainable(ctx, conf.NNConf));                      // newB: a fresh random net (arena.go:205-224)
       B->Init(seed * 3 + 100 + epoch);
+      applySolver(*B);
       useDummy = useDummy && false;                                        // the dummy is only used in epoch 0 (agogo.go:83-87)
       log.push_back(st);
     }

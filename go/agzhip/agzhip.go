@@ -819,6 +819,42 @@ func (t *Trainer) SetComputeMode(mode int) error {
 	return lastErr(C.agz_trainer_set_compute_mode(t.h, C.int(mode)))
 }
 
+// SolverConf holds the options of the solver dual.Train constructs (dualnet/meta.go:20): gorgonia.NewMomentum's momentum, WithL2Reg,
+// WithClip.  The zero value is the reference's vanilla solver.
+type SolverConf struct {
+	Momentum, L2Reg, Clip float32
+}
+
+// SetSolver sets the solver options (agz_trainer_set_solver): per element L2, then clip, then v = Momentum*v - lr*g, w += v.
+func (t *Trainer) SetSolver(c SolverConf) error {
+	defer t.ctx.enter()()
+	cc := C.agz_solver_conf{momentum: C.float(c.Momentum), l2reg: C.float(c.L2Reg), clip: C.float(c.Clip)}
+	return lastErr(C.agz_trainer_set_solver(t.h, &cc))
+}
+
+// Solver returns the options in force.
+func (t *Trainer) Solver() (SolverConf, error) {
+	defer t.ctx.enter()()
+	var cc C.agz_solver_conf
+	err := lastErr(C.agz_trainer_get_solver(t.h, &cc))
+	return SolverConf{Momentum: float32(cc.momentum), L2Reg: float32(cc.l2reg), Clip: float32(cc.clip)}, err
+}
+
+// Velocity reads the momentum state of learnable i (Model() order, the shape of the learnable) into data; zeros while Momentum is 0.
+func (t *Trainer) Velocity(i int, data []float32) error {
+	defer t.ctx.enter()()
+	return lastErr(C.agz_trainer_get_velocity(t.h, C.int(i), (*C.float)(unsafe.Pointer(&data[0])), C.size_t(len(data))))
+}
+
+// SetVelocity writes the momentum state of learnable i.
+func (t *Trainer) SetVelocity(i int, data []float32) error {
+	defer t.ctx.enter()()
+	return lastErr(C.agz_trainer_set_velocity(t.h, C.int(i), (*C.float)(unsafe.Pointer(&data[0])), C.size_t(len(data))))
+}
+
+// ResetSolver zeroes the velocity and keeps the options.
+func (t *Trainer) ResetSolver() error { defer t.ctx.enter()(); return lastErr(C.agz_trainer_reset_solver(t.h)) }
+
 func (t *Trainer) Export(n *Net) error { defer t.ctx.enter()(); return lastErr(C.agz_trainer_export(t.h, n.h)) }
 
 func (t *Trainer) Close() error { defer t.ctx.enter()(); C.agz_trainer_destroy(t.h); t.h = nil; return nil }

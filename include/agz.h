@@ -199,7 +199,8 @@ int agz_trainer_init_random(agz_trainer* t, uint64_t seed);
  * gradients are NOT materialised: agz_trainer_get_grad / agz_trainer_grads_dev then return what an earlier forward_backward left there
  * for those tensors (zeros on a fresh trainer); filter and head gradients are current.  To read every gradient, run
  * agz_trainer_forward_backward (or agz_trainer_batch with lr = 0).  A step that fails part-way may have stepped some layers' gamma / beta
- * already: treat the trainer's parameters as undefined after an error (reload a checkpoint, agz_trainer_load). */
+ * already: treat the trainer's parameters — and, with a momentum set (agz_trainer_set_solver), the velocity, which the same kernel steps —
+ * as undefined after an error (reload a checkpoint, agz_trainer_load). */
 int agz_trainer_batch(agz_trainer* t, const float* planes, const float* pi, const float* v, float lr, float* cost);
 /* Split form for data-parallel training: forward_backward fills the flat gradient buffer; all-reduce it over RCCL
  * (agz_trainer_grads_dev gives the device pointer: ONE collective per step); apply does w -= lr*grad_scale*grad. */
@@ -208,6 +209,35 @@ int agz_trainer_forward_backward(agz_trainer* t, const float* planes, const floa
 int agz_trainer_forward_backward_dev(agz_trainer* t, const float* planes_dev, const float* pi_dev, const float* v_dev, float* cost);
 int agz_trainer_apply(agz_trainer* t, float lr, float grad_scale);
 int agz_trainer_grads_dev(agz_trainer* t, float** dev_ptr, size_t* n_floats);
+/* Solver options: what the reference chooses in its solver constructor, gorgonia.NewVanillaSolver(WithLearnRate(0.1)) (dualnet/meta.go:20)
+ * — WithL2Reg, WithClip, or NewMomentum in its place.  Per learnable element, in fp32, with the per-call lr and grad_scale
+ * (grad_scale is 1 on the fused path of agz_trainer_batch / agz_train / agz_train_dev):
+ *     g1 = grad_scale * g
+ *     g2 = g1 + l2reg * w                  (only if l2reg != 0)
+ *     g3 = min(max(g2, -clip), clip)       (only if clip > 0)
+ *     momentum == 0:  w = w + (-lr) * g3
+ *     momentum != 0:  v = momentum * v + (-lr) * g3;  w = w + v        (v starts at 0)
+ * L2 and clip apply to every learnable of Model(), the batch-shaped gamma / beta and FC biases included.  All options 0 (the default)
+ * is the vanilla step: every path then runs exactly the kernels it ran before these options existed.  With any option set,
+ * agz_trainer_batch still steps the tower's gamma / beta (and their velocity) inside the BatchNorm backward kernel; agz_trainer_apply
+ * honours grad_scale on the two-pass and data-parallel paths.  The velocity is one device buffer the size of the learnables (7.7 GB at
+ * 19x19 / K = 256 / 20 blocks / batch 256), allocated and zeroed when a momentum != 0 is first set (AGZ_E_NOMEM if it does not fit; the
+ * options are then unchanged) and released when the momentum is set back to 0.  Note that a momentum step with lr = 0 still moves the
+ * parameters by momentum * v: read gradients with agz_trainer_forward_backward.  Sharded trainers: every rank sets the same options
+ * (a local call); a rank holds the velocity rows of the batch-shaped tensors it owns, the shared tensors' velocity is computed
+ * identically on every rank from the summed gradient — no further collective.
+ * set: AGZ_E_INVALID unless 0 <= momentum < 1, l2reg >= 0, clip >= 0, all finite and reserved == 0; the options stay as they were.
+ * Tests: tests/test_solver_cpu.py (ABI), tests/test_solver_gpu.py (recurrence, fused = two-pass, oracle trajectory, validation). */
+typedef struct agz_solver_conf { float momentum, l2reg, clip; int32_t reserved; } agz_solver_conf; /* 16 bytes, reserved = 0 */
+int agz_trainer_set_solver(agz_trainer* t, const agz_solver_conf* conf);
+int agz_trainer_get_solver(const agz_trainer* t, agz_solver_conf* out);
+/* The velocity of learnable `index` (gorgonia's Momentum keeps one `cached` value per learnable; the reference never reads it): the
+ * indexing, shapes and — on a sharded trainer — row ownership of agz_trainer_get_param.  get: zeros while no velocity exists
+ * (momentum 0).  set: AGZ_E_STATE while no velocity exists.  Tests: test_solver_gpu.py (recurrence, checkpoint), test_solver_sharded_gpu.py. */
+int agz_trainer_get_velocity(const agz_trainer* t, int index, float* host, size_t n);
+int agz_trainer_set_velocity(agz_trainer* t, int index, const float* host, size_t n);
+/* velocity := 0, the options kept (a fresh gorgonia solver with the same options).  Test: test_solver_gpu.py (checkpoint case). */
+int agz_trainer_reset_solver(agz_trainer* t);
 /* Arithmetic of training's three GEMMs (forward convolution, data gradient, weight gradient): AGZ_COMPUTE_F32_MFMA (default),
  * AGZ_COMPUTE_BF16X3 (all three on the bf16 pipe; weights re-split on the device every step) or AGZ_COMPUTE_WINO_H2 (fp16x2
  * products throughout: forward = the DIRECT 3x3 convolution with fp16 hi/lo operands, weight image split on the device every step;
@@ -229,7 +259,10 @@ int agz_train(agz_trainer* t, float* Xs, float* policies, float* values, int bat
 int agz_train_dev(agz_trainer* t, const float* Xs_dev, const float* policies_dev, const float* values_dev, int batches,
                   int iterations, uint64_t seed, float* last_cost);
 /* Checkpoint of the trainable network in its full batch-shaped form (AZ.Save/AZ.Load agogo.go:175-209 for the side that
- * keeps learning; gob is Go-only, the format is documented in train.hip). load: the file must match the configuration. */
+ * keeps learning; gob is Go-only, the format is documented in train.hip). load: the file must match the configuration.
+ * A trainer with a velocity (momentum != 0) writes the "AGZTRN02" form — the AGZTRN01 payload, agz_solver_conf, every tensor's
+ * velocity — and any other trainer the AGZTRN01 file it always wrote.  load reads both: 02 sets the options and velocity it carries,
+ * 01 zeroes the velocity and keeps the options; a truncated 02 file is rejected (AGZ_E_INVALID) before anything is changed. */
 int agz_trainer_save(const agz_trainer* t, const char* path);
 int agz_trainer_load(agz_trainer* t, const char* path);
 /* dual.Infer's copy loop (dualnet/meta.go:141-146): row 0 of every learnable -> the inference net; commits it. */
