@@ -231,6 +231,8 @@ def lib():
     sig("agz_net_set_wino_h2_gemm", i32, vp, i32)
     sig("agz_net_min_same_batch", i32, vp, i32, i32, C.POINTER(C.c_int))
     sig("agz_arena_set_prep_compact", i32, vp, i32)
+    sig("agz_arena_set_split", i32, vp, i32)
+    sig("agz_arena_split_steps", i32, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int))
     sig("agz_trainer_set_dma_forward", i32, vp, i32)
     sig("agz_arena_last_prep_batch", i32, vp, C.POINTER(C.c_int), C.POINTER(C.c_int))
     sig("agz_arena_debug_counter", i32, vp, i32, C.POINTER(C.c_int64))
@@ -739,6 +741,17 @@ class Arena:
     def set_prep_compact(self, on=True):
         """agz_debug.h: prepareRoot's forward on the packed batch of the roots that need it (default) or on the whole arena batch"""
         _check(lib().agz_arena_set_prep_compact(self.h, int(on)), "agz_arena_set_prep_compact")
+
+    def set_split(self, mode=1):
+        """agz_debug.h: 0 = the joined simulation step, 1 = the two half-arenas as pipelines of their own (default where it applies),
+        2 = the same with the skew between the halves held by events"""
+        _check(lib().agz_arena_set_split(self.h, int(mode)), "agz_arena_set_split")
+
+    def split_steps(self):
+        """agz_debug.h: (simulation steps on the split path, on the joined path, whether the last one was split)"""
+        s_, j_, l_ = C.c_int64(0), C.c_int64(0), C.c_int(0)
+        _check(lib().agz_arena_split_steps(self.h, C.byref(s_), C.byref(j_), C.byref(l_)), "agz_arena_split_steps")
+        return s_.value, j_.value, bool(l_.value)
 
     def last_prep_batch(self):
         """agz_debug.h: (boards the last begin_move's forward ran on, roots it had to evaluate)"""

@@ -41,16 +41,35 @@ struct ProfClass {
 
 }  // namespace agz
 
+struct agz_ctx;
+namespace agz {
+// The context's main queue.  After an arena's split step (engine.hip) work is pending on the second queue with no event towards this one
+// ("open" context); whoever takes the main queue to enqueue on it or to wait for it gets it JOINED first (agz_ctx::join: one event
+// record + one wait, only when open), so every entry point of the library that uses ctx->stream sees all earlier work — by
+// construction, not by a list of call sites.  The split step itself takes the queue through raw().
+struct MainStream {
+  agz_ctx* c = nullptr;
+  hipStream_t s = nullptr;
+  inline operator hipStream_t() const;
+  hipStream_t raw() const { return s; }
+};
+}  // namespace agz
+
 struct agz_ctx {
   int device = 0;
-  hipStream_t stream = nullptr;
+  agz::MainStream stream;
   hipStream_t stream2 = nullptr;          // second queue: the other half of a batch (agz_net two-stream tower), created on first use
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  hipEvent_t ev_mid[2] = {nullptr, nullptr};   // split step: queue q has passed the middle of its tower
+  bool open2 = false;                     // work is pending on stream2 that stream has not waited for (split step)
+  const void* open_owner = nullptr;       // the arena whose split steps opened the context
+  int ensure_stream2();                   // second queue and its events, on first use
+  void join();                            // stream waits for everything enqueued on stream2 so far; closes the context
   bool prof_on = false;
   unsigned prof_mask = ~0u;   // classes that record events while prof_on (agz_ctx_prof_enable)
   int prof_stride[AGZ_PROF_NCLASS];   // every prof_stride[k]-th launch of class k is bracketed (agz_ctx_prof_set_stride; default 1)
   int64_t prof_seen[AGZ_PROF_NCLASS] = {};
-  agz_ctx() { for (auto& v : prof_stride) v = 1; }
+  agz_ctx() { for (auto& v : prof_stride) v = 1; stream.c = this; }
   agz::ProfClass prof[AGZ_PROF_NCLASS];
   int prof_open = 0;   // scopes begun and not yet ended (classes nest: a layer scope around its kernels' scopes)
   int num_cus = 256;
@@ -63,6 +82,8 @@ struct agz_ctx {
   void prof_end(int klass);
   int prof_collect();  // sync + fold recorded pairs into totals
 };
+
+inline agz::MainStream::operator hipStream_t() const { if (c->open2) c->join(); return s; }
 
 namespace agz {
 struct ProfScope {

@@ -1235,13 +1235,13 @@ static void wino_h2_launch(agz_ctx* ctx, WinoH2Args& h, bool wide, hipStream_t s
   h.fuse_prev = (h.fuse_prev && fuse) ? 1 : 0;
   h.amax_self = const_cast<unsigned*>(h.amax_in);
   {
-    ProfScopeOn ps(ctx, AGZ_PROF_WINO_IN, st == ctx->stream);
+    ProfScopeOn ps(ctx, AGZ_PROF_WINO_IN, st == ctx->stream.raw());
     const size_t n_in = (size_t)a.T * (a.C / 2);
     if (tm == 5) hipLaunchKernelGGL(wino_in_h2_kernel<5>, dim3((unsigned)((n_in + 255) / 256)), dim3(256), 0, st, h);
     else hipLaunchKernelGGL(wino_in_h2_kernel<4>, dim3((unsigned)((n_in + 255) / 256)), dim3(256), 0, st, h);
   }
   {
-    ProfScopeOn ps(ctx, AGZ_PROF_WINO_GEMM, st == ctx->stream);
+    ProfScopeOn ps(ctx, AGZ_PROF_WINO_GEMM, st == ctx->stream.raw());
     const dim3 gw(h.npos * a.n_mtiles * ceil_div(a.Ntot, 256)), gn(h.npos * a.n_mtiles * a.n_ntiles);
     // the unrolled form with the A operand fetched two steps ahead, instantiated per K extent (32-channel steps); other extents take
     // the plain single-prefetch kernels
@@ -1264,7 +1264,7 @@ static void wino_h2_launch(agz_ctx* ctx, WinoH2Args& h, bool wide, hipStream_t s
     else hipLaunchKernelGGL(wino_gemm_h2_kernel, gn, dim3(256), 0, st, h);
   }
   {
-    ProfScopeOn ps(ctx, AGZ_PROF_WINO_OUT, st == ctx->stream);
+    ProfScopeOn ps(ctx, AGZ_PROF_WINO_OUT, st == ctx->stream.raw());
     const size_t n_out = (size_t)a.T * a.Cout_p;
     if (h.raw) {
       const unsigned bd = a.Ntot % 256 == 0 ? 256u : (a.Ntot % 128 == 0 ? 128u : (a.Ntot % 64 == 0 ? 64u : 32u));

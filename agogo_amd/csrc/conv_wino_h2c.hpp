@@ -927,7 +927,7 @@ static void wino_h2c_geometry(WinoH2Args& h) {
 static void wino_h2c_in(agz_ctx* ctx, WinoH2Args& h, hipStream_t st) {     // block 0: x -> V2c (exact range: h.amax_in, fuse_prev = 0)
   wino_h2c_geometry(h);
   h.fuse_prev = 0; h.amax_self = const_cast<unsigned*>(h.amax_in);
-  ProfScopeOn ps(ctx, AGZ_PROF_WINO_IN, st == ctx->stream);
+  ProfScopeOn ps(ctx, AGZ_PROF_WINO_IN, st == ctx->stream.raw());
   const size_t n_in = (size_t)h.w.T * (h.w.C / 2);
   if (h.tm == 5) hipLaunchKernelGGL(wino_in_h2_kernel<5>, dim3((unsigned)((n_in + 255) / 256)), dim3(256), 0, st, h);
   else hipLaunchKernelGGL(wino_in_h2_kernel<4>, dim3((unsigned)((n_in + 255) / 256)), dim3(256), 0, st, h);
@@ -935,7 +935,7 @@ static void wino_h2c_in(agz_ctx* ctx, WinoH2Args& h, hipStream_t st) {     // bl
 constexpr int WINO_H2_GEMM_DEFAULT = 1;   // 1: wino_gemm_h2g_kernel (three workgroups per CU), 2: wino_gemm_h2p_kernel (persistent)
 static void wino_h2c_gemm(agz_ctx* ctx, WinoH2Args& h, hipStream_t st) {
   wino_h2c_geometry(h);
-  ProfScopeOn ps(ctx, AGZ_PROF_WINO_GEMM, st == ctx->stream);
+  ProfScopeOn ps(ctx, AGZ_PROF_WINO_GEMM, st == ctx->stream.raw());
   const dim3 g(h.npos * h.w.n_mtiles * (h.w.Ntot >> 8));
   // (the DMA form addresses V and U2c through buffer descriptors: 31-bit byte offsets)
   const bool dma_ok = wino_h2_rows(h.npos, (size_t)h.w.T) * h.w.C * 4 < ((size_t)1 << 31) && (size_t)h.npos * h.w.C * h.w.Ntot * 4 < ((size_t)1 << 31);
@@ -972,7 +972,7 @@ static void wino_h2c_gemm(agz_ctx* ctx, WinoH2Args& h, hipStream_t st) {
 // variant 4: the pipelined kernel (default); 1: the plain one (A/B hook; also the last block, whose y goes to HBM, and tensors past 2 GB)
 static void wino_h2c_oi(agz_ctx* ctx, WinoH2Args& h, bool last, hipStream_t st, int variant = 4) {
   wino_h2c_geometry(h);
-  ProfScopeOn ps(ctx, AGZ_PROF_WINO_OUT, st == ctx->stream);
+  ProfScopeOn ps(ctx, AGZ_PROF_WINO_OUT, st == ctx->stream.raw());
   const WinoArgs& a = h.w;
   const dim3 g((unsigned)ceil_div(a.T, 16), (unsigned)(a.C >> 5));
   const size_t shm = last ? 0 : (size_t)(16 / a.TPB) * a.H * a.W * 32 * sizeof(float);

@@ -30,6 +30,23 @@ void agz_ctx::prof_end(int klass) {
   if (prof_open > 0) prof_open--;
   if (p.used >= 4096 && prof_open == 0) prof_collect();  // bound the number of live events (never while an outer scope is open)
 }
+int agz_ctx::ensure_stream2() {
+  if (stream2) return AGZ_OK;
+  AGZ_HIP_TRY(hipStreamCreateWithFlags(&stream2, hipStreamNonBlocking));
+  AGZ_HIP_TRY(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
+  AGZ_HIP_TRY(hipEventCreateWithFlags(&ev_join, hipEventDisableTiming));
+  for (auto& e : ev_mid) AGZ_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  return AGZ_OK;
+}
+void agz_ctx::join() {
+  if (!open2) return;
+  open2 = false; open_owner = nullptr;
+  // (an event that cannot be recorded or waited for: fall back to waiting on the host — never lose the ordering)
+  if (hipEventRecord(ev_join, stream2) != hipSuccess || hipStreamWaitEvent(stream.s, ev_join, 0) != hipSuccess) {
+    (void)hipGetLastError();
+    hipStreamSynchronize(stream2);
+  }
+}
 int agz_ctx::prof_collect() {
   AGZ_HIP_TRY(hipStreamSynchronize(stream));
   for (int k = 0; k < AGZ_PROF_NCLASS; k++) {
@@ -67,7 +84,7 @@ int agz_ctx_create(int device, agz_ctx** out) {
   hipDeviceProp_t prop;
   AGZ_HIP_TRY(hipGetDeviceProperties(&prop, device));
   c->num_cus = prop.multiProcessorCount;
-  AGZ_HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+  AGZ_HIP_TRY(hipStreamCreateWithFlags(&c->stream.s, hipStreamNonBlocking));
   *out = c;
   return AGZ_OK;
 }
@@ -92,17 +109,20 @@ int agz_host_free(agz_ctx* ctx, void* p) {
 void agz_ctx_destroy(agz_ctx* c) {
   if (!c) return;
   hipSetDevice(c->device);
+  c->join();
   hipStreamSynchronize(c->stream);
   for (auto& p : c->prof)
     for (auto& pr : p.pairs) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
   if (c->stream2) hipStreamDestroy(c->stream2);
   if (c->ev_fork) hipEventDestroy(c->ev_fork);
   if (c->ev_join) hipEventDestroy(c->ev_join);
+  for (auto e : c->ev_mid) if (e) hipEventDestroy(e);
   hipStreamDestroy(c->stream);
   delete c;
 }
 int agz_ctx_sync(agz_ctx* c) {
   AGZ_REQUIRE(c, AGZ_E_INVALID, "ctx is NULL");
+  c->join();   // (an open context: the second queue's work too)
   AGZ_HIP_TRY(hipStreamSynchronize(c->stream));
   return AGZ_OK;
 }

@@ -446,9 +446,10 @@ __global__ __launch_bounds__(64) void k_begin_move(Dev d, GameCfg c, MctsCfg mc)
 
 // pipeline() descent: mcts/search.go:209-257 up to (and excluding) the network call.
 // prep != 0 runs prepareRoot (search.go:392-408) instead: the root itself is the leaf if it is expandable.
-__global__ __launch_bounds__(64) void k_select(Dev d, GameCfg c, MctsCfg mc, float* act_in0, float* act_in1, int prep, int nl) {
+// g0: first game of this launch (the split step runs the two halves of an arena as launches of their own)
+__global__ __launch_bounds__(64) void k_select(Dev d, GameCfg c, MctsCfg mc, float* act_in0, float* act_in1, int prep, int nl, int g0) {
   __shared__ Sh s;
-  int g = blockIdx.x, lane = threadIdx.x;
+  int g = g0 + blockIdx.x, lane = threadIdx.x;
   const size_t q0 = (size_t)g * d.V;
   if (d.ended[g]) { if (lane < nl) d.leaf_kind[q0 + lane] = LEAF_NONE; return; }
   int agent = agent_of(d, g);
@@ -779,9 +780,9 @@ __global__ __launch_bounds__(64) void k_expand_commit(Dev d, GameCfg c, MctsCfg 
 }
 
 // expandAndSimulate (mcts/search.go:259-339) after the network call + the BACKPROPAGATE half of pipeline().
-__global__ __launch_bounds__(64) void k_expand(Dev d, GameCfg c, MctsCfg mc, InfDesc inf, int prep, int nl) {
+__global__ __launch_bounds__(64) void k_expand(Dev d, GameCfg c, MctsCfg mc, InfDesc inf, int prep, int nl, int g0) {
   __shared__ Sh s;
-  int g = blockIdx.x, lane = threadIdx.x;
+  int g = g0 + blockIdx.x, lane = threadIdx.x;
   if (d.ended[g]) return;
   int agent = agent_of(d, g);
   int t = agent * d.G + g;
@@ -1374,6 +1375,12 @@ struct agz_arena {
   int cb_run(int nl);                // leaves of callback agents -> host function -> d_policy / d_value
   int update_slots();
   int nn_step(int prep, int nl = 1);   // nl lanes per tree in this round (<= d.V)
+  // Split step (agz_arena_set_split, agz_debug.h): games [0, G/2) and [G/2, G) as two pipelines on the context's two queues
+  int split_mode = 1;                  // 0: joined step; 1: split, free-running after the first step's skew; 2: split, skew held by two events per step
+  bool last_step_split = false;
+  int64_t split_steps = 0, joined_steps = 0;
+  bool split_eligible() const;
+  int nn_step_split();
 };
 
 // prepareRoot evaluates only roots without children (search.go:392-408): with tree reuse a minority of an arena's games (19x19, 512
@@ -1579,7 +1586,62 @@ int agz_arena::update_slots() {
   return AGZ_OK;
 }
 
+// ---- the split step --------------------------------------------------------------------------------------------------------------
+// Games never interact inside a search, and the network keeps boards apart (agz_net::forward_half), so the two halves of an arena need not
+// meet once per step:
+//     ctx->stream : k_select(games 0..h-1) -> net half 0 -> k_expand(games 0..h-1)
+//     ctx->stream2: k_select(games h..G-1) -> net half 1 -> k_expand(games h..G-1)
+// with NO event between the queues: one half's select / input layer / heads / expand (latency-bound, a fraction of the chip) run under the
+// other half's tower.  Shared writes are integer atomics on d.counters only.  Two chains that start together stay in phase and hide
+// nothing, so the first split step after a join holds queue 1 back until queue 0 has passed the middle of its tower; split_mode 2 keeps
+// that skew with two events per step (never a full join).  The context stays "open" afterwards: whoever next takes ctx->stream gets it
+// joined (common.hpp).  Everything else — lane rounds, two nets, callbacks, prepareRoot, other towers, one queue, profiled steps —
+// takes the joined step below.
+bool agz_arena::split_eligible() const {
+  if (split_mode == 0 || d.V != 1 || d.cb_mask != 0 || (G & 1)) return false;
+  if (inf_kind[0] != AGZ_INF_NET || inf_kind[1] != AGZ_INF_NET || net[0] != net[1] || !net[0]) return false;
+  if (ctx->prof_on && (ctx->prof_mask & ((1u << AGZ_PROF_NCLASS) - 1u) & ~(1u << AGZ_PROF_MOVE))) return false;   // the step's classes are timed on the joined path
+  return net[0]->half_ok(G);
+}
+
+int agz_arena::nn_step_split() {
+  agz_net* n = net[0];
+  const int h = G / 2;
+  int r = ctx->ensure_stream2();
+  if (r != AGZ_OK) return r;
+  if (ctx->open2 && ctx->open_owner != this) ctx->join();   // another arena's halves are in flight on the same net
+  r = n->forward_half_reserve(G);                           // (joins and synchronises if it has to grow anything)
+  if (r != AGZ_OK) return r;
+  InfDesc inf{};
+  for (int a = 0; a < 2; a++) {
+    inf.kind[a] = AGZ_INF_NET; inf.policy[a] = d_policy[0]; inf.value[a] = d_value[0];
+    inf.dummy_player[a] = 0; inf.policy_len[a] = n->conf.ActionSpace;
+  }
+  const bool first = !ctx->open2;
+  const bool hold = split_mode == 2;
+  hipStream_t q[2] = {first ? (hipStream_t)ctx->stream : ctx->stream.raw(), ctx->stream2};
+  float* act = n->d_act_in;
+  for (int k = 0; k < 2; k++) {
+    // queue 1 starts behind queue 0's mid-tower event (first step: that also orders it behind everything enqueued on ctx->stream so far);
+    // held skew: queue 0 in turn starts behind queue 1's mid-tower event of the previous step
+    if (k == 1 && (first || hold)) AGZ_HIP_TRY(hipStreamWaitEvent(q[1], ctx->ev_mid[0], 0));
+    if (k == 0 && hold && !first) AGZ_HIP_TRY(hipStreamWaitEvent(q[0], ctx->ev_mid[1], 0));
+    hipLaunchKernelGGL(k_select, dim3(h), dim3(64), 0, q[k], d, gc, mc, act, act, 0, 1, k * h);
+    r = n->forward_half(G, k, q[k], d_policy[0], d_value[0], (k == 0 && (first || hold)) || (k == 1 && hold) ? ctx->ev_mid[k] : nullptr);
+    if (r != AGZ_OK) { ctx->open2 = true; ctx->open_owner = this; ctx->join(); return r; }
+    hipLaunchKernelGGL(k_expand, dim3(h), dim3(64), 0, q[k], d, gc, mc, inf, 0, 1, k * h);
+    if (k == 0) { ctx->open2 = true; ctx->open_owner = this; }   // from here on work is pending on the second queue
+  }
+  AGZ_HIP_TRY(hipGetLastError());
+  return AGZ_OK;
+}
+
 int agz_arena::nn_step(int prep, int nl) {
+  if (prep == 0 && nl == 1 && split_eligible()) {
+    last_step_split = true; split_steps++;
+    return nn_step_split();
+  }
+  if (!prep) { last_step_split = false; joined_steps++; }
   // select -> network -> expand, all asynchronous on the ctx stream
   float* act0 = nullptr; float* act1 = nullptr;
   const size_t slot_elems = (size_t)(gc.m + 2) * (gc.n + 2) * 32;
@@ -1593,7 +1655,7 @@ int agz_arena::nn_step(int prep, int nl) {
       hipLaunchKernelGGL(k_select_paths, dim3(G), dim3(64), 0, ctx->stream, d, gc, mc, prep, nl);
       hipLaunchKernelGGL(k_leaf, dim3(G * nl), dim3(64), 0, ctx->stream, d, gc, mc, act0, act1, prep, nl);
     } else {
-      hipLaunchKernelGGL(k_select, dim3(G), dim3(64), 0, ctx->stream, d, gc, mc, act0, act1, prep, nl);
+      hipLaunchKernelGGL(k_select, dim3(G), dim3(64), 0, ctx->stream, d, gc, mc, act0, act1, prep, nl, 0);
     }
   }
   // prepareRoot evaluates the network only for a root without children (search.go:392-408).  With tree reuse that is the rare
@@ -1666,7 +1728,7 @@ int agz_arena::nn_step(int prep, int nl) {
       hipLaunchKernelGGL(k_expand_prep, dim3(G * nl), dim3(64), 0, ctx->stream, dx, gc, mc, inf, nl);
       hipLaunchKernelGGL(k_expand_commit, dim3(G), dim3(64), 0, ctx->stream, dx, gc, mc, prep, nl);
     } else {
-      hipLaunchKernelGGL(k_expand, dim3(G), dim3(64), 0, ctx->stream, dx, gc, mc, inf, prep, nl);
+      hipLaunchKernelGGL(k_expand, dim3(G), dim3(64), 0, ctx->stream, dx, gc, mc, inf, prep, nl, 0);
     }
   }
   AGZ_HIP_TRY(hipGetLastError());
@@ -1938,6 +2000,21 @@ int agz_arena_set_prep_compact(agz_arena* a, int on) {
 int agz_arena_last_prep_batch(agz_arena* a, int* boards, int* roots) {
   AGZ_REQUIRE(a && boards && roots, AGZ_E_INVALID, "agz_arena_last_prep_batch: NULL argument");
   *boards = a->last_prep_batch; *roots = a->last_prep_roots;
+  return AGZ_OK;
+}
+
+int agz_arena_set_split(agz_arena* a, int mode) {
+  AGZ_REQUIRE(a && mode >= 0 && mode <= 2, AGZ_E_INVALID, "agz_arena_set_split: mode 0 (joined), 1 (split) or 2 (split, skew held)");
+  a->ctx->join();
+  a->split_mode = mode;
+  return AGZ_OK;
+}
+
+int agz_arena_split_steps(agz_arena* a, int64_t* split, int64_t* joined, int* last_split) {
+  AGZ_REQUIRE(a, AGZ_E_INVALID, "arena is NULL");
+  if (split) *split = a->split_steps;
+  if (joined) *joined = a->joined_steps;
+  if (last_split) *last_split = a->last_step_split ? 1 : 0;
   return AGZ_OK;
 }
 

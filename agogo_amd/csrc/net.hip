@@ -1165,6 +1165,174 @@ int agz_net::min_same_batch(int n, int G) const {
   return G;
 }
 
+// ---- the AGZ_COMPUTE_WINO_H2 tower's board chunks, scratch and one block of one chunk: shared by forward_packed (all chunks, fork / join
+// around the tower) and forward_half (one chunk's whole forward on one queue)
+agz_net::H2Tower agz_net::wino_h2_tower(int B) const {
+  H2Tower t{};
+  t.npos = (wino_tm + 2) * (wino_tm + 2);
+  t.tpb = ceil_div(H, wino_tm) * ceil_div(W, wino_tm);
+  // Board chunks and queues (agz_net_set_tower_queues; AGZ_WINO_H2_CHUNK = boards per chunk, AGZ_WINO_H2_QUEUES = 1 | 2 override):
+  // chunk i runs its block chain on queue i % queues with that queue's scratch — chains of different boards are independent
+  // (per-board ranges, bit-identical results), so one half-batch's HBM-bound transform kernels run under the other's GEMM and
+  // fill the GEMM's last partial round of workgroups: 15.39 -> 14.51 ms per 512-board pass (round 2), the default from 256 boards.
+  static const int chunk_env = [] { const char* e = getenv("AGZ_WINO_H2_CHUNK"); return e ? atoi(e) : 0; }();
+  static const int queues_env = [] { const char* e = getenv("AGZ_WINO_H2_QUEUES"); return e ? atoi(e) : 0; }();
+  const int queues_want = queues_env > 0 ? queues_env : (tower_queues > 0 ? tower_queues : (B >= 256 ? 2 : 1));
+  // 32-bit byte offsets into V: npos * (tiles rounded up to 128 + pad) * Kp * 4 < 2^32
+  const int chunk_max = (int)std::min<size_t>((size_t)B, ((((size_t)1 << 32) - 1) / ((size_t)t.npos * Kp * 4) - 127) / t.tpb);
+  t.chunk = chunk_env >= 1 ? std::min(chunk_env, chunk_max) : chunk_max;
+  t.ns = (queues_want == 2 && B >= 64) ? 2 : 1;
+  if (t.ns == 2 && t.chunk >= B) t.chunk = (B + 1) / 2;
+  t.v_elems = wino_h2_rows(t.npos, (size_t)t.chunk * t.tpb) * Kp; t.m_elems = 2 * t.v_elems;
+  // Chained form (conv_wino_h2c.hpp; AGZ_WINO_H2_FORM = 0 keeps the three-kernel block): output transform of block l and input
+  // transform of block l+1 in one kernel, y never leaves the chip between blocks.  V2(l+1) of a chunk lives in scratch from one
+  // block to the next, so every CHUNK keeps its own scratch there (the three-kernel block: every queue)
+  static const int form_env = [] { const char* e = getenv("AGZ_WINO_H2_FORM"); return e ? atoi(e) : -1; }();
+  t.form_want = wino_form >= 0 ? wino_form : form_env;
+  t.chained = t.form_want != 0 && (int)d_u2c_dual.size() == conf.SharedLayers && agz::wino_h2c_ok(H, W, wino_tm, Kp);
+  t.n_scr = t.chained ? ceil_div(B, t.chunk) : t.ns;
+  // per-wave maxima of the output kernel: every chunk of boards keeps its own region from one block to the next (the next
+  // block's input transform reduces them), one word per tile and 64 channels
+  t.wm_board = t.chained ? (size_t)t.tpb * (Kp >> 5) * 2 : (size_t)t.tpb * (Kp >> 6);   // (chained: two arrays, ping-pong)
+  return t;
+}
+
+int agz_net::wino_h2_reserve(int B, const H2Tower& t, bool* amax_moved) {
+  if (t.v_elems * t.n_scr > wino_v_cap) {
+    AGZ_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (ctx->stream2) AGZ_HIP_TRY(hipStreamSynchronize(ctx->stream2));
+    if (d_wV) hipFree(d_wV);
+    if (d_wM) hipFree(d_wM);
+    d_wV = d_wM = nullptr; wino_chunk_cap = 0;
+    AGZ_HIP_TRY(hipMalloc(&d_wV, t.v_elems * t.n_scr * sizeof(float)));
+    AGZ_HIP_TRY(hipMalloc(&d_wM, t.m_elems * t.n_scr * sizeof(float)));
+    wino_v_cap = t.v_elems * t.n_scr; wino_chunk_cap = 0;   // (the fp32-V Winograd path sizes by boards: force its re-allocation)
+  }
+  // per-board ranges [blocks+1][B], then the per-wave maxima of the output kernel [boards][wm_board] (as floats)
+  const size_t need_amax = (size_t)(conf.SharedLayers + 1) * B + t.wm_board * B;
+  if (need_amax > amax_cap) {
+    AGZ_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (ctx->stream2) AGZ_HIP_TRY(hipStreamSynchronize(ctx->stream2));
+    if (d_amax) hipFree(d_amax);
+    d_amax = nullptr; amax_cap = 0;
+    AGZ_HIP_TRY(hipMalloc(&d_amax, need_amax * sizeof(unsigned)));
+    amax_cap = need_amax;
+    if (amax_moved) *amax_moved = true;
+  }
+  return AGZ_OK;
+}
+
+// block l of the chained tower for boards [b0, b0 + chunk) of a B-board batch (chunk index ci: its own scratch) on queue st
+void agz_net::wino_h2c_block(int l, int B, int b0, int ci, const H2Tower& t, hipStream_t st, float* cur, float* nxt) {
+  const size_t wmb = (size_t)t.tpb * (Kp >> 5);
+  const bool last = l + 1 == conf.SharedLayers;
+  float* d_wave_max = reinterpret_cast<float*>(d_amax + (size_t)(conf.SharedLayers + 1) * B);
+  WinoH2Args hh{};
+  WinoArgs& wa = hh.w;
+  wa.x = cur + (size_t)b0 * Hp * Wp * Kp; wa.y = nxt + (size_t)b0 * Hp * Wp * Kp;   // x: block 0 only; y: the last block only
+  wa.V = d_wV + (size_t)ci * t.v_elems; wa.Mb = d_wM + (size_t)ci * t.m_elems; wa.ep = d_ep_h2[l];   // (the chunk's own scratch)
+  wa.B = std::min(t.chunk, B - b0); wa.H = H; wa.W = W; wa.Hp = Hp; wa.Wp = Wp; wa.C = Kp; wa.Cout_p = Kp; wa.Ntot = 2 * Kp;
+  hh.U2c = d_u2c_dual[l]; hh.w_unscale = 1.f; hh.tm = wino_tm;
+  hh.amax_in = d_amax + (size_t)l * B + b0;                                       // the range word V2(l) was written with
+  hh.amax_next = last ? nullptr : d_amax + (size_t)(l + 1) * B + b0;
+  hh.amax_true = l == 0 ? reinterpret_cast<const float*>(d_amax + b0) : nullptr;  // block 0: board_amax_kernel's exact word
+  hh.wm_prev = d_wave_max + ((size_t)((l + 1) & 1) * B + b0) * wmb;
+  hh.wm_out = d_wave_max + ((size_t)(l & 1) * B + b0) * wmb;
+  hh.g1 = wino_g1[l]; hh.g0 = wino_g0[l];
+  {   // which GEMM kernel / store policy: agz_net_set_wino_h2_gemm, else AGZ_WINO_H2_GEMM (1 | 2, + 64 = round 4's stores), else the default
+    // (the environment reaches the two product kernels only: 1 | 2, + 64; anything else — 2 + 16 * mode are the persistent kernel's
+    //  timing-only decomposition instances, wrong results by design, agz_debug.h — is ignored with one line on stderr)
+    static const int gemm_env = [] {
+      const char* e = getenv("AGZ_WINO_H2_GEMM");
+      const int v = e ? atoi(e) : 0;
+      if (v == 0 || (((v & 63) == 1 || (v & 63) == 2) && (v >> 6) <= 1)) return v;
+      fprintf(stderr, "libagz: AGZ_WINO_H2_GEMM=%s ignored (want 1 or 2, optionally + 64)\n", e);
+      return 0;
+    }();
+    const int gv = wino_gemm > 0 ? wino_gemm : gemm_env;
+    hh.gemm_variant = gv & 63; hh.temporal_stores = (gv >> 6) & 1;
+  }
+  if (l == 0) agz::wino_h2c_in(ctx, hh, st);
+  agz::wino_h2c_gemm(ctx, hh, st);
+  agz::wino_h2c_oi(ctx, hh, last, st, t.form_want == 1 ? 1 : 4);   // (A/B hook: form 1 = the plain out->in kernel)
+}
+
+// the spread heads (heads_feat / heads_fc / heads_out) for boards [b0, b0 + nb) of a B-board batch on queue st; h describes the whole batch
+void agz_net::heads_spread_range(agz::HeadArgs h, bool nb4, int B, int b0, int nb, hipStream_t st) {
+  h.x += (size_t)b0 * Hp * Wp * Kp;
+  h.feat = d_hs + (size_t)b0 * 3 * HW; h.cols = d_hs + (size_t)B * 3 * HW + (size_t)b0 * (conf.ActionSpace + conf.FC);
+  h.policy += (size_t)b0 * conf.ActionSpace; h.value += b0;
+  hipLaunchKernelGGL(heads_feat_kernel, dim3(ceil_div(HW, 4), nb), dim3(256), 0, st, h);
+  if (nb4)
+    hipLaunchKernelGGL(heads_fc_nb_kernel<4>, dim3(ceil_div(conf.ActionSpace + conf.FC, 64), ceil_div(nb, 4)), dim3(1024), 0, st, h, nb);
+  else
+    hipLaunchKernelGGL(heads_fc_kernel, dim3(ceil_div(conf.ActionSpace + conf.FC, 64), nb), dim3(1024), 0, st, h);
+  hipLaunchKernelGGL(heads_out_kernel, dim3(nb), dim3(256), 0, st, h);
+}
+
+// ---- one half of a batch as a pipeline of its own --------------------------------------------------------------------------------
+// The boards of a batch never meet inside the network (per-board ranges, per-chunk scratch), so when forward_packed(B) would run the
+// chained AGZ_COMPUTE_WINO_H2 tower as exactly two chunks of B / 2 boards, each chunk's WHOLE forward — input convolution, tower, heads —
+// can be enqueued on one queue without any event towards the other.  half_ok says whether forward_packed(B) is that case (and a batch of
+// B / 2 takes the same kernels: per board the results are those of the whole batch, bit for bit).
+bool agz_net::half_ok(int B) const {
+  if (!committed || B < 2 || B > max_batch || (B & 1) || (B / 2) % 4 != 0 || cfg != 0 || conf.SharedLayers <= 0) return false;
+  if (min_same_batch(B / 2, B) != B / 2) return false;
+  const FwdPlan plan = fwd_plan(B);
+  int mode = compute_mode;
+  if (mode == AGZ_COMPUTE_AUTO) mode = !d_u2_dual.empty() ? AGZ_COMPUTE_WINO_H2 : AGZ_COMPUTE_BF16X3;
+  if (!plan.split_ok || plan.latency || mode != AGZ_COMPUTE_WINO_H2 || !plan.heads_spread || !plan.heads_nb) return false;
+  if ((int)d_u2_dual.size() != conf.SharedLayers || !d_ep_init_h2) return false;
+  if (!d_w3_init || Kp % 128 != 0 || (size_t)B * Hp * Wp * Fp * sizeof(float) >= ((size_t)1 << 32)) return false;   // the bf16x3 input convolution
+  const H2Tower t = wino_h2_tower(B);
+  return t.chained && t.ns == 2 && t.chunk * 2 == B;
+}
+
+// boards [half * B / 2, (half + 1) * B / 2) of the batch in d_act_in: everything on queue st; mid != nullptr is recorded on st after the
+// kernels of block SharedLayers / 2.  Scratch for the whole batch must exist already: forward_half_reserve(B), which may synchronise.
+int agz_net::forward_half_reserve(int B) {
+  const H2Tower t = wino_h2_tower(B);
+  int r = wino_h2_reserve(B, t, nullptr);
+  if (r != AGZ_OK) return r;
+  const size_t need = (size_t)B * (3 * HW + conf.ActionSpace + conf.FC);
+  if (need > hs_cap) {
+    AGZ_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (d_hs) hipFree(d_hs);
+    d_hs = nullptr; hs_cap = 0;
+    AGZ_HIP_TRY(hipMalloc(&d_hs, need * sizeof(float)));
+    hs_cap = need;
+  }
+  return AGZ_OK;
+}
+
+int agz_net::forward_half(int B, int half, hipStream_t st, float* policy_dev, float* value_dev, hipEvent_t mid) {
+  const int nb = B / 2, b0 = half * nb;
+  const FwdPlan plan = fwd_plan(B);
+  const H2Tower t = wino_h2_tower(B);
+  // input convolution (bf16x3 products) with the tower's per-board input ranges out of its epilogue
+  ConvArgs a{};
+  a.M = nb * HW; a.HW = HW; a.W = W; a.Wp = Wp; a.HpWp = Hp * Wp;
+  a.x = d_act_in + (size_t)b0 * Hp * Wp * Fp; a.w = d_w_init; a.ep = d_ep_init_h2; a.y = d_actA + (size_t)b0 * Hp * Wp * Kp;
+  a.Cin_p = Fp; a.Cout_p = Kp; a.Ntot = Kp;
+  a.n_ntiles = ceil_div(a.Ntot, 128); a.n_mtiles = ceil_div(a.M, 128);
+  a.splits = 1; a.per = 0; a.ws = nullptr; a.raw = 0;
+  AGZ_HIP_TRY(hipMemsetAsync(d_amax + b0, 0, (size_t)nb * sizeof(unsigned), st));
+  a.amax_out = d_amax + b0;
+  hipLaunchKernelGGL((conv3x3_x3_kernel<false>), dim3(a.n_mtiles * a.n_ntiles), dim3(256), 0, st, a, d_w3_init);
+  const int L = conf.SharedLayers;
+  for (int l = 0; l < L; l++) {
+    wino_h2c_block(l, B, b0, half, t, st, d_actA, d_actB);
+    if (mid && l == L / 2) AGZ_HIP_TRY(hipEventRecord(mid, st));
+  }
+  HeadArgs h{};
+  h.x = d_actB; h.conv = d_head_conv; h.bn = d_head_bn; h.Wp = d_Wp; h.bp = d_bp; h.W1 = d_W1; h.b1 = d_b1; h.W2 = d_W2;
+  h.b2 = d_b2; h.policy = policy_dev; h.value = value_dev;
+  h.H = H; h.W = W; h.HW = HW; h.Wp_ = Wp; h.HpWp = Hp * Wp; h.Kp = Kp; h.A = conf.ActionSpace; h.FC = conf.FC;
+  heads_spread_range(h, plan.heads_nb, B, b0, nb, st);
+  AGZ_HIP_TRY(hipGetLastError());
+  return AGZ_OK;
+}
+
 int agz_net::forward_packed(int B, float* policy_dev, float* value_dev) {
   AGZ_REQUIRE(committed, AGZ_E_STATE, "agz_net: infer before agz_net_commit");
   AGZ_REQUIRE(B >= 1 && B <= max_batch, AGZ_E_INVALID, "agz_net: batch %d exceeds allocated %d", B, max_batch);
@@ -1245,104 +1413,31 @@ int agz_net::forward_packed(int B, float* policy_dev, float* value_dev) {
     AGZ_REQUIRE((int)d_u2_dual.size() == conf.SharedLayers, AGZ_E_STATE, "agz_net: Winograd fp16x2 weights not built");
     // GEMM form (measured on G19/B=512, profiles/r02/wino_h2_gemm_variants.log): 128x256 tile with the A operand fetched two
     // steps ahead 0.385 ms, 128x128 0.40 ms, the plain single-prefetch kernels 0.47-0.50 ms.
-    const int npos = (wino_tm + 2) * (wino_tm + 2);
-    const int tpb = ceil_div(H, wino_tm) * ceil_div(W, wino_tm);
-    // ... and the 128-column tile when the 256-column grid would leave CUs without a workgroup (a lane round of 16 boards: 196
-    // against 392 workgroups, 0.0747 -> 0.0726 ms per block, p50 move 0.250 -> 0.241 s)
     const bool wide = plan.wino_wide;
-    // Board chunks and queues (agz_net_set_tower_queues; AGZ_WINO_H2_CHUNK = boards per chunk, AGZ_WINO_H2_QUEUES = 1 | 2 override):
-    // chunk i runs its block chain on queue i % queues with that queue's scratch — chains of different boards are independent
-    // (per-board ranges, bit-identical results), so one half-batch's HBM-bound transform kernels run under the other's GEMM and
-    // fill the GEMM's last partial round of workgroups: 15.39 -> 14.51 ms per 512-board pass (round 2), the default from 256 boards.
-    static const int chunk_env = [] { const char* e = getenv("AGZ_WINO_H2_CHUNK"); return e ? atoi(e) : 0; }();
-    static const int queues_env = [] { const char* e = getenv("AGZ_WINO_H2_QUEUES"); return e ? atoi(e) : 0; }();
-    const int queues_want = queues_env > 0 ? queues_env : (tower_queues > 0 ? tower_queues : (B >= 256 ? 2 : 1));
-    // 32-bit byte offsets into V: npos * (tiles rounded up to 128 + pad) * Kp * 4 < 2^32
-    const int chunk_max = (int)std::min<size_t>((size_t)B, ((((size_t)1 << 32) - 1) / ((size_t)npos * Kp * 4) - 127) / tpb);
-    int chunk = chunk_env >= 1 ? std::min(chunk_env, chunk_max) : chunk_max;
-    const int ns = (queues_want == 2 && B >= 64) ? 2 : 1;
-    if (ns == 2 && chunk >= B) chunk = (B + 1) / 2;
-    const size_t v_elems = wino_h2_rows(npos, (size_t)chunk * tpb) * Kp, m_elems = 2 * v_elems;
-    // Chained form (conv_wino_h2c.hpp; AGZ_WINO_H2_FORM = 0 keeps the three-kernel block): output transform of block l and input
-    // transform of block l+1 in one kernel, y never leaves the chip between blocks.  V2(l+1) of a chunk lives in scratch from one
-    // block to the next, so every CHUNK keeps its own scratch there (the three-kernel block: every queue)
-    static const int form_env = [] { const char* e = getenv("AGZ_WINO_H2_FORM"); return e ? atoi(e) : -1; }();
-    const int form_want = wino_form >= 0 ? wino_form : form_env;
-    const bool chained = form_want != 0 && (int)d_u2c_dual.size() == conf.SharedLayers && agz::wino_h2c_ok(H, W, wino_tm, Kp);
-    const int n_scr = chained ? ceil_div(B, chunk) : ns;
-    if (v_elems * n_scr > wino_v_cap) {
-      AGZ_HIP_TRY(hipStreamSynchronize(ctx->stream));
-      if (ctx->stream2) AGZ_HIP_TRY(hipStreamSynchronize(ctx->stream2));
-      if (d_wV) hipFree(d_wV);
-      if (d_wM) hipFree(d_wM);
-      d_wV = d_wM = nullptr; wino_chunk_cap = 0;
-      AGZ_HIP_TRY(hipMalloc(&d_wV, v_elems * n_scr * sizeof(float)));
-      AGZ_HIP_TRY(hipMalloc(&d_wM, m_elems * n_scr * sizeof(float)));
-      wino_v_cap = v_elems * n_scr; wino_chunk_cap = 0;   // (the fp32-V Winograd path sizes by boards: force its re-allocation)
-    }
-    // per-board ranges [blocks+1][B], then the per-wave maxima of the output kernel [queues][chunk tiles][Kp/64] (as floats)
-    // per-wave maxima of the output kernel: every chunk of boards keeps its own region from one block to the next (the next
-    // block's input transform reduces them), one word per tile and 64 channels
-    const size_t wm_board = chained ? (size_t)tpb * (Kp >> 5) * 2 : (size_t)tpb * (Kp >> 6);   // (chained: two arrays, ping-pong)
-    const size_t need_amax = (size_t)(conf.SharedLayers + 1) * B + wm_board * B;
-    if (need_amax > amax_cap) {
-      AGZ_HIP_TRY(hipStreamSynchronize(ctx->stream));
-      if (ctx->stream2) AGZ_HIP_TRY(hipStreamSynchronize(ctx->stream2));
-      if (d_amax) hipFree(d_amax);
-      d_amax = nullptr; amax_cap = 0;
-      AGZ_HIP_TRY(hipMalloc(&d_amax, need_amax * sizeof(unsigned)));
-      amax_cap = need_amax;
-      amax0_done = false;   // (the words just written went with the old buffer)
+    const H2Tower tw = wino_h2_tower(B);
+    const int chunk = tw.chunk, ns = tw.ns;
+    const size_t v_elems = tw.v_elems, m_elems = tw.m_elems, wm_board = tw.wm_board;
+    const bool chained = tw.chained;
+    {
+      bool amax_moved = false;
+      const int rr = wino_h2_reserve(B, tw, &amax_moved);
+      if (rr != AGZ_OK) return rr;
+      if (amax_moved) amax0_done = false;   // (the words just written went with the old buffer)
     }
     float* d_wave_max = reinterpret_cast<float*>(d_amax + (size_t)(conf.SharedLayers + 1) * B);
     if (!amax0_done)
       hipLaunchKernelGGL(board_amax_kernel, dim3(B), dim3(256), 0, ctx->stream, cur, d_amax, HW, W, Wp, Hp * Wp, Kp, (const float*)nullptr);   // (pre-scaled input)
     if (ns == 2) {
-      if (!ctx->stream2) {
-        AGZ_HIP_TRY(hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking));
-        AGZ_HIP_TRY(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
-        AGZ_HIP_TRY(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
-      }
+      { const int rs = ctx->ensure_stream2(); if (rs != AGZ_OK) return rs; }
       AGZ_HIP_TRY(hipEventRecord(ctx->ev_fork, ctx->stream));
       AGZ_HIP_TRY(hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
     }
     for (int l = 0; chained && l < conf.SharedLayers; l++) {
       ProfScope ps(ctx, AGZ_PROF_CONV);
       int ci = 0;
-      const size_t wmb = (size_t)tpb * (Kp >> 5);
       const bool last = l + 1 == conf.SharedLayers;
-      for (int b0 = 0; b0 < B; b0 += chunk, ci++) {
-        const int q = ci % ns;
-        hipStream_t st = q ? ctx->stream2 : ctx->stream;
-        WinoH2Args hh{};
-        WinoArgs& wa = hh.w;
-        wa.x = cur + (size_t)b0 * Hp * Wp * Kp; wa.y = nxt + (size_t)b0 * Hp * Wp * Kp;   // x: block 0 only; y: the last block only
-        wa.V = d_wV + (size_t)ci * v_elems; wa.Mb = d_wM + (size_t)ci * m_elems; wa.ep = d_ep_h2[l];   // (the chunk's own scratch)
-        wa.B = std::min(chunk, B - b0); wa.H = H; wa.W = W; wa.Hp = Hp; wa.Wp = Wp; wa.C = Kp; wa.Cout_p = Kp; wa.Ntot = 2 * Kp;
-        hh.U2c = d_u2c_dual[l]; hh.w_unscale = 1.f; hh.tm = wino_tm;
-        hh.amax_in = d_amax + (size_t)l * B + b0;                                       // the range word V2(l) was written with
-        hh.amax_next = last ? nullptr : d_amax + (size_t)(l + 1) * B + b0;
-        hh.amax_true = l == 0 ? reinterpret_cast<const float*>(d_amax + b0) : nullptr;  // block 0: board_amax_kernel's exact word
-        hh.wm_prev = d_wave_max + ((size_t)((l + 1) & 1) * B + b0) * wmb;
-        hh.wm_out = d_wave_max + ((size_t)(l & 1) * B + b0) * wmb;
-        hh.g1 = wino_g1[l]; hh.g0 = wino_g0[l];
-        {   // which GEMM kernel / store policy: agz_net_set_wino_h2_gemm, else AGZ_WINO_H2_GEMM (1 | 2, + 64 = round 4's stores), else the default
-          // (the environment reaches the two product kernels only: 1 | 2, + 64; anything else — 2 + 16 * mode are the persistent kernel's
-          //  timing-only decomposition instances, wrong results by design, agz_debug.h — is ignored with one line on stderr)
-          static const int gemm_env = [] {
-            const char* e = getenv("AGZ_WINO_H2_GEMM");
-            const int v = e ? atoi(e) : 0;
-            if (v == 0 || (((v & 63) == 1 || (v & 63) == 2) && (v >> 6) <= 1)) return v;
-            fprintf(stderr, "libagz: AGZ_WINO_H2_GEMM=%s ignored (want 1 or 2, optionally + 64)\n", e);
-            return 0;
-          }();
-          const int gv = wino_gemm > 0 ? wino_gemm : gemm_env;
-          hh.gemm_variant = gv & 63; hh.temporal_stores = (gv >> 6) & 1;
-        }
-        if (l == 0) agz::wino_h2c_in(ctx, hh, st);
-        agz::wino_h2c_gemm(ctx, hh, st);
-        agz::wino_h2c_oi(ctx, hh, last, st, form_want == 1 ? 1 : 4);   // (A/B hook: form 1 = the plain out->in kernel)
-      }
+      for (int b0 = 0; b0 < B; b0 += chunk, ci++)
+        wino_h2c_block(l, B, b0, ci, tw, (ci % ns) ? ctx->stream2 : (hipStream_t)ctx->stream, cur, nxt);
       if (last) std::swap(cur, nxt);
     }
     for (int l = 0; !chained && l < conf.SharedLayers; l++) {
@@ -1470,13 +1565,7 @@ int agz_net::forward_packed(int B, float* policy_dev, float* value_dev) {
         AGZ_HIP_TRY(hipMalloc(&d_hs, need * sizeof(float)));
         hs_cap = need;
       }
-      h.feat = d_hs; h.cols = d_hs + (size_t)B * 3 * HW;
-      hipLaunchKernelGGL(heads_feat_kernel, dim3(ceil_div(HW, 4), B), dim3(256), 0, ctx->stream, h);
-      if (plan.heads_nb)
-        hipLaunchKernelGGL(heads_fc_nb_kernel<4>, dim3(ceil_div(conf.ActionSpace + conf.FC, 64), ceil_div(B, 4)), dim3(1024), 0, ctx->stream, h, B);
-      else
-        hipLaunchKernelGGL(heads_fc_kernel, dim3(ceil_div(conf.ActionSpace + conf.FC, 64), B), dim3(1024), 0, ctx->stream, h);
-      hipLaunchKernelGGL(heads_out_kernel, dim3(B), dim3(256), 0, ctx->stream, h);
+      heads_spread_range(h, plan.heads_nb, B, 0, B, ctx->stream);
     } else {
       hipLaunchKernelGGL(heads_kernel, dim3(B), dim3(256), smem, ctx->stream, h);
     }

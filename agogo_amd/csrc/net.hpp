@@ -47,6 +47,7 @@ int conv3x3_raw_wino_h2(agz_ctx* ctx, const float* x, const float* w, float* y, 
                         const unsigned* ranges = nullptr, const RawWeights* pre = nullptr);
 bool conv3x3_raw_wino_h2_fits(int B, int H, int W, int Cin_p, int Cout_p);
 void wino_raw_scratch_free(WinoRawScratch* sc);
+struct HeadArgs;
 }  // namespace agz
 
 struct agz_net {
@@ -145,4 +146,16 @@ struct agz_net {
   struct FwdPlan { bool half_init, half_dual, small, forced_split, latency, heads_spread, split_ok, heads_nb, wino_wide; };
   FwdPlan fwd_plan(int B) const;
   int min_same_batch(int n, int G) const;   // smallest batch >= n (from n, 16, 32, ... ) with the plan of G; G if there is none
+  // The AGZ_COMPUTE_WINO_H2 tower of a B-board batch: board chunks, queues, scratch sizes (net.hip)
+  struct H2Tower { int npos, tpb, chunk, ns, n_scr, form_want; bool chained; size_t v_elems, m_elems, wm_board; };
+  H2Tower wino_h2_tower(int B) const;
+  int wino_h2_reserve(int B, const H2Tower& t, bool* amax_moved);   // grows d_wV / d_wM / d_amax (synchronises both queues when it does)
+  void wino_h2c_block(int l, int B, int b0, int ci, const H2Tower& t, hipStream_t st, float* cur, float* nxt);
+  void heads_spread_range(agz::HeadArgs h, bool nb4, int B, int b0, int nb, hipStream_t st);
+  // One half of a B-board batch as a pipeline of its own on one queue (the arena's split step, engine.hip): half_ok(B) when
+  // forward_packed(B) is the chained tower in two chunks of B / 2 and a B / 2 batch runs the same kernels; forward_half_reserve(B)
+  // before the first forward_half(B, ...) (it may synchronise); forward_half enqueues on st only and records `mid` after block L / 2.
+  bool half_ok(int B) const;
+  int forward_half_reserve(int B);
+  int forward_half(int B, int half, hipStream_t st, float* policy_dev, float* value_dev, hipEvent_t mid);
 };

@@ -64,6 +64,17 @@ int agz_net_set_wino_h2_gemm(agz_net* net, int variant);
 int agz_arena_set_prep_compact(agz_arena* arena, int on);
 int agz_arena_last_prep_batch(agz_arena* arena, int* boards, int* roots);
 
+/* The split step.  Where one shared AGZ_INF_NET net runs the chained AGZ_COMPUTE_WINO_H2 tower of the arena's batch as two half-batch chains
+ * on two queues (agz_net_set_tower_queues != 1, from 256 games by default), no lane rounds, no callback inferencer and no kernel-class
+ * timer other than AGZ_PROF_MOVE running, agz_arena_simulate enqueues games [0, G/2) and [G/2, G) as two pipelines — select, network half,
+ * expand — on the context's two queues with no event between them, the second half a tower behind the first; the queues are joined
+ * lazily, by whatever next uses the context's stream (agz_ctx_sync included).  Results are bit-identical to the joined step.
+ * mode 0: the joined step everywhere (A/B and parity hook); 1 (default): split, free-running after the first step's skew; 2: split with
+ * the skew held by two events per step.  agz_arena_split_steps: simulation steps that took the split / the joined path since the arena
+ * was created, and whether the last one was split (any pointer may be NULL). */
+int agz_arena_set_split(agz_arena* arena, int mode);
+int agz_arena_split_steps(agz_arena* arena, int64_t* split, int64_t* joined, int* last_split);
+
 /* A/B hook: the trainer's AGZ_COMPUTE_WINO_H2 forward convolutions through the DMA GEMM on pre-split fp16 planes (k_conv_h2dma, train.hip;
  * default on) or through conv3x3_h2w_kernel, which splits the fp32 activations while staging them (bit 0 of `on` clear).  Bit 2 of `on` set:
  * the first form of the head kernels (one thread per output, three-block BatchNorm passes) instead of the second (default).  Bit 3 set: every
