@@ -183,6 +183,14 @@ def lib():
     sig("agz_trainer_get_velocity", i32, vp, i32, pf, C.c_size_t)
     sig("agz_trainer_set_velocity", i32, vp, i32, pf, C.c_size_t)
     sig("agz_trainer_reset_solver", i32, vp)
+    sig("agz_trainer_set_bn_tracking", i32, vp, i32, C.c_float)
+    sig("agz_trainer_get_bn_tracking", i32, vp, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_double))
+    sig("agz_trainer_num_bn", i32, vp)
+    sig("agz_trainer_get_bn_stats", i32, vp, i32, pf, pf, C.c_size_t)
+    sig("agz_trainer_set_bn_stats", i32, vp, i32, pf, pf, C.c_size_t, C.c_double)
+    sig("agz_trainer_reset_bn_stats", i32, vp)
+    sig("agz_trainer_eval", i32, vp, pf, pf, pf, pf)
+    sig("agz_trainer_eval_dev", i32, vp, vp, vp, vp, pf)
     sig("agz_trainer_set_compute_mode", i32, vp, i32)
     sig("agz_train", i32, vp, pf, pf, pf, i32, i32, u64, pf)
     sig("agz_trainer_export", i32, vp, vp)
@@ -574,6 +582,57 @@ class Trainer:
     def reset_solver(self):
         """velocity := 0, the options kept"""
         _check(lib().agz_trainer_reset_solver(self.h), "agz_trainer_reset_solver")
+
+    def set_bn_tracking(self, on=True, momentum=0.997):
+        """running BatchNorm statistics (agz_trainer_set_bn_tracking): every training forward adds its batch mean / biased variance to
+        accumulators that decay by `momentum`; off keeps the state"""
+        _check(lib().agz_trainer_set_bn_tracking(self.h, int(on), momentum), "agz_trainer_set_bn_tracking")
+
+    def get_bn_tracking(self):
+        """{"on", "momentum", "weight"}: weight = N, the accumulated weight of the estimates (0: none yet)"""
+        on, m, w = C.c_int(0), C.c_float(0), C.c_double(0)
+        _check(lib().agz_trainer_get_bn_tracking(self.h, C.byref(on), C.byref(m), C.byref(w)), "agz_trainer_get_bn_tracking")
+        return {"on": bool(on.value), "momentum": m.value, "weight": w.value}
+
+    def num_bn(self):
+        return lib().agz_trainer_num_bn(self.h)
+
+    def bn_channels(self, bi):
+        """channels of BatchNorm op bi (the order of Net.set_bn_stats): K for the tower's ops, 2 / 1 for the policy / value head"""
+        n = self.num_bn()
+        return self.conf.K if bi < n - 2 else (2 if bi == n - 2 else 1)
+
+    def get_bn_stats(self, bi):
+        """(mean, var) estimates of op bi; AGZ_E_STATE while nothing has been tracked"""
+        m = np.zeros(self.bn_channels(bi), np.float32)
+        v = np.zeros_like(m)
+        _check(lib().agz_trainer_get_bn_stats(self.h, bi, _pf(m), _pf(v), m.size), "agz_trainer_get_bn_stats")
+        return m, v
+
+    def set_bn_stats(self, bi, mean, var, weight=1.0):
+        m = np.ascontiguousarray(mean, np.float32).ravel()
+        v = np.ascontiguousarray(var, np.float32).ravel()
+        assert m.size == v.size
+        _check(lib().agz_trainer_set_bn_stats(self.h, bi, _pf(m), _pf(v), m.size, weight), "agz_trainer_set_bn_stats")
+
+    def reset_bn_stats(self):
+        """S = 0, N = 0; the tracking setting is kept"""
+        _check(lib().agz_trainer_reset_bn_stats(self.h), "agz_trainer_reset_bn_stats")
+
+    def eval(self, planes, pi, v):
+        """the forward pass alone under the tracked statistics (a held-out loss); nothing of the trainer changes"""
+        x = np.ascontiguousarray(planes, np.float32)
+        p = np.ascontiguousarray(pi, np.float32)
+        vv = np.ascontiguousarray(v, np.float32)
+        c = C.c_float(0)
+        _check(lib().agz_trainer_eval(self.h, _pf(x), _pf(p), _pf(vv), C.byref(c)), "agz_trainer_eval")
+        return c.value
+
+    def eval_dev(self, planes_ptr, pi_ptr, v_ptr, want_cost=True):
+        c = C.c_float(0)
+        _check(lib().agz_trainer_eval_dev(self.h, C.c_void_p(planes_ptr), C.c_void_p(pi_ptr), C.c_void_p(v_ptr),
+                                          C.byref(c) if want_cost else None), "agz_trainer_eval_dev")
+        return c.value if want_cost else None
 
     def set_compute_mode(self, mode):
         _check(lib().agz_trainer_set_compute_mode(self.h, int(mode)), "agz_trainer_set_compute_mode")

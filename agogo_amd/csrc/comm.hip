@@ -263,8 +263,8 @@ static int sh_agree(agz_comm* c, const Rccl* R, int r, const char* what) {
 
 // End of a sharded step, whatever happened on this rank: the gathers the forward / backward pass did not reach are entered (a collective one
 // rank never enters is a hang for its peers), then the shared gradients are summed and the status word is exchanged.
-static int sh_step(agz_comm* c, agz_trainer* t, const Rccl* R, const std::function<int()>& body) {
-  agz_trainer_exchange_plan(t, c->sh_plan);
+static int sh_step(agz_comm* c, agz_trainer* t, const Rccl* R, const std::function<int()>& body, bool eval = false) {
+  agz_trainer_exchange_plan(t, c->sh_plan, eval);
   c->sh_issued = 0;
   int r = body();
   if (r == AGZ_OK && c->sh_issued != c->sh_plan.size()) {
@@ -280,6 +280,11 @@ static int sh_step(agz_comm* c, agz_trainer* t, const Rccl* R, const std::functi
     coll = R->AllGather(xg + (size_t)c->rank * cnt, xg, cnt, ncclFloat64, c->comm, s) == ncclSuccess && coll;
   }
   c->sh_plan.clear();
+  if (eval) {   // agz_trainer_eval: forward only, the cost words were the one exchange
+    if (r != AGZ_OK) set_error("%s", first.c_str());
+    else if (!coll) { set_error("sharded eval: a collective failed (fatal for the process group)"); r = AGZ_E_HIP; }
+    return sh_agree(c, R, r, "sharded eval");
+  }
   float* g = nullptr;
   size_t n_all = 0;
   std::vector<std::pair<size_t, size_t>> shared;
@@ -320,6 +325,7 @@ int agz_trainer_create_sharded(agz_comm* c, const agz_net_conf* conf, agz_traine
     return AGZ_OK;
   };
   h.step = [c, t, R](const std::function<int()>& body) -> int { return sh_step(c, t, R, body); };
+  h.eval_step = [c, t, R](const std::function<int()>& body) -> int { return sh_step(c, t, R, body, true); };
   h.allgather_bytes = [c, R](const void* send, void* recv, size_t bytes) -> int {
     AGZ_NCCL_TRY(R->AllGather(send, recv, bytes, ncclUint8, c->comm, c->ctx->stream));
     AGZ_HIP_TRY(hipStreamSynchronize(c->ctx->stream));

@@ -19,6 +19,9 @@ struct agz_shard_hooks {
   // gathers body did not reach, sums the shared tensors' gradients over the ranks and exchanges the one-word status.  Returns body's error
   // on the rank that failed and AGZ_E_PEER on the others.
   std::function<int(const std::function<int()>& body)> step;
+  // one collective forward-only pass (agz_trainer_eval): body, then the one gather of the cost words if body did not reach it, then the
+  // status word.  No gradient is summed.
+  std::function<int(const std::function<int()>& body)> eval_step;
   // all-gather of `bytes` from every rank into recv [n][bytes] (synchronous; agz_trainer_save)
   std::function<int(const void* send, void* recv, size_t bytes)> allgather_bytes;
   // broadcast of `bytes` from rank 0 (synchronous; agz_trainer_export)
@@ -31,7 +34,8 @@ struct agz_shard_hooks {
 int agz_trainer_bind_shard(agz_trainer* t, int rank, int n, agz_shard_hooks hooks);
 bool agz_trainer_is_sharded(const agz_trainer* t);
 // the element counts of the gathers one step issues, in issue order, and the buffer they land in ([n][largest count])
-void agz_trainer_exchange_plan(const agz_trainer* t, std::vector<size_t>& counts);
+// (eval: the plan of agz_trainer_eval's pass, the one gather of the cost words)
+void agz_trainer_exchange_plan(const agz_trainer* t, std::vector<size_t>& counts, bool eval = false);
 double* agz_trainer_gather_buf(agz_trainer* t);
 // (offset, count) of the shared tensors in the flat gradient buffer: every filter, the heads' 1x1 convolution, Wp, W1, W2
 void agz_trainer_shared_ranges(const agz_trainer* t, std::vector<std::pair<size_t, size_t>>& out);

@@ -72,11 +72,34 @@ __global__ void k_bn_sum(TGeo g, const float* __restrict__ z, int C, const float
     atomicAdd(&acc[c], s);
   }
 }
+// ---- running statistics (agz_trainer_set_bn_tracking; the `bn-running` row of DESIGN §2) -------------------------------------------------
+// The state of one finalize launch (a tower layer = one or two BatchNorm ops side by side, or the heads' 2 + 1 channels), all double:
+// st = S_mean[C] | S_var[C] | N[C / Kop], Kop = channels per op (channel c belongs to op c / Kop).  Every training forward adds the mean and
+// the biased variance it normalises with — the doubles the finalize kernels hold anyway — to accumulators that decay by lam, and N takes the
+// same recurrence with 1: S / N is then a weighted mean of the batches' statistics, exact from the first step (N = 1: the very values of
+// that forward).  TRACK is a template parameter of the finalize kernels: the <false> instantiation is the code that ran before the state
+// existed (BnTrack is then an unused kernel argument, as SolverDev is for k_bn_bwd1<false, false>).
+struct BnTrack { double* st; int C; int Kop; double lam; };
+__device__ __forceinline__ void bn_track_mean(const BnTrack& tr, int c, double mu) { tr.st[c] = tr.lam * tr.st[c] + mu; }
+__device__ __forceinline__ void bn_track_var(const BnTrack& tr, int c, double var) {   // (the last statistic of a forward: N steps with it)
+  tr.st[tr.C + c] = tr.lam * tr.st[tr.C + c] + var;
+  if (c % tr.Kop == 0) { double* n = tr.st + 2 * tr.C + c / tr.Kop; *n = tr.lam * *n + 1.0; }
+}
+// the estimates as a layer's mean / inv (agz_trainer_eval in place of the statistics kernels): inv is the finalize kernels' float expression
+__global__ void k_bn_from_running(BnTrack tr, float eps, float* __restrict__ mean, float* __restrict__ inv) {
+  int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= tr.C) return;
+  const double n = tr.st[2 * tr.C + c / tr.Kop];
+  mean[c] = (float)(tr.st[c] / n);
+  inv[c] = 1.0f / sqrtf((float)(tr.st[tr.C + c] / n) + eps);
+}
 // finalize: pass 0 -> mean = acc/m ; pass 1 -> inv = 1/sqrt(acc/m + eps).  Clears acc.
-__global__ void k_bn_fin(double* acc, int C, double m, float eps, float* mean, float* inv, int pass) {
+template <bool TRACK>
+__global__ void k_bn_fin(double* acc, int C, double m, float eps, float* mean, float* inv, int pass, BnTrack tr) {
   int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
   if (pass == 0) mean[c] = (float)(acc[c] / m); else inv[c] = 1.0f / sqrtf((float)(acc[c] / m) + eps);
+  if (TRACK) { if (pass == 0) bn_track_mean(tr, c, acc[c] / m); else bn_track_var(tr, c, acc[c] / m); }
   acc[c] = 0;
 }
 
@@ -118,7 +141,8 @@ __global__ __launch_bounds__(256) void k_bn_stats(TGeo g, const float* __restric
   }
   for (int c = tid; c < C; c += 256) { atomicAdd(&acc[c], red[0][c]); atomicAdd(&acc[1024 + c], red[1][c]); }
 }
-__global__ void k_bn_fin2(double* acc, int C, double m, float eps, float* mean, float* inv) {
+template <bool TRACK>
+__global__ void k_bn_fin2(double* acc, int C, double m, float eps, float* mean, float* inv, BnTrack tr) {
   int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
   const double mu = acc[c] / m;
@@ -126,6 +150,7 @@ __global__ void k_bn_fin2(double* acc, int C, double m, float eps, float* mean, 
   var = var > 0 ? var : 0;
   mean[c] = (float)mu;
   inv[c] = 1.0f / sqrtf((float)var + eps);
+  if (TRACK) { bn_track_mean(tr, c, mu); bn_track_var(tr, c, var); }
   acc[c] = 0; acc[1024 + c] = 0;
 }
 
@@ -134,8 +159,9 @@ __global__ void k_bn_fin2(double* acc, int C, double m, float eps, float* mean, 
 // same bits, run after run, whatever the collective's own reduction algorithm.  mode 2: the single-pass statistics (sums at [0, C), sums
 // of squares at [1024, 1024 + C)) -> mean, inv as k_bn_fin2; mode 0 / 1: the two passes of k_bn_fin.  m = rows of the GLOBAL batch.
 // With n = 1 the expressions are those of k_bn_fin2 / k_bn_fin on the same values.  Clears this rank's acc.
+template <bool TRACK>
 __global__ void k_bn_fin_ranks(const double* __restrict__ xg, int n, int stride, double* __restrict__ acc, int C, double m, float eps,
-                               float* __restrict__ mean, float* __restrict__ inv, int mode) {
+                               float* __restrict__ mean, float* __restrict__ inv, int mode, BnTrack tr) {
   int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
   double s = xg[c];
@@ -148,9 +174,11 @@ __global__ void k_bn_fin_ranks(const double* __restrict__ xg, int n, int stride,
     var = var > 0 ? var : 0;
     mean[c] = (float)mu;
     inv[c] = 1.0f / sqrtf((float)var + eps);
+    if (TRACK) { bn_track_mean(tr, c, mu); bn_track_var(tr, c, var); }   // (the global batch's values: the same bits on every rank)
     acc[c] = 0; acc[1024 + c] = 0;
   } else {
     if (mode == 0) mean[c] = (float)(s / m); else inv[c] = 1.0f / sqrtf((float)(s / m) + eps);
+    if (TRACK) { if (mode == 0) bn_track_mean(tr, c, s / m); else bn_track_var(tr, c, s / m); }
     acc[c] = 0;
   }
 }
@@ -1061,7 +1089,8 @@ __global__ void k_head_conv(TGeo g, const float* __restrict__ x, const float* __
   zh[idx] = s;
 }
 // per-channel stats of zh [M][3]: one block per channel (the same summation order as the single-block form: 0.28 -> 0.09 ms at G19)
-__global__ void k_head_stats(TGeo g, const float* __restrict__ zh, float eps, float* __restrict__ mean, float* __restrict__ inv) {
+template <bool TRACK>
+__global__ void k_head_stats(TGeo g, const float* __restrict__ zh, float eps, float* __restrict__ mean, float* __restrict__ inv, BnTrack tr) {
   __shared__ double red[256];
   {
     const int j = blockIdx.x;
@@ -1069,12 +1098,15 @@ __global__ void k_head_stats(TGeo g, const float* __restrict__ zh, float eps, fl
     for (int r = threadIdx.x; r < g.M; r += 256) s += zh[r * 3 + j];
     red[threadIdx.x] = s; __syncthreads();
     for (int o = 128; o > 0; o >>= 1) { if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
-    float mu = (float)(red[0] / g.M); __syncthreads();
+    float mu = (float)(red[0] / g.M);
+    if (TRACK) { if (threadIdx.x == 0) bn_track_mean(tr, j, red[0] / g.M); }
+    __syncthreads();
     s = 0;
     for (int r = threadIdx.x; r < g.M; r += 256) { float d = zh[r * 3 + j] - mu; s += (double)d * d; }
     red[threadIdx.x] = s; __syncthreads();
     for (int o = 128; o > 0; o >>= 1) { if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
     if (threadIdx.x == 0) { mean[j] = mu; inv[j] = 1.0f / sqrtf((float)(red[0] / g.M) + eps); }
+    if (TRACK) { if (threadIdx.x == 0) bn_track_var(tr, j, red[0] / g.M); }
     __syncthreads();
   }
 }
@@ -1283,7 +1315,8 @@ __global__ __launch_bounds__(256) void k_head_stats_part(TGeo g, const float* __
   __syncthreads();
   if (threadIdx.x < 6) atomicAdd(&hacc[threadIdx.x], red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3]);
 }
-__global__ void k_head_stats_fin(TGeo g, const double* __restrict__ hacc, float eps, float* __restrict__ mean, float* __restrict__ inv, double m) {
+template <bool TRACK>
+__global__ void k_head_stats_fin(TGeo g, const double* __restrict__ hacc, float eps, float* __restrict__ mean, float* __restrict__ inv, double m, BnTrack tr) {
   const int j = threadIdx.x;
   if (j >= 3) return;
   const double mu = hacc[j] / m;
@@ -1291,6 +1324,7 @@ __global__ void k_head_stats_fin(TGeo g, const double* __restrict__ hacc, float 
   if (var < 0) var = 0;
   mean[j] = (float)mu;
   inv[j] = 1.0f / sqrtf((float)var + eps);
+  if (TRACK) { bn_track_mean(tr, j, mu); bn_track_var(tr, j, var); }
 }
 // out[b][j] = sum_i y[b][i] * Wt[i][j] + bias[b][j] for eight batch rows per block: grid (ceil(N / 256), ceil(B / 8), 2); z = 0: the policy
 // logits (y = channels 0, 1 of yh flattened, K = 2 HW), z = 1: the value head's hidden layer (y = channel 2, K = HW)
@@ -1873,7 +1907,8 @@ struct agz_trainer {
     AGZ_HIP_TRY(hipMemsetAsync(q, 0, n * sizeof(T), ctx->stream));
     allocs.push_back(q); *p = (T*)q; return AGZ_OK;
   }
-  int forward_backward_dev(const float* planes_dev, const float* pi_dev, const float* v_dev);
+  // eval (agz_trainer_eval): the forward pass alone, normalising with the tracked estimates; touches neither G nor the tracked state
+  int forward_backward_dev(const float* planes_dev, const float* pi_dev, const float* v_dev, bool eval = false);
   // data-parallel step (comm.hip, agz_trainer_forward_backward_allreduce): called once per slice of the flat gradient buffer as soon
   // as the kernels that write it have been ENQUEUED — heads first, then layer L .. 0 (the order of the backward pass, the same on
   // every rank) — with the stream whose completion means "slice written"; the slices tile [0, n_flat) exactly
@@ -1907,13 +1942,51 @@ struct agz_trainer {
   bool one_stream = false;  // bit 4 of the same hook: no side stream at all (diagnostic: a kernel table without overlap shows every kernel's own duration)
   hipEvent_t ev_w0 = nullptr, ev_bw = nullptr;
   int side_stream();
-  int prep_weights();
+  int prep_weights(bool fwd_only = false);
   // solver options (agz_trainer_set_solver; all 0 = the vanilla step, which then runs the kernels it always ran) and the first-order state:
   // V, one flat buffer laid out exactly like P / G, exists only while momentum != 0 (allocated and zeroed when it is first set, released
   // when it is set back to 0): a trainer that never asks for momentum allocates nothing more
   agz_solver_conf solver{0.f, 0.f, 0.f, 0};
   float* V = nullptr;
   bool solver_on() const { return solver.momentum != 0.f || solver.l2reg != 0.f || solver.clip != 0.f; }
+  // running BatchNorm statistics (agz_trainer_set_bn_tracking; BnTrack above).  bn_st: one device allocation, made when tracking is first
+  // turned on (or a state is first set / loaded): per finalize launch — tower layer 0 .. L, then the heads — S_mean[C] | S_var[C] | N[ops],
+  // C the launch's (padded) channels.  bn_have[op]: N(op) > 0, known on the host without a read-back (a tracked forward makes every N >= 1).
+  bool bn_on = false;
+  float bn_lam = 0.997f;
+  double* bn_st = nullptr;
+  size_t bn_total = 0;
+  std::vector<size_t> bn_base;         // [L + 2] offset of each launch's block in bn_st
+  std::vector<char> bn_have;           // [2 L + 3] in the op order of agz_net_set_bn_stats
+  struct BnOp { size_t mean, var, n; int C; };   // offsets into bn_st of one op's S_mean[C], S_var[C], N
+  int bn_num() const { return 2 * L + 3; }
+  BnOp bn_op(int i) const {
+    if (i >= 2 * L + 1) {                // policy head (channels 0, 1), value head (channel 2)
+      const size_t b = bn_base[L + 1]; const int v = i - (2 * L + 1);
+      return BnOp{b + 2 * v, b + 3 + 2 * v, b + 6 + v, v ? 1 : 2};
+    }
+    const int l = (i + 1) / 2, br = i == 0 ? 0 : (i - 1) % 2, C = layers[l].Cout_p;   // Init, then L1 / L2 = branch a / b of block l
+    const size_t b = bn_base[l];
+    return BnOp{b + (size_t)br * Kp, b + C + (size_t)br * Kp, b + 2 * (size_t)C + br, K};
+  }
+  BnTrack bn_track(int launch) const {   // launch: tower layer 0 .. L, L + 1 = the heads
+    const int C = launch <= L ? layers[launch].Cout_p : 3;
+    return BnTrack{bn_st ? bn_st + bn_base[launch] : nullptr, C, launch <= L ? Kp : 2, (double)bn_lam};
+  }
+  bool bn_all() const { for (char h : bn_have) if (!h) return false; return !bn_have.empty(); }
+  int bn_alloc() {
+    if (bn_st) return AGZ_OK;
+    bn_base.assign(L + 2, 0);
+    size_t off = 0;
+    for (int l = 0; l <= L; l++) { bn_base[l] = off; off += 2 * (size_t)layers[l].Cout_p + layers[l].nbr; }
+    bn_base[L + 1] = off; off += 8;
+    bn_total = off;
+    bn_have.assign(bn_num(), 0);
+    int r = alloc(&bn_st, bn_total);     // (zeroed: S = 0, N = 0)
+    if (r != AGZ_OK) { bn_st = nullptr; return r; }
+    AGZ_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return AGZ_OK;
+  }
   float fuse_lr = 0.f;      // != 0 during a fused step: k_bn_bwd1 updates gamma / beta in place, apply() skips them
   bool fused_done = false;  // the backward that just ran took the fused path
   // sharded trainer (agz_trainer_create_sharded): this rank's rows [rank * B, (rank + 1) * B) of a global batch of n_ranks * B rows.
@@ -1927,6 +2000,7 @@ struct agz_trainer {
   int exchange(int site, const double* send, size_t count) { return shard.gather(site, send, xg, count); }
   bool bn_single_pass(int C) const { return C % 4 == 0 && C <= 1024 && g.M >= 4096; }
   int step(const float* planes, const float* pi, const float* v);   // forward_backward_dev, collective on a sharded trainer
+  int eval_pass(const float* planes, const float* pi, const float* v);   // the forward-only pass; collective on a sharded trainer
 };
 
 static inline int nblk(size_t n, int bs = 256) { return (int)((n + bs - 1) / bs); }
@@ -1957,7 +2031,7 @@ int agz_trainer::side_stream() {
 // word + fp16 hi / lo image for the DMA forward convolution (2 kernels), transpose + Winograd image for the data gradient (3 kernels), each a
 // few MB of work that cannot fill the chip: 17 + 73 us per layer in line at G19 — are queued here on the side stream, which is otherwise
 // idle until the backward pass: forward images first, in layer order with an event each, then the data gradient's with one event
-int agz_trainer::prep_weights() {
+int agz_trainer::prep_weights(bool fwd_only) {
   for (auto& ly : layers) { ly.fw_ready = false; ly.bw_ready = false; }
   if (!wino || !hoist_w || one_stream) return AGZ_OK;
   int r = side_stream();
@@ -1973,7 +2047,7 @@ int agz_trainer::prep_weights() {
     AGZ_HIP_TRY(hipEventRecord(ly.ev_fw, sw));
     ly.fw_ready = true;
   }
-  for (int l = L; l >= 1; l--) {
+  for (int l = L; l >= 1 && !fwd_only; l--) {
     TLayer& ly = layers[l];
     const int C = ly.Cout_p;
     if (!use_wino(C, ly.Cin_p)) continue;
@@ -1985,16 +2059,20 @@ int agz_trainer::prep_weights() {
   return AGZ_OK;
 }
 
-int agz_trainer::forward_backward_dev(const float* planes, const float* pi, const float* v) {
+int agz_trainer::forward_backward_dev(const float* planes, const float* pi, const float* v, bool eval) {
   hipStream_t s = ctx->stream;
   const int RPB = 64;
-  { int r0 = prep_weights(); if (r0 != AGZ_OK) return r0; }
+  const bool trk = bn_on && !eval;   // this forward's statistics go into the running estimates (the <true> finalize kernels)
+  if (trk) std::fill(bn_have.begin(), bn_have.end(), (char)1);
+  { int r0 = prep_weights(eval); if (r0 != AGZ_OK) return r0; }
   hipLaunchKernelGGL(k_pack_planes_t, dim3(nblk((size_t)g.M * Fp)), dim3(256), 0, s, planes, x0, g, F, Fp);
+  if (!eval) {
   // zero the gradient regions that are ACCUMULATED into (filters: atomics; heads).  The batch-shaped gamma / beta gradients — 98 % of
   // the flat buffer — are plain stores of every element (k_bn_bwd1) and need no clearing (one 7.7 GB memset per G19 step saved)
   hipLaunchKernelGGL(k_zero_regions, dim3(64, L + 1), dim3(256), 0, s, G, zero_tab, L + 1);
   AGZ_HIP_TRY(hipMemsetAsync(G + o_hc, 0, (n_flat - o_hc) * sizeof(float), s));
   AGZ_HIP_TRY(hipMemsetAsync(acc_b, 0, (size_t)(L + 1) * 2048 * sizeof(double), s));
+  }
   AGZ_HIP_TRY(hipMemcpyAsync(amax_prev, amax_words, (size_t)(L + 2) * 2 * sizeof(unsigned), hipMemcpyDeviceToDevice, s));   // (last step's ranges: estimates for the fused plane split)
   AGZ_HIP_TRY(hipMemsetAsync(amax_words, 0, (size_t)(L + 2) * 2 * sizeof(unsigned), s));
   AGZ_HIP_TRY(hipMemsetAsync(board_words, 0, (size_t)2 * (L + 2) * B * sizeof(unsigned), s));
@@ -2042,22 +2120,25 @@ int agz_trainer::forward_backward_dev(const float* planes, const float* pi, cons
     }
     if (r != AGZ_OK) return r;
     int C = ly.Cout_p;
+    const BnTrack bt = bn_track(l);
     // (sharded: this rank's partial sums are gathered from every rank and k_bn_fin_ranks sums them in rank order over the global rows)
-    if (bn_single_pass(C)) {   // (small problems keep the two-pass form: nothing to gain, and it is the oracle's order)
+    if (eval) {   // the tracked estimates in place of this batch's statistics
+      hipLaunchKernelGGL(k_bn_from_running, dim3(nblk(C)), dim3(256), 0, s, bt, conf.bn_eps, ly.mean, ly.inv);
+    } else if (bn_single_pass(C)) {   // (small problems keep the two-pass form: nothing to gain, and it is the oracle's order)
       hipLaunchKernelGGL(k_bn_stats, dim3(nblk(g.M, 128)), dim3(256), 0, s, g, ly.z, C, acc, 128);   // (256 / 128 / 64 / 32 rows: 46 / 37 / 46 / 71 us at G19)
       if (sharded) {
         if ((r = exchange(l, acc, 2048)) != AGZ_OK) return r;
-        hipLaunchKernelGGL(k_bn_fin_ranks, dim3(nblk(C)), dim3(256), 0, s, xg, n_ranks, 2048, acc, C, (double)m_glob(), conf.bn_eps, ly.mean, ly.inv, 2);
+        hipLaunchKernelGGL(trk ? k_bn_fin_ranks<true> : k_bn_fin_ranks<false>, dim3(nblk(C)), dim3(256), 0, s, xg, n_ranks, 2048, acc, C, (double)m_glob(), conf.bn_eps, ly.mean, ly.inv, 2, bt);
       } else
-        hipLaunchKernelGGL(k_bn_fin2, dim3(nblk(C)), dim3(256), 0, s, acc, C, (double)g.M, conf.bn_eps, ly.mean, ly.inv);
+        hipLaunchKernelGGL(trk ? k_bn_fin2<true> : k_bn_fin2<false>, dim3(nblk(C)), dim3(256), 0, s, acc, C, (double)g.M, conf.bn_eps, ly.mean, ly.inv, bt);
     } else {
       for (int pass = 0; pass < 2; pass++) {   // the mean over the global rows first, then the centred sums around it (the oracle's order)
         hipLaunchKernelGGL(k_bn_sum, dim3(nblk(g.M, RPB)), dim3(std::min(C, 512)), 0, s, g, ly.z, C, pass ? (const float*)ly.mean : (const float*)nullptr, acc, RPB);
         if (sharded) {
           if ((r = exchange(l, acc, 1024)) != AGZ_OK) return r;
-          hipLaunchKernelGGL(k_bn_fin_ranks, dim3(nblk(C)), dim3(256), 0, s, xg, n_ranks, 1024, acc, C, (double)m_glob(), conf.bn_eps, ly.mean, ly.inv, pass);
+          hipLaunchKernelGGL(trk ? k_bn_fin_ranks<true> : k_bn_fin_ranks<false>, dim3(nblk(C)), dim3(256), 0, s, xg, n_ranks, 1024, acc, C, (double)m_glob(), conf.bn_eps, ly.mean, ly.inv, pass, bt);
         } else
-          hipLaunchKernelGGL(k_bn_fin, dim3(nblk(C)), dim3(256), 0, s, acc, C, (double)g.M, conf.bn_eps, ly.mean, ly.inv, pass);
+          hipLaunchKernelGGL(trk ? k_bn_fin<true> : k_bn_fin<false>, dim3(nblk(C)), dim3(256), 0, s, acc, C, (double)g.M, conf.bn_eps, ly.mean, ly.inv, pass, bt);
       }
     }
     x_amax_ready[l + 1] = 0; xb_ready[l + 1] = 0;
@@ -2093,16 +2174,20 @@ int agz_trainer::forward_backward_dev(const float* planes, const float* pi, cons
   // (second form of the head kernels: see k_head_conv2 ... above; fast_heads = 0, agz_debug.h, keeps the first form for A/B)
   const int fcK = 2 * g.HW > FC ? 2 * g.HW : FC, fcJ = A > FC ? A : FC;
   const bool fh = (fast_heads || sharded) && (size_t)8 * (2 * g.HW) * 4 <= 60000 && (size_t)B * 8 * 4 <= 60000 && (size_t)8 * fcJ * 4 <= 60000 && fcK > 0;
+  const BnTrack hbt = bn_track(L + 1);
   if (fh) {
     AGZ_HIP_TRY(hipMemsetAsync(head_acc, 0, 16 * sizeof(double), s));
     hipLaunchKernelGGL(k_head_conv2, dim3(std::min(nblk(g.M, 4), ctx->num_cus * 16)), dim3(256), 0, s, g, cur, P + o_hc, zh, Kp);
+    if (eval) hipLaunchKernelGGL(k_bn_from_running, dim3(1), dim3(64), 0, s, hbt, conf.bn_eps, hmean, hinv);
+    else {
     hipLaunchKernelGGL(k_head_stats_part, dim3(std::min(nblk(g.M), ctx->num_cus)), dim3(256), 0, s, g, zh, head_acc);
     if (sharded) {   // (head_acc [16] is gathered whole; each exchange sums the ranks' part it concerns into this rank's head_acc)
       int r = exchange(L + 1, head_acc, 16);
       if (r != AGZ_OK) return r;
       hipLaunchKernelGGL(k_sum_ranks, dim3(1), dim3(64), 0, s, xg, n_ranks, 16, head_acc, 0, 6);
     }
-    hipLaunchKernelGGL(k_head_stats_fin, dim3(1), dim3(64), 0, s, g, head_acc, conf.bn_eps, hmean, hinv, (double)m_glob());
+    hipLaunchKernelGGL(trk ? k_head_stats_fin<true> : k_head_stats_fin<false>, dim3(1), dim3(64), 0, s, g, head_acc, conf.bn_eps, hmean, hinv, (double)m_glob(), hbt);
+    }
     hipLaunchKernelGGL(k_head_apply, dim3(nblk((size_t)g.M * 3)), dim3(256), 0, s, g, zh, P + o_hg, P + o_hb, hmean, hinv, yh);
     hipLaunchKernelGGL(k_fc_fwd2, dim3(nblk(std::max(A, FC)), nblk(B, 8), 2), dim3(256), (size_t)8 * 2 * g.HW * sizeof(float), s, h);
     hipLaunchKernelGGL(k_value_out2, dim3(B), dim3(64), 0, s, h);
@@ -2115,12 +2200,14 @@ int agz_trainer::forward_backward_dev(const float* planes, const float* pi, cons
     hipLaunchKernelGGL(k_cost_fin, dim3(1), dim3(64), 0, s, h, head_acc);
   } else {
   hipLaunchKernelGGL(k_head_conv, dim3(nblk((size_t)g.M * 3)), dim3(256), 0, s, g, cur, P + o_hc, zh, Kp);
-  hipLaunchKernelGGL(k_head_stats, dim3(3), dim3(256), 0, s, g, zh, conf.bn_eps, hmean, hinv);
+  if (eval) hipLaunchKernelGGL(k_bn_from_running, dim3(1), dim3(64), 0, s, hbt, conf.bn_eps, hmean, hinv);
+  else hipLaunchKernelGGL(trk ? k_head_stats<true> : k_head_stats<false>, dim3(3), dim3(256), 0, s, g, zh, conf.bn_eps, hmean, hinv, hbt);
   hipLaunchKernelGGL(k_head_apply, dim3(nblk((size_t)g.M * 3)), dim3(256), 0, s, g, zh, P + o_hg, P + o_hb, hmean, hinv, yh);
   hipLaunchKernelGGL(k_fc_fwd, dim3(nblk((size_t)B * A + (size_t)B * FC)), dim3(256), 0, s, h);
   hipLaunchKernelGGL(k_value_out, dim3(nblk(B)), dim3(256), 0, s, h);
   hipLaunchKernelGGL(k_cost, dim3(1), dim3(256), 0, s, h);
   }
+  if (eval) { AGZ_HIP_TRY(hipGetLastError()); return AGZ_OK; }   // (forward only: no gradient, no state touched)
   // ---- heads backward
   size_t n_fc = (size_t)2 * g.HW * A + (size_t)B * A + (size_t)g.HW * FC + (size_t)B * FC + FC + B + (size_t)B * 3 * g.HW;
   if (fh) {
@@ -2291,6 +2378,11 @@ int agz_trainer::step(const float* planes, const float* pi, const float* v) {
   });
 }
 
+int agz_trainer::eval_pass(const float* planes, const float* pi, const float* v) {
+  if (!sharded) return forward_backward_dev(planes, pi, v, true);
+  return shard.eval_step([&]() -> int { return forward_backward_dev(planes, pi, v, true); });
+}
+
 int agz_trainer_bind_shard(agz_trainer* t, int rank, int n, agz_shard_hooks hooks) {
   AGZ_REQUIRE(t && n >= 1 && rank >= 0 && rank < n, AGZ_E_INVALID, "agz_trainer_bind_shard: rank %d of %d", rank, n);
   // the sharded step exchanges the partial sums of the second form of the head kernels (forward_backward_dev: fh)
@@ -2307,8 +2399,9 @@ int agz_trainer_bind_shard(agz_trainer* t, int rank, int n, agz_shard_hooks hook
 bool agz_trainer_is_sharded(const agz_trainer* t) { return t && t->sharded; }
 // the gathers of forward_backward_dev in issue order: per tower layer 0 .. L one (single-pass statistics) or two (two-pass), the heads'
 // statistics, cost and BatchNorm backward, then the backward BatchNorm sums of layer L .. 0
-void agz_trainer_exchange_plan(const agz_trainer* t, std::vector<size_t>& out) {
+void agz_trainer_exchange_plan(const agz_trainer* t, std::vector<size_t>& out, bool eval) {
   out.clear();
+  if (eval) { out.push_back(16); return; }   // agz_trainer_eval: the cost words alone
   for (const auto& ly : t->layers) {
     if (t->bn_single_pass(ly.Cout_p)) out.push_back(2048);
     else { out.push_back(1024); out.push_back(1024); }
@@ -2892,6 +2985,175 @@ int agz_train_dev(agz_trainer* t, const float* Xs_dev, const float* policies_dev
   return AGZ_OK;
 }
 
+
+// ---- running BatchNorm statistics (BnTrack above; include/agz.h) --------------------------------------------------------------------------
+static bool bn_momentum_valid(float m) { return std::isfinite(m) && m >= 0.f && m < 1.f; }
+// the whole state on the host (a few KB to a few hundred KB); empty while none exists
+static int bn_download(const agz_trainer* t, std::vector<double>& h) {
+  h.assign(t->bn_total, 0.0);
+  if (!t->bn_st) return AGZ_OK;
+  AGZ_HIP_TRY(hipSetDevice(t->ctx->device));
+  AGZ_HIP_TRY(hipStreamSynchronize(t->ctx->stream));
+  AGZ_HIP_TRY(hipMemcpy(h.data(), t->bn_st, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+  return AGZ_OK;
+}
+static int bn_upload(agz_trainer* t, const std::vector<double>& h) {
+  AGZ_HIP_TRY(hipSetDevice(t->ctx->device));
+  AGZ_HIP_TRY(hipStreamSynchronize(t->ctx->stream));
+  AGZ_HIP_TRY(hipMemcpy(t->bn_st, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+  return AGZ_OK;
+}
+static void bn_estimates(const agz_trainer* t, const std::vector<double>& h, int i, float* mean, float* var) {
+  const agz_trainer::BnOp op = t->bn_op(i);
+  const double n = h[op.n];
+  for (int c = 0; c < op.C; c++) { mean[c] = (float)(h[op.mean + c] / n); var[c] = (float)(h[op.var + c] / n); }
+}
+
+int agz_trainer_set_bn_tracking(agz_trainer* t, int on, float momentum) {
+  AGZ_REQUIRE(t, AGZ_E_INVALID, "agz_trainer_set_bn_tracking: NULL trainer");
+  AGZ_REQUIRE((on == 0 || on == 1) && bn_momentum_valid(momentum), AGZ_E_INVALID,
+              "agz_trainer_set_bn_tracking: need on = 0 / 1 and a finite 0 <= momentum < 1 (got %d, %g)", on, (double)momentum);
+  if (on) {
+    AGZ_HIP_TRY(hipSetDevice(t->ctx->device));
+    int r = t->bn_alloc();
+    if (r != AGZ_OK) return r;
+  }
+  t->bn_on = on != 0; t->bn_lam = momentum;
+  return AGZ_OK;
+}
+int agz_trainer_get_bn_tracking(const agz_trainer* t, int* on, float* momentum, double* weight) {
+  AGZ_REQUIRE(t, AGZ_E_INVALID, "agz_trainer_get_bn_tracking: NULL trainer");
+  if (on) *on = t->bn_on ? 1 : 0;
+  if (momentum) *momentum = t->bn_lam;
+  if (weight) {
+    *weight = 0.0;
+    if (t->bn_st) {   // N of the first op (every op's N is the same unless agz_trainer_set_bn_stats gave them different weights)
+      AGZ_HIP_TRY(hipSetDevice(t->ctx->device));
+      AGZ_HIP_TRY(hipStreamSynchronize(t->ctx->stream));
+      AGZ_HIP_TRY(hipMemcpy(weight, t->bn_st + t->bn_op(0).n, sizeof(double), hipMemcpyDeviceToHost));
+    }
+  }
+  return AGZ_OK;
+}
+int agz_trainer_num_bn(const agz_trainer* t) { return t ? t->bn_num() : 0; }
+int agz_trainer_get_bn_stats(const agz_trainer* t, int bi, float* mean, float* var, size_t C) {
+  AGZ_REQUIRE(t && mean && var && bi >= 0 && bi < t->bn_num(), AGZ_E_INVALID, "agz_trainer_get_bn_stats: bad argument");
+  AGZ_REQUIRE(t->bn_st && t->bn_have[bi], AGZ_E_STATE, "agz_trainer_get_bn_stats: no statistics tracked yet (N = 0)");
+  AGZ_REQUIRE(C == (size_t)t->bn_op(bi).C, AGZ_E_INVALID, "agz_trainer_get_bn_stats: op %d has %d channels, got %zu", bi, t->bn_op(bi).C, C);
+  std::vector<double> h;
+  int r = bn_download(t, h);
+  if (r != AGZ_OK) return r;
+  bn_estimates(t, h, bi, mean, var);
+  return AGZ_OK;
+}
+int agz_trainer_set_bn_stats(agz_trainer* t, int bi, const float* mean, const float* var, size_t C, double weight) {
+  AGZ_REQUIRE(t && mean && var && bi >= 0 && bi < t->bn_num(), AGZ_E_INVALID, "agz_trainer_set_bn_stats: bad argument");
+  AGZ_REQUIRE(std::isfinite(weight) && weight > 0, AGZ_E_INVALID, "agz_trainer_set_bn_stats: the weight must be finite and > 0 (got %g)", weight);
+  AGZ_HIP_TRY(hipSetDevice(t->ctx->device));
+  int r = t->bn_alloc();
+  if (r != AGZ_OK) return r;
+  const agz_trainer::BnOp op = t->bn_op(bi);
+  AGZ_REQUIRE(C == (size_t)op.C, AGZ_E_INVALID, "agz_trainer_set_bn_stats: op %d has %d channels, got %zu", bi, op.C, C);
+  std::vector<double> sm(C), sv(C);
+  for (size_t c = 0; c < C; c++) { sm[c] = weight * (double)mean[c]; sv[c] = weight * (double)var[c]; }
+  AGZ_HIP_TRY(hipStreamSynchronize(t->ctx->stream));
+  AGZ_HIP_TRY(hipMemcpy(t->bn_st + op.mean, sm.data(), C * sizeof(double), hipMemcpyHostToDevice));
+  AGZ_HIP_TRY(hipMemcpy(t->bn_st + op.var, sv.data(), C * sizeof(double), hipMemcpyHostToDevice));
+  AGZ_HIP_TRY(hipMemcpy(t->bn_st + op.n, &weight, sizeof(double), hipMemcpyHostToDevice));
+  t->bn_have[bi] = 1;
+  return AGZ_OK;
+}
+int agz_trainer_reset_bn_stats(agz_trainer* t) {
+  AGZ_REQUIRE(t, AGZ_E_INVALID, "agz_trainer_reset_bn_stats: NULL trainer");
+  if (!t->bn_st) return AGZ_OK;
+  AGZ_HIP_TRY(hipSetDevice(t->ctx->device));
+  AGZ_HIP_TRY(hipMemsetAsync(t->bn_st, 0, t->bn_total * sizeof(double), t->ctx->stream));
+  AGZ_HIP_TRY(hipStreamSynchronize(t->ctx->stream));
+  std::fill(t->bn_have.begin(), t->bn_have.end(), (char)0);
+  return AGZ_OK;
+}
+
+// The forward pass alone under the tracked estimates: a held-out loss.  Sharded: collective, the cost words alone are exchanged.
+int agz_trainer_eval_dev(agz_trainer* t, const float* planes_dev, const float* pi_dev, const float* v_dev, float* cost) {
+  AGZ_REQUIRE(t && planes_dev && pi_dev && v_dev, AGZ_E_INVALID, "agz_trainer_eval_dev: NULL argument");
+  AGZ_REQUIRE(t->bn_all(), AGZ_E_STATE, "agz_trainer_eval: no running statistics yet (N = 0): track a training forward or set them first");
+  AGZ_HIP_TRY(hipSetDevice(t->ctx->device));
+  int r = t->eval_pass(planes_dev, pi_dev, v_dev);
+  if (r != AGZ_OK) return r;
+  if (cost) {
+    float c[2] = {0, 0};
+    AGZ_HIP_TRY(hipMemcpyAsync(c, t->cost, 8, hipMemcpyDeviceToHost, t->ctx->stream));
+    AGZ_HIP_TRY(hipStreamSynchronize(t->ctx->stream));
+    *cost = c[0] + c[1];
+  }
+  return AGZ_OK;
+}
+int agz_trainer_eval(agz_trainer* t, const float* planes, const float* pi, const float* v, float* cost) {
+  AGZ_REQUIRE(t && planes && pi && v, AGZ_E_INVALID, "agz_trainer_eval: NULL argument");
+  AGZ_REQUIRE(t->bn_all(), AGZ_E_STATE, "agz_trainer_eval: no running statistics yet (N = 0): track a training forward or set them first");
+  AGZ_HIP_TRY(hipSetDevice(t->ctx->device));
+  hipStream_t s = t->ctx->stream;
+  AGZ_HIP_TRY(hipMemcpyAsync(t->d_planes, planes, (size_t)t->B * t->F * t->g.HW * 4, hipMemcpyHostToDevice, s));
+  AGZ_HIP_TRY(hipMemcpyAsync(t->d_pi, pi, (size_t)t->B * t->A * 4, hipMemcpyHostToDevice, s));
+  AGZ_HIP_TRY(hipMemcpyAsync(t->d_v, v, (size_t)t->B * 4, hipMemcpyHostToDevice, s));
+  float c = 0.f;
+  int r = agz_trainer_eval_dev(t, t->d_planes, t->d_pi, t->d_v, &c);
+  if (r != AGZ_OK) return r;
+  if (cost) *cost = c;
+  return AGZ_OK;
+}
+
+// ---- the BatchNorm block of an AGZTRN03 checkpoint: float momentum, uint32 on, uint32 n_ops, per op {uint64 C, double N, S_mean[C], S_var[C]}
+static uint64_t bn_block_bytes(const agz_trainer* t) {
+  uint64_t n = 12;
+  for (int i = 0; i < t->bn_num(); i++) n += 16 + 16 * (uint64_t)(i >= 2 * t->L + 1 ? (i == 2 * t->L + 1 ? 2 : 1) : t->K);
+  return n;
+}
+static bool bn_block_write(const agz_trainer* t, FILE* f) {
+  std::vector<double> h;
+  if (bn_download(t, h) != AGZ_OK) return false;
+  const uint32_t on = t->bn_on ? 1u : 0u, nops = (uint32_t)t->bn_num();
+  bool ok = fwrite(&t->bn_lam, 4, 1, f) == 1 && fwrite(&on, 4, 1, f) == 1 && fwrite(&nops, 4, 1, f) == 1;
+  for (int i = 0; ok && i < t->bn_num(); i++) {
+    const agz_trainer::BnOp op = t->bn_op(i);
+    const uint64_t C = (uint64_t)op.C;
+    ok = fwrite(&C, 8, 1, f) == 1 && fwrite(&h[op.n], 8, 1, f) == 1 && fwrite(&h[op.mean], 8, C, f) == C && fwrite(&h[op.var], 8, C, f) == C;
+  }
+  return ok;
+}
+struct BnBlock { float lam; uint32_t on; std::vector<double> n; std::vector<std::vector<double>> sm, sv; };
+// reads and validates the block at the file's current position; nothing of the trainer is changed
+static bool bn_block_read(const agz_trainer* t, FILE* f, BnBlock& b) {
+  uint32_t nops = 0;
+  if (fread(&b.lam, 4, 1, f) != 1 || fread(&b.on, 4, 1, f) != 1 || fread(&nops, 4, 1, f) != 1) return false;
+  if (!bn_momentum_valid(b.lam) || b.on > 1 || nops != (uint32_t)t->bn_num()) return false;
+  b.n.resize(nops); b.sm.resize(nops); b.sv.resize(nops);
+  for (uint32_t i = 0; i < nops; i++) {
+    uint64_t C = 0;
+    const uint64_t want = (uint64_t)(i >= 2u * t->L + 1 ? (i == 2u * t->L + 1 ? 2 : 1) : t->K);
+    if (fread(&C, 8, 1, f) != 1 || C != want || fread(&b.n[i], 8, 1, f) != 1 || !(std::isfinite(b.n[i]) && b.n[i] > 0)) return false;
+    b.sm[i].resize(C); b.sv[i].resize(C);
+    if (fread(b.sm[i].data(), 8, C, f) != C || fread(b.sv[i].data(), 8, C, f) != C) return false;
+    for (uint64_t c = 0; c < C; c++) if (!std::isfinite(b.sm[i][c]) || !std::isfinite(b.sv[i][c])) return false;
+  }
+  return true;
+}
+static int bn_block_apply(agz_trainer* t, const BnBlock& b) {
+  AGZ_HIP_TRY(hipSetDevice(t->ctx->device));
+  int r = t->bn_alloc();
+  if (r != AGZ_OK) return r;
+  std::vector<double> h(t->bn_total, 0.0);
+  for (int i = 0; i < t->bn_num(); i++) {
+    const agz_trainer::BnOp op = t->bn_op(i);
+    h[op.n] = b.n[i];
+    for (int c = 0; c < op.C; c++) { h[op.mean + c] = b.sm[i][c]; h[op.var + c] = b.sv[i][c]; }
+  }
+  if ((r = bn_upload(t, h)) != AGZ_OK) return r;
+  std::fill(t->bn_have.begin(), t->bn_have.end(), (char)1);
+  t->bn_on = b.on != 0; t->bn_lam = b.lam;
+  return AGZ_OK;
+}
+
 // the configuration a checkpoint of this trainer carries: BatchSize is the GLOBAL batch of a sharded trainer
 static agz_net_conf global_conf(const agz_trainer* t) {
   agz_net_conf c = t->conf;
@@ -2901,12 +3163,32 @@ static agz_net_conf global_conf(const agz_trainer* t) {
 
 // An AGZTRN02 file is checked for its full length BEFORE anything of it is loaded (the header has been read; the position is restored):
 // a truncated file is rejected with the trainer's parameters, options and velocity untouched.  nr: ranks the global tensors are split over.
-static bool checkpoint_complete(FILE* f, const agz_trainer* t, int nr) {
+// (AGZTRN03: v2 says whether the inner form carries a velocity; the BatchNorm block after it is read and validated here as well, into *bn)
+static bool checkpoint_complete(FILE* f, const agz_trainer* t, int nr, bool v2 = true, BnBlock* bn = nullptr) {
   const long at = ftell(f);
-  uint64_t need = (uint64_t)at + sizeof(agz_solver_conf);
-  for (const auto& p : t->prefs) need += 2 * (8 + 4 * (uint64_t)pref_size(p) * (pref_batch_shaped(p) ? nr : 1));
-  const bool ok = at >= 0 && fseek(f, 0, SEEK_END) == 0 && (uint64_t)ftell(f) == need;
+  uint64_t body = v2 ? sizeof(agz_solver_conf) : 0;
+  for (const auto& p : t->prefs) body += (v2 ? 2 : 1) * (8 + 4 * (uint64_t)pref_size(p) * (pref_batch_shaped(p) ? nr : 1));
+  const uint64_t need = (uint64_t)at + body + (bn ? bn_block_bytes(t) : 0);
+  bool ok = at >= 0 && fseek(f, 0, SEEK_END) == 0 && (uint64_t)ftell(f) == need;
+  if (ok && bn) ok = fseek(f, (long)((uint64_t)at + body), SEEK_SET) == 0 && bn_block_read(t, f, *bn);
   return fseek(f, at, SEEK_SET) == 0 && ok;
+}
+// the magic of a checkpoint (and, for AGZTRN03, the uint32 naming the inner form): form 1 / 2 / 3, v2 = a velocity follows the learnables
+static bool read_magic(FILE* f, int* form, bool* v2) {
+  char magic[8];
+  if (fread(magic, 1, 8, f) != 8 || memcmp(magic, "AGZTRN0", 7) != 0 || magic[7] < '1' || magic[7] > '3') return false;
+  *form = magic[7] - '0';
+  *v2 = *form == 2;
+  if (*form == 3) {
+    uint32_t inner = 0;
+    if (fread(&inner, 4, 1, f) != 1 || (inner != 1 && inner != 2)) return false;
+    *v2 = inner == 2;
+  }
+  return true;
+}
+static bool write_magic(const agz_trainer* t, FILE* f) {
+  if (t->bn_all()) { const uint32_t inner = t->V ? 2u : 1u; return fwrite("AGZTRN03", 1, 8, f) == 8 && fwrite(&inner, 4, 1, f) == 1; }
+  return fwrite(t->V ? "AGZTRN02" : "AGZTRN01", 1, 8, f) == 8;
 }
 
 // Sharded save (collective): rank 0 writes the plain trainer's file at the global batch.  Tensor by tensor, batch-shaped ones are gathered
@@ -2926,7 +3208,7 @@ static int save_sharded(const agz_trainer* t, const char* path) {
   const agz_net_conf gc = global_conf(t);
   const uint64_t np = t->prefs.size();
   // (AGZTRN02 when this trainer has a velocity — the same on every rank, like the options themselves: agz_trainer_save)
-  bool ok = f == nullptr || (fwrite(t->V ? "AGZTRN02" : "AGZTRN01", 1, 8, f) == 8 && fwrite(&gc, sizeof(gc), 1, f) == 1 && fwrite(&np, 8, 1, f) == 1);
+  bool ok = f == nullptr || (write_magic(t, f) && fwrite(&gc, sizeof(gc), 1, f) == 1 && fwrite(&np, 8, 1, f) == 1);
   std::vector<float> v, all;
   const int np_i = (int)t->prefs.size();
   for (int k = 0; k < (t->V ? 2 * np_i : np_i); k++) {   // the learnables, then (02) the options and every tensor's velocity
@@ -2950,6 +3232,7 @@ static int save_sharded(const agz_trainer* t, const char* path) {
     }
     if (f && ok) ok = fwrite(&cnt, 8, 1, f) == 1 && fwrite(out, 4, cnt, f) == cnt;
   }
+  if (f && ok && t->bn_all()) ok = bn_block_write(t, f);   // (03: the running statistics, the same bits on every rank)
   if (f) ok = (fclose(f) == 0) && ok;
   hipFree(d);
   if (!ok && rc == AGZ_OK) { agz::set_error("agz_trainer_save: write to %s failed", path); rc = AGZ_E_INVALID; }
@@ -2960,15 +3243,15 @@ static int save_sharded(const agz_trainer* t, const char* path) {
 static int load_sharded(agz_trainer* t, const char* path) {
   FILE* f = fopen(path, "rb");
   AGZ_REQUIRE(f, AGZ_E_INVALID, "agz_trainer_load: cannot open %s", path);
-  char magic[8];
   agz_net_conf c;
   uint64_t np = 0;
   const agz_net_conf gc = global_conf(t);
-  bool ok = fread(magic, 1, 8, f) == 8 && (memcmp(magic, "AGZTRN01", 8) == 0 || memcmp(magic, "AGZTRN02", 8) == 0) && fread(&c, sizeof(c), 1, f) == 1 && fread(&np, 8, 1, f) == 1;
+  int form = 0; bool v2 = false;
+  bool ok = read_magic(f, &form, &v2) && fread(&c, sizeof(c), 1, f) == 1 && fread(&np, 8, 1, f) == 1;
   if (ok) ok = memcmp(&c, &gc, sizeof(c)) == 0 && np == t->prefs.size();
   if (!ok) { fclose(f); agz::set_error("agz_trainer_load: %s is not a checkpoint of this trainer configuration (global batch %d)", path, gc.BatchSize); return AGZ_E_INVALID; }
-  const bool v2 = magic[7] == '2';
-  if (v2 && !checkpoint_complete(f, t, t->n_ranks)) { fclose(f); agz::set_error("agz_trainer_load: %s is truncated or mismatched", path); return AGZ_E_INVALID; }
+  BnBlock bnb;
+  if ((v2 || form == 3) && !checkpoint_complete(f, t, t->n_ranks, v2, form == 3 ? &bnb : nullptr)) { fclose(f); agz::set_error("agz_trainer_load: %s is truncated or mismatched", path); return AGZ_E_INVALID; }
   const int np_i = (int)t->prefs.size();
   for (int k = 0; ok && k < (v2 ? 2 * np_i : np_i); k++) {
     const int i = k % np_i;
@@ -2989,6 +3272,8 @@ static int load_sharded(agz_trainer* t, const char* path) {
   }
   fclose(f);
   AGZ_REQUIRE(ok, AGZ_E_INVALID, "agz_trainer_load: %s is truncated or mismatched", path);
+  // 03: the tracking setting and state the file carries; 01 / 02: no statistics (N = 0), the setting stays
+  { int r = form == 3 ? bn_block_apply(t, bnb) : agz_trainer_reset_bn_stats(t); if (r != AGZ_OK) return r; }
   if (!v2) return agz_trainer_reset_solver(t);   // a file without velocity: v := 0, the options stay
   return AGZ_OK;
 }
@@ -2999,12 +3284,17 @@ static int load_sharded(agz_trainer* t, const char* path) {
 // (16 bytes), then per tensor {n, n floats} of velocity in the same order and layout.  Without a velocity the file is AGZTRN01, byte for
 // byte what it always was (l2reg / clip alone are not stored: they are the caller's configuration, like lr).  Load reads both: an 02 file
 // sets the options it carries and the velocity, an 01 file zeroes the velocity and keeps the trainer's options.
+// A trainer that holds running BatchNorm statistics (N > 0: agz_trainer_set_bn_tracking) writes "AGZTRN03": the magic, a uint32 naming the
+// inner form (1 or 2), the complete body of that 01 / 02 file after its magic, then float momentum, uint32 on, uint32 n_ops and per op (the
+// order of agz_net_set_bn_stats) {uint64 C, double N, double S_mean[C], double S_var[C]}.  Any other trainer writes the 01 / 02 file it
+// always wrote.  Load: 03 sets the tracking setting and state it carries (checked for its full length and a consistent block before
+// anything is changed); 01 / 02 reset the state to N = 0 and keep the setting.
 int agz_trainer_save(const agz_trainer* t, const char* path) {
   AGZ_REQUIRE(t && path, AGZ_E_INVALID, "agz_trainer_save: NULL argument");
   if (t->sharded) return save_sharded(t, path);
   FILE* f = fopen(path, "wb");
   AGZ_REQUIRE(f, AGZ_E_INVALID, "agz_trainer_save: cannot open %s", path);
-  bool ok = fwrite(t->V ? "AGZTRN02" : "AGZTRN01", 1, 8, f) == 8 && fwrite(&t->conf, sizeof(t->conf), 1, f) == 1;
+  bool ok = write_magic(t, f) && fwrite(&t->conf, sizeof(t->conf), 1, f) == 1;
   uint64_t np = t->prefs.size();
   ok = ok && fwrite(&np, 8, 1, f) == 1;
   for (int i = 0; ok && i < (int)t->prefs.size(); i++) {
@@ -3022,6 +3312,7 @@ int agz_trainer_save(const agz_trainer* t, const char* path) {
       ok = fwrite(&cnt, 8, 1, f) == 1 && fwrite(v.data(), 4, cnt, f) == cnt;
     }
   }
+  if (ok && t->bn_all()) ok = bn_block_write(t, f);
   ok = (fclose(f) == 0) && ok;
   AGZ_REQUIRE(ok, AGZ_E_INVALID, "agz_trainer_save: write to %s failed", path);
   return AGZ_OK;
@@ -3032,14 +3323,14 @@ int agz_trainer_load(agz_trainer* t, const char* path) {
   if (t->sharded) return load_sharded(t, path);
   FILE* f = fopen(path, "rb");
   AGZ_REQUIRE(f, AGZ_E_INVALID, "agz_trainer_load: cannot open %s", path);
-  char magic[8];
   agz_net_conf c;
   uint64_t np = 0;
-  bool ok = fread(magic, 1, 8, f) == 8 && (memcmp(magic, "AGZTRN01", 8) == 0 || memcmp(magic, "AGZTRN02", 8) == 0) && fread(&c, sizeof(c), 1, f) == 1 && fread(&np, 8, 1, f) == 1;
+  int form = 0; bool v2 = false;
+  bool ok = read_magic(f, &form, &v2) && fread(&c, sizeof(c), 1, f) == 1 && fread(&np, 8, 1, f) == 1;
   if (ok) ok = memcmp(&c, &t->conf, sizeof(c)) == 0 && np == t->prefs.size();
   if (!ok) { fclose(f); agz::set_error("agz_trainer_load: %s is not a checkpoint of this trainer configuration", path); return AGZ_E_INVALID; }
-  const bool v2 = magic[7] == '2';
-  if (v2 && !checkpoint_complete(f, t, 1)) { fclose(f); agz::set_error("agz_trainer_load: %s is truncated or mismatched", path); return AGZ_E_INVALID; }
+  BnBlock bnb;
+  if ((v2 || form == 3) && !checkpoint_complete(f, t, 1, v2, form == 3 ? &bnb : nullptr)) { fclose(f); agz::set_error("agz_trainer_load: %s is truncated or mismatched", path); return AGZ_E_INVALID; }
   for (int i = 0; ok && i < (int)t->prefs.size(); i++) {
     uint64_t cnt = 0;
     std::vector<float> v(pref_size(t->prefs[i]));
@@ -3059,7 +3350,24 @@ int agz_trainer_load(agz_trainer* t, const char* path) {
   }
   fclose(f);
   AGZ_REQUIRE(ok, AGZ_E_INVALID, "agz_trainer_load: %s is truncated or mismatched", path);
+  // 03: the tracking setting and state the file carries; 01 / 02: no statistics (N = 0), the setting stays
+  { int r = form == 3 ? bn_block_apply(t, bnb) : agz_trainer_reset_bn_stats(t); if (r != AGZ_OK) return r; }
   if (!v2) return agz_trainer_reset_solver(t);   // a file without velocity: v := 0, the options stay
+  return AGZ_OK;
+}
+
+// the running statistics, if the trainer holds any (N > 0), as the net's AGZ_BN_RUNNING statistics; nothing otherwise
+static int export_bn(const agz_trainer* t, agz_net* net) {
+  if (!t->bn_all()) return AGZ_OK;
+  std::vector<double> h;
+  int r = bn_download(t, h);
+  if (r != AGZ_OK) return r;
+  for (int i = 0; i < t->bn_num(); i++) {
+    const int C = t->bn_op(i).C;
+    std::vector<float> m(C), v(C);
+    bn_estimates(t, h, i, m.data(), v.data());
+    if ((r = agz_net_set_bn_stats(net, i, m.data(), v.data(), (size_t)C)) != AGZ_OK) return r;
+  }
   return AGZ_OK;
 }
 
@@ -3095,6 +3403,7 @@ static int export_sharded(const agz_trainer* t, agz_net* net) {
     if (rc == AGZ_OK && (r = agz_net_set_param(net, i, v.data(), want)) != AGZ_OK) rc = r;
   }
   hipFree(d);
+  if (rc == AGZ_OK) rc = export_bn(t, net);   // (every rank holds the same bits and exports its own)
   rc = t->shard.agree(rc);
   return rc == AGZ_OK ? agz_net_commit(net) : rc;
 }
@@ -3119,6 +3428,7 @@ int agz_trainer_export(const agz_trainer* t, agz_net* net) {
     r = agz_net_set_param(net, i, v.data(), v.size());  // takes row 0 of batch-shaped tensors
     if (r != AGZ_OK) return r;
   }
+  { int r = export_bn(t, net); if (r != AGZ_OK) return r; }
   return agz_net_commit(net);
 }
 

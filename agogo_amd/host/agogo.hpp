@@ -94,7 +94,17 @@ struct Trainable {
   }
   agz_solver_conf Solver() const { agz_solver_conf sc{}; agz::check(agz_trainer_get_solver(h, &sc), "solver options"); return sc; }
   void ResetSolver() { agz::check(agz_trainer_reset_solver(h), "solver reset"); }   // velocity := 0
-  // dual.Infer (meta.go:125-162): copy row 0 of every learnable into an inference net
+  // running BatchNorm statistics (the reference asks gorgonia for momentum 0.997, ermahagerdmonards.go:54): from here on every training
+  // forward feeds the estimates that SwitchToInference, Eval and Save use.  Off by default.
+  void TrackBatchNorm(float momentum = 0.997f) { agz::check(agz_trainer_set_bn_tracking(h, 1, momentum), "BatchNorm tracking"); }
+  // a held-out loss: the forward pass alone under the tracked statistics; planes [B,F,H,W], pi [B,ActionSpace], v [B]
+  float Eval(const std::vector<float>& planes, const std::vector<float>& pi, const std::vector<float>& v) {
+    float cost = 0;
+    agz::check(agz_trainer_eval(h, planes.data(), pi.data(), v.data(), &cost), "Eval");
+    return cost;
+  }
+  // dual.Infer (meta.go:125-162): copy row 0 of every learnable into an inference net.  After TrackBatchNorm the tracked statistics go
+  // with them: a Dual made with AGZ_BN_RUNNING then plays with the statistics the network was trained under.
   void SwitchToInference(Dual& inf) const { agz::check(agz_trainer_export(h, inf.h), "SwitchToInference"); }
   // AZ.Save / AZ.Load (agogo.go:175-209) of the learning side, full batch-shaped learnables
   void Save(const std::string& path) const { agz::check(agz_trainer_save(h, path.c_str()), "AZ.Save"); }

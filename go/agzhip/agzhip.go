@@ -855,6 +855,72 @@ func (t *Trainer) SetVelocity(i int, data []float32) error {
 // ResetSolver zeroes the velocity and keeps the options.
 func (t *Trainer) ResetSolver() error { defer t.ctx.enter()(); return lastErr(C.agz_trainer_reset_solver(t.h)) }
 
+// SetBNTracking turns the running BatchNorm statistics on or off (agz_trainer_set_bn_tracking): while on, every training forward adds
+// its batch mean and biased variance to accumulators that decay by momentum (the reference asks gorgonia for 0.997,
+// dualnet/ermahagerdmonards.go:54).  Turning it off keeps the state; Export, Eval and Save still use it.
+func (t *Trainer) SetBNTracking(on bool, momentum float32) error {
+	defer t.ctx.enter()()
+	v := 0
+	if on {
+		v = 1
+	}
+	return lastErr(C.agz_trainer_set_bn_tracking(t.h, C.int(v), C.float(momentum)))
+}
+
+// BNTracking returns the setting and the accumulated weight N of the estimates (0: nothing tracked yet).
+func (t *Trainer) BNTracking() (bool, float32, float64, error) {
+	defer t.ctx.enter()()
+	var on C.int
+	var m C.float
+	var w C.double
+	err := lastErr(C.agz_trainer_get_bn_tracking(t.h, &on, &m, &w))
+	return on != 0, float32(m), float64(w), err
+}
+
+// NumBN is the number of BatchNorm ops, 2*SharedLayers + 3, in the order of Net.SetBNStats.
+func (t *Trainer) NumBN() int { defer t.ctx.enter()(); return int(C.agz_trainer_num_bn(t.h)) }
+
+// BNStats reads the running estimates of op i into mean and var (one value per channel of the op).
+func (t *Trainer) BNStats(i int, mean, variance []float32) error {
+	if len(mean) == 0 || len(mean) != len(variance) {
+		return fmt.Errorf("agzhip: BNStats: mean and variance need the op's channel count, got %d / %d", len(mean), len(variance))
+	}
+	defer t.ctx.enter()()
+	return lastErr(C.agz_trainer_get_bn_stats(t.h, C.int(i), (*C.float)(unsafe.Pointer(&mean[0])), (*C.float)(unsafe.Pointer(&variance[0])), C.size_t(len(mean))))
+}
+
+// SetBNStats seeds op i: S = weight * value, N = weight (weight > 0).
+func (t *Trainer) SetBNStats(i int, mean, variance []float32, weight float64) error {
+	if len(mean) == 0 || len(mean) != len(variance) {
+		return fmt.Errorf("agzhip: SetBNStats: mean and variance need the op's channel count, got %d / %d", len(mean), len(variance))
+	}
+	defer t.ctx.enter()()
+	return lastErr(C.agz_trainer_set_bn_stats(t.h, C.int(i), (*C.float)(unsafe.Pointer(&mean[0])), (*C.float)(unsafe.Pointer(&variance[0])), C.size_t(len(mean)), C.double(weight)))
+}
+
+// ResetBNStats clears the estimates (N = 0) and keeps the setting.
+func (t *Trainer) ResetBNStats() error { defer t.ctx.enter()(); return lastErr(C.agz_trainer_reset_bn_stats(t.h)) }
+
+// Eval is a held-out loss: the forward pass alone with every BatchNorm under the running estimates; nothing of the trainer changes.
+// planes [B, F, H, W], pi [B, ActionSpace], v [B] as flat float32 slices.
+func (t *Trainer) Eval(planes, pi, v []float32) (float32, error) {
+	if len(planes) == 0 || len(pi) == 0 || len(v) == 0 {
+		return 0, fmt.Errorf("agzhip: Eval: empty batch")
+	}
+	defer t.ctx.enter()()
+	var cost C.float
+	err := lastErr(C.agz_trainer_eval(t.h, (*C.float)(unsafe.Pointer(&planes[0])), (*C.float)(unsafe.Pointer(&pi[0])), (*C.float)(unsafe.Pointer(&v[0])), &cost))
+	return float32(cost), err
+}
+
+// EvalDev is Eval on device buffers (one batch of an Examples set's tensors).
+func (t *Trainer) EvalDev(planes, pi, v unsafe.Pointer) (float32, error) {
+	defer t.ctx.enter()()
+	var cost C.float
+	err := lastErr(C.agz_trainer_eval_dev(t.h, (*C.float)(planes), (*C.float)(pi), (*C.float)(v), &cost))
+	return float32(cost), err
+}
+
 func (t *Trainer) Export(n *Net) error { defer t.ctx.enter()(); return lastErr(C.agz_trainer_export(t.h, n.h)) }
 
 func (t *Trainer) Close() error { defer t.ctx.enter()(); C.agz_trainer_destroy(t.h); t.h = nil; return nil }

@@ -262,11 +262,51 @@ int agz_train_dev(agz_trainer* t, const float* Xs_dev, const float* policies_dev
  * keeps learning; gob is Go-only, the format is documented in train.hip). load: the file must match the configuration.
  * A trainer with a velocity (momentum != 0) writes the "AGZTRN02" form — the AGZTRN01 payload, agz_solver_conf, every tensor's
  * velocity — and any other trainer the AGZTRN01 file it always wrote.  load reads both: 02 sets the options and velocity it carries,
- * 01 zeroes the velocity and keeps the options; a truncated 02 file is rejected (AGZ_E_INVALID) before anything is changed. */
+ * 01 zeroes the velocity and keeps the options; a truncated 02 file is rejected (AGZ_E_INVALID) before anything is changed.
+ * A trainer with running BatchNorm statistics (N > 0) writes "AGZTRN03": the magic, a uint32 naming the inner form (1 or 2), the body of
+ * that 01 / 02 file after its magic, then float momentum, uint32 on, uint32 n_ops and per op {uint64 C, double N, double S_mean[C],
+ * double S_var[C]}.  load: 03 sets the tracking setting and state it carries; 01 / 02 reset the state to N = 0 and keep the setting; a
+ * truncated or inconsistent 03 file is rejected (AGZ_E_INVALID) before anything is changed.  Sharded: rank 0 writes, every rank loads
+ * the same block.  Test: tests/test_bn_tracking_gpu.py (checkpoint). */
 int agz_trainer_save(const agz_trainer* t, const char* path);
 int agz_trainer_load(agz_trainer* t, const char* path);
-/* dual.Infer's copy loop (dualnet/meta.go:141-146): row 0 of every learnable -> the inference net; commits it. */
+/* dual.Infer's copy loop (dualnet/meta.go:141-146): row 0 of every learnable -> the inference net; commits it.  A trainer that holds
+ * running BatchNorm statistics (N > 0, below) also hands them to the net (agz_net_set_bn_stats for every op) before the commit, whatever
+ * the net's bn_mode; they matter under AGZ_BN_RUNNING.  Test: tests/test_bn_tracking_gpu.py (plays as trained). */
 int agz_trainer_export(const agz_trainer* t, agz_net* net);
+/* Running BatchNorm statistics (the reference asks gorgonia for them with momentum 0.997, dualnet/ermahagerdmonards.go:54; the update rule
+ * is declared here, DESIGN §2 `bn-running`).  Per BatchNorm op — 2 * SharedLayers + 3 of them in the order of agz_net_set_bn_stats — and
+ * channel c, in double on the device, on every training forward t while tracking is on:
+ *     S_mean[c] = momentum * S_mean[c] + mu_t[c];   S_var[c] = momentum * S_var[c] + var_t[c];   N = momentum * N + 1
+ *     estimates: mean[c] = (float)(S_mean[c] / N),  var[c] = (float)(S_var[c] / N)
+ * mu_t / var_t: the batch mean and the biased batch variance (clamped at 0) that forward normalises with — the global batch's on a sharded
+ * trainer — so after ONE forward the estimates are bit for bit what it normalised with, whatever the momentum.  S and N start at 0.  A
+ * training forward is every forward of agz_trainer_forward_backward(_dev), agz_trainer_batch, agz_train(_dev),
+ * agz_trainer_forward_backward_allreduce(_dev), on plain and sharded handles; after a call that fails part-way the state is undefined.
+ * The accumulation runs inside the kernels that finalize the statistics: no launch and no synchronisation is added to the step, and with
+ * tracking off every path launches exactly the kernels it launched before.  Turning tracking off keeps the state (export, eval and save
+ * still use it), turning it on again continues it, another momentum changes only the coming updates.  Sharded: a local call, every rank
+ * sets the same; every rank holds the same bits.
+ * set_bn_tracking: AGZ_E_INVALID unless on is 0 / 1 and 0 <= momentum < 1, finite; the setting then stays as it was.  The default is
+ * off, momentum 0.997.  get_bn_tracking: any pointer may be NULL; *weight = N.  Tests: tests/test_bn_tracking_cpu.py (ABI),
+ * tests/test_bn_tracking_gpu.py (off is untouched, first step, float64 statistics, recurrence, validation), test_bn_tracking_sharded_gpu.py. */
+int agz_trainer_set_bn_tracking(agz_trainer* t, int on, float momentum);
+int agz_trainer_get_bn_tracking(const agz_trainer* t, int* on, float* momentum, double* weight);
+/* 2 * SharedLayers + 3: Init, L1 / L2 of each shared layer (K channels each), the policy head (2), the value head (1) */
+int agz_trainer_num_bn(const agz_trainer* t);
+/* The estimates of op bn_index (C = its channel count).  get: AGZ_E_STATE while N == 0.  set: S = weight * value, N(op) = weight, weight > 0
+ * (seeding a trainer from a net's statistics).  reset: S = 0, N = 0 for every op, the setting kept.
+ * Tests: tests/test_bn_tracking_gpu.py (recurrence, validation, checkpoint). */
+int agz_trainer_get_bn_stats(const agz_trainer* t, int bn_index, float* mean, float* var, size_t C);
+int agz_trainer_set_bn_stats(agz_trainer* t, int bn_index, const float* mean, const float* var, size_t C, double weight);
+int agz_trainer_reset_bn_stats(agz_trainer* t);
+/* A held-out loss: the training graph's forward pass alone, every BatchNorm normalising with the estimates above instead of the batch's
+ * statistics; *cost as agz_trainer_forward_backward.  No backward pass; learnables, gradients, velocity, S and N are untouched.  Needs
+ * N > 0 for every op (AGZ_E_STATE otherwise); works with tracking on or off.  On a sharded handle the call is collective, only the cost
+ * words are exchanged, and *cost is the global batch's, identical on every rank.  _dev: device buffers, cost may be NULL.
+ * Tests: tests/test_bn_tracking_gpu.py (eval equals the forward it was made from, eval against float64), test_bn_tracking_sharded_gpu.py. */
+int agz_trainer_eval(agz_trainer* t, const float* planes, const float* pi, const float* v, float* cost);
+int agz_trainer_eval_dev(agz_trainer* t, const float* planes_dev, const float* pi_dev, const float* v_dev, float* cost);
 
 /* ---- batched self-play arenas: game.State + mcts.MCTS + agogo.Arena on device ---------------- */
 #define AGZ_GAME_MNK 0  /* game/mnk  (m,n,k) */
