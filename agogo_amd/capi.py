@@ -40,6 +40,11 @@ class SolverConf(C.Structure):
     _fields_ = [("momentum", C.c_float), ("l2reg", C.c_float), ("clip", C.c_float), ("reserved", C.c_int32)]
 
 
+class AdamConf(C.Structure):
+    """agz_adam_conf: gorgonia.NewAdamSolver's options (dualnet/meta.go:20) — beta1, beta2, eps; on = 0 / 1."""
+    _fields_ = [("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("on", C.c_int32)]
+
+
 class GameConf(C.Structure):
     _fields_ = [("kind", C.c_int32), ("m", C.c_int32), ("n", C.c_int32), ("k", C.c_int32), ("komi", C.c_float),
                 ("max_moves", C.c_int32), ("encoder", C.c_int32)]
@@ -183,6 +188,10 @@ def lib():
     sig("agz_trainer_get_velocity", i32, vp, i32, pf, C.c_size_t)
     sig("agz_trainer_set_velocity", i32, vp, i32, pf, C.c_size_t)
     sig("agz_trainer_reset_solver", i32, vp)
+    sig("agz_trainer_set_adam", i32, vp, C.POINTER(AdamConf))
+    sig("agz_trainer_get_adam", i32, vp, C.POINTER(AdamConf), C.POINTER(C.c_uint64))
+    sig("agz_trainer_get_moments", i32, vp, i32, pf, pf, C.c_size_t)
+    sig("agz_trainer_set_moments", i32, vp, i32, pf, pf, C.c_size_t)
     sig("agz_trainer_set_bn_tracking", i32, vp, i32, C.c_float)
     sig("agz_trainer_get_bn_tracking", i32, vp, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_double))
     sig("agz_trainer_num_bn", i32, vp)
@@ -582,6 +591,32 @@ class Trainer:
     def reset_solver(self):
         """velocity := 0, the options kept"""
         _check(lib().agz_trainer_reset_solver(self.h), "agz_trainer_reset_solver")
+
+    def set_adam(self, beta1=0.9, beta2=0.999, eps=1e-8, on=True):
+        """Adam (agz_trainer_set_adam): L2, then clip, then m = b1 m + (1 - b1) g, v = b2 v + (1 - b2) g^2,
+        w -= lr * (m / (1 - b1^t)) / (sqrt(v / (1 - b2^t)) + eps); excludes a momentum; off releases the moments and resets t"""
+        ac = AdamConf(beta1, beta2, eps, int(on))
+        _check(lib().agz_trainer_set_adam(self.h, C.byref(ac)), "agz_trainer_set_adam")
+
+    def get_adam(self):
+        """the settings in force and the step counter t"""
+        ac, t = AdamConf(), C.c_uint64(0)
+        _check(lib().agz_trainer_get_adam(self.h, C.byref(ac), C.byref(t)), "agz_trainer_get_adam")
+        return {"beta1": ac.beta1, "beta2": ac.beta2, "eps": ac.eps, "on": bool(ac.on), "t": int(t.value)}
+
+    def get_moments(self, i):
+        """(m, v) of learnable i, shaped and indexed like get_param(i); zeros while Adam is off"""
+        m = np.zeros(self.param_info(i)[1], np.float32)
+        v = np.zeros_like(m)
+        _check(lib().agz_trainer_get_moments(self.h, i, _pf(m), _pf(v), m.size), "agz_trainer_get_moments")
+        return m, v
+
+    def set_moments(self, i, m, v):
+        a = np.ascontiguousarray(m, dtype=np.float32).ravel()
+        b = np.ascontiguousarray(v, dtype=np.float32).ravel()
+        if a.size != b.size:
+            raise ValueError("set_moments: m and v differ in size")
+        _check(lib().agz_trainer_set_moments(self.h, i, _pf(a), _pf(b), a.size), "agz_trainer_set_moments")
 
     def set_bn_tracking(self, on=True, momentum=0.997):
         """running BatchNorm statistics (agz_trainer_set_bn_tracking): every training forward adds its batch mean / biased variance to

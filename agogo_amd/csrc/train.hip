@@ -315,7 +315,16 @@ __global__ __launch_bounds__(256) void k_bn_apply_v(TGeo g, const float* __restr
 // gm / bt already in registers, the clamp, and with MOM the velocity of gamma / beta read and written at the same (r * C + cc) index of the
 // flat velocity buffer.  A template parameter, not a run-time branch: the <false, false> instantiation is the code above, instruction for
 // instruction (SolverDev is then an unused kernel argument).
-struct SolverDev { float mu, l2, clip; float* vgamma; float* vbeta; };
+//
+// The template parameter is the solver kind: SK_VANILLA / SK_OPTIONS / SK_MOMENTUM are the three kernels above (the former <false, false>,
+// <true, false>, <true, true>); SK_ADAM (agz_trainer_set_adam) steps gamma / beta through adam_step below, the two moments of each read and
+// written at the same (r * C + cc) index of the flat moment buffers M1 / M2.  The Adam members of SolverDev come AFTER the ones that
+// existed: the argument offsets the other three kinds read are the ones they always read.
+enum SolverKind { SK_VANILLA = 0, SK_OPTIONS = 1, SK_MOMENTUM = 2, SK_ADAM = 3 };
+// the per-step constants of Adam: beta, 1 - beta (rounded to float on the host), the bias corrections 1 / (1 - beta^t) (computed in
+// double on the host, rounded once), eps
+struct AdamK { float b1, omb1, b2, omb2, rc1, rc2, eps; };
+struct SolverDev { float mu, l2, clip; float* vgamma; float* vbeta; AdamK ak; float* m1gamma; float* m1beta; float* m2gamma; float* m2beta; };
 // One element of the solver step (gorgonia's VanillaSolver / Momentum as documented: L2, then clip, then the update), fp32:
 //   g2 = g + l2 * w (l2 != 0);  g3 = clamp(g2, -clip, clip) (clip > 0);  MOM: v = mu * v + (-lr) * g3, w += v;  else w += (-lr) * g3
 template <bool MOM>
@@ -325,12 +334,24 @@ __device__ __forceinline__ void solver_step(float& w, float& v, float gr, float 
   if (MOM) { v = mu * v + (-lr) * gr; w = w + v; }
   else w = w + (-lr) * gr;
 }
-template <bool SOLVER, bool MOM>
+// One element of the Adam step (agz_trainer_set_adam; the declared definition of DESIGN §2 `solver-adam`), fp32 — the ONE statement of the
+// arithmetic, called by the fused kernel and by the sweep:
+//   g2 = g + l2 * w (l2 != 0);  g3 = clamp(g2, -clip, clip) (clip > 0);  m = b1 * m + (1 - b1) * g3;  v = b2 * v + (1 - b2) * g3^2;
+//   w += (-lr) * ((m * rc1) / (sqrtf(v * rc2) + eps))
+__device__ __forceinline__ void adam_step(float& w, float& m, float& v, float gr, float lr, float l2, float clip, const AdamK& a) {
+  if (l2 != 0.f) gr = gr + l2 * w;
+  if (clip > 0.f) gr = fminf(fmaxf(gr, -clip), clip);
+  m = a.b1 * m + a.omb1 * gr;
+  v = a.b2 * v + a.omb2 * (gr * gr);
+  w = w + (-lr) * ((m * a.rc1) / (sqrtf(v * a.rc2) + a.eps));
+}
+template <int KIND>
 __global__ void k_bn_bwd1(TGeo g, const float* __restrict__ z, float* gamma, float* beta,
                           const float* __restrict__ mean, const float* __restrict__ inv, const float* __restrict__ out,
                           const float* __restrict__ dout, float* __restrict__ dgamma, float* __restrict__ dbeta,
                           float* __restrict__ dz, double* __restrict__ s1, double* __restrict__ s2, int Kp, int nbr,
                           int rows_per_block, float fuse_lr, SolverDev sv) {
+  constexpr bool SOLVER = KIND != SK_VANILLA, MOM = KIND == SK_MOMENTUM;
   int C = nbr * Kp;
   int r0 = blockIdx.x * rows_per_block, r1 = min(r0 + rows_per_block, g.M);
   for (int cc = threadIdx.x; cc < C; cc += blockDim.x) {
@@ -345,7 +366,15 @@ __global__ void k_bn_bwd1(TGeo g, const float* __restrict__ z, float* gamma, flo
       float bt = beta[(size_t)r * C + cc];
       float y = gm * xh + bt;
       float gg = y > 0.f ? g0 : 0.f;
-      if (SOLVER) {           // (fused steps only: fuse_lr != 0)
+      if (KIND == SK_ADAM) {  // (fused steps only: fuse_lr != 0)
+        const size_t e = (size_t)r * C + cc;
+        float wg = gm, wb = bt, mg = sv.m1gamma[e], ug = sv.m2gamma[e], mb = sv.m1beta[e], ub = sv.m2beta[e];
+        adam_step(wg, mg, ug, gg * xh, fuse_lr, sv.l2, sv.clip, sv.ak);
+        adam_step(wb, mb, ub, gg, fuse_lr, sv.l2, sv.clip, sv.ak);
+        sv.m1gamma[e] = mg; sv.m2gamma[e] = ug; sv.m1beta[e] = mb; sv.m2beta[e] = ub;
+        gamma[e] = wg;
+        beta[e] = wb;
+      } else if (SOLVER) {    // (fused steps only: fuse_lr != 0)
         float wg = gm, wb = bt, vg = 0.f, vb = 0.f;
         if (MOM) { vg = sv.vgamma[(size_t)r * C + cc]; vb = sv.vbeta[(size_t)r * C + cc]; }
         solver_step<MOM>(wg, vg, gg * xh, fuse_lr, sv.mu, sv.l2, sv.clip);
@@ -1060,12 +1089,26 @@ __global__ void k_axpy(float* __restrict__ p, const float* __restrict__ g, float
 }
 // The solver form of the same sweep (agz_trainer_set_solver): solver_step over n4 float4 of p / g (/ v with MOM), g scaled by gs first
 // (grad_scale of the two-pass and data-parallel paths).  Grid-stride, the grid sized by the CU count: it streams p, g, v -> p, v.
-template <bool MOM>
+// SK_ADAM (agz_trainer_set_adam): adam_step over p / g / m / m2 (v is then the first moment, m2 the second); the two arguments it adds
+// come last and the other kinds do not read them.
+template <int KIND>
 __global__ __launch_bounds__(256) void k_solver_sweep(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ v, size_t n4,
-                                                      float lr, float gs, float mu, float l2, float clip) {
+                                                      float lr, float gs, float mu, float l2, float clip, float* __restrict__ m2, AdamK ak) {
+  constexpr bool MOM = KIND == SK_MOMENTUM;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
     const float4 gg = reinterpret_cast<const float4*>(g)[i];
     float4 w = reinterpret_cast<float4*>(p)[i];
+    if (KIND == SK_ADAM) {
+      float4 m = reinterpret_cast<float4*>(v)[i], u = reinterpret_cast<float4*>(m2)[i];
+      adam_step(w.x, m.x, u.x, gs * gg.x, lr, l2, clip, ak);
+      adam_step(w.y, m.y, u.y, gs * gg.y, lr, l2, clip, ak);
+      adam_step(w.z, m.z, u.z, gs * gg.z, lr, l2, clip, ak);
+      adam_step(w.w, m.w, u.w, gs * gg.w, lr, l2, clip, ak);
+      reinterpret_cast<float4*>(v)[i] = m;
+      reinterpret_cast<float4*>(m2)[i] = u;
+      reinterpret_cast<float4*>(p)[i] = w;
+      continue;
+    }
     float4 vv = make_float4(0.f, 0.f, 0.f, 0.f);
     if (MOM) vv = reinterpret_cast<float4*>(v)[i];
     solver_step<MOM>(w.x, vv.x, gs * gg.x, lr, mu, l2, clip);
@@ -1949,6 +1992,18 @@ struct agz_trainer {
   agz_solver_conf solver{0.f, 0.f, 0.f, 0};
   float* V = nullptr;
   bool solver_on() const { return solver.momentum != 0.f || solver.l2reg != 0.f || solver.clip != 0.f; }
+  // Adam (agz_trainer_set_adam; excludes a momentum): M1 / M2, two flat buffers laid out like P / G / V, exist only while adam.on (allocated
+  // and zeroed when it is turned on, released when it is turned off); adam_t counts the solver steps taken since.  agz_trainer_apply
+  // advances adam_t; the fused kernels of the same step, which run before it, are given the constants of adam_t + 1.
+  agz_adam_conf adam{0.9f, 0.999f, 1e-8f, 0};
+  float* M1 = nullptr;
+  float* M2 = nullptr;
+  uint64_t adam_t = 0;
+  AdamK adam_k(uint64_t step) const {
+    const double b1 = adam.beta1, b2 = adam.beta2, n = (double)step;
+    return AdamK{adam.beta1, (float)(1.0 - b1), adam.beta2, (float)(1.0 - b2), (float)(1.0 / (1.0 - std::pow(b1, n))),
+                 (float)(1.0 / (1.0 - std::pow(b2, n))), adam.eps};
+  }
   // running BatchNorm statistics (agz_trainer_set_bn_tracking; BnTrack above).  bn_st: one device allocation, made when tracking is first
   // turned on (or a state is first set / loaded): per finalize launch — tower layer 0 .. L, then the heads — S_mean[C] | S_var[C] | N[ops],
   // C the launch's (padded) channels.  bn_have[op]: N(op) > 0, known on the host without a read-back (a tracked forward makes every N >= 1).
@@ -2257,9 +2312,14 @@ int agz_trainer::forward_backward_dev(const float* planes, const float* pi, cons
     if (sw != s && l < L) AGZ_HIP_TRY(hipStreamWaitEvent(s, ev_split, 0));   // the previous layer's weight gradient has taken its copy of dz
     {
       // (the solver variants only on a fused step with an option set: everything else launches the instantiation without them)
-      const bool sv_on = fuse_lr != 0.f && solver_on(), sv_mom = sv_on && solver.momentum != 0.f;
-      const SolverDev sd{solver.momentum, solver.l2reg, solver.clip, sv_mom ? V + ly.o_gamma : nullptr, sv_mom ? V + ly.o_beta : nullptr};
-      auto* bwd1 = sv_mom ? k_bn_bwd1<true, true> : sv_on ? k_bn_bwd1<true, false> : k_bn_bwd1<false, false>;
+      const bool sv_adam = fuse_lr != 0.f && adam.on, sv_on = fuse_lr != 0.f && solver_on(), sv_mom = sv_on && solver.momentum != 0.f;
+      SolverDev sd{solver.momentum, solver.l2reg, solver.clip, sv_mom ? V + ly.o_gamma : nullptr, sv_mom ? V + ly.o_beta : nullptr,
+                   AdamK{}, nullptr, nullptr, nullptr, nullptr};
+      if (sv_adam) {   // (the step agz_trainer_apply is about to count: adam_t + 1)
+        sd.ak = adam_k(adam_t + 1);
+        sd.m1gamma = M1 + ly.o_gamma; sd.m1beta = M1 + ly.o_beta; sd.m2gamma = M2 + ly.o_gamma; sd.m2beta = M2 + ly.o_beta;
+      }
+      auto* bwd1 = sv_adam ? k_bn_bwd1<SK_ADAM> : sv_mom ? k_bn_bwd1<SK_MOMENTUM> : sv_on ? k_bn_bwd1<SK_OPTIONS> : k_bn_bwd1<SK_VANILLA>;
       hipLaunchKernelGGL(bwd1, dim3(nblk(g.M, RPB)), dim3(std::min(C, 512)), 0, s, g, ly.z, P + ly.o_gamma, P + ly.o_beta, ly.mean, ly.inv,
                          ly.out, dcur, G + ly.o_gamma, G + ly.o_beta, dz, s1, s2, Kp, ly.nbr, RPB, fuse_lr, sd);
     }
@@ -2520,6 +2580,8 @@ void agz_trainer_destroy(agz_trainer* t) {
   if (t->dz_h2) hipFree(t->dz_h2);
   if (t->x_h2) hipFree(t->x_h2);
   if (t->V) hipFree(t->V);
+  if (t->M1) hipFree(t->M1);
+  if (t->M2) hipFree(t->M2);
   delete t;
 }
 
@@ -2661,6 +2723,8 @@ int agz_trainer_set_solver(agz_trainer* t, const agz_solver_conf* c) {
   AGZ_REQUIRE(solver_conf_valid(c), AGZ_E_INVALID,
               "agz_trainer_set_solver: need 0 <= momentum < 1, l2reg >= 0, clip >= 0, all finite, reserved = 0 (got %g, %g, %g, %d)",
               (double)c->momentum, (double)c->l2reg, (double)c->clip, (int)c->reserved);
+  AGZ_REQUIRE(!(c->momentum != 0.f && t->adam.on), AGZ_E_STATE,
+              "agz_trainer_set_solver: a momentum and Adam exclude each other (turn Adam off first: agz_trainer_set_adam)");
   AGZ_HIP_TRY(hipSetDevice(t->ctx->device));
   AGZ_HIP_TRY(hipStreamSynchronize(t->ctx->stream));
   if (c->momentum != 0.f && !t->V) {
@@ -2705,11 +2769,84 @@ int agz_trainer_set_velocity(agz_trainer* t, int i, const float* host, size_t n)
 }
 int agz_trainer_reset_solver(agz_trainer* t) {
   AGZ_REQUIRE(t, AGZ_E_INVALID, "agz_trainer_reset_solver: NULL trainer");
-  if (!t->V) return AGZ_OK;
+  t->adam_t = 0;
+  if (!t->V && !t->M1) return AGZ_OK;
   AGZ_HIP_TRY(hipSetDevice(t->ctx->device));
-  AGZ_HIP_TRY(hipMemsetAsync(t->V, 0, t->n_flat * sizeof(float), t->ctx->stream));
+  if (t->V) AGZ_HIP_TRY(hipMemsetAsync(t->V, 0, t->n_flat * sizeof(float), t->ctx->stream));
+  if (t->M1) {
+    AGZ_HIP_TRY(hipMemsetAsync(t->M1, 0, t->n_flat * sizeof(float), t->ctx->stream));
+    AGZ_HIP_TRY(hipMemsetAsync(t->M2, 0, t->n_flat * sizeof(float), t->ctx->stream));
+  }
   AGZ_HIP_TRY(hipStreamSynchronize(t->ctx->stream));
   return AGZ_OK;
+}
+
+// ---- Adam (gorgonia.NewAdamSolver on the solver line, dualnet/meta.go:20; the definition: include/agz.h, DESIGN §2 `solver-adam`) ------
+static bool adam_conf_valid(const agz_adam_conf* c) {
+  return std::isfinite(c->beta1) && std::isfinite(c->beta2) && std::isfinite(c->eps) && c->beta1 >= 0.f && c->beta1 < 1.f && c->beta2 >= 0.f &&
+         c->beta2 < 1.f && c->eps > 0.f && (c->on == 0 || c->on == 1);
+}
+// on for the first time: the two moment buffers, zeroed, and t = 0; off: both released, t = 0.  The settings change only if the call
+// succeeds.  (Sharded: a local call; every rank makes it alike.)
+int agz_trainer_set_adam(agz_trainer* t, const agz_adam_conf* c) {
+  AGZ_REQUIRE(t && c, AGZ_E_INVALID, "agz_trainer_set_adam: NULL argument");
+  AGZ_REQUIRE(adam_conf_valid(c), AGZ_E_INVALID, "agz_trainer_set_adam: need 0 <= beta1 < 1, 0 <= beta2 < 1, eps > 0, all finite, on = 0 / 1 (got %g, %g, %g, %d)",
+              (double)c->beta1, (double)c->beta2, (double)c->eps, (int)c->on);
+  AGZ_REQUIRE(!(c->on && t->solver.momentum != 0.f), AGZ_E_STATE,
+              "agz_trainer_set_adam: Adam and a momentum exclude each other (set the momentum to 0 first: agz_trainer_set_solver)");
+  AGZ_HIP_TRY(hipSetDevice(t->ctx->device));
+  AGZ_HIP_TRY(hipStreamSynchronize(t->ctx->stream));
+  if (c->on && !t->M1) {
+    const size_t bytes = t->n_flat * sizeof(float);
+    float* m1 = nullptr; float* m2 = nullptr;
+    if (hipMalloc(&m1, bytes) != hipSuccess || hipMalloc(&m2, bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      if (m1) hipFree(m1);
+      agz::set_error("agz_trainer_set_adam: out of device memory for the moments (2 x %zu bytes)", bytes);
+      return AGZ_E_NOMEM;
+    }
+    if (hipMemsetAsync(m1, 0, bytes, t->ctx->stream) != hipSuccess || hipMemsetAsync(m2, 0, bytes, t->ctx->stream) != hipSuccess ||
+        hipStreamSynchronize(t->ctx->stream) != hipSuccess) {
+      hipFree(m1); hipFree(m2);
+      agz::set_error("agz_trainer_set_adam: clearing the moments failed");
+      return AGZ_E_HIP;
+    }
+    t->M1 = m1; t->M2 = m2; t->adam_t = 0;
+  } else if (!c->on && t->M1) {
+    AGZ_HIP_TRY(hipFree(t->M1)); t->M1 = nullptr;
+    AGZ_HIP_TRY(hipFree(t->M2)); t->M2 = nullptr;
+    t->adam_t = 0;
+  }
+  t->adam = *c;
+  return AGZ_OK;
+}
+int agz_trainer_get_adam(const agz_trainer* t, agz_adam_conf* out, uint64_t* step) {
+  AGZ_REQUIRE(t, AGZ_E_INVALID, "agz_trainer_get_adam: NULL trainer");
+  if (out) *out = t->adam;
+  if (step) *step = t->adam_t;
+  return AGZ_OK;
+}
+int agz_trainer_get_moments(const agz_trainer* t, int i, float* m, float* v, size_t n) {
+  AGZ_REQUIRE(t && m && v, AGZ_E_INVALID, "agz_trainer_get_moments: NULL argument");
+  AGZ_REQUIRE(i >= 0 && i < (int)t->prefs.size() && n >= pref_size(t->prefs[i]), AGZ_E_INVALID, "agz_trainer_get_moments: bad argument");
+  if (!t->M1) {   // (Adam off: no moments)
+    std::fill(m, m + pref_size(t->prefs[i]), 0.f); std::fill(v, v + pref_size(t->prefs[i]), 0.f);
+    return AGZ_OK;
+  }
+  AGZ_HIP_TRY(hipSetDevice(t->ctx->device));
+  AGZ_HIP_TRY(hipStreamSynchronize(t->ctx->stream));
+  int r = xfer_param(t, t->M1, i, m, 1);
+  return r != AGZ_OK ? r : xfer_param(t, t->M2, i, v, 1);
+}
+int agz_trainer_set_moments(agz_trainer* t, int i, const float* m, const float* v, size_t n) {
+  AGZ_REQUIRE(t && m && v, AGZ_E_INVALID, "agz_trainer_set_moments: NULL argument");
+  AGZ_REQUIRE(i >= 0 && i < (int)t->prefs.size(), AGZ_E_INVALID, "agz_trainer_set_moments: bad index");
+  AGZ_REQUIRE(n == pref_size(t->prefs[i]), AGZ_E_INVALID, "agz_trainer_set_moments(%s): need %zu floats, got %zu", t->prefs[i].name.c_str(), pref_size(t->prefs[i]), n);
+  AGZ_REQUIRE(t->M1, AGZ_E_STATE, "agz_trainer_set_moments: the trainer has no moments (turn Adam on first: agz_trainer_set_adam)");
+  AGZ_HIP_TRY(hipSetDevice(t->ctx->device));
+  AGZ_HIP_TRY(hipStreamSynchronize(t->ctx->stream));
+  int r = xfer_param(t, t->M1, i, const_cast<float*>(m), 0);
+  return r != AGZ_OK ? r : xfer_param(t, t->M2, i, const_cast<float*>(v), 0);
 }
 
 // A sharded trainer draws its rows' slice of the GLOBAL tensors: the stream position of its first element, the Glorot deviation of the
@@ -2805,15 +2942,18 @@ int agz_trainer_forward_backward_dev(agz_trainer* t, const float* planes_dev, co
 // solver.Step with options (agz_trainer_set_solver): the regions the vanilla step sweeps with k_axpy, through k_solver_sweep
 static int apply_solver(agz_trainer* t, float lr, float grad_scale) {
   const agz_solver_conf& sc = t->solver;
-  const bool mom = sc.momentum != 0.f;
+  const bool mom = sc.momentum != 0.f, adam = t->adam.on != 0;
+  if (adam) t->adam_t++;   // one count per solver step: the fused kernels of this step were given the same value
+  const AdamK ak = adam ? t->adam_k(t->adam_t) : AdamK{};
   hipStream_t s = t->ctx->stream;
   auto sweep = [&](size_t off, size_t n) {   // (every region starts and ends on a multiple of four floats: take() in agz_trainer_create)
     const size_t n4 = n / 4;
     const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>(nblk(n4), (size_t)t->ctx->num_cus * 8));
-    if (mom) hipLaunchKernelGGL(k_solver_sweep<true>, dim3(grid), dim3(256), 0, s, t->P + off, t->G + off, t->V + off, n4, lr, grad_scale, sc.momentum, sc.l2reg, sc.clip);
-    else hipLaunchKernelGGL(k_solver_sweep<false>, dim3(grid), dim3(256), 0, s, t->P + off, t->G + off, (float*)nullptr, n4, lr, grad_scale, sc.momentum, sc.l2reg, sc.clip);
+    if (adam) hipLaunchKernelGGL(k_solver_sweep<SK_ADAM>, dim3(grid), dim3(256), 0, s, t->P + off, t->G + off, t->M1 + off, n4, lr, grad_scale, 0.f, sc.l2reg, sc.clip, t->M2 + off, ak);
+    else if (mom) hipLaunchKernelGGL(k_solver_sweep<SK_MOMENTUM>, dim3(grid), dim3(256), 0, s, t->P + off, t->G + off, t->V + off, n4, lr, grad_scale, sc.momentum, sc.l2reg, sc.clip, (float*)nullptr, ak);
+    else hipLaunchKernelGGL(k_solver_sweep<SK_OPTIONS>, dim3(grid), dim3(256), 0, s, t->P + off, t->G + off, (float*)nullptr, n4, lr, grad_scale, sc.momentum, sc.l2reg, sc.clip, (float*)nullptr, ak);
   };
-  if (t->fused_done) {   // k_bn_bwd1<true, .> stepped the tower's gamma / beta and their velocity: the filters and the head region remain
+  if (t->fused_done) {   // k_bn_bwd1<SK_OPTIONS / SK_MOMENTUM / SK_ADAM> stepped the tower's gamma / beta and their velocity: the filters and the head region remain
     AGZ_REQUIRE(grad_scale == 1.0f, AGZ_E_STATE, "agz_trainer_apply: a fused step takes no gradient scale");
     for (const auto& ly : t->layers) sweep(ly.o_wf, (size_t)9 * ly.Cout_p * ly.Cin_p);
     sweep(t->o_hc, t->n_flat - t->o_hc);
@@ -2827,7 +2967,7 @@ static int apply_solver(agz_trainer* t, float lr, float grad_scale) {
 int agz_trainer_apply(agz_trainer* t, float lr, float grad_scale) {  // solver.Step (meta.go:40): w -= lr * grad
   AGZ_REQUIRE(t, AGZ_E_INVALID, "trainer is NULL");
   AGZ_HIP_TRY(hipSetDevice(t->ctx->device));
-  if (t->solver_on()) return apply_solver(t, lr, grad_scale);
+  if (t->solver_on() || t->adam.on) return apply_solver(t, lr, grad_scale);
   if (t->fused_done) {
     // the backward that just ran stepped the tower's gamma / beta itself (k_bn_bwd1): the filters of every layer and the head region remain
     AGZ_REQUIRE(grad_scale == 1.0f, AGZ_E_STATE, "agz_trainer_apply: a fused step takes no gradient scale");
@@ -3164,32 +3304,69 @@ static agz_net_conf global_conf(const agz_trainer* t) {
 // An AGZTRN02 file is checked for its full length BEFORE anything of it is loaded (the header has been read; the position is restored):
 // a truncated file is rejected with the trainer's parameters, options and velocity untouched.  nr: ranks the global tensors are split over.
 // (AGZTRN03: v2 says whether the inner form carries a velocity; the BatchNorm block after it is read and validated here as well, into *bn)
-static bool checkpoint_complete(FILE* f, const agz_trainer* t, int nr, bool v2 = true, BnBlock* bn = nullptr) {
+// (AGZTRN04 / inner form 3, ad != nullptr: the learnables, agz_solver_conf, agz_adam_conf, uint64 t, every tensor's first and then second
+// moment.  Its options, its counter and every count word are read and checked here too, into *ad, so that an inconsistent file changes nothing.)
+struct AdamHead { agz_solver_conf sc; agz_adam_conf ac; uint64_t step; };
+static bool checkpoint_complete(FILE* f, const agz_trainer* t, int nr, bool v2 = true, BnBlock* bn = nullptr, AdamHead* ad = nullptr) {
   const long at = ftell(f);
-  uint64_t body = v2 ? sizeof(agz_solver_conf) : 0;
-  for (const auto& p : t->prefs) body += (v2 ? 2 : 1) * (8 + 4 * (uint64_t)pref_size(p) * (pref_batch_shaped(p) ? nr : 1));
+  const int groups = ad ? 3 : v2 ? 2 : 1;
+  uint64_t body = ad ? sizeof(agz_solver_conf) + sizeof(agz_adam_conf) + 8 : v2 ? sizeof(agz_solver_conf) : 0;
+  for (const auto& p : t->prefs) body += groups * (8 + 4 * (uint64_t)pref_size(p) * (pref_batch_shaped(p) ? nr : 1));
   const uint64_t need = (uint64_t)at + body + (bn ? bn_block_bytes(t) : 0);
   bool ok = at >= 0 && fseek(f, 0, SEEK_END) == 0 && (uint64_t)ftell(f) == need;
+  if (ok && ad) {
+    ok = fseek(f, at, SEEK_SET) == 0;
+    for (int k = 0; ok && k < groups; k++) {
+      if (k == 1)
+        ok = fread(&ad->sc, sizeof(ad->sc), 1, f) == 1 && fread(&ad->ac, sizeof(ad->ac), 1, f) == 1 && fread(&ad->step, 8, 1, f) == 1 &&
+             solver_conf_valid(&ad->sc) && ad->sc.momentum == 0.f && adam_conf_valid(&ad->ac) && ad->ac.on == 1;
+      for (size_t i = 0; ok && i < t->prefs.size(); i++) {
+        const TParamRef& p = t->prefs[i];
+        uint64_t cnt = 0;
+        ok = fread(&cnt, 8, 1, f) == 1 && cnt == (uint64_t)pref_size(p) * (pref_batch_shaped(p) ? nr : 1) && fseek(f, (long)(cnt * 4), SEEK_CUR) == 0;
+      }
+    }
+  }
   if (ok && bn) ok = fseek(f, (long)((uint64_t)at + body), SEEK_SET) == 0 && bn_block_read(t, f, *bn);
   return fseek(f, at, SEEK_SET) == 0 && ok;
 }
-// the magic of a checkpoint (and, for AGZTRN03, the uint32 naming the inner form): form 1 / 2 / 3, v2 = a velocity follows the learnables
-static bool read_magic(FILE* f, int* form, bool* v2) {
+// the magic of a checkpoint (and, for AGZTRN03, the uint32 naming the inner form): form 1 / 2 / 3 / 4, v2 = a velocity follows the
+// learnables, ad = the Adam block follows them (AGZTRN04, or AGZTRN03 with inner form 3)
+static bool read_magic(FILE* f, int* form, bool* v2, bool* ad) {
   char magic[8];
-  if (fread(magic, 1, 8, f) != 8 || memcmp(magic, "AGZTRN0", 7) != 0 || magic[7] < '1' || magic[7] > '3') return false;
+  if (fread(magic, 1, 8, f) != 8 || memcmp(magic, "AGZTRN0", 7) != 0 || magic[7] < '1' || magic[7] > '4') return false;
   *form = magic[7] - '0';
   *v2 = *form == 2;
+  *ad = *form == 4;
   if (*form == 3) {
     uint32_t inner = 0;
-    if (fread(&inner, 4, 1, f) != 1 || (inner != 1 && inner != 2)) return false;
+    if (fread(&inner, 4, 1, f) != 1 || inner < 1 || inner > 3) return false;
     *v2 = inner == 2;
+    *ad = inner == 3;
   }
   return true;
 }
 static bool write_magic(const agz_trainer* t, FILE* f) {
-  if (t->bn_all()) { const uint32_t inner = t->V ? 2u : 1u; return fwrite("AGZTRN03", 1, 8, f) == 8 && fwrite(&inner, 4, 1, f) == 1; }
-  return fwrite(t->V ? "AGZTRN02" : "AGZTRN01", 1, 8, f) == 8;
+  if (t->bn_all()) { const uint32_t inner = t->M1 ? 3u : t->V ? 2u : 1u; return fwrite("AGZTRN03", 1, 8, f) == 8 && fwrite(&inner, 4, 1, f) == 1; }
+  return fwrite(t->M1 ? "AGZTRN04" : t->V ? "AGZTRN02" : "AGZTRN01", 1, 8, f) == 8;
 }
+// the options an Adam checkpoint carries, into the trainer (the head was validated by checkpoint_complete): momentum 0 releases a
+// velocity, Adam on allocates the moments if there are none
+static int adam_head_apply(agz_trainer* t, const AdamHead& h) {
+  int r = agz_trainer_set_solver(t, &h.sc);
+  if (r == AGZ_OK) r = agz_trainer_set_adam(t, &h.ac);
+  if (r == AGZ_OK) t->adam_t = h.step;
+  return r;
+}
+// a file with a velocity, loaded into a trainer with Adam on: the file's solver is taken and Adam turned off
+static int adam_off(agz_trainer* t) {
+  if (!t->adam.on) return AGZ_OK;
+  agz_adam_conf c = t->adam;
+  c.on = 0;
+  return agz_trainer_set_adam(t, &c);
+}
+// group 0 / 1 / 2 of a checkpoint's tensor blocks: the learnables, then the velocity or (Adam) the first moments, then the second moments
+static float* group_buf(const agz_trainer* t, int group) { return group == 0 ? t->P : t->M1 ? (group == 1 ? t->M1 : t->M2) : t->V; }
 
 // Sharded save (collective): rank 0 writes the plain trainer's file at the global batch.  Tensor by tensor, batch-shaped ones are gathered
 // from every rank (rows in rank order = the global tensor) through one device buffer of n slices; nothing larger than one global tensor is
@@ -3211,12 +3388,14 @@ static int save_sharded(const agz_trainer* t, const char* path) {
   bool ok = f == nullptr || (write_magic(t, f) && fwrite(&gc, sizeof(gc), 1, f) == 1 && fwrite(&np, 8, 1, f) == 1);
   std::vector<float> v, all;
   const int np_i = (int)t->prefs.size();
-  for (int k = 0; k < (t->V ? 2 * np_i : np_i); k++) {   // the learnables, then (02) the options and every tensor's velocity
+  // the learnables, then (02) the options and every tensor's velocity, or (04) the options, Adam's settings and counter and both moments
+  for (int k = 0; k < (t->M1 ? 3 : t->V ? 2 : 1) * np_i; k++) {
     const int i = k % np_i;
     if (k == np_i && f && ok) ok = fwrite(&t->solver, sizeof(t->solver), 1, f) == 1;
+    if (k == np_i && f && ok && t->M1) ok = fwrite(&t->adam, sizeof(t->adam), 1, f) == 1 && fwrite(&t->adam_t, 8, 1, f) == 1;
     const TParamRef& p = t->prefs[i];
     v.assign(pref_size(p), 0.f);
-    if ((k < np_i ? agz_trainer_get_param(t, i, v.data(), v.size()) : agz_trainer_get_velocity(t, i, v.data(), v.size())) != AGZ_OK && rc == AGZ_OK) rc = AGZ_E_HIP;
+    if ((k < np_i ? agz_trainer_get_param(t, i, v.data(), v.size()) : xfer_param(t, group_buf(t, k / np_i), i, v.data(), 1)) != AGZ_OK && rc == AGZ_OK) rc = AGZ_E_HIP;
     const float* out = v.data();
     uint64_t cnt = v.size();
     if (pref_batch_shaped(p)) {
@@ -3246,19 +3425,25 @@ static int load_sharded(agz_trainer* t, const char* path) {
   agz_net_conf c;
   uint64_t np = 0;
   const agz_net_conf gc = global_conf(t);
-  int form = 0; bool v2 = false;
-  bool ok = read_magic(f, &form, &v2) && fread(&c, sizeof(c), 1, f) == 1 && fread(&np, 8, 1, f) == 1;
+  int form = 0; bool v2 = false, ad = false;
+  bool ok = read_magic(f, &form, &v2, &ad) && fread(&c, sizeof(c), 1, f) == 1 && fread(&np, 8, 1, f) == 1;
   if (ok) ok = memcmp(&c, &gc, sizeof(c)) == 0 && np == t->prefs.size();
   if (!ok) { fclose(f); agz::set_error("agz_trainer_load: %s is not a checkpoint of this trainer configuration (global batch %d)", path, gc.BatchSize); return AGZ_E_INVALID; }
   BnBlock bnb;
-  if ((v2 || form == 3) && !checkpoint_complete(f, t, t->n_ranks, v2, form == 3 ? &bnb : nullptr)) { fclose(f); agz::set_error("agz_trainer_load: %s is truncated or mismatched", path); return AGZ_E_INVALID; }
+  AdamHead ah;
+  if ((v2 || ad || form == 3) && !checkpoint_complete(f, t, t->n_ranks, v2, form == 3 ? &bnb : nullptr, ad ? &ah : nullptr)) { fclose(f); agz::set_error("agz_trainer_load: %s is truncated or mismatched", path); return AGZ_E_INVALID; }
   const int np_i = (int)t->prefs.size();
-  for (int k = 0; ok && k < (v2 ? 2 * np_i : np_i); k++) {
+  for (int k = 0; ok && k < (ad ? 3 : v2 ? 2 : 1) * np_i; k++) {
     const int i = k % np_i;
-    if (k == np_i) {   // (02) the options, then every tensor's velocity
+    if (k == np_i && ad) {   // (04) the options, Adam's settings and counter (read and checked above), then both moments
+      ok = fseek(f, (long)(sizeof(ah.sc) + sizeof(ah.ac) + 8), SEEK_CUR) == 0;
+      if (!ok) break;
+      const int r = adam_head_apply(t, ah);
+      if (r != AGZ_OK) { fclose(f); return r; }
+    } else if (k == np_i) {   // (02) the options, then every tensor's velocity
       agz_solver_conf sc;
       ok = fread(&sc, sizeof(sc), 1, f) == 1 && solver_conf_valid(&sc) && sc.momentum != 0.f;
-      if (ok && agz_trainer_set_solver(t, &sc) != AGZ_OK) { fclose(f); return AGZ_E_HIP; }
+      if (ok && (adam_off(t) != AGZ_OK || agz_trainer_set_solver(t, &sc) != AGZ_OK)) { fclose(f); return AGZ_E_HIP; }
       if (!ok) break;
     }
     const TParamRef& p = t->prefs[i];
@@ -3268,13 +3453,13 @@ static int load_sharded(agz_trainer* t, const char* path) {
     uint64_t cnt = 0;
     ok = fread(&cnt, 8, 1, f) == 1 && cnt == want && fseek(f, (long)(skip * 4), SEEK_CUR) == 0 && fread(v.data(), 4, v.size(), f) == v.size() &&
          fseek(f, (long)((want - skip - v.size()) * 4), SEEK_CUR) == 0;
-    if (ok && (k < np_i ? agz_trainer_set_param(t, i, v.data(), v.size()) : agz_trainer_set_velocity(t, i, v.data(), v.size())) != AGZ_OK) { fclose(f); return AGZ_E_HIP; }
+    if (ok && (k < np_i ? agz_trainer_set_param(t, i, v.data(), v.size()) : xfer_param(t, group_buf(t, k / np_i), i, v.data(), 0)) != AGZ_OK) { fclose(f); return AGZ_E_HIP; }
   }
   fclose(f);
   AGZ_REQUIRE(ok, AGZ_E_INVALID, "agz_trainer_load: %s is truncated or mismatched", path);
   // 03: the tracking setting and state the file carries; 01 / 02: no statistics (N = 0), the setting stays
   { int r = form == 3 ? bn_block_apply(t, bnb) : agz_trainer_reset_bn_stats(t); if (r != AGZ_OK) return r; }
-  if (!v2) return agz_trainer_reset_solver(t);   // a file without velocity: v := 0, the options stay
+  if (!v2 && !ad) return agz_trainer_reset_solver(t);   // a file without solver state: v := 0 (Adam: the moments and t := 0), the options stay
   return AGZ_OK;
 }
 
@@ -3289,6 +3474,11 @@ static int load_sharded(agz_trainer* t, const char* path) {
 // order of agz_net_set_bn_stats) {uint64 C, double N, double S_mean[C], double S_var[C]}.  Any other trainer writes the 01 / 02 file it
 // always wrote.  Load: 03 sets the tracking setting and state it carries (checked for its full length and a consistent block before
 // anything is changed); 01 / 02 reset the state to N = 0 and keep the setting.
+// A trainer with Adam on (agz_trainer_set_adam) writes "AGZTRN04": the 01 payload, agz_solver_conf (16 bytes, momentum 0), agz_adam_conf
+// (16 bytes), uint64 t, then per tensor {n, n floats} of the first moment and per tensor {n, n floats} of the second, in the payload's order;
+// with running statistics as well it is AGZTRN03 with inner form 3.  Load: the Adam forms set the options, t and the moments (Adam turned
+// on, the moments allocated), checked for their full length, valid options and every count word before anything is changed; 01 loaded into
+// a trainer with Adam on zeroes the moments and t and keeps the setting; 02 takes the file's solver and turns Adam off.
 int agz_trainer_save(const agz_trainer* t, const char* path) {
   AGZ_REQUIRE(t && path, AGZ_E_INVALID, "agz_trainer_save: NULL argument");
   if (t->sharded) return save_sharded(t, path);
@@ -3312,6 +3502,16 @@ int agz_trainer_save(const agz_trainer* t, const char* path) {
       ok = fwrite(&cnt, 8, 1, f) == 1 && fwrite(v.data(), 4, cnt, f) == cnt;
     }
   }
+  if (t->M1) {   // (04) the options, Adam's settings and counter, every tensor's first moment, then every tensor's second moment
+    ok = ok && fwrite(&t->solver, sizeof(t->solver), 1, f) == 1 && fwrite(&t->adam, sizeof(t->adam), 1, f) == 1 && fwrite(&t->adam_t, 8, 1, f) == 1;
+    for (int k = 0; ok && k < 2 * (int)t->prefs.size(); k++) {
+      const int i = k % (int)t->prefs.size();
+      std::vector<float> v(pref_size(t->prefs[i]));
+      if (xfer_param(t, group_buf(t, 1 + k / (int)t->prefs.size()), i, v.data(), 1) != AGZ_OK) { fclose(f); return AGZ_E_HIP; }
+      uint64_t cnt = v.size();
+      ok = fwrite(&cnt, 8, 1, f) == 1 && fwrite(v.data(), 4, cnt, f) == cnt;
+    }
+  }
   if (ok && t->bn_all()) ok = bn_block_write(t, f);
   ok = (fclose(f) == 0) && ok;
   AGZ_REQUIRE(ok, AGZ_E_INVALID, "agz_trainer_save: write to %s failed", path);
@@ -3325,12 +3525,13 @@ int agz_trainer_load(agz_trainer* t, const char* path) {
   AGZ_REQUIRE(f, AGZ_E_INVALID, "agz_trainer_load: cannot open %s", path);
   agz_net_conf c;
   uint64_t np = 0;
-  int form = 0; bool v2 = false;
-  bool ok = read_magic(f, &form, &v2) && fread(&c, sizeof(c), 1, f) == 1 && fread(&np, 8, 1, f) == 1;
+  int form = 0; bool v2 = false, ad = false;
+  bool ok = read_magic(f, &form, &v2, &ad) && fread(&c, sizeof(c), 1, f) == 1 && fread(&np, 8, 1, f) == 1;
   if (ok) ok = memcmp(&c, &t->conf, sizeof(c)) == 0 && np == t->prefs.size();
   if (!ok) { fclose(f); agz::set_error("agz_trainer_load: %s is not a checkpoint of this trainer configuration", path); return AGZ_E_INVALID; }
   BnBlock bnb;
-  if ((v2 || form == 3) && !checkpoint_complete(f, t, 1, v2, form == 3 ? &bnb : nullptr)) { fclose(f); agz::set_error("agz_trainer_load: %s is truncated or mismatched", path); return AGZ_E_INVALID; }
+  AdamHead ah;
+  if ((v2 || ad || form == 3) && !checkpoint_complete(f, t, 1, v2, form == 3 ? &bnb : nullptr, ad ? &ah : nullptr)) { fclose(f); agz::set_error("agz_trainer_load: %s is truncated or mismatched", path); return AGZ_E_INVALID; }
   for (int i = 0; ok && i < (int)t->prefs.size(); i++) {
     uint64_t cnt = 0;
     std::vector<float> v(pref_size(t->prefs[i]));
@@ -3340,7 +3541,7 @@ int agz_trainer_load(agz_trainer* t, const char* path) {
   if (ok && v2) {
     agz_solver_conf sc;
     ok = fread(&sc, sizeof(sc), 1, f) == 1 && solver_conf_valid(&sc) && sc.momentum != 0.f;
-    if (ok && agz_trainer_set_solver(t, &sc) != AGZ_OK) { fclose(f); return AGZ_E_HIP; }
+    if (ok && (adam_off(t) != AGZ_OK || agz_trainer_set_solver(t, &sc) != AGZ_OK)) { fclose(f); return AGZ_E_HIP; }
     for (int i = 0; ok && i < (int)t->prefs.size(); i++) {
       uint64_t cnt = 0;
       std::vector<float> v(pref_size(t->prefs[i]));
@@ -3348,11 +3549,22 @@ int agz_trainer_load(agz_trainer* t, const char* path) {
       if (ok && agz_trainer_set_velocity(t, i, v.data(), v.size()) != AGZ_OK) { fclose(f); return AGZ_E_HIP; }
     }
   }
+  if (ok && ad) {   // (the options, Adam's settings and counter were read and checked by checkpoint_complete)
+    ok = fseek(f, (long)(sizeof(ah.sc) + sizeof(ah.ac) + 8), SEEK_CUR) == 0;
+    if (ok) { const int r = adam_head_apply(t, ah); if (r != AGZ_OK) { fclose(f); return r; } }
+    for (int k = 0; ok && k < 2 * (int)t->prefs.size(); k++) {
+      const int i = k % (int)t->prefs.size();
+      uint64_t cnt = 0;
+      std::vector<float> v(pref_size(t->prefs[i]));
+      ok = fread(&cnt, 8, 1, f) == 1 && cnt == v.size() && fread(v.data(), 4, cnt, f) == cnt;
+      if (ok && xfer_param(t, group_buf(t, 1 + k / (int)t->prefs.size()), i, v.data(), 0) != AGZ_OK) { fclose(f); return AGZ_E_HIP; }
+    }
+  }
   fclose(f);
   AGZ_REQUIRE(ok, AGZ_E_INVALID, "agz_trainer_load: %s is truncated or mismatched", path);
   // 03: the tracking setting and state the file carries; 01 / 02: no statistics (N = 0), the setting stays
   { int r = form == 3 ? bn_block_apply(t, bnb) : agz_trainer_reset_bn_stats(t); if (r != AGZ_OK) return r; }
-  if (!v2) return agz_trainer_reset_solver(t);   // a file without velocity: v := 0, the options stay
+  if (!v2 && !ad) return agz_trainer_reset_solver(t);   // a file without solver state: v := 0 (Adam: the moments and t := 0), the options stay
   return AGZ_OK;
 }
 

@@ -855,6 +855,52 @@ func (t *Trainer) SetVelocity(i int, data []float32) error {
 // ResetSolver zeroes the velocity and keeps the options.
 func (t *Trainer) ResetSolver() error { defer t.ctx.enter()(); return lastErr(C.agz_trainer_reset_solver(t.h)) }
 
+// AdamConf holds the options of gorgonia.NewAdamSolver on the solver line of dual.Train (dualnet/meta.go:20).  Excludes a Momentum.
+type AdamConf struct {
+	Beta1, Beta2, Eps float32
+	On                bool
+}
+
+// DefaultAdamConf returns Adam's usual settings (0.9, 0.999, 1e-8), turned on.
+func DefaultAdamConf() AdamConf { return AdamConf{Beta1: 0.9, Beta2: 0.999, Eps: 1e-8, On: true} }
+
+// SetAdam turns Adam on or off (agz_trainer_set_adam): on allocates and zeroes the two moments, off releases them and resets the counter.
+func (t *Trainer) SetAdam(c AdamConf) error {
+	defer t.ctx.enter()()
+	cc := C.agz_adam_conf{beta1: C.float(c.Beta1), beta2: C.float(c.Beta2), eps: C.float(c.Eps)}
+	if c.On {
+		cc.on = 1
+	}
+	return lastErr(C.agz_trainer_set_adam(t.h, &cc))
+}
+
+// Adam returns the settings in force and the number of solver steps taken since Adam was turned on.
+func (t *Trainer) Adam() (AdamConf, uint64, error) {
+	defer t.ctx.enter()()
+	var cc C.agz_adam_conf
+	var step C.uint64_t
+	err := lastErr(C.agz_trainer_get_adam(t.h, &cc, &step))
+	return AdamConf{Beta1: float32(cc.beta1), Beta2: float32(cc.beta2), Eps: float32(cc.eps), On: cc.on != 0}, uint64(step), err
+}
+
+// Moments reads the two Adam moments of learnable i (Model() order, the shape of the learnable) into m and v; zeros while Adam is off.
+func (t *Trainer) Moments(i int, m []float32, v []float32) error {
+	defer t.ctx.enter()()
+	if len(m) != len(v) {
+		return errors.New("agzhip: Moments: m and v differ in length")
+	}
+	return lastErr(C.agz_trainer_get_moments(t.h, C.int(i), (*C.float)(unsafe.Pointer(&m[0])), (*C.float)(unsafe.Pointer(&v[0])), C.size_t(len(m))))
+}
+
+// SetMoments writes the two Adam moments of learnable i.
+func (t *Trainer) SetMoments(i int, m []float32, v []float32) error {
+	defer t.ctx.enter()()
+	if len(m) != len(v) {
+		return errors.New("agzhip: SetMoments: m and v differ in length")
+	}
+	return lastErr(C.agz_trainer_set_moments(t.h, C.int(i), (*C.float)(unsafe.Pointer(&m[0])), (*C.float)(unsafe.Pointer(&v[0])), C.size_t(len(m))))
+}
+
 // SetBNTracking turns the running BatchNorm statistics on or off (agz_trainer_set_bn_tracking): while on, every training forward adds
 // its batch mean and biased variance to accumulators that decay by momentum (the reference asks gorgonia for 0.997,
 // dualnet/ermahagerdmonards.go:54).  Turning it off keeps the state; Export, Eval and Save still use it.

@@ -200,7 +200,8 @@ int agz_trainer_init_random(agz_trainer* t, uint64_t seed);
  * for those tensors (zeros on a fresh trainer); filter and head gradients are current.  To read every gradient, run
  * agz_trainer_forward_backward (or agz_trainer_batch with lr = 0).  A step that fails part-way may have stepped some layers' gamma / beta
  * already: treat the trainer's parameters — and, with a momentum set (agz_trainer_set_solver), the velocity, which the same kernel steps —
- * as undefined after an error (reload a checkpoint, agz_trainer_load). */
+ * as undefined after an error (reload a checkpoint, agz_trainer_load).  With Adam on (agz_trainer_set_adam) the same holds for the two
+ * moments, which that kernel steps as well, and for the step counter t: both are undefined after a step that fails part-way. */
 int agz_trainer_batch(agz_trainer* t, const float* planes, const float* pi, const float* v, float lr, float* cost);
 /* Split form for data-parallel training: forward_backward fills the flat gradient buffer; all-reduce it over RCCL
  * (agz_trainer_grads_dev gives the device pointer: ONE collective per step); apply does w -= lr*grad_scale*grad. */
@@ -238,6 +239,38 @@ int agz_trainer_get_velocity(const agz_trainer* t, int index, float* host, size_
 int agz_trainer_set_velocity(agz_trainer* t, int index, const float* host, size_t n);
 /* velocity := 0, the options kept (a fresh gorgonia solver with the same options).  Test: test_solver_gpu.py (checkpoint case). */
 int agz_trainer_reset_solver(agz_trainer* t);
+/* Adam: gorgonia.NewAdamSolver in place of NewVanillaSolver on the same line (dualnet/meta.go:20).  Off by default; with it off every
+ * path launches the kernels it launches without this option.  State: one step counter t per trainer (uint64, starts at 0) and two flat
+ * device buffers M1, M2 laid out like the learnables, zero at the start.  On every solver step (agz_trainer_apply, and the step inside
+ * agz_trainer_batch / agz_train / agz_train_dev) the host increments t, computes rc1 = 1 / (1 - beta1^t) and rc2 = 1 / (1 - beta2^t) in
+ * double and rounds each once to float; then per learnable element, in fp32, with the per-call lr and grad_scale:
+ *     g1 = grad_scale * g
+ *     g2 = g1 + l2reg * w                  (only if l2reg != 0)   } agz_solver_conf's l2reg / clip, as above
+ *     g3 = min(max(g2, -clip), clip)       (only if clip > 0)     }
+ *     m  = beta1 * m + (1 - beta1) * g3                           ((1 - beta1), (1 - beta2): rounded to float on the host)
+ *     v  = beta2 * v + (1 - beta2) * (g3 * g3)
+ *     w  = w + (-lr) * ((m * rc1) / (sqrtf(v * rc2) + eps))
+ * With lr = 0 the moments move and w does not.  agz_trainer_batch steps the tower's gamma / beta and their moments inside the BatchNorm
+ * backward kernel (no gradient is materialised, as for the other solvers) with the same t as the sweep that follows it in that step;
+ * agz_trainer_eval touches neither t nor the moments.  The moments are 2 x the size of the learnables (2 x 7.7 GB at 19x19 / K = 256 /
+ * 20 blocks / batch 256), allocated and zeroed when Adam is first turned on (AGZ_E_NOMEM if they do not fit; the settings are then
+ * unchanged) and released, with t reset to 0, when it is turned off; a trainer that never asks for Adam allocates nothing.
+ * agz_trainer_reset_solver also zeroes M1, M2 and t.  Sharded trainers: every rank makes the same call (a local call); a rank holds the
+ * moment rows of the batch-shaped tensors it owns, the shared tensors' moments follow from the summed gradient identically on every rank —
+ * no further collective.
+ * set: AGZ_E_INVALID unless on is 0 or 1, 0 <= beta1 < 1, 0 <= beta2 < 1, eps > 0 and all are finite.  Adam and a momentum exclude each
+ * other: set_adam with on = 1 while agz_solver_conf.momentum != 0, and agz_trainer_set_solver with momentum != 0 while Adam is on, return
+ * AGZ_E_STATE and change nothing.  get: either pointer may be NULL; *step = t.
+ * Tests: tests/test_adam_cpu.py (ABI, the restated definition against float64), tests/test_adam_gpu.py (off is untouched, recurrence,
+ * fused = two-pass, headline width, oracle trajectory, checkpoint, validation, agz_train_dev), tests/test_adam_sharded_gpu.py. */
+typedef struct agz_adam_conf { float beta1, beta2, eps; int32_t on; } agz_adam_conf; /* 16 bytes; defaults 0.9, 0.999, 1e-8, on = 0 */
+int agz_trainer_set_adam(agz_trainer* t, const agz_adam_conf* conf);
+int agz_trainer_get_adam(const agz_trainer* t, agz_adam_conf* out, uint64_t* step);
+/* The two moments of learnable `index`: the indexing, shapes and — on a sharded trainer — row ownership of agz_trainer_get_velocity.
+ * get: zeros while Adam is off.  set: AGZ_E_STATE while Adam is off.  Tests: test_adam_gpu.py (recurrence, checkpoint, validation),
+ * test_adam_sharded_gpu.py. */
+int agz_trainer_get_moments(const agz_trainer* t, int index, float* m, float* v, size_t n);
+int agz_trainer_set_moments(agz_trainer* t, int index, const float* m, const float* v, size_t n);
 /* Arithmetic of training's three GEMMs (forward convolution, data gradient, weight gradient): AGZ_COMPUTE_F32_MFMA (default),
  * AGZ_COMPUTE_BF16X3 (all three on the bf16 pipe; weights re-split on the device every step) or AGZ_COMPUTE_WINO_H2 (fp16x2
  * products throughout: forward = the DIRECT 3x3 convolution with fp16 hi/lo operands, weight image split on the device every step;
@@ -263,6 +296,12 @@ int agz_train_dev(agz_trainer* t, const float* Xs_dev, const float* policies_dev
  * A trainer with a velocity (momentum != 0) writes the "AGZTRN02" form — the AGZTRN01 payload, agz_solver_conf, every tensor's
  * velocity — and any other trainer the AGZTRN01 file it always wrote.  load reads both: 02 sets the options and velocity it carries,
  * 01 zeroes the velocity and keeps the options; a truncated 02 file is rejected (AGZ_E_INVALID) before anything is changed.
+ * A trainer with Adam on (agz_trainer_set_adam) writes "AGZTRN04": the AGZTRN01 payload, agz_solver_conf, agz_adam_conf, uint64 t, then
+ * per tensor {uint64 n, float m[n]} and per tensor {uint64 n, float v[n]} in the payload's order (with running BatchNorm statistics:
+ * AGZTRN03 with inner form 3).  load: the Adam forms set the options, t and the moments, turning Adam on; 01 / 02 (and 03 with inner form
+ * 1 / 2) loaded into a trainer with Adam on zero the moments and t, and keep the Adam setting only if the file's momentum is 0 — otherwise
+ * they take the file's solver and turn Adam off; a truncated or inconsistent Adam file is rejected (AGZ_E_INVALID) before anything is
+ * changed.  Sharded: rank 0 writes the global file, every rank loads its own rows.  Test: tests/test_adam_gpu.py (checkpoint).
  * A trainer with running BatchNorm statistics (N > 0) writes "AGZTRN03": the magic, a uint32 naming the inner form (1 or 2), the body of
  * that 01 / 02 file after its magic, then float momentum, uint32 on, uint32 n_ops and per op {uint64 C, double N, double S_mean[C],
  * double S_var[C]}.  load: 03 sets the tracking setting and state it carries; 01 / 02 reset the state to N = 0 and keep the setting; a
