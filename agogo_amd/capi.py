@@ -171,6 +171,8 @@ def lib():
     sig("agz_net_load", i32, vp, C.c_char_p)
     sig("agz_arena_get_results", i32, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64))
     sig("agz_trainer_create", i32, vp, C.POINTER(NetConf), pvp)
+    sig("agz_trainer_create_tied", i32, vp, C.POINTER(NetConf), pvp)
+    sig("agz_trainer_is_tied", i32, vp, C.POINTER(i32))
     sig("agz_trainer_destroy", None, vp)
     sig("agz_trainer_num_params", i32, vp)
     sig("agz_trainer_param_info", i32, vp, i32, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t))
@@ -480,12 +482,23 @@ class Net:
 class Trainer:
     """dual.Train on device (dualnet/meta.go:16-54): full-shape learnables, training-mode BN, backward, vanilla SGD."""
 
-    def __init__(self, ctx, K, SharedLayers, FC, Width, Height, Features, ActionSpace, BatchSize, bn_eps=1e-5):
+    def __init__(self, ctx, K, SharedLayers, FC, Width, Height, Features, ActionSpace, BatchSize, bn_eps=1e-5, tied=False):
+        """tied=True (agz_trainer_create_tied): BatchNorm gamma / beta [C,H,W] and FC biases [units] stored once and shared by every batch
+        row — the inference net's shapes; their gradient is the sum over the rows"""
         self.ctx = ctx
         self.conf = NetConf(K, SharedLayers, FC, BatchSize, Width, Height, Features, ActionSpace, 0, bn_eps)
         self.h = C.c_void_p()
-        _check(lib().agz_trainer_create(ctx.h, C.byref(self.conf), C.byref(self.h)), "agz_trainer_create")
+        if tied:
+            _check(lib().agz_trainer_create_tied(ctx.h, C.byref(self.conf), C.byref(self.h)), "agz_trainer_create_tied")
+        else:
+            _check(lib().agz_trainer_create(ctx.h, C.byref(self.conf), C.byref(self.h)), "agz_trainer_create")
         ctx._adopt(self)
+
+    def is_tied(self):
+        """True for a trainer created with tied=True (agz_trainer_is_tied)"""
+        v = C.c_int(0)
+        _check(lib().agz_trainer_is_tied(self.h, C.byref(v)), "agz_trainer_is_tied")
+        return bool(v.value)
 
     @classmethod
     def sharded(cls, ctx, comm, K, SharedLayers, FC, Width, Height, Features, ActionSpace, BatchSize, bn_eps=1e-5):

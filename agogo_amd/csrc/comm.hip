@@ -217,6 +217,7 @@ int agz_comm_debug_fail_slice(agz_comm* c, int k) {
 int agz_trainer_forward_backward_allreduce(agz_comm* c, agz_trainer* t, const float* planes, const float* pi, const float* v, float* cost) {
   AGZ_REQUIRE(c && t && planes && pi && v, AGZ_E_INVALID, "agz_trainer_forward_backward_allreduce: NULL argument");
   AGZ_REQUIRE(!agz_trainer_is_sharded(t), AGZ_E_STATE, "agz_trainer_forward_backward_allreduce: not for a sharded trainer (its own step is collective)");
+  { int tied = 0; AGZ_REQUIRE(agz_trainer_is_tied(t, &tied) == AGZ_OK && !tied, AGZ_E_STATE, "agz_trainer_forward_backward_allreduce: not for a tied trainer (agz_trainer_create_tied): its flat gradient buffer is small, reduce it with one agz_trainer_allreduce after agz_trainer_forward_backward"); }
   AGZ_REQUIRE(agz_trainer_ctx(t) == c->ctx, AGZ_E_INVALID, "agz_trainer_forward_backward_allreduce: the communicator and the trainer belong to different contexts");
   const Rccl* R = rccl();
   if (!R) return AGZ_E_UNSUPPORTED;
@@ -229,6 +230,7 @@ int agz_trainer_forward_backward_allreduce(agz_comm* c, agz_trainer* t, const fl
 int agz_trainer_forward_backward_allreduce_dev(agz_comm* c, agz_trainer* t, const float* planes_dev, const float* pi_dev, const float* v_dev, float* cost) {
   AGZ_REQUIRE(c && t && planes_dev && pi_dev && v_dev, AGZ_E_INVALID, "agz_trainer_forward_backward_allreduce_dev: NULL argument");
   AGZ_REQUIRE(!agz_trainer_is_sharded(t), AGZ_E_STATE, "agz_trainer_forward_backward_allreduce_dev: not for a sharded trainer (its own step is collective)");
+  { int tied = 0; AGZ_REQUIRE(agz_trainer_is_tied(t, &tied) == AGZ_OK && !tied, AGZ_E_STATE, "agz_trainer_forward_backward_allreduce_dev: not for a tied trainer (agz_trainer_create_tied): its flat gradient buffer is small, reduce it with one agz_trainer_allreduce after agz_trainer_forward_backward"); }
   AGZ_REQUIRE(agz_trainer_ctx(t) == c->ctx, AGZ_E_INVALID, "agz_trainer_forward_backward_allreduce_dev: the communicator and the trainer belong to different contexts");
   const Rccl* R = rccl();
   if (!R) return AGZ_E_UNSUPPORTED;

@@ -192,6 +192,11 @@ __global__ void k_sum_ranks(const double* __restrict__ xg, int n, int stride, do
 }
 
 // ---- tower BN apply (+ReLU, + dual add + ReLU).  z [pix][nbr*Kp]; gamma/beta [M][nbr*Kp]; out [pix][Kp] --------
+// TIED (agz_trainer_create_tied; DESIGN §2 `tied-affine`): gamma / beta are ONE [HW][nbr*Kp] tensor shared by every board, indexed by the
+// pixel within the board.  A template parameter: the <false> instantiation is the kernel that ran before the option existed.
+template <bool TIED>
+__device__ __forceinline__ int affine_row(int r, int HW) { return TIED ? r % HW : r; }
+template <bool TIED>
 __global__ void k_bn_apply(TGeo g, const float* __restrict__ z, const float* __restrict__ gamma, const float* __restrict__ beta,
                            const float* __restrict__ mean, const float* __restrict__ inv, float* __restrict__ out, int Kp, int nbr) {
   size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -203,7 +208,7 @@ __global__ void k_bn_apply(TGeo g, const float* __restrict__ z, const float* __r
   for (int br = 0; br < nbr; br++) {
     int cc = br * Kp + c;
     float xh = (z[po * C + cc] - mean[cc]) * inv[cc];
-    float y = gamma[(size_t)r * C + cc] * xh + beta[(size_t)r * C + cc];
+    float y = gamma[(size_t)(TIED ? r % g.HW : r) * C + cc] * xh + beta[(size_t)(TIED ? r % g.HW : r) * C + cc];
     acc += y > 0.f ? y : 0.f;
   }
   out[po * Kp + c] = (nbr == 2) ? (acc > 0.f ? acc : 0.f) : acc;
@@ -245,6 +250,7 @@ __device__ __forceinline__ void board_amax_commit(unsigned m0, unsigned m1, int 
 // scale is what the exact range prescribes, the results do not depend on the history) and re-splits the tensor otherwise.
 __device__ __forceinline__ float wg_h2_scale(unsigned amax_bits);
 typedef _Float16 bn_f16x4_t __attribute__((ext_vector_type(4)));
+template <bool TIED>
 __global__ __launch_bounds__(256) void k_bn_apply_v(TGeo g, const float* __restrict__ z, const float* __restrict__ gamma,
                                                     const float* __restrict__ beta, const float* __restrict__ mean,
                                                     const float* __restrict__ inv, float* __restrict__ out, int Kp, int nbr,
@@ -266,8 +272,8 @@ __global__ __launch_bounds__(256) void k_bn_apply_v(TGeo g, const float* __restr
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
     for (int br = 0; br < nbr; br++) {
       const float4 zz = reinterpret_cast<const float4*>(z + po * C + br * Kp)[cq];
-      const float4 gm = reinterpret_cast<const float4*>(gamma + (size_t)r * C + br * Kp)[cq];
-      const float4 bt = reinterpret_cast<const float4*>(beta + (size_t)r * C + br * Kp)[cq];
+      const float4 gm = reinterpret_cast<const float4*>(gamma + (size_t)affine_row<TIED>(r, g.HW) * C + br * Kp)[cq];
+      const float4 bt = reinterpret_cast<const float4*>(beta + (size_t)affine_row<TIED>(r, g.HW) * C + br * Kp)[cq];
       const float zv[4] = {zz.x, zz.y, zz.z, zz.w}, gv[4] = {gm.x, gm.y, gm.z, gm.w}, bv[4] = {bt.x, bt.y, bt.z, bt.w};
       const float mv[4] = {mu[br].x, mu[br].y, mu[br].z, mu[br].w}, nv[4] = {iv[br].x, iv[br].y, iv[br].z, iv[br].w};
 #pragma unroll
@@ -395,6 +401,160 @@ __global__ void k_bn_bwd1(TGeo g, const float* __restrict__ z, float* gamma, flo
     }
     atomicAdd(&s1[cc], a1);
     atomicAdd(&s2[cc], a2);
+  }
+}
+// ---- tied affine (agz_trainer_create_tied; DESIGN §2 `tied-affine`): step 1 with gamma / beta [HW][C] shared by every board ------------
+// One workgroup owns 64 channels of ONE pixel p for all B boards: 256 threads = 64 channels x TB_RS row slices, slice s walks the boards
+// b = s, s + TB_RS, ... (a wave reads 256 contiguous bytes of z per board).  Per element it does what k_bn_bwd1 does — gg, xhat,
+// dz = gg * gamma, the channel sums — and accumulates dgamma = sum_b gg * xhat and dbeta = sum_b gg (each term the untied trainer's fp32
+// per-row gradient) in double, in board order within the slice; the slices are then added in slice order through LDS and the sum is
+// rounded once: no atomics, and the same bits for the same dout whatever the launch geometry.  Channels and pixels, not rows, are split
+// across workgroups (grid = HW x ceil(C / 64): 2888 workgroups for 361 pixels x 512 channels).
+// fuse_lr != 0: slice 0 — the owner of gamma / beta [p][cc]; every slice of this workgroup, the only readers of the element in the launch,
+// read them before the barrier, so dz is computed with the value before the step — takes the solver step of its KIND in place (velocity or
+// both moments at the same index) through tied_step (= solver_step / adam_step, out of line); no tied gradient is materialised.  Otherwise it stores dgamma, dbeta.
+// The channel sums leave as per-pixel partial sums part[which][p][cc] (double) and k_bn_tied_sums adds them in a fixed order: s1 / s2 do not
+// depend on the order workgroups finish in either (k_bn_bwd1 adds its blocks' sums with double atomics).
+constexpr int TB_RS = 4;
+// The solver step of ONE tied gamma / beta element, compiled ONCE and out of line: solver_step's `mu * v + (-lr) * g` and adam_step's
+// `b1 * m + (1 - b1) * g` each have two multiply-adds the compiler may contract them into, and it chooses per call site (inlined into
+// k_bn_bwd1_tied it took fma(-lr, g, mu * v) where k_solver_sweep takes fma(mu, v, -(lr * g)): a fused momentum step differed from the
+// two-pass step in the last bit).  The fused owner below and the two-pass sweep of the same tensors (k_tied_sweep) both CALL this one body,
+// so the two paths of a tied trainer run the same instructions on the same operands.  Everything travels in registers (values in, a
+// three-float struct out): no scratch.  a, b: the velocity (b unused) or Adam's two moments; gr: the gradient, grad_scale applied.
+// This rests on the compiler honouring __noinline__; test_fused_step_is_the_two_pass_step_to_the_bit_where_a_step_is_one_workgroup
+// (tests/test_tied_gpu.py) compares the two paths on bytes for every solver and is the guard: if it fails, look here first.
+struct TiedSt { float w, a, b; };
+template <int KIND>
+__device__ __noinline__ TiedSt tied_step(float w, float a, float b, float gr, float lr, float mu, float l2, float clip, AdamK ak) {
+  if (KIND == SK_ADAM) adam_step(w, a, b, gr, lr, l2, clip, ak);
+  else solver_step<KIND == SK_MOMENTUM>(w, a, gr, lr, mu, l2, clip);
+  return TiedSt{w, a, b};
+}
+// the two-pass solver step (agz_trainer_apply after agz_trainer_forward_backward, grad_scale honoured) of a tied trainer's tower gamma /
+// beta: n elements of p / g (/ v, or m and m2) through tied_step.  0.13 GB per G19 trainer: one element per thread, grid-stride
+template <int KIND>
+__global__ __launch_bounds__(256) void k_tied_sweep(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ v, float* __restrict__ m2,
+                                                    size_t n, float lr, float gs, float mu, float l2, float clip, AdamK ak) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+    const float a = KIND == SK_OPTIONS ? 0.f : v[i], b = KIND == SK_ADAM ? m2[i] : 0.f;
+    const TiedSt r = tied_step<KIND>(p[i], a, b, gs * g[i], lr, mu, l2, clip, ak);
+    p[i] = r.w;
+    if (KIND != SK_OPTIONS) v[i] = r.a;
+    if (KIND == SK_ADAM) m2[i] = r.b;
+  }
+}
+template <int KIND>
+__global__ __launch_bounds__(256) void k_bn_bwd1_tied(TGeo g, const float* __restrict__ z, float* gamma, float* beta,
+                                                      const float* __restrict__ mean, const float* __restrict__ inv, const float* __restrict__ out,
+                                                      const float* __restrict__ dout, float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                                      float* __restrict__ dz, double* __restrict__ part, int Kp, int nbr, float fuse_lr, SolverDev sv) {
+  constexpr bool SOLVER = KIND != SK_VANILLA, MOM = KIND == SK_MOMENTUM;
+  __shared__ double red[4][TB_RS - 1][64];
+  const int C = nbr * Kp, chunks = (C + 63) >> 6;
+  const int p = blockIdx.x / chunks, ch = blockIdx.x - p * chunks;
+  const int lane = threadIdx.x & 63, rs = threadIdx.x >> 6;
+  const int cc = ch * 64 + lane;
+  const bool act = cc < C;
+  const size_t e = (size_t)p * C + cc;
+  // (dgamma / dbeta start from -0.0, the identity of IEEE addition: a sum of one row, and a slice without rows, leave the term as it is —
+  // its sign of zero included — so that B = 1 stores the untied trainer's bits)
+  double dg = -0.0, db = -0.0, a1 = 0, a2 = 0;
+  float gm = 0.f, bt = 0.f;
+  if (act) {
+    const int c = cc % Kp;
+    const int h = p / g.W, w = p - h * g.W;
+    const float mu = mean[cc], iv = inv[cc];
+    gm = gamma[e]; bt = beta[e];
+    const size_t board = (size_t)g.Hp * g.Wp;
+    size_t po = ((size_t)rs * g.Hp + h + 1) * g.Wp + w + 1;   // pix_off of row b * HW + p, b = rs
+#pragma unroll 2
+    for (int b = rs; b < g.B; b += TB_RS, po += TB_RS * board) {
+      float g0 = dout[po * Kp + c];
+      if (nbr == 2 && !(out[po * Kp + c] > 0.f)) g0 = 0.f;
+      const float xh = (z[po * C + cc] - mu) * iv;
+      const float y = gm * xh + bt;
+      const float gg = y > 0.f ? g0 : 0.f;
+      const float gx = gg * xh;
+      dg += (double)gx; db += (double)gg;
+      const float dxh = gg * gm;
+      dz[po * C + cc] = dxh;
+      a1 += dxh; a2 += (double)dxh * xh;
+    }
+  }
+  if (rs > 0) { red[0][rs - 1][lane] = dg; red[1][rs - 1][lane] = db; red[2][rs - 1][lane] = a1; red[3][rs - 1][lane] = a2; }
+  __syncthreads();
+  if (rs != 0 || !act) return;
+#pragma unroll
+  for (int k = 0; k < TB_RS - 1; k++) { dg += red[0][k][lane]; db += red[1][k][lane]; a1 += red[2][k][lane]; a2 += red[3][k][lane]; }
+  part[e] = a1;
+  part[(size_t)g.HW * C + e] = a2;
+  const float fg = (float)dg, fb = (float)db;   // (rounded once)
+  if (KIND == SK_ADAM) {  // (fused steps only: fuse_lr != 0)
+    const TiedSt rg = tied_step<SK_ADAM>(gm, sv.m1gamma[e], sv.m2gamma[e], fg, fuse_lr, 0.f, sv.l2, sv.clip, sv.ak);
+    const TiedSt rb = tied_step<SK_ADAM>(bt, sv.m1beta[e], sv.m2beta[e], fb, fuse_lr, 0.f, sv.l2, sv.clip, sv.ak);
+    sv.m1gamma[e] = rg.a; sv.m2gamma[e] = rg.b; sv.m1beta[e] = rb.a; sv.m2beta[e] = rb.b;
+    gamma[e] = rg.w;
+    beta[e] = rb.w;
+  } else if (SOLVER) {    // (fused steps only: fuse_lr != 0)
+    float vg = 0.f, vb = 0.f;
+    if (MOM) { vg = sv.vgamma[e]; vb = sv.vbeta[e]; }
+    const TiedSt rg = tied_step<KIND>(gm, vg, 0.f, fg, fuse_lr, sv.mu, sv.l2, sv.clip, sv.ak);
+    const TiedSt rb = tied_step<KIND>(bt, vb, 0.f, fb, fuse_lr, sv.mu, sv.l2, sv.clip, sv.ak);
+    if (MOM) { sv.vgamma[e] = rg.a; sv.vbeta[e] = rb.a; }
+    gamma[e] = rg.w;
+    beta[e] = rb.w;
+  } else if (fuse_lr != 0.f) {   // (uniform) p += alpha * g with alpha = -lr, exactly k_axpy's expression
+    gamma[e] = gm + (-fuse_lr) * fg;
+    beta[e] = bt + (-fuse_lr) * fb;
+  } else {
+    dgamma[e] = fg;
+    dbeta[e] = fb;
+  }
+}
+// s1[cc] = sum over the pixels p of part[0][p][cc]; s2 likewise from part[1].  A workgroup holds 16 channels x TS_NS pixel slices: slice k
+// adds the pixels [k * TS_PS, (k + 1) * TS_PS) in pixel order (and every TS_NS-th such run after it, on boards of more than TS_NS * TS_PS
+// pixels); the slices then meet in LDS and slice 0 adds them in slice order.  The order is fixed by HW alone, whatever the grid, and a board
+// of up to TS_PS pixels is one run in pixel order.  (One thread per channel walking all 361 pixels, 16 waves in the whole launch, took
+// 131 us per layer at G19 — one memory latency per pixel — and ate the saving of k_bn_bwd1_tied: profiles/tied/train_tied_kernel_stats.txt.)
+constexpr int TS_NS = 16, TS_PS = 24;
+__global__ __launch_bounds__(256) void k_bn_tied_sums(const double* __restrict__ part, int HW, int C, double* __restrict__ s1, double* __restrict__ s2) {
+  __shared__ double red[TS_NS][16];
+  const int ci = threadIdx.x & 15, k = threadIdx.x >> 4;
+  const int i = blockIdx.x * 16 + ci;
+  const bool act = i < 2 * C;
+  int which = 0, cc = 0;
+  double s = 0;
+  if (act) {
+    which = i / C; cc = i - which * C;
+    const double* q = part + (size_t)which * HW * C + cc;
+    for (int p0 = k * TS_PS; p0 < HW; p0 += TS_NS * TS_PS) {
+      const int p1 = min(p0 + TS_PS, HW);
+#pragma unroll 8
+      for (int p = p0; p < p1; p++) s += q[(size_t)p * C];
+    }
+  }
+  red[k][ci] = s;
+  __syncthreads();
+  if (k != 0 || !act) return;
+  const int ns = min(TS_NS, (HW + TS_PS - 1) / TS_PS);
+  for (int j = 1; j < ns; j++) s += red[j][ci];
+  (which ? s2 : s1)[cc] = s;
+}
+// Tied head gamma / beta and FC biases: the head kernels write the untied trainer's per-row gradients into a scratch of the untied shapes;
+// dst[i] = sum over the B rows, in row order, in double, rounded once, for up to five tensors in one launch (n[k] elements per row each)
+struct RowSum { const float* src[5]; float* dst[5]; int n[5]; };
+__global__ __launch_bounds__(256) void k_rows_sum(RowSum a, int B) {
+  int i = blockIdx.x * 256 + threadIdx.x;
+#pragma unroll
+  for (int k = 0; k < 5; k++) {
+    if (i < a.n[k]) {
+      double s = -0.0;   // (the identity of IEEE addition: one row is copied with its sign of zero)
+      for (int b = 0; b < B; b++) s += (double)a.src[k][(size_t)b * a.n[k] + i];
+      a.dst[k][i] = (float)s;
+      return;
+    }
+    i -= a.n[k];
   }
 }
 // step 2: dz = inv * (dxhat - s1/m - xhat*s2/m); m = the rows the sums run over (g.M, or the global batch's rows of a sharded trainer)
@@ -1154,6 +1314,7 @@ __global__ void k_head_stats(TGeo g, const float* __restrict__ zh, float eps, fl
   }
 }
 // yh[b][j][p] = relu(gamma*xhat+beta); head gamma/beta layout [B][3][HW]
+template <bool TIED>
 __global__ void k_head_apply(TGeo g, const float* __restrict__ zh, const float* __restrict__ hg, const float* __restrict__ hb,
                              const float* __restrict__ mean, const float* __restrict__ inv, float* __restrict__ yh) {
   int idx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1162,7 +1323,8 @@ __global__ void k_head_apply(TGeo g, const float* __restrict__ zh, const float* 
   int b = r / g.HW, p = r - b * g.HW;
   float xh = (zh[idx] - mean[j]) * inv[j];
   size_t o = ((size_t)b * 3 + j) * g.HW + p;
-  float y = hg[o] * xh + hb[o];
+  const size_t og = TIED ? (size_t)j * g.HW + p : o;   // (tied: head gamma / beta [3][HW], shared by every board)
+  float y = hg[og] * xh + hb[og];
   yh[o] = y > 0.f ? y : 0.f;
 }
 struct HeadT {
@@ -1175,6 +1337,8 @@ struct HeadT {
   float *dWp, *dbp, *dW1, *db1, *dW2, *db2, *dyh;  // dyh [B][3][HW]
   float* cost;  // [2]: pcost, vcost sums
 };
+// TIED: the biases are [A], [FC], [1], shared by every row
+template <bool TIED>
 __global__ void k_fc_fwd(HeadT h) {
   int idx = blockIdx.x * blockDim.x + threadIdx.x;
   int nl = h.B * h.A, nh = h.B * h.FC;
@@ -1183,22 +1347,23 @@ __global__ void k_fc_fwd(HeadT h) {
     const float* yp = h.yh + (size_t)b * 3 * h.HW;  // policy features: channels 0,1 contiguous = flatten c-major
     float s = 0.f;
     for (int i = 0; i < 2 * h.HW; i++) s += yp[i] * h.Wp[(size_t)i * h.A + j];
-    h.logits[idx] = s + h.bp[idx];
+    h.logits[idx] = s + h.bp[TIED ? j : idx];
   } else if (idx < nl + nh) {
     int k = idx - nl;
     int b = k / h.FC, j = k - b * h.FC;
     const float* yv = h.yh + ((size_t)b * 3 + 2) * h.HW;
     float s = 0.f;
     for (int i = 0; i < h.HW; i++) s += yv[i] * h.W1[(size_t)i * h.FC + j];
-    h.hpre[k] = s + h.b1[k];
+    h.hpre[k] = s + h.b1[TIED ? j : k];
   }
 }
+template <bool TIED>
 __global__ void k_value_out(HeadT h) {
   int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= h.B) return;
   float s = 0.f;
   for (int j = 0; j < h.FC; j++) { float hv = h.hpre[(size_t)b * h.FC + j]; s += (hv > 0.f ? hv : 0.f) * h.W2[j]; }
-  h.o[b] = s + h.b2[b];
+  h.o[b] = s + h.b2[TIED ? 0 : b];
 }
 __global__ void k_cost(HeadT h) {  // single block
   __shared__ double red[256];
@@ -1272,6 +1437,8 @@ __global__ void k_fc_bwd(HeadT h) {
   }
 }
 // head BN backward (3 channels, one block each): dzh[r][j], dgamma/dbeta [B][3][HW]
+// TIED: hg is the shared [3][HW] tensor; dhg / dhb stay per board (a scratch of the untied shape, summed over the boards by k_rows_sum)
+template <bool TIED>
 __global__ void k_head_bn_bwd(TGeo g, const float* __restrict__ zh, const float* __restrict__ yh, const float* __restrict__ dyh,
                               const float* __restrict__ hg, const float* __restrict__ mean, const float* __restrict__ inv,
                               float* __restrict__ dhg, float* __restrict__ dhb, float* __restrict__ dzh) {
@@ -1285,7 +1452,7 @@ __global__ void k_head_bn_bwd(TGeo g, const float* __restrict__ zh, const float*
       float gg = yh[o] > 0.f ? dyh[o] : 0.f;
       float xh = (zh[r * 3 + j] - mean[j]) * inv[j];
       dhg[o] = gg * xh; dhb[o] = gg;
-      float dxh = gg * hg[o];
+      float dxh = gg * hg[TIED ? (size_t)j * g.HW + p : o];
       dzh[r * 3 + j] = dxh;
       a1 += dxh; a2 += (double)dxh * xh;
     }
@@ -1371,6 +1538,7 @@ __global__ void k_head_stats_fin(TGeo g, const double* __restrict__ hacc, float 
 }
 // out[b][j] = sum_i y[b][i] * Wt[i][j] + bias[b][j] for eight batch rows per block: grid (ceil(N / 256), ceil(B / 8), 2); z = 0: the policy
 // logits (y = channels 0, 1 of yh flattened, K = 2 HW), z = 1: the value head's hidden layer (y = channel 2, K = HW)
+template <bool TIED>
 __global__ __launch_bounds__(256) void k_fc_fwd2(HeadT h) {
   extern __shared__ float ys[];                      // [8][K]
   const bool pol = blockIdx.z == 0;
@@ -1394,17 +1562,18 @@ __global__ __launch_bounds__(256) void k_fc_fwd2(HeadT h) {
   for (int t = 0; t < 8; t++) {
     const int b = b0 + t;
     if (b >= h.B) break;
-    const size_t o = (size_t)b * N + j;
-    if (pol) h.logits[o] = acc[t] + h.bp[o]; else h.hpre[o] = acc[t] + h.b1[o];
+    const size_t o = (size_t)b * N + j, ob = TIED ? (size_t)j : o;
+    if (pol) h.logits[o] = acc[t] + h.bp[ob]; else h.hpre[o] = acc[t] + h.b1[ob];
   }
 }
+template <bool TIED>
 __global__ __launch_bounds__(64) void k_value_out2(HeadT h) {   // one wave per batch row
   const int b = blockIdx.x, lane = threadIdx.x;
   float s = 0.f;
   for (int j = lane; j < h.FC; j += 64) { const float hv = h.hpre[(size_t)b * h.FC + j]; s += (hv > 0.f ? hv : 0.f) * h.W2[j]; }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-  if (lane == 0) h.o[b] = s + h.b2[b];
+  if (lane == 0) h.o[b] = s + h.b2[TIED ? 0 : b];
 }
 // cost sums -> hacc[6] (policy), hacc[7] (value), zeroed by the caller; k_cost_fin writes cost[0..1]
 __global__ __launch_bounds__(256) void k_cost_part(HeadT h, double* __restrict__ hacc) {
@@ -1507,6 +1676,7 @@ __global__ __launch_bounds__(256) void k_fc_bwd_y(HeadT h) {
 }
 // head BatchNorm backward in two passes over all rows: (1) dgamma / dbeta, dxh -> dzh, the two channel sums -> hacc[8..13] (zeroed by the
 // caller); (2) dzh = inv * (dxh - s1 / m - xh * s2 / m)
+template <bool TIED>
 __global__ __launch_bounds__(256) void k_head_bn_bwd_a(TGeo g, const float* __restrict__ zh, const float* __restrict__ yh, const float* __restrict__ dyh,
                                                        const float* __restrict__ hg, const float* __restrict__ mean, const float* __restrict__ inv,
                                                        float* __restrict__ dhg, float* __restrict__ dhb, float* __restrict__ dzh, double* __restrict__ hacc) {
@@ -1520,7 +1690,7 @@ __global__ __launch_bounds__(256) void k_head_bn_bwd_a(TGeo g, const float* __re
       const float gg = yh[o] > 0.f ? dyh[o] : 0.f;
       const float xh = (zh[(size_t)r * 3 + j] - mean[j]) * inv[j];
       dhg[o] = gg * xh; dhb[o] = gg;
-      const float dxh = gg * hg[o];
+      const float dxh = gg * hg[TIED ? (size_t)j * g.HW + p : o];
       dzh[(size_t)r * 3 + j] = dxh;
       a1[j] += dxh; a2[j] += (double)dxh * xh;
     }
@@ -2042,6 +2212,14 @@ struct agz_trainer {
     AGZ_HIP_TRY(hipStreamSynchronize(ctx->stream));
     return AGZ_OK;
   }
+  // tied affine (agz_trainer_create_tied; DESIGN §2 `tied-affine`): every batch-shaped learnable is stored ONCE, at its row-0 shape (Bp = 1
+  // parameter rows instead of B), in the same flat P / G / V / M1 / M2 layout.  tied_rows: the head kernels' per-row gradients of the head
+  // gamma / beta and the FC biases (untied shapes: dhg, dhb [B][3][HW], dbp [B][A], db1 [B][FC], db2 [B]), summed into G by k_rows_sum;
+  // tied_part [2][HW][2 Kp]: the per-pixel channel sums of k_bn_bwd1_tied.
+  bool tied = false;
+  int Bp = 0;               // parameter rows of a batch-shaped learnable: B, or 1 on a tied trainer
+  float* tied_rows = nullptr;
+  double* tied_part = nullptr;
   float fuse_lr = 0.f;      // != 0 during a fused step: k_bn_bwd1 updates gamma / beta in place, apply() skips them
   bool fused_done = false;  // the backward that just ran took the fused path
   // sharded trainer (agz_trainer_create_sharded): this rank's rows [rank * B, (rank + 1) * B) of a global batch of n_ranks * B rows.
@@ -2209,14 +2387,14 @@ int agz_trainer::forward_backward_dev(const float* planes, const float* pi, cons
         nph = nx.xh2;
         planes_fused[l + 1] = 1;
       } else if (l < L) planes_fused[l + 1] = 0;
-      hipLaunchKernelGGL(k_bn_apply_v, dim3(nblk(g.M, rpb)), dim3(256), 0, s, g, ly.z, P + ly.o_gamma, P + ly.o_beta, ly.mean, ly.inv, ly.out,
+      hipLaunchKernelGGL(tied ? k_bn_apply_v<true> : k_bn_apply_v<false>, dim3(nblk(g.M, rpb)), dim3(256), 0, s, g, ly.z, P + ly.o_gamma, P + ly.o_beta, ly.mean, ly.inv, ly.out,
                          Kp, ly.nbr, rpb, amax_words + 2 * (l + 1) + 1, per_board ? board_words + (size_t)(l + 1) * B : nullptr,
                          nph, nph ? nph + (size_t)B * g.Hp * g.Wp * Kp : nullptr, (const unsigned*)(amax_prev + 2 * (l + 1) + 1));
       x_amax_ready[l + 1] = 1;
       xb_ready[l + 1] = per_board;
     } else {
       if (l < L) planes_fused[l + 1] = 0;
-      hipLaunchKernelGGL(k_bn_apply, dim3(nblk((size_t)g.M * Kp)), dim3(256), 0, s, g, ly.z, P + ly.o_gamma, P + ly.o_beta, ly.mean,
+      hipLaunchKernelGGL(tied ? k_bn_apply<true> : k_bn_apply<false>, dim3(nblk((size_t)g.M * Kp)), dim3(256), 0, s, g, ly.z, P + ly.o_gamma, P + ly.o_beta, ly.mean,
                          ly.inv, ly.out, Kp, ly.nbr);
     }
     cur = ly.out;
@@ -2226,6 +2404,12 @@ int agz_trainer::forward_backward_dev(const float* planes, const float* pi, cons
   h.B = B; h.Bn = B * n_ranks; h.HW = g.HW; h.A = A; h.FC = FC; h.yh = yh; h.Wp = P + o_Wp; h.bp = P + o_bp; h.W1 = P + o_W1; h.b1 = P + o_b1;
   h.W2 = P + o_W2; h.b2 = P + o_b2; h.Pi = pi; h.V = v; h.logits = logits; h.hpre = hpre; h.o = o;
   h.dWp = G + o_Wp; h.dbp = G + o_bp; h.dW1 = G + o_W1; h.db1 = G + o_b1; h.dW2 = G + o_W2; h.db2 = G + o_b2; h.dyh = dyh; h.cost = cost;
+  // tied: the head kernels write their per-row gradients of the batch-shaped tensors into tied_rows; k_rows_sum adds the rows into G
+  float *dhg = G + o_hg, *dhb = G + o_hb;
+  if (tied) {
+    dhg = tied_rows; dhb = dhg + (size_t)B * 3 * g.HW;
+    h.dbp = dhb + (size_t)B * 3 * g.HW; h.db1 = h.dbp + (size_t)B * A; h.db2 = h.db1 + (size_t)B * FC;
+  }
   // (second form of the head kernels: see k_head_conv2 ... above; fast_heads = 0, agz_debug.h, keeps the first form for A/B)
   const int fcK = 2 * g.HW > FC ? 2 * g.HW : FC, fcJ = A > FC ? A : FC;
   const bool fh = (fast_heads || sharded) && (size_t)8 * (2 * g.HW) * 4 <= 60000 && (size_t)B * 8 * 4 <= 60000 && (size_t)8 * fcJ * 4 <= 60000 && fcK > 0;
@@ -2243,9 +2427,9 @@ int agz_trainer::forward_backward_dev(const float* planes, const float* pi, cons
     }
     hipLaunchKernelGGL(trk ? k_head_stats_fin<true> : k_head_stats_fin<false>, dim3(1), dim3(64), 0, s, g, head_acc, conf.bn_eps, hmean, hinv, (double)m_glob(), hbt);
     }
-    hipLaunchKernelGGL(k_head_apply, dim3(nblk((size_t)g.M * 3)), dim3(256), 0, s, g, zh, P + o_hg, P + o_hb, hmean, hinv, yh);
-    hipLaunchKernelGGL(k_fc_fwd2, dim3(nblk(std::max(A, FC)), nblk(B, 8), 2), dim3(256), (size_t)8 * 2 * g.HW * sizeof(float), s, h);
-    hipLaunchKernelGGL(k_value_out2, dim3(B), dim3(64), 0, s, h);
+    hipLaunchKernelGGL(tied ? k_head_apply<true> : k_head_apply<false>, dim3(nblk((size_t)g.M * 3)), dim3(256), 0, s, g, zh, P + o_hg, P + o_hb, hmean, hinv, yh);
+    hipLaunchKernelGGL(tied ? k_fc_fwd2<true> : k_fc_fwd2<false>, dim3(nblk(std::max(A, FC)), nblk(B, 8), 2), dim3(256), (size_t)8 * 2 * g.HW * sizeof(float), s, h);
+    hipLaunchKernelGGL(tied ? k_value_out2<true> : k_value_out2<false>, dim3(B), dim3(64), 0, s, h);
     hipLaunchKernelGGL(k_cost_part, dim3(std::min(nblk((size_t)B * A), 64)), dim3(256), 0, s, h, head_acc);
     if (sharded) {
       int r = exchange(L + 1, head_acc, 16);
@@ -2257,9 +2441,9 @@ int agz_trainer::forward_backward_dev(const float* planes, const float* pi, cons
   hipLaunchKernelGGL(k_head_conv, dim3(nblk((size_t)g.M * 3)), dim3(256), 0, s, g, cur, P + o_hc, zh, Kp);
   if (eval) hipLaunchKernelGGL(k_bn_from_running, dim3(1), dim3(64), 0, s, hbt, conf.bn_eps, hmean, hinv);
   else hipLaunchKernelGGL(trk ? k_head_stats<true> : k_head_stats<false>, dim3(3), dim3(256), 0, s, g, zh, conf.bn_eps, hmean, hinv, hbt);
-  hipLaunchKernelGGL(k_head_apply, dim3(nblk((size_t)g.M * 3)), dim3(256), 0, s, g, zh, P + o_hg, P + o_hb, hmean, hinv, yh);
-  hipLaunchKernelGGL(k_fc_fwd, dim3(nblk((size_t)B * A + (size_t)B * FC)), dim3(256), 0, s, h);
-  hipLaunchKernelGGL(k_value_out, dim3(nblk(B)), dim3(256), 0, s, h);
+  hipLaunchKernelGGL(tied ? k_head_apply<true> : k_head_apply<false>, dim3(nblk((size_t)g.M * 3)), dim3(256), 0, s, g, zh, P + o_hg, P + o_hb, hmean, hinv, yh);
+  hipLaunchKernelGGL(tied ? k_fc_fwd<true> : k_fc_fwd<false>, dim3(nblk((size_t)B * A + (size_t)B * FC)), dim3(256), 0, s, h);
+  hipLaunchKernelGGL(tied ? k_value_out<true> : k_value_out<false>, dim3(nblk(B)), dim3(256), 0, s, h);
   hipLaunchKernelGGL(k_cost, dim3(1), dim3(256), 0, s, h);
   }
   if (eval) { AGZ_HIP_TRY(hipGetLastError()); return AGZ_OK; }   // (forward only: no gradient, no state touched)
@@ -2269,7 +2453,7 @@ int agz_trainer::forward_backward_dev(const float* planes, const float* pi, cons
     hipLaunchKernelGGL(k_fc_bwd_w, dim3(nblk(std::max(A, FC)), nblk(2 * g.HW, 8), 2), dim3(256), (size_t)B * 8 * sizeof(float), s, h);
     hipLaunchKernelGGL(k_fc_bwd_small, dim3(nblk((size_t)B * A + (size_t)B * FC + FC + B)), dim3(256), 0, s, h);
     hipLaunchKernelGGL(k_fc_bwd_y, dim3(nblk(2 * g.HW), nblk(B, 8), 2), dim3(256), (size_t)8 * fcJ * sizeof(float), s, h);
-    hipLaunchKernelGGL(k_head_bn_bwd_a, dim3(std::min(nblk(g.M), ctx->num_cus)), dim3(256), 0, s, g, zh, yh, dyh, P + o_hg, hmean, hinv, G + o_hg, G + o_hb, dzh, head_acc);
+    hipLaunchKernelGGL(tied ? k_head_bn_bwd_a<true> : k_head_bn_bwd_a<false>, dim3(std::min(nblk(g.M), ctx->num_cus)), dim3(256), 0, s, g, zh, yh, dyh, P + o_hg, hmean, hinv, dhg, dhb, dzh, head_acc);
     if (sharded) {
       int r = exchange(L + 1, head_acc, 16);
       if (r != AGZ_OK) return r;
@@ -2279,8 +2463,12 @@ int agz_trainer::forward_backward_dev(const float* planes, const float* pi, cons
     hipLaunchKernelGGL(k_head_conv_bwd_w2, dim3(nblk(g.M, RPB)), dim3(256), 0, s, g, cur, dzh, G + o_hc, Kp, RPB);
   } else {
   hipLaunchKernelGGL(k_fc_bwd, dim3(nblk(n_fc)), dim3(256), 0, s, h);
-  hipLaunchKernelGGL(k_head_bn_bwd, dim3(3), dim3(256), 0, s, g, zh, yh, dyh, P + o_hg, hmean, hinv, G + o_hg, G + o_hb, dzh);
+  hipLaunchKernelGGL(tied ? k_head_bn_bwd<true> : k_head_bn_bwd<false>, dim3(3), dim3(256), 0, s, g, zh, yh, dyh, P + o_hg, hmean, hinv, dhg, dhb, dzh);
   hipLaunchKernelGGL(k_head_conv_bwd_w, dim3(nblk(g.M, RPB)), dim3(256), 0, s, g, cur, dzh, G + o_hc, Kp, RPB);
+  }
+  if (tied) {
+    RowSum rs{{dhg, dhb, h.dbp, h.db1, h.db2}, {G + o_hg, G + o_hb, G + o_bp, G + o_b1, G + o_b2}, {3 * g.HW, 3 * g.HW, A, FC, 1}};
+    hipLaunchKernelGGL(k_rows_sum, dim3(nblk((size_t)6 * g.HW + A + FC + 1)), dim3(256), 0, s, rs, B);
   }
   float* dcur = dA;
   float* dnext = dB;
@@ -2319,9 +2507,16 @@ int agz_trainer::forward_backward_dev(const float* planes, const float* pi, cons
         sd.ak = adam_k(adam_t + 1);
         sd.m1gamma = M1 + ly.o_gamma; sd.m1beta = M1 + ly.o_beta; sd.m2gamma = M2 + ly.o_gamma; sd.m2beta = M2 + ly.o_beta;
       }
+      if (tied) {   // one workgroup per (pixel, 64 channels) owns the element for all B boards; then the channel sums in a fixed pixel order
+        auto* bwd1t = sv_adam ? k_bn_bwd1_tied<SK_ADAM> : sv_mom ? k_bn_bwd1_tied<SK_MOMENTUM> : sv_on ? k_bn_bwd1_tied<SK_OPTIONS> : k_bn_bwd1_tied<SK_VANILLA>;
+        hipLaunchKernelGGL(bwd1t, dim3(g.HW * ceil_div(C, 64)), dim3(256), 0, s, g, ly.z, P + ly.o_gamma, P + ly.o_beta, ly.mean, ly.inv,
+                           ly.out, dcur, G + ly.o_gamma, G + ly.o_beta, dz, tied_part, Kp, ly.nbr, fuse_lr, sd);
+        hipLaunchKernelGGL(k_bn_tied_sums, dim3(nblk((size_t)2 * C, 16)), dim3(256), 0, s, tied_part, g.HW, C, s1, s2);
+      } else {
       auto* bwd1 = sv_adam ? k_bn_bwd1<SK_ADAM> : sv_mom ? k_bn_bwd1<SK_MOMENTUM> : sv_on ? k_bn_bwd1<SK_OPTIONS> : k_bn_bwd1<SK_VANILLA>;
       hipLaunchKernelGGL(bwd1, dim3(nblk(g.M, RPB)), dim3(std::min(C, 512)), 0, s, g, ly.z, P + ly.o_gamma, P + ly.o_beta, ly.mean, ly.inv,
                          ly.out, dcur, G + ly.o_gamma, G + ly.o_beta, dz, s1, s2, Kp, ly.nbr, RPB, fuse_lr, sd);
+      }
     }
     if (sharded) {   // the two channel sums over the global batch (in place: acc_b of this layer holds the ranks' sum afterwards)
       int r = exchange(l, s1, 2048);
@@ -2492,19 +2687,29 @@ int agz_trainer_shard(const agz_trainer* t, int* row0, int* rows, int* n_ranks) 
   return AGZ_OK;
 }
 
-int agz_trainer_create(agz_ctx* ctx, const agz_net_conf* c, agz_trainer** out) {
+static int trainer_create(agz_ctx* ctx, const agz_net_conf* c, agz_trainer** out, bool tied);
+int agz_trainer_create(agz_ctx* ctx, const agz_net_conf* c, agz_trainer** out) { return trainer_create(ctx, c, out, false); }
+// every batch-shaped learnable at its row-0 shape, shared by the BatchSize rows of a step (include/agz.h; DESIGN §2 `tied-affine`)
+int agz_trainer_create_tied(agz_ctx* ctx, const agz_net_conf* c, agz_trainer** out) { return trainer_create(ctx, c, out, true); }
+int agz_trainer_is_tied(const agz_trainer* t, int* tied) {
+  AGZ_REQUIRE(t && tied, AGZ_E_INVALID, "agz_trainer_is_tied: NULL argument");
+  *tied = t->tied ? 1 : 0;
+  return AGZ_OK;
+}
+static int trainer_create(agz_ctx* ctx, const agz_net_conf* c, agz_trainer** out, bool tied) {
   AGZ_REQUIRE(ctx && c && out, AGZ_E_INVALID, "agz_trainer_create: NULL argument");
   AGZ_REQUIRE(c->K >= 1 && c->ActionSpace >= 3 && c->SharedLayers >= 0 && c->FC > 1 && c->BatchSize >= 1 && c->Features > 0,
               AGZ_E_INVALID, "agz_trainer_create: NNConf is not valid");
   AGZ_REQUIRE(c->Features <= 32, AGZ_E_UNSUPPORTED, "Features > 32 unsupported");
   AGZ_HIP_TRY(hipSetDevice(ctx->device));
   agz_trainer* t = new agz_trainer();
-  t->ctx = ctx; t->conf = *c;
+  t->ctx = ctx; t->conf = *c; t->tied = tied; t->Bp = tied ? 1 : c->BatchSize;
   t->K = c->K; t->Kp = round_up(c->K, 32); t->L = c->SharedLayers; t->A = c->ActionSpace; t->FC = c->FC; t->B = c->BatchSize; t->F = c->Features;
   AGZ_REQUIRE(2 * t->Kp <= 1024, AGZ_E_UNSUPPORTED, "K > 512 unsupported by the trainer");
   TGeo& g = t->g;
   g.B = t->B; g.H = c->Height; g.W = c->Width; g.HW = g.H * g.W; g.Hp = g.H + 2; g.Wp = g.W + 2; g.M = g.B * g.HW;
   const int K = t->K, Kp = t->Kp, HW = g.HW, B = t->B, H = g.H, W = g.W, A = t->A, FCn = t->FC, F = t->F;
+  const int Bp = t->Bp;   // rows of the batch-shaped learnables (1 on a tied trainer: the shapes below are then the inference net's)
   size_t off = 0;
   auto take = [&](size_t n) { size_t o = off; off += (n + 3) & ~(size_t)3; return o; };
   t->layers.resize(t->L + 1);
@@ -2512,26 +2717,26 @@ int agz_trainer_create(agz_ctx* ctx, const agz_net_conf* c, agz_trainer** out) {
     TLayer& ly = t->layers[l];
     ly.nbr = l == 0 ? 1 : 2; ly.Cin_p = l == 0 ? t->Fp : Kp; ly.Cout_p = ly.nbr * Kp;
     ly.o_wf = take((size_t)9 * ly.Cout_p * ly.Cin_p);
-    ly.o_gamma = take((size_t)g.M * ly.Cout_p);
-    ly.o_beta = take((size_t)g.M * ly.Cout_p);
+    ly.o_gamma = take((size_t)Bp * HW * ly.Cout_p);
+    ly.o_beta = take((size_t)Bp * HW * ly.Cout_p);
   }
-  t->o_hc = take((size_t)3 * Kp); t->o_hg = take((size_t)B * 3 * HW); t->o_hb = take((size_t)B * 3 * HW);
-  t->o_Wp = take((size_t)2 * HW * A); t->o_bp = take((size_t)B * A); t->o_W1 = take((size_t)HW * FCn); t->o_b1 = take((size_t)B * FCn);
-  t->o_W2 = take(FCn); t->o_b2 = take(B);
+  t->o_hc = take((size_t)3 * Kp); t->o_hg = take((size_t)Bp * 3 * HW); t->o_hb = take((size_t)Bp * 3 * HW);
+  t->o_Wp = take((size_t)2 * HW * A); t->o_bp = take((size_t)Bp * A); t->o_W1 = take((size_t)HW * FCn); t->o_b1 = take((size_t)Bp * FCn);
+  t->o_W2 = take(FCn); t->o_b2 = take(Bp);
   t->n_flat = off;
   // reference Model() order (include/agz.h)
   auto pr = [&](const std::string& nm, int kind, std::vector<int> shp, int layer, int sub) { t->prefs.push_back(TParamRef{nm, kind, shp, layer, sub}); };
-  pr("FilterInit", 0, {K, F, 3, 3}, 0, 0); pr("Init_gamma", 1, {B, K, H, W}, 0, 1); pr("Init_beta", 1, {B, K, H, W}, 0, 2);
+  pr("FilterInit", 0, {K, F, 3, 3}, 0, 0); pr("Init_gamma", 1, {Bp, K, H, W}, 0, 1); pr("Init_beta", 1, {Bp, K, H, W}, 0, 2);
   for (int i = 0; i < t->L; i++) {
     std::string s = std::to_string(i);
-    pr("FilterLayer1 of Shared Layer " + s, 0, {K, K, 3, 3}, i + 1, 0); pr("L1_" + s + "_gamma", 1, {B, K, H, W}, i + 1, 1); pr("L1_" + s + "_beta", 1, {B, K, H, W}, i + 1, 2);
-    pr("FilterLayer2 of Shared Layer " + s, 0, {K, K, 3, 3}, i + 1, 10); pr("L2_" + s + "_gamma", 1, {B, K, H, W}, i + 1, 11); pr("L2_" + s + "_beta", 1, {B, K, H, W}, i + 1, 12);
+    pr("FilterLayer1 of Shared Layer " + s, 0, {K, K, 3, 3}, i + 1, 0); pr("L1_" + s + "_gamma", 1, {Bp, K, H, W}, i + 1, 1); pr("L1_" + s + "_beta", 1, {Bp, K, H, W}, i + 1, 2);
+    pr("FilterLayer2 of Shared Layer " + s, 0, {K, K, 3, 3}, i + 1, 10); pr("L2_" + s + "_gamma", 1, {Bp, K, H, W}, i + 1, 11); pr("L2_" + s + "_beta", 1, {Bp, K, H, W}, i + 1, 12);
   }
-  pr("FilterPolicyHead", 0, {2, K, 1, 1}, -1, 0); pr("PolicyHead_gamma", 1, {B, 2, H, W}, -1, 1); pr("PolicyHead_beta", 1, {B, 2, H, W}, -1, 2);
-  pr("Policy_w", 2, {2 * HW, A}, -1, 3); pr("Policy_b", 3, {B, A}, -1, 4);
-  pr("FilterValueHead", 0, {1, K, 1, 1}, -2, 0); pr("ValueHead_gamma", 1, {B, 1, H, W}, -2, 1); pr("ValueHead_beta", 1, {B, 1, H, W}, -2, 2);
-  pr("Value_w", 2, {HW, FCn}, -2, 3); pr("Value_b", 3, {B, FCn}, -2, 4);
-  pr("ValueOutput_w", 2, {FCn, 1}, -2, 5); pr("ValueOutput_b", 3, {B, 1}, -2, 6);
+  pr("FilterPolicyHead", 0, {2, K, 1, 1}, -1, 0); pr("PolicyHead_gamma", 1, {Bp, 2, H, W}, -1, 1); pr("PolicyHead_beta", 1, {Bp, 2, H, W}, -1, 2);
+  pr("Policy_w", 2, {2 * HW, A}, -1, 3); pr("Policy_b", 3, {Bp, A}, -1, 4);
+  pr("FilterValueHead", 0, {1, K, 1, 1}, -2, 0); pr("ValueHead_gamma", 1, {Bp, 1, H, W}, -2, 1); pr("ValueHead_beta", 1, {Bp, 1, H, W}, -2, 2);
+  pr("Value_w", 2, {HW, FCn}, -2, 3); pr("Value_b", 3, {Bp, FCn}, -2, 4);
+  pr("ValueOutput_w", 2, {FCn, 1}, -2, 5); pr("ValueOutput_b", 3, {Bp, 1}, -2, 6);
   int r = AGZ_OK;
 #define TAL(p, n) if ((r = t->alloc(&t->p, (size_t)(n))) != AGZ_OK) { agz_trainer_destroy(t); return r; }
   TAL(P, t->n_flat) TAL(G, t->n_flat)
@@ -2558,6 +2763,7 @@ int agz_trainer_create(agz_ctx* ctx, const agz_net_conf* c, agz_trainer** out) {
   TAL(zh, (size_t)g.M * 3) TAL(yh, (size_t)g.M * 3) TAL(dyh, (size_t)g.M * 3) TAL(dzh, (size_t)g.M * 3) TAL(hmean, 4) TAL(hinv, 4)
   TAL(logits, (size_t)B * A) TAL(hpre, (size_t)B * FCn) TAL(o, B) TAL(cost, 2) TAL(head_acc, 16) TAL(amax_prev, (size_t)(t->L + 2) * 2)
   TAL(d_planes, (size_t)B * F * HW) TAL(d_pi, (size_t)B * A) TAL(d_v, B)
+  if (tied) { TAL(tied_rows, (size_t)B * (6 * HW + A + FCn + 1)) TAL(tied_part, (size_t)2 * HW * 2 * Kp) }
 #undef TAL
   AGZ_HIP_TRY(hipStreamSynchronize(ctx->stream));
   *out = t;
@@ -2598,9 +2804,10 @@ int agz_trainer_param_info(const agz_trainer* t, int i, char* name, size_t cap, 
 
 // reference layout <-> device layout for parameter i of flat buffer `buf` (P or G). dir 0: host -> device, 1: device -> host
 // nb_sel > 0: only the first nb_sel batch rows of a conv-layer gamma/beta (agz_trainer_export needs row 0 only)
+// (B below is the number of PARAMETER rows: a tied trainer's batch-shaped tensors have one, and a tied tensor is its own row 0)
 static int xfer_param(const agz_trainer* t, float* buf, int i, float* host, int dir, int nb_sel = 0) {
   const TParamRef& p = t->prefs[i];
-  const int K = t->K, Kp = t->Kp, HW = t->g.HW, B = (nb_sel > 0 && nb_sel < t->B && t->prefs[i].layer >= 0 && (t->prefs[i].sub % 10) != 0) ? nb_sel : t->B, A = t->A, FCn = t->FC, F = t->F, Fp = t->Fp;
+  const int K = t->K, Kp = t->Kp, HW = t->g.HW, B = (nb_sel > 0 && nb_sel < t->Bp && t->prefs[i].layer >= 0 && (t->prefs[i].sub % 10) != 0) ? nb_sel : t->Bp, A = t->A, FCn = t->FC, F = t->F, Fp = t->Fp;
   hipStream_t s = t->ctx->stream;
   auto dev_rw = [&](size_t off, std::vector<float>& tmp) -> int {
     if (dir == 0) AGZ_HIP_TRY(hipMemcpyAsync(buf + off, tmp.data(), tmp.size() * 4, hipMemcpyHostToDevice, s));
@@ -2861,7 +3068,9 @@ int agz_trainer_init_random(agz_trainer* t, uint64_t seed) {  // same recipe as 
   for (int i = 0; i < (int)t->prefs.size(); i++) {
     const TParamRef& p = t->prefs[i];
     std::vector<float> v(pref_size(p));
-    const int nr = pref_batch_shaped(p) ? t->n_ranks : 1;   // this rank's slice: elements [g0, g0 + v.size()) of a tensor of n elements
+    // this rank's slice: elements [g0, g0 + v.size()) of a tensor of n elements.  A tied trainer draws row 0 of the BatchSize rows a plain
+    // trainer draws (the same stream positions, the Glorot deviation of the batch-shaped tensor): the slice of "rank 0 of B"
+    const int nr = pref_batch_shaped(p) ? (t->tied ? t->B : t->n_ranks) : 1;
     double field = 1; for (size_t k = 2; k < p.shape.size(); k++) field *= p.shape[k];
     const double stdev = std::sqrt(2.0 / ((double)(p.shape[0] * nr + p.shape[1]) * field));
     const size_t n = v.size() * nr, g0 = v.size() * (nr > 1 ? t->rank : 0);
@@ -2958,6 +3167,21 @@ static int apply_solver(agz_trainer* t, float lr, float grad_scale) {
     for (const auto& ly : t->layers) sweep(ly.o_wf, (size_t)9 * ly.Cout_p * ly.Cin_p);
     sweep(t->o_hc, t->n_flat - t->o_hc);
     t->fused_done = false;
+  } else if (t->tied) {
+    // the tower's tied gamma / beta through tied_step, the code the fused owner runs (k_bn_bwd1_tied): both paths give the same bits
+    auto tsweep = [&](size_t off, size_t n) {
+      const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>(nblk(n), (size_t)t->ctx->num_cus * 8));
+      if (adam) hipLaunchKernelGGL(k_tied_sweep<SK_ADAM>, dim3(grid), dim3(256), 0, s, t->P + off, t->G + off, t->M1 + off, t->M2 + off, n, lr, grad_scale, 0.f, sc.l2reg, sc.clip, ak);
+      else if (mom) hipLaunchKernelGGL(k_tied_sweep<SK_MOMENTUM>, dim3(grid), dim3(256), 0, s, t->P + off, t->G + off, t->V + off, (float*)nullptr, n, lr, grad_scale, sc.momentum, sc.l2reg, sc.clip, ak);
+      else hipLaunchKernelGGL(k_tied_sweep<SK_OPTIONS>, dim3(grid), dim3(256), 0, s, t->P + off, t->G + off, (float*)nullptr, (float*)nullptr, n, lr, grad_scale, sc.momentum, sc.l2reg, sc.clip, ak);
+    };
+    const int L = (int)t->layers.size() - 1;
+    for (int l = 0; l <= L; l++) {
+      const TLayer& ly = t->layers[l];
+      sweep(ly.o_wf, (size_t)9 * ly.Cout_p * ly.Cin_p);
+      tsweep(ly.o_gamma, (l < L ? t->layers[l + 1].o_wf : t->o_hc) - ly.o_gamma);   // [gamma | beta], contiguous
+    }
+    sweep(t->o_hc, t->n_flat - t->o_hc);
   } else
     sweep(0, t->n_flat);
   AGZ_HIP_TRY(hipGetLastError());
@@ -3332,9 +3556,19 @@ static bool checkpoint_complete(FILE* f, const agz_trainer* t, int nr, bool v2 =
 }
 // the magic of a checkpoint (and, for AGZTRN03, the uint32 naming the inner form): form 1 / 2 / 3 / 4, v2 = a velocity follows the
 // learnables, ad = the Adam block follows them (AGZTRN04, or AGZTRN03 with inner form 3)
-static bool read_magic(FILE* f, int* form, bool* v2, bool* ad) {
+// AGZTRN05 (a tied trainer's file): a uint32 inner form 1 .. 4, a uint32 flags word (bit 0 = tied, the only one defined), then that inner
+// file after its magic (for inner form 3 its own uint32 comes next).  *tied = the flag: agz_trainer_load refuses a file whose flag is not
+// the trainer's before anything is changed (at BatchSize 1 the tensor sizes of the two kinds coincide: the flag tells them apart).
+static bool read_magic(FILE* f, int* form, bool* v2, bool* ad, bool* tied) {
   char magic[8];
-  if (fread(magic, 1, 8, f) != 8 || memcmp(magic, "AGZTRN0", 7) != 0 || magic[7] < '1' || magic[7] > '4') return false;
+  *tied = false;
+  if (fread(magic, 1, 8, f) != 8 || memcmp(magic, "AGZTRN0", 7) != 0 || magic[7] < '1' || magic[7] > '5') return false;
+  if (magic[7] == '5') {
+    uint32_t inner = 0, flags = 0;
+    if (fread(&inner, 4, 1, f) != 1 || fread(&flags, 4, 1, f) != 1 || inner < 1 || inner > 4 || flags != 1u) return false;
+    magic[7] = (char)('0' + inner);
+    *tied = true;
+  }
   *form = magic[7] - '0';
   *v2 = *form == 2;
   *ad = *form == 4;
@@ -3347,6 +3581,13 @@ static bool read_magic(FILE* f, int* form, bool* v2, bool* ad) {
   return true;
 }
 static bool write_magic(const agz_trainer* t, FILE* f) {
+  if (t->tied) {   // AGZTRN05: the form a plain trainer in this state would write, the flags, then that file after its magic
+    const uint32_t form = t->bn_all() ? 3u : t->M1 ? 4u : t->V ? 2u : 1u, flags = 1u;
+    if (fwrite("AGZTRN05", 1, 8, f) != 8 || fwrite(&form, 4, 1, f) != 1 || fwrite(&flags, 4, 1, f) != 1) return false;
+    if (form != 3u) return true;
+    const uint32_t inner = t->M1 ? 3u : t->V ? 2u : 1u;
+    return fwrite(&inner, 4, 1, f) == 1;
+  }
   if (t->bn_all()) { const uint32_t inner = t->M1 ? 3u : t->V ? 2u : 1u; return fwrite("AGZTRN03", 1, 8, f) == 8 && fwrite(&inner, 4, 1, f) == 1; }
   return fwrite(t->M1 ? "AGZTRN04" : t->V ? "AGZTRN02" : "AGZTRN01", 1, 8, f) == 8;
 }
@@ -3425,8 +3666,8 @@ static int load_sharded(agz_trainer* t, const char* path) {
   agz_net_conf c;
   uint64_t np = 0;
   const agz_net_conf gc = global_conf(t);
-  int form = 0; bool v2 = false, ad = false;
-  bool ok = read_magic(f, &form, &v2, &ad) && fread(&c, sizeof(c), 1, f) == 1 && fread(&np, 8, 1, f) == 1;
+  int form = 0; bool v2 = false, ad = false, tied5 = false;
+  bool ok = read_magic(f, &form, &v2, &ad, &tied5) && !tied5 && fread(&c, sizeof(c), 1, f) == 1 && fread(&np, 8, 1, f) == 1;   // (no tied sharded trainer)
   if (ok) ok = memcmp(&c, &gc, sizeof(c)) == 0 && np == t->prefs.size();
   if (!ok) { fclose(f); agz::set_error("agz_trainer_load: %s is not a checkpoint of this trainer configuration (global batch %d)", path, gc.BatchSize); return AGZ_E_INVALID; }
   BnBlock bnb;
@@ -3525,13 +3766,20 @@ int agz_trainer_load(agz_trainer* t, const char* path) {
   AGZ_REQUIRE(f, AGZ_E_INVALID, "agz_trainer_load: cannot open %s", path);
   agz_net_conf c;
   uint64_t np = 0;
-  int form = 0; bool v2 = false, ad = false;
-  bool ok = read_magic(f, &form, &v2, &ad) && fread(&c, sizeof(c), 1, f) == 1 && fread(&np, 8, 1, f) == 1;
+  int form = 0; bool v2 = false, ad = false, tied5 = false;
+  bool ok = read_magic(f, &form, &v2, &ad, &tied5) && fread(&c, sizeof(c), 1, f) == 1 && fread(&np, 8, 1, f) == 1;
+  if (ok && tied5 != t->tied) {
+    fclose(f);
+    agz::set_error("agz_trainer_load: %s is the checkpoint of a %s trainer, this trainer is %s", path, tied5 ? "tied (agz_trainer_create_tied)" : "plain",
+                   t->tied ? "tied" : "plain");
+    return AGZ_E_INVALID;
+  }
   if (ok) ok = memcmp(&c, &t->conf, sizeof(c)) == 0 && np == t->prefs.size();
   if (!ok) { fclose(f); agz::set_error("agz_trainer_load: %s is not a checkpoint of this trainer configuration", path); return AGZ_E_INVALID; }
   BnBlock bnb;
   AdamHead ah;
-  if ((v2 || ad || form == 3) && !checkpoint_complete(f, t, 1, v2, form == 3 ? &bnb : nullptr, ad ? &ah : nullptr)) { fclose(f); agz::set_error("agz_trainer_load: %s is truncated or mismatched", path); return AGZ_E_INVALID; }
+  // (an AGZTRN05 file is checked for its full length in every inner form)
+  if ((v2 || ad || form == 3 || tied5) && !checkpoint_complete(f, t, 1, v2, form == 3 ? &bnb : nullptr, ad ? &ah : nullptr)) { fclose(f); agz::set_error("agz_trainer_load: %s is truncated or mismatched", path); return AGZ_E_INVALID; }
   for (int i = 0; ok && i < (int)t->prefs.size(); i++) {
     uint64_t cnt = 0;
     std::vector<float> v(pref_size(t->prefs[i]));

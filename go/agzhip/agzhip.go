@@ -776,7 +776,7 @@ func NewTrainer(ctx *Ctx, d *dual.Dual) (*Trainer, error) {
 // [rows, ActionSpace], values [rows] as flat float32 slices (tensor.Dense.Data()).
 func (t *Trainer) Train(Xs, policies, values []float32, batches, iterations int, seed uint64) error {
 	if t.d == nil {
-		return fmt.Errorf("agzhip: Train: a sharded trainer has no dual.Dual to copy back into: use TrainDev")
+		return fmt.Errorf("agzhip: Train: a sharded or tied trainer (NewShardedTrainer, NewTrainerTied) has no dual.Dual to copy back into: use TrainDev")
 	}
 	rows := batches * t.d.BatchSize
 	if batches < 1 || len(Xs) < rows*t.d.Features*t.d.Height*t.d.Width || len(policies) < rows*t.d.ActionSpace || len(values) < rows {
@@ -1059,6 +1059,33 @@ func NewShardedTrainer(comm *Comm, conf dual.Config) (*Trainer, error) {
 		return nil, err
 	}
 	return t, nil
+}
+
+// NewTrainerTied is a trainer whose BatchNorm gamma / beta and FC biases are stored once, at the inference net's shapes ([C,H,W],
+// [units]), and shared by every row of the batch (agz_trainer_create_tied): the gradient of such a tensor is the sum over the rows, the
+// solver steps it once, and Export hands the WHOLE trained state to the inference net (a plain trainer exports row 0 of BatchSize copies).
+// conf.BatchSize stays the rows of a step.  Start the learnables with InitRandom or Load; Train is not available (dual.Dual's Model()
+// holds the batch-shaped tensors: there is nothing of the tied shapes to copy back into).
+func NewTrainerTied(ctx *Ctx, conf dual.Config) (*Trainer, error) {
+	defer ctx.enter()()
+	cc := C.agz_net_conf{
+		K: C.int32_t(conf.K), SharedLayers: C.int32_t(conf.SharedLayers), FC: C.int32_t(conf.FC), BatchSize: C.int32_t(conf.BatchSize),
+		Width: C.int32_t(conf.Width), Height: C.int32_t(conf.Height), Features: C.int32_t(conf.Features),
+		ActionSpace: C.int32_t(conf.ActionSpace), bn_mode: C.AGZ_BN_DEGENERATE_EPS, bn_eps: 1e-5,
+	}
+	t := &Trainer{ctx: ctx}
+	if err := lastErr(C.agz_trainer_create_tied(ctx.h, &cc, &t.h)); err != nil {
+		return nil, err
+	}
+	return t, nil
+}
+
+// IsTied reports whether the trainer was made by NewTrainerTied (agz_trainer_is_tied).
+func (t *Trainer) IsTied() (bool, error) {
+	defer t.ctx.enter()()
+	var v C.int
+	err := lastErr(C.agz_trainer_is_tied(t.h, &v))
+	return v != 0, err
 }
 
 // InitRandom fills the learnables from the library's initialiser (agz_trainer_init_random); a sharded trainer draws its rows of the

@@ -185,6 +185,21 @@ typedef struct agz_trainer agz_trainer;
  * reference's FULL shapes in Model() order: conv filter [out,in,k,k]; BN gamma/beta [B,C,H,W]; FC w [in,units];
  * FC b [B,units]  (batch-shaped).  BatchNorm runs in training mode (batch statistics). */
 int agz_trainer_create(agz_ctx* ctx, const agz_net_conf* conf, agz_trainer** out);
+/* Tied affine (opt-in; DESIGN §2 `tied-affine`): the same learnables in the same Model() order, but every batch-shaped one is stored ONCE,
+ * at its row-0 shape — BatchNorm gamma / beta [C,H,W], Policy_b / Value_b / ValueOutput_b [units] — and shared by every row of a step:
+ * agz_trainer_param_info returns exactly agz_net_param_info's sizes, and agz_trainer_export copies the whole trained state (nothing of
+ * it is dropped, where a plain trainer exports row 0 of BatchSize independently trained copies).  Declared definition: forward and cost
+ * are those of the plain trainer whose batch-shaped tensors hold the tied tensor in every row; the gradient of a tied tensor is the sum
+ * over the batch rows of that plain trainer's per-row gradients (accumulated in double in row order, rounded once: no atomics,
+ * reproducible to the bit); the solver step of the configured kind (vanilla, L2 / clip, momentum, Adam) is applied to the tied tensor
+ * once, with that sum.  conf->BatchSize stays the number of rows of a step; it also still feeds the Glorot fans of
+ * agz_trainer_init_random, so that a tied trainer draws row 0 of what a plain trainer of the same conf and seed draws.  Every entry
+ * point of a plain trainer works on a tied handle (velocity and moments take the tied shapes; agz_trainer_allreduce reduces the now
+ * small flat buffer in one call), except agz_trainer_forward_backward_allreduce(_dev), which return AGZ_E_STATE; there is no tied
+ * sharded trainer.  Checkpoints are "AGZTRN05" (agz_trainer_save below) and load only into a tied trainer.  A trainer made by
+ * agz_trainer_create / agz_trainer_create_sharded runs exactly the kernels it ran before this option existed. */
+int agz_trainer_create_tied(agz_ctx* ctx, const agz_net_conf* conf, agz_trainer** out);
+int agz_trainer_is_tied(const agz_trainer* t, int* tied);   /* *tied = 1 for a handle of agz_trainer_create_tied, else 0 */
 void agz_trainer_destroy(agz_trainer* t);
 int agz_trainer_num_params(const agz_trainer* t);
 int agz_trainer_param_info(const agz_trainer* t, int index, char* name, size_t name_cap, size_t* n_elems);
@@ -306,7 +321,12 @@ int agz_train_dev(agz_trainer* t, const float* Xs_dev, const float* policies_dev
  * that 01 / 02 file after its magic, then float momentum, uint32 on, uint32 n_ops and per op {uint64 C, double N, double S_mean[C],
  * double S_var[C]}.  load: 03 sets the tracking setting and state it carries; 01 / 02 reset the state to N = 0 and keep the setting; a
  * truncated or inconsistent 03 file is rejected (AGZ_E_INVALID) before anything is changed.  Sharded: rank 0 writes, every rank loads
- * the same block.  Test: tests/test_bn_tracking_gpu.py (checkpoint). */
+ * the same block.  Test: tests/test_bn_tracking_gpu.py (checkpoint).
+ * A tied trainer (agz_trainer_create_tied) writes "AGZTRN05": the magic, a uint32 inner form (1 .. 4: the form a plain trainer in the same
+ * state would write), a uint32 flags word (bit 0 = tied, always set; the other bits 0), then the body of that 01 - 04 file after its magic,
+ * with the tied tensor sizes.  load: an 05 file into a plain trainer, and an 01 - 04 file into a tied trainer, are AGZ_E_INVALID before
+ * anything is changed — also at BatchSize 1, where the tensor sizes of the two kinds coincide (which is what the flag is for); an 05 file is
+ * checked for its full length in every inner form.  Plain trainers write byte for byte what they wrote before.  Test: tests/test_tied_gpu.py. */
 int agz_trainer_save(const agz_trainer* t, const char* path);
 int agz_trainer_load(agz_trainer* t, const char* path);
 /* dual.Infer's copy loop (dualnet/meta.go:141-146): row 0 of every learnable -> the inference net; commits it.  A trainer that holds
