@@ -34,6 +34,7 @@
 
 #include "net.hpp"
 #include "conv_maps.hpp"
+#include "ckpt.hpp"
 #include "shard.hpp"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -2919,10 +2920,7 @@ int agz_trainer_get_grad(const agz_trainer* t, int i, float* host, size_t n) {
 }
 
 // ---- solver options (gorgonia's solver constructor options, dualnet/meta.go:20) ---------------------------------------------------------
-static bool solver_conf_valid(const agz_solver_conf* c) {
-  return std::isfinite(c->momentum) && std::isfinite(c->l2reg) && std::isfinite(c->clip) && c->momentum >= 0.f && c->momentum < 1.f &&
-         c->l2reg >= 0.f && c->clip >= 0.f && c->reserved == 0;
-}
+using agz::ckpt::solver_conf_valid;   // (the options' validity rules: ckpt.hpp, which applies them to a checkpoint as well)
 // momentum != 0 for the first time: the velocity buffer, zeroed; momentum back to 0: released (v has no meaning without it).  The options
 // change only if the call succeeds.  (Sharded: a local call; every rank sets the same options, as every rank passes the same lr.)
 int agz_trainer_set_solver(agz_trainer* t, const agz_solver_conf* c) {
@@ -2989,10 +2987,7 @@ int agz_trainer_reset_solver(agz_trainer* t) {
 }
 
 // ---- Adam (gorgonia.NewAdamSolver on the solver line, dualnet/meta.go:20; the definition: include/agz.h, DESIGN §2 `solver-adam`) ------
-static bool adam_conf_valid(const agz_adam_conf* c) {
-  return std::isfinite(c->beta1) && std::isfinite(c->beta2) && std::isfinite(c->eps) && c->beta1 >= 0.f && c->beta1 < 1.f && c->beta2 >= 0.f &&
-         c->beta2 < 1.f && c->eps > 0.f && (c->on == 0 || c->on == 1);
-}
+using agz::ckpt::adam_conf_valid;
 // on for the first time: the two moment buffers, zeroed, and t = 0; off: both released, t = 0.  The settings change only if the call
 // succeeds.  (Sharded: a local call; every rank makes it alike.)
 int agz_trainer_set_adam(agz_trainer* t, const agz_adam_conf* c) {
@@ -3351,7 +3346,7 @@ int agz_train_dev(agz_trainer* t, const float* Xs_dev, const float* policies_dev
 
 
 // ---- running BatchNorm statistics (BnTrack above; include/agz.h) --------------------------------------------------------------------------
-static bool bn_momentum_valid(float m) { return std::isfinite(m) && m >= 0.f && m < 1.f; }
+using agz::ckpt::bn_momentum_valid;
 // the whole state on the host (a few KB to a few hundred KB); empty while none exists
 static int bn_download(const agz_trainer* t, std::vector<double>& h) {
   h.assign(t->bn_total, 0.0);
@@ -3467,42 +3462,34 @@ int agz_trainer_eval(agz_trainer* t, const float* planes, const float* pi, const
   return AGZ_OK;
 }
 
-// ---- the BatchNorm block of an AGZTRN03 checkpoint: float momentum, uint32 on, uint32 n_ops, per op {uint64 C, double N, S_mean[C], S_var[C]}
-static uint64_t bn_block_bytes(const agz_trainer* t) {
-  uint64_t n = 12;
-  for (int i = 0; i < t->bn_num(); i++) n += 16 + 16 * (uint64_t)(i >= 2 * t->L + 1 ? (i == 2 * t->L + 1 ? 2 : 1) : t->K);
-  return n;
+// ---- checkpoints.  The file's format and what each form does to the trainer that loads it: ckpt.hpp, which also checks a whole file
+// before anything here is changed.  This side describes the trainer (ckpt_layout), fetches and delivers tensors, and applies what a file
+// carries.
+namespace ckpt = agz::ckpt;
+
+// BatchSize and the batch-shaped tensors are the GLOBAL batch's on a sharded trainer: its file is the plain trainer's at that batch size
+static ckpt::Layout ckpt_layout(const agz_trainer* t) {
+  ckpt::Layout lay{t->conf, t->tied, {}, {}};
+  lay.conf.BatchSize = t->B * t->n_ranks;
+  for (const auto& p : t->prefs) lay.tensors.push_back({(uint64_t)pref_size(p) * (pref_batch_shaped(p) ? t->n_ranks : 1), pref_batch_shaped(p)});
+  for (int i = 0; i < t->bn_num(); i++) lay.bn_C.push_back((uint64_t)(i >= 2 * t->L + 1 ? (i == 2 * t->L + 1 ? 2 : 1) : t->K));
+  return lay;
 }
-static bool bn_block_write(const agz_trainer* t, FILE* f) {
+// the running statistics (the trainer holds some: bn_all()) as a checkpoint's BatchNorm block, and back
+static int bn_block_get(const agz_trainer* t, ckpt::BnBlock& b) {
   std::vector<double> h;
-  if (bn_download(t, h) != AGZ_OK) return false;
-  const uint32_t on = t->bn_on ? 1u : 0u, nops = (uint32_t)t->bn_num();
-  bool ok = fwrite(&t->bn_lam, 4, 1, f) == 1 && fwrite(&on, 4, 1, f) == 1 && fwrite(&nops, 4, 1, f) == 1;
-  for (int i = 0; ok && i < t->bn_num(); i++) {
+  int r = bn_download(t, h);
+  if (r != AGZ_OK) return r;
+  b = ckpt::BnBlock{t->bn_lam, t->bn_on ? 1u : 0u, {}, {}, {}};
+  for (int i = 0; i < t->bn_num(); i++) {
     const agz_trainer::BnOp op = t->bn_op(i);
-    const uint64_t C = (uint64_t)op.C;
-    ok = fwrite(&C, 8, 1, f) == 1 && fwrite(&h[op.n], 8, 1, f) == 1 && fwrite(&h[op.mean], 8, C, f) == C && fwrite(&h[op.var], 8, C, f) == C;
+    b.n.push_back(h[op.n]);
+    b.sm.emplace_back(h.begin() + op.mean, h.begin() + op.mean + op.C);
+    b.sv.emplace_back(h.begin() + op.var, h.begin() + op.var + op.C);
   }
-  return ok;
+  return AGZ_OK;
 }
-struct BnBlock { float lam; uint32_t on; std::vector<double> n; std::vector<std::vector<double>> sm, sv; };
-// reads and validates the block at the file's current position; nothing of the trainer is changed
-static bool bn_block_read(const agz_trainer* t, FILE* f, BnBlock& b) {
-  uint32_t nops = 0;
-  if (fread(&b.lam, 4, 1, f) != 1 || fread(&b.on, 4, 1, f) != 1 || fread(&nops, 4, 1, f) != 1) return false;
-  if (!bn_momentum_valid(b.lam) || b.on > 1 || nops != (uint32_t)t->bn_num()) return false;
-  b.n.resize(nops); b.sm.resize(nops); b.sv.resize(nops);
-  for (uint32_t i = 0; i < nops; i++) {
-    uint64_t C = 0;
-    const uint64_t want = (uint64_t)(i >= 2u * t->L + 1 ? (i == 2u * t->L + 1 ? 2 : 1) : t->K);
-    if (fread(&C, 8, 1, f) != 1 || C != want || fread(&b.n[i], 8, 1, f) != 1 || !(std::isfinite(b.n[i]) && b.n[i] > 0)) return false;
-    b.sm[i].resize(C); b.sv[i].resize(C);
-    if (fread(b.sm[i].data(), 8, C, f) != C || fread(b.sv[i].data(), 8, C, f) != C) return false;
-    for (uint64_t c = 0; c < C; c++) if (!std::isfinite(b.sm[i][c]) || !std::isfinite(b.sv[i][c])) return false;
-  }
-  return true;
-}
-static int bn_block_apply(agz_trainer* t, const BnBlock& b) {
+static int bn_block_apply(agz_trainer* t, const ckpt::BnBlock& b) {
   AGZ_HIP_TRY(hipSetDevice(t->ctx->device));
   int r = t->bn_alloc();
   if (r != AGZ_OK) return r;
@@ -3517,86 +3504,11 @@ static int bn_block_apply(agz_trainer* t, const BnBlock& b) {
   t->bn_on = b.on != 0; t->bn_lam = b.lam;
   return AGZ_OK;
 }
-
-// the configuration a checkpoint of this trainer carries: BatchSize is the GLOBAL batch of a sharded trainer
-static agz_net_conf global_conf(const agz_trainer* t) {
-  agz_net_conf c = t->conf;
-  c.BatchSize = t->B * t->n_ranks;
-  return c;
-}
-
-// An AGZTRN02 file is checked for its full length BEFORE anything of it is loaded (the header has been read; the position is restored):
-// a truncated file is rejected with the trainer's parameters, options and velocity untouched.  nr: ranks the global tensors are split over.
-// (AGZTRN03: v2 says whether the inner form carries a velocity; the BatchNorm block after it is read and validated here as well, into *bn)
-// (AGZTRN04 / inner form 3, ad != nullptr: the learnables, agz_solver_conf, agz_adam_conf, uint64 t, every tensor's first and then second
-// moment.  Its options, its counter and every count word are read and checked here too, into *ad, so that an inconsistent file changes nothing.)
-struct AdamHead { agz_solver_conf sc; agz_adam_conf ac; uint64_t step; };
-static bool checkpoint_complete(FILE* f, const agz_trainer* t, int nr, bool v2 = true, BnBlock* bn = nullptr, AdamHead* ad = nullptr) {
-  const long at = ftell(f);
-  const int groups = ad ? 3 : v2 ? 2 : 1;
-  uint64_t body = ad ? sizeof(agz_solver_conf) + sizeof(agz_adam_conf) + 8 : v2 ? sizeof(agz_solver_conf) : 0;
-  for (const auto& p : t->prefs) body += groups * (8 + 4 * (uint64_t)pref_size(p) * (pref_batch_shaped(p) ? nr : 1));
-  const uint64_t need = (uint64_t)at + body + (bn ? bn_block_bytes(t) : 0);
-  bool ok = at >= 0 && fseek(f, 0, SEEK_END) == 0 && (uint64_t)ftell(f) == need;
-  if (ok && ad) {
-    ok = fseek(f, at, SEEK_SET) == 0;
-    for (int k = 0; ok && k < groups; k++) {
-      if (k == 1)
-        ok = fread(&ad->sc, sizeof(ad->sc), 1, f) == 1 && fread(&ad->ac, sizeof(ad->ac), 1, f) == 1 && fread(&ad->step, 8, 1, f) == 1 &&
-             solver_conf_valid(&ad->sc) && ad->sc.momentum == 0.f && adam_conf_valid(&ad->ac) && ad->ac.on == 1;
-      for (size_t i = 0; ok && i < t->prefs.size(); i++) {
-        const TParamRef& p = t->prefs[i];
-        uint64_t cnt = 0;
-        ok = fread(&cnt, 8, 1, f) == 1 && cnt == (uint64_t)pref_size(p) * (pref_batch_shaped(p) ? nr : 1) && fseek(f, (long)(cnt * 4), SEEK_CUR) == 0;
-      }
-    }
-  }
-  if (ok && bn) ok = fseek(f, (long)((uint64_t)at + body), SEEK_SET) == 0 && bn_block_read(t, f, *bn);
-  return fseek(f, at, SEEK_SET) == 0 && ok;
-}
-// the magic of a checkpoint (and, for AGZTRN03, the uint32 naming the inner form): form 1 / 2 / 3 / 4, v2 = a velocity follows the
-// learnables, ad = the Adam block follows them (AGZTRN04, or AGZTRN03 with inner form 3)
-// AGZTRN05 (a tied trainer's file): a uint32 inner form 1 .. 4, a uint32 flags word (bit 0 = tied, the only one defined), then that inner
-// file after its magic (for inner form 3 its own uint32 comes next).  *tied = the flag: agz_trainer_load refuses a file whose flag is not
-// the trainer's before anything is changed (at BatchSize 1 the tensor sizes of the two kinds coincide: the flag tells them apart).
-static bool read_magic(FILE* f, int* form, bool* v2, bool* ad, bool* tied) {
-  char magic[8];
-  *tied = false;
-  if (fread(magic, 1, 8, f) != 8 || memcmp(magic, "AGZTRN0", 7) != 0 || magic[7] < '1' || magic[7] > '5') return false;
-  if (magic[7] == '5') {
-    uint32_t inner = 0, flags = 0;
-    if (fread(&inner, 4, 1, f) != 1 || fread(&flags, 4, 1, f) != 1 || inner < 1 || inner > 4 || flags != 1u) return false;
-    magic[7] = (char)('0' + inner);
-    *tied = true;
-  }
-  *form = magic[7] - '0';
-  *v2 = *form == 2;
-  *ad = *form == 4;
-  if (*form == 3) {
-    uint32_t inner = 0;
-    if (fread(&inner, 4, 1, f) != 1 || inner < 1 || inner > 3) return false;
-    *v2 = inner == 2;
-    *ad = inner == 3;
-  }
-  return true;
-}
-static bool write_magic(const agz_trainer* t, FILE* f) {
-  if (t->tied) {   // AGZTRN05: the form a plain trainer in this state would write, the flags, then that file after its magic
-    const uint32_t form = t->bn_all() ? 3u : t->M1 ? 4u : t->V ? 2u : 1u, flags = 1u;
-    if (fwrite("AGZTRN05", 1, 8, f) != 8 || fwrite(&form, 4, 1, f) != 1 || fwrite(&flags, 4, 1, f) != 1) return false;
-    if (form != 3u) return true;
-    const uint32_t inner = t->M1 ? 3u : t->V ? 2u : 1u;
-    return fwrite(&inner, 4, 1, f) == 1;
-  }
-  if (t->bn_all()) { const uint32_t inner = t->M1 ? 3u : t->V ? 2u : 1u; return fwrite("AGZTRN03", 1, 8, f) == 8 && fwrite(&inner, 4, 1, f) == 1; }
-  return fwrite(t->M1 ? "AGZTRN04" : t->V ? "AGZTRN02" : "AGZTRN01", 1, 8, f) == 8;
-}
-// the options an Adam checkpoint carries, into the trainer (the head was validated by checkpoint_complete): momentum 0 releases a
-// velocity, Adam on allocates the moments if there are none
-static int adam_head_apply(agz_trainer* t, const AdamHead& h) {
-  int r = agz_trainer_set_solver(t, &h.sc);
-  if (r == AGZ_OK) r = agz_trainer_set_adam(t, &h.ac);
-  if (r == AGZ_OK) t->adam_t = h.step;
+// the options an Adam checkpoint carries, into the trainer: momentum 0 releases a velocity, Adam on allocates the moments if there are none
+static int adam_head_apply(agz_trainer* t, const ckpt::Options& o) {
+  int r = agz_trainer_set_solver(t, &o.solver);
+  if (r == AGZ_OK) r = agz_trainer_set_adam(t, &o.adam);
+  if (r == AGZ_OK) t->adam_t = o.step;
   return r;
 }
 // a file with a velocity, loaded into a trainer with Adam on: the file's solver is taken and Adam turned off
@@ -3609,211 +3521,84 @@ static int adam_off(agz_trainer* t) {
 // group 0 / 1 / 2 of a checkpoint's tensor blocks: the learnables, then the velocity or (Adam) the first moments, then the second moments
 static float* group_buf(const agz_trainer* t, int group) { return group == 0 ? t->P : t->M1 ? (group == 1 ? t->M1 : t->M2) : t->V; }
 
-// Sharded save (collective): rank 0 writes the plain trainer's file at the global batch.  Tensor by tensor, batch-shaped ones are gathered
-// from every rank (rows in rank order = the global tensor) through one device buffer of n slices; nothing larger than one global tensor is
-// ever staged on the host.  Every rank enters every gather whatever failed locally, and the call ends with the status exchange.
-static int save_sharded(const agz_trainer* t, const char* path) {
+// Sharded (collective): rank 0 writes the plain trainer's file at the global batch.  Tensor by tensor, batch-shaped ones are gathered from
+// every rank (rows in rank order = the global tensor) through one device buffer of n slices; nothing larger than one global tensor is ever
+// staged on the host.  Every rank enters every gather whatever failed locally, and the call ends with the status exchange.  The options,
+// and so the form, are the same on every rank; so are the running statistics rank 0 writes.
+int agz_trainer_save(const agz_trainer* t, const char* path) {
+  AGZ_REQUIRE(t && path, AGZ_E_INVALID, "agz_trainer_save: NULL argument");
   const int n = t->n_ranks;
-  int rc = AGZ_OK;
+  auto agree = [&](int rc) { return t->sharded ? t->shard.agree(rc) : rc; };
+  int rc = hipSetDevice(t->ctx->device) == hipSuccess && hipStreamSynchronize(t->ctx->stream) == hipSuccess ? AGZ_OK : AGZ_E_HIP;
   FILE* f = nullptr;
   if (t->rank == 0 && !(f = fopen(path, "wb"))) { agz::set_error("agz_trainer_save: cannot open %s", path); rc = AGZ_E_INVALID; }
   size_t mx = 0;
-  for (const auto& p : t->prefs) if (pref_batch_shaped(p)) mx = std::max(mx, pref_size(p));
-  float* d = nullptr;   // [n][mx] gathered slices, then this rank's slice
-  if (hipMalloc(&d, (size_t)(n + 1) * mx * 4) != hipSuccess) { d = nullptr; if (rc == AGZ_OK) { agz::set_error("agz_trainer_save: out of device memory for the gather"); rc = AGZ_E_NOMEM; } }
-  int a = t->shard.agree(rc);
+  for (const auto& p : t->prefs) if (t->sharded && pref_batch_shaped(p)) mx = std::max(mx, pref_size(p));
+  float* d = nullptr;   // (sharded) [n][mx] gathered slices, then this rank's slice
+  if (mx && hipMalloc(&d, (size_t)(n + 1) * mx * 4) != hipSuccess) { d = nullptr; if (rc == AGZ_OK) { agz::set_error("agz_trainer_save: out of device memory for the gather"); rc = AGZ_E_NOMEM; } }
+  const int a = agree(rc);
   if (a != AGZ_OK) { if (f) fclose(f); if (d) hipFree(d); return a; }
-  const agz_net_conf gc = global_conf(t);
-  const uint64_t np = t->prefs.size();
-  // (AGZTRN02 when this trainer has a velocity — the same on every rank, like the options themselves: agz_trainer_save)
-  bool ok = f == nullptr || (write_magic(t, f) && fwrite(&gc, sizeof(gc), 1, f) == 1 && fwrite(&np, 8, 1, f) == 1);
+  const ckpt::Form form{t->tied, t->M1 ? ckpt::ADAM : t->V ? ckpt::VELOCITY : ckpt::NONE, t->bn_all()};
+  ckpt::BnBlock bn;
+  if (f && form.bn && bn_block_get(t, bn) != AGZ_OK) rc = AGZ_E_HIP;
   std::vector<float> v, all;
-  const int np_i = (int)t->prefs.size();
-  // the learnables, then (02) the options and every tensor's velocity, or (04) the options, Adam's settings and counter and both moments
-  for (int k = 0; k < (t->M1 ? 3 : t->V ? 2 : 1) * np_i; k++) {
-    const int i = k % np_i;
-    if (k == np_i && f && ok) ok = fwrite(&t->solver, sizeof(t->solver), 1, f) == 1;
-    if (k == np_i && f && ok && t->M1) ok = fwrite(&t->adam, sizeof(t->adam), 1, f) == 1 && fwrite(&t->adam_t, 8, 1, f) == 1;
+  const bool ok = ckpt::write(f, ckpt_layout(t), form, ckpt::Options{t->solver, t->adam, t->adam_t}, bn, [&](int g, size_t i) {
     const TParamRef& p = t->prefs[i];
     v.assign(pref_size(p), 0.f);
-    if ((k < np_i ? agz_trainer_get_param(t, i, v.data(), v.size()) : xfer_param(t, group_buf(t, k / np_i), i, v.data(), 1)) != AGZ_OK && rc == AGZ_OK) rc = AGZ_E_HIP;
-    const float* out = v.data();
-    uint64_t cnt = v.size();
-    if (pref_batch_shaped(p)) {
-      float* mine = d + (size_t)n * mx;
-      if (hipMemcpy(mine, v.data(), v.size() * 4, hipMemcpyHostToDevice) != hipSuccess && rc == AGZ_OK) rc = AGZ_E_HIP;
-      int r = t->shard.allgather_bytes(mine, d, v.size() * 4);
-      if (r != AGZ_OK && rc == AGZ_OK) rc = r;
-      if (f) {
-        all.resize(v.size() * n);
-        if (hipMemcpy(all.data(), d, all.size() * 4, hipMemcpyDeviceToHost) != hipSuccess && rc == AGZ_OK) rc = AGZ_E_HIP;
-        out = all.data(); cnt = all.size();
-      }
-    }
-    if (f && ok) ok = fwrite(&cnt, 8, 1, f) == 1 && fwrite(out, 4, cnt, f) == cnt;
-  }
-  if (f && ok && t->bn_all()) ok = bn_block_write(t, f);   // (03: the running statistics, the same bits on every rank)
-  if (f) ok = (fclose(f) == 0) && ok;
-  hipFree(d);
-  if (!ok && rc == AGZ_OK) { agz::set_error("agz_trainer_save: write to %s failed", path); rc = AGZ_E_INVALID; }
-  return t->shard.agree(rc);
+    if (xfer_param(t, group_buf(t, g), (int)i, v.data(), 1) != AGZ_OK && rc == AGZ_OK) rc = AGZ_E_HIP;
+    if (!t->sharded || !pref_batch_shaped(p)) return std::make_pair((const float*)v.data(), (uint64_t)v.size());
+    float* mine = d + (size_t)n * mx;
+    if (hipMemcpy(mine, v.data(), v.size() * 4, hipMemcpyHostToDevice) != hipSuccess && rc == AGZ_OK) rc = AGZ_E_HIP;
+    const int r = t->shard.allgather_bytes(mine, d, v.size() * 4);
+    if (r != AGZ_OK && rc == AGZ_OK) rc = r;
+    all.resize(f ? v.size() * n : 0);
+    if (f && hipMemcpy(all.data(), d, all.size() * 4, hipMemcpyDeviceToHost) != hipSuccess && rc == AGZ_OK) rc = AGZ_E_HIP;
+    return std::make_pair((const float*)all.data(), (uint64_t)all.size());
+  });
+  const bool closed = !f || fclose(f) == 0;
+  if (d) hipFree(d);
+  if (f && !(ok && closed) && rc == AGZ_OK) { agz::set_error("agz_trainer_save: write to %s failed", path); rc = AGZ_E_INVALID; }
+  return agree(rc);
 }
 
-// Sharded load (local): a checkpoint of the GLOBAL configuration; this rank reads its rows of every batch-shaped tensor
-static int load_sharded(agz_trainer* t, const char* path) {
-  FILE* f = fopen(path, "rb");
-  AGZ_REQUIRE(f, AGZ_E_INVALID, "agz_trainer_load: cannot open %s", path);
-  agz_net_conf c;
-  uint64_t np = 0;
-  const agz_net_conf gc = global_conf(t);
-  int form = 0; bool v2 = false, ad = false, tied5 = false;
-  bool ok = read_magic(f, &form, &v2, &ad, &tied5) && !tied5 && fread(&c, sizeof(c), 1, f) == 1 && fread(&np, 8, 1, f) == 1;   // (no tied sharded trainer)
-  if (ok) ok = memcmp(&c, &gc, sizeof(c)) == 0 && np == t->prefs.size();
-  if (!ok) { fclose(f); agz::set_error("agz_trainer_load: %s is not a checkpoint of this trainer configuration (global batch %d)", path, gc.BatchSize); return AGZ_E_INVALID; }
-  BnBlock bnb;
-  AdamHead ah;
-  if ((v2 || ad || form == 3) && !checkpoint_complete(f, t, t->n_ranks, v2, form == 3 ? &bnb : nullptr, ad ? &ah : nullptr)) { fclose(f); agz::set_error("agz_trainer_load: %s is truncated or mismatched", path); return AGZ_E_INVALID; }
-  const int np_i = (int)t->prefs.size();
-  for (int k = 0; ok && k < (ad ? 3 : v2 ? 2 : 1) * np_i; k++) {
-    const int i = k % np_i;
-    if (k == np_i && ad) {   // (04) the options, Adam's settings and counter (read and checked above), then both moments
-      ok = fseek(f, (long)(sizeof(ah.sc) + sizeof(ah.ac) + 8), SEEK_CUR) == 0;
-      if (!ok) break;
-      const int r = adam_head_apply(t, ah);
-      if (r != AGZ_OK) { fclose(f); return r; }
-    } else if (k == np_i) {   // (02) the options, then every tensor's velocity
-      agz_solver_conf sc;
-      ok = fread(&sc, sizeof(sc), 1, f) == 1 && solver_conf_valid(&sc) && sc.momentum != 0.f;
-      if (ok && (adam_off(t) != AGZ_OK || agz_trainer_set_solver(t, &sc) != AGZ_OK)) { fclose(f); return AGZ_E_HIP; }
-      if (!ok) break;
-    }
-    const TParamRef& p = t->prefs[i];
-    const bool bs = pref_batch_shaped(p);
-    std::vector<float> v(pref_size(p));
-    const uint64_t want = v.size() * (bs ? t->n_ranks : 1), skip = bs ? (uint64_t)v.size() * t->rank : 0;
-    uint64_t cnt = 0;
-    ok = fread(&cnt, 8, 1, f) == 1 && cnt == want && fseek(f, (long)(skip * 4), SEEK_CUR) == 0 && fread(v.data(), 4, v.size(), f) == v.size() &&
-         fseek(f, (long)((want - skip - v.size()) * 4), SEEK_CUR) == 0;
-    if (ok && (k < np_i ? agz_trainer_set_param(t, i, v.data(), v.size()) : xfer_param(t, group_buf(t, k / np_i), i, v.data(), 0)) != AGZ_OK) { fclose(f); return AGZ_E_HIP; }
-  }
-  fclose(f);
-  AGZ_REQUIRE(ok, AGZ_E_INVALID, "agz_trainer_load: %s is truncated or mismatched", path);
-  // 03: the tracking setting and state the file carries; 01 / 02: no statistics (N = 0), the setting stays
-  { int r = form == 3 ? bn_block_apply(t, bnb) : agz_trainer_reset_bn_stats(t); if (r != AGZ_OK) return r; }
-  if (!v2 && !ad) return agz_trainer_reset_solver(t);   // a file without solver state: v := 0 (Adam: the moments and t := 0), the options stay
-  return AGZ_OK;
-}
-
-// Checkpoint of the TRAINABLE network (AZ.Save / AZ.Load, agogo.go:175-209, for the side that keeps learning): every
-// learnable in its full batch-shaped form.  File: "AGZTRN01", agz_net_conf, count, then per tensor {n, n floats}.
-// A trainer that holds a velocity (momentum != 0, agz_trainer_set_solver) writes "AGZTRN02": the same payload, then agz_solver_conf
-// (16 bytes), then per tensor {n, n floats} of velocity in the same order and layout.  Without a velocity the file is AGZTRN01, byte for
-// byte what it always was (l2reg / clip alone are not stored: they are the caller's configuration, like lr).  Load reads both: an 02 file
-// sets the options it carries and the velocity, an 01 file zeroes the velocity and keeps the trainer's options.
-// A trainer that holds running BatchNorm statistics (N > 0: agz_trainer_set_bn_tracking) writes "AGZTRN03": the magic, a uint32 naming the
-// inner form (1 or 2), the complete body of that 01 / 02 file after its magic, then float momentum, uint32 on, uint32 n_ops and per op (the
-// order of agz_net_set_bn_stats) {uint64 C, double N, double S_mean[C], double S_var[C]}.  Any other trainer writes the 01 / 02 file it
-// always wrote.  Load: 03 sets the tracking setting and state it carries (checked for its full length and a consistent block before
-// anything is changed); 01 / 02 reset the state to N = 0 and keep the setting.
-// A trainer with Adam on (agz_trainer_set_adam) writes "AGZTRN04": the 01 payload, agz_solver_conf (16 bytes, momentum 0), agz_adam_conf
-// (16 bytes), uint64 t, then per tensor {n, n floats} of the first moment and per tensor {n, n floats} of the second, in the payload's order;
-// with running statistics as well it is AGZTRN03 with inner form 3.  Load: the Adam forms set the options, t and the moments (Adam turned
-// on, the moments allocated), checked for their full length, valid options and every count word before anything is changed; 01 loaded into
-// a trainer with Adam on zeroes the moments and t and keeps the setting; 02 takes the file's solver and turns Adam off.
-int agz_trainer_save(const agz_trainer* t, const char* path) {
-  AGZ_REQUIRE(t && path, AGZ_E_INVALID, "agz_trainer_save: NULL argument");
-  if (t->sharded) return save_sharded(t, path);
-  FILE* f = fopen(path, "wb");
-  AGZ_REQUIRE(f, AGZ_E_INVALID, "agz_trainer_save: cannot open %s", path);
-  bool ok = write_magic(t, f) && fwrite(&t->conf, sizeof(t->conf), 1, f) == 1;
-  uint64_t np = t->prefs.size();
-  ok = ok && fwrite(&np, 8, 1, f) == 1;
-  for (int i = 0; ok && i < (int)t->prefs.size(); i++) {
-    std::vector<float> v(pref_size(t->prefs[i]));
-    if (agz_trainer_get_param(t, i, v.data(), v.size()) != AGZ_OK) { fclose(f); return AGZ_E_HIP; }
-    uint64_t cnt = v.size();
-    ok = fwrite(&cnt, 8, 1, f) == 1 && fwrite(v.data(), 4, cnt, f) == cnt;
-  }
-  if (t->V) {
-    ok = ok && fwrite(&t->solver, sizeof(t->solver), 1, f) == 1;
-    for (int i = 0; ok && i < (int)t->prefs.size(); i++) {
-      std::vector<float> v(pref_size(t->prefs[i]));
-      if (agz_trainer_get_velocity(t, i, v.data(), v.size()) != AGZ_OK) { fclose(f); return AGZ_E_HIP; }
-      uint64_t cnt = v.size();
-      ok = fwrite(&cnt, 8, 1, f) == 1 && fwrite(v.data(), 4, cnt, f) == cnt;
-    }
-  }
-  if (t->M1) {   // (04) the options, Adam's settings and counter, every tensor's first moment, then every tensor's second moment
-    ok = ok && fwrite(&t->solver, sizeof(t->solver), 1, f) == 1 && fwrite(&t->adam, sizeof(t->adam), 1, f) == 1 && fwrite(&t->adam_t, 8, 1, f) == 1;
-    for (int k = 0; ok && k < 2 * (int)t->prefs.size(); k++) {
-      const int i = k % (int)t->prefs.size();
-      std::vector<float> v(pref_size(t->prefs[i]));
-      if (xfer_param(t, group_buf(t, 1 + k / (int)t->prefs.size()), i, v.data(), 1) != AGZ_OK) { fclose(f); return AGZ_E_HIP; }
-      uint64_t cnt = v.size();
-      ok = fwrite(&cnt, 8, 1, f) == 1 && fwrite(v.data(), 4, cnt, f) == cnt;
-    }
-  }
-  if (ok && t->bn_all()) ok = bn_block_write(t, f);
-  ok = (fclose(f) == 0) && ok;
-  AGZ_REQUIRE(ok, AGZ_E_INVALID, "agz_trainer_save: write to %s failed", path);
-  return AGZ_OK;
-}
-
+// Local also on a sharded trainer: a checkpoint of the GLOBAL configuration, of which this rank reads its rows of every batch-shaped tensor.
+// Nothing is changed unless ckpt::scan accepts the whole file; after a failure further down (a device error) the state is undefined.
 int agz_trainer_load(agz_trainer* t, const char* path) {
   AGZ_REQUIRE(t && path, AGZ_E_INVALID, "agz_trainer_load: NULL argument");
-  if (t->sharded) return load_sharded(t, path);
   FILE* f = fopen(path, "rb");
   AGZ_REQUIRE(f, AGZ_E_INVALID, "agz_trainer_load: cannot open %s", path);
-  agz_net_conf c;
-  uint64_t np = 0;
-  int form = 0; bool v2 = false, ad = false, tied5 = false;
-  bool ok = read_magic(f, &form, &v2, &ad, &tied5) && fread(&c, sizeof(c), 1, f) == 1 && fread(&np, 8, 1, f) == 1;
-  if (ok && tied5 != t->tied) {
+  const ckpt::Layout lay = ckpt_layout(t);
+  ckpt::Scan sc;
+  const ckpt::Status st = ckpt::scan(f, lay, &sc);
+  if (st != ckpt::OK) {
     fclose(f);
-    agz::set_error("agz_trainer_load: %s is the checkpoint of a %s trainer, this trainer is %s", path, tied5 ? "tied (agz_trainer_create_tied)" : "plain",
-                   t->tied ? "tied" : "plain");
+    if (st == ckpt::KIND)   // (also a tied file offered to a sharded trainer: there is no tied sharded trainer)
+      agz::set_error("agz_trainer_load: %s is the checkpoint of a %s trainer, this trainer is %s", path, sc.form.tied ? "tied (agz_trainer_create_tied)" : "plain",
+                     t->tied ? "tied" : "plain");
+    else if (st == ckpt::NOT_THIS) agz::set_error("agz_trainer_load: %s is not a checkpoint of this trainer configuration (batch size %d)", path, lay.conf.BatchSize);
+    else agz::set_error("agz_trainer_load: %s is truncated or mismatched", path);
     return AGZ_E_INVALID;
   }
-  if (ok) ok = memcmp(&c, &t->conf, sizeof(c)) == 0 && np == t->prefs.size();
-  if (!ok) { fclose(f); agz::set_error("agz_trainer_load: %s is not a checkpoint of this trainer configuration", path); return AGZ_E_INVALID; }
-  BnBlock bnb;
-  AdamHead ah;
-  // (an AGZTRN05 file is checked for its full length in every inner form)
-  if ((v2 || ad || form == 3 || tied5) && !checkpoint_complete(f, t, 1, v2, form == 3 ? &bnb : nullptr, ad ? &ah : nullptr)) { fclose(f); agz::set_error("agz_trainer_load: %s is truncated or mismatched", path); return AGZ_E_INVALID; }
-  for (int i = 0; ok && i < (int)t->prefs.size(); i++) {
-    uint64_t cnt = 0;
-    std::vector<float> v(pref_size(t->prefs[i]));
-    ok = fread(&cnt, 8, 1, f) == 1 && cnt == v.size() && fread(v.data(), 4, cnt, f) == cnt;
-    if (ok && agz_trainer_set_param(t, i, v.data(), v.size()) != AGZ_OK) { fclose(f); return AGZ_E_HIP; }
-  }
-  if (ok && v2) {
-    agz_solver_conf sc;
-    ok = fread(&sc, sizeof(sc), 1, f) == 1 && solver_conf_valid(&sc) && sc.momentum != 0.f;
-    if (ok && (adam_off(t) != AGZ_OK || agz_trainer_set_solver(t, &sc) != AGZ_OK)) { fclose(f); return AGZ_E_HIP; }
-    for (int i = 0; ok && i < (int)t->prefs.size(); i++) {
-      uint64_t cnt = 0;
-      std::vector<float> v(pref_size(t->prefs[i]));
-      ok = fread(&cnt, 8, 1, f) == 1 && cnt == v.size() && fread(v.data(), 4, cnt, f) == cnt;
-      if (ok && agz_trainer_set_velocity(t, i, v.data(), v.size()) != AGZ_OK) { fclose(f); return AGZ_E_HIP; }
+  auto apply_group = [&](int g) -> int {   // every tensor of the group (of a batch-shaped one: this rank's rows) into the group's buffer
+    std::vector<float> v;
+    for (size_t i = 0; i < t->prefs.size(); i++) {
+      const std::pair<long, uint64_t> rows = ckpt::rows(lay.tensors[i], sc.off[g][i], t->rank, t->n_ranks);
+      v.resize(rows.second);
+      if (fseek(f, rows.first, SEEK_SET) != 0 || fread(v.data(), 4, v.size(), f) != v.size()) { agz::set_error("agz_trainer_load: reading %s failed", path); return AGZ_E_INVALID; }
+      if (xfer_param(t, group_buf(t, g), (int)i, v.data(), 0) != AGZ_OK) return AGZ_E_HIP;
     }
-  }
-  if (ok && ad) {   // (the options, Adam's settings and counter were read and checked by checkpoint_complete)
-    ok = fseek(f, (long)(sizeof(ah.sc) + sizeof(ah.ac) + 8), SEEK_CUR) == 0;
-    if (ok) { const int r = adam_head_apply(t, ah); if (r != AGZ_OK) { fclose(f); return r; } }
-    for (int k = 0; ok && k < 2 * (int)t->prefs.size(); k++) {
-      const int i = k % (int)t->prefs.size();
-      uint64_t cnt = 0;
-      std::vector<float> v(pref_size(t->prefs[i]));
-      ok = fread(&cnt, 8, 1, f) == 1 && cnt == v.size() && fread(v.data(), 4, cnt, f) == cnt;
-      if (ok && xfer_param(t, group_buf(t, 1 + k / (int)t->prefs.size()), i, v.data(), 0) != AGZ_OK) { fclose(f); return AGZ_E_HIP; }
-    }
-  }
+    return AGZ_OK;
+  };
+  const ckpt::State state = sc.form.state;
+  int r = hipSetDevice(t->ctx->device) == hipSuccess && hipStreamSynchronize(t->ctx->stream) == hipSuccess ? AGZ_OK : AGZ_E_HIP;
+  if (r == AGZ_OK) r = apply_group(0);
+  if (r == AGZ_OK && state == ckpt::ADAM) r = adam_head_apply(t, sc.opt);
+  if (r == AGZ_OK && state == ckpt::VELOCITY && (r = adam_off(t)) == AGZ_OK) r = agz_trainer_set_solver(t, &sc.opt.solver);
+  for (int g = 1; r == AGZ_OK && g < ckpt::groups(state); g++) r = apply_group(g);
   fclose(f);
-  AGZ_REQUIRE(ok, AGZ_E_INVALID, "agz_trainer_load: %s is truncated or mismatched", path);
-  // 03: the tracking setting and state the file carries; 01 / 02: no statistics (N = 0), the setting stays
-  { int r = form == 3 ? bn_block_apply(t, bnb) : agz_trainer_reset_bn_stats(t); if (r != AGZ_OK) return r; }
-  if (!v2 && !ad) return agz_trainer_reset_solver(t);   // a file without solver state: v := 0 (Adam: the moments and t := 0), the options stay
-  return AGZ_OK;
+  if (r == AGZ_OK) r = sc.form.bn ? bn_block_apply(t, sc.bn) : agz_trainer_reset_bn_stats(t);
+  if (r == AGZ_OK && state == ckpt::NONE) r = agz_trainer_reset_solver(t);   // v := 0 (Adam: the moments and t := 0), the options stay
+  return r;
 }
 
 // the running statistics, if the trainer holds any (N > 0), as the net's AGZ_BN_RUNNING statistics; nothing otherwise

@@ -307,26 +307,26 @@ int agz_train(agz_trainer* t, float* Xs, float* policies, float* values, int bat
 int agz_train_dev(agz_trainer* t, const float* Xs_dev, const float* policies_dev, const float* values_dev, int batches,
                   int iterations, uint64_t seed, float* last_cost);
 /* Checkpoint of the trainable network in its full batch-shaped form (AZ.Save/AZ.Load agogo.go:175-209 for the side that
- * keeps learning; gob is Go-only, the format is documented in train.hip). load: the file must match the configuration.
- * A trainer with a velocity (momentum != 0) writes the "AGZTRN02" form — the AGZTRN01 payload, agz_solver_conf, every tensor's
- * velocity — and any other trainer the AGZTRN01 file it always wrote.  load reads both: 02 sets the options and velocity it carries,
- * 01 zeroes the velocity and keeps the options; a truncated 02 file is rejected (AGZ_E_INVALID) before anything is changed.
- * A trainer with Adam on (agz_trainer_set_adam) writes "AGZTRN04": the AGZTRN01 payload, agz_solver_conf, agz_adam_conf, uint64 t, then
- * per tensor {uint64 n, float m[n]} and per tensor {uint64 n, float v[n]} in the payload's order (with running BatchNorm statistics:
- * AGZTRN03 with inner form 3).  load: the Adam forms set the options, t and the moments, turning Adam on; 01 / 02 (and 03 with inner form
- * 1 / 2) loaded into a trainer with Adam on zero the moments and t, and keep the Adam setting only if the file's momentum is 0 — otherwise
- * they take the file's solver and turn Adam off; a truncated or inconsistent Adam file is rejected (AGZ_E_INVALID) before anything is
- * changed.  Sharded: rank 0 writes the global file, every rank loads its own rows.  Test: tests/test_adam_gpu.py (checkpoint).
- * A trainer with running BatchNorm statistics (N > 0) writes "AGZTRN03": the magic, a uint32 naming the inner form (1 or 2), the body of
- * that 01 / 02 file after its magic, then float momentum, uint32 on, uint32 n_ops and per op {uint64 C, double N, double S_mean[C],
- * double S_var[C]}.  load: 03 sets the tracking setting and state it carries; 01 / 02 reset the state to N = 0 and keep the setting; a
- * truncated or inconsistent 03 file is rejected (AGZ_E_INVALID) before anything is changed.  Sharded: rank 0 writes, every rank loads
- * the same block.  Test: tests/test_bn_tracking_gpu.py (checkpoint).
- * A tied trainer (agz_trainer_create_tied) writes "AGZTRN05": the magic, a uint32 inner form (1 .. 4: the form a plain trainer in the same
- * state would write), a uint32 flags word (bit 0 = tied, always set; the other bits 0), then the body of that 01 - 04 file after its magic,
- * with the tied tensor sizes.  load: an 05 file into a plain trainer, and an 01 - 04 file into a tied trainer, are AGZ_E_INVALID before
- * anything is changed — also at BatchSize 1, where the tensor sizes of the two kinds coincide (which is what the flag is for); an 05 file is
- * checked for its full length in every inner form.  Plain trainers write byte for byte what they wrote before.  Test: tests/test_tied_gpu.py. */
+ * keeps learning; gob is Go-only, the format is specified in agogo_amd/csrc/ckpt.hpp, the one place that reads and writes it).
+ * save: the file's form follows the trainer's state.  Without solver state "AGZTRN01" (l2reg / clip alone are the caller's
+ * configuration, like lr, and are not stored); with a velocity (momentum != 0) "AGZTRN02": the 01 payload, agz_solver_conf, every tensor's
+ * velocity; with Adam on "AGZTRN04": the 01 payload, agz_solver_conf, agz_adam_conf, uint64 t, every tensor's first and then second moment;
+ * with running BatchNorm statistics (N > 0) "AGZTRN03": a uint32 inner form 1 / 2 / 3 (none / velocity / Adam), that body, then float
+ * momentum, uint32 on, uint32 n_ops and per op {uint64 C, double N, double S_mean[C], double S_var[C]}.  A tied trainer
+ * (agz_trainer_create_tied) writes "AGZTRN05": a uint32 inner form 1 .. 4 (the form a plain trainer in the same state would write), a
+ * uint32 flags word (bit 0 = tied, always set; the other bits 0), then the body of that file after its magic, with the tied tensor sizes.
+ * load: the file must match the configuration and the kind of the trainer (a tied file into a plain trainer and the reverse are refused,
+ * also at BatchSize 1 where the tensor sizes coincide: that is what the flag is for).  A file without solver state zeroes the velocity (or the
+ * moments and t) and keeps the options; one with a velocity sets the solver options and the velocity it carries and turns Adam off; an
+ * Adam file sets the solver options, the Adam settings, t and the moments and turns Adam on.  A file with a BatchNorm block sets the tracking
+ * setting and state it carries; any other resets the state to N = 0 and keeps the setting.
+ * A bad file changes nothing, whatever its form: the WHOLE file — magic and form words, configuration, every count word, the options, the
+ * BatchNorm block, and that it ends exactly where it should — is checked before the first value is applied; a truncated, overlong or
+ * inconsistent file is AGZ_E_INVALID with the trainer untouched.  After a device error while the tensors are applied (AGZ_E_HIP) the
+ * state is undefined.
+ * Sharded: save is collective, rank 0 writes the plain trainer's file at the global batch; load is local, every rank reads its own rows.
+ * Tests: tests/test_ckpt_cpu.py (the format and every refusal, without a GPU), tests/test_ckpt_golden_gpu.py (files written before the
+ * codec existed), and the checkpoint tests of test_solver_gpu.py, test_adam_gpu.py, test_bn_tracking_gpu.py, test_tied_gpu.py. */
 int agz_trainer_save(const agz_trainer* t, const char* path);
 int agz_trainer_load(agz_trainer* t, const char* path);
 /* dual.Infer's copy loop (dualnet/meta.go:141-146): row 0 of every learnable -> the inference net; commits it.  A trainer that holds

@@ -323,6 +323,8 @@ def test_initialisation_checkpoints_and_refusals(ctx, n, tmp_path):
     plain = A.Trainer(ctx, K, L, FC, W, H, F, Aspace, Bg)
     plain.init_random(77)
     init = [plain.get_param(i) for i in range(plain.num_params())]
+    init_file = tmp_path / "init.agz"
+    plain.save(init_file)
     plain.init_random(78)
     global_file = tmp_path / "global.agz"
     plain.save(global_file)
@@ -340,7 +342,9 @@ def test_initialisation_checkpoints_and_refusals(ctx, n, tmp_path):
         assert "(-1)" in str(R[r]["e_div"]) and "not a multiple" in str(R[r]["e_div"]), str(R[r]["e_div"])
         for k in ("e_ar", "e_fba", "e_fbad"):
             assert "(-4)" in str(R[r][k]), (k, str(R[r][k]))
-    # the sharded save is a plain checkpoint at the global batch: it loads into a plain trainer and holds the ranks' slices
+    # the sharded save is a plain checkpoint at the global batch: the plain trainer's file byte for byte; it loads into a plain trainer
+    # and holds the ranks' slices
+    assert open(sharded_file, "rb").read() == open(init_file, "rb").read()
     plain.load(sharded_file)
     for i, nm in enumerate(names):
         np.testing.assert_array_equal(plain.get_param(i).view(np.uint32), init[i].view(np.uint32), err_msg=nm)
