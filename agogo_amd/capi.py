@@ -288,6 +288,7 @@ def lib():
     sig("agz_trainer_forward_backward_allreduce_dev", i32, vp, vp, vp, vp, vp, pf)
     sig("agz_comm_debug_fail_slice", i32, vp, i32)
     sig("agz_trainer_create_sharded", i32, vp, C.POINTER(NetConf), pvp)
+    sig("agz_trainer_create_sharded_tied", i32, vp, C.POINTER(NetConf), pvp)
     sig("agz_trainer_shard", i32, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32))
     sig("agz_comm_debug_fail_layer", i32, vp, i32)
     _LIB = L
@@ -501,15 +502,20 @@ class Trainer:
         return bool(v.value)
 
     @classmethod
-    def sharded(cls, ctx, comm, K, SharedLayers, FC, Width, Height, Features, ActionSpace, BatchSize, bn_eps=1e-5):
+    def sharded(cls, ctx, comm, K, SharedLayers, FC, Width, Height, Features, ActionSpace, BatchSize, bn_eps=1e-5, tied=False):
         """dual.Train at the GLOBAL batch BatchSize split over the ranks of `comm` (agz_trainer_create_sharded): this rank holds rows
-        shard() of every batch-shaped learnable; forward_backward / batch / train / train_dev / export / save are collective"""
+        shard() of every batch-shaped learnable; forward_backward / batch / train / train_dev / export / save are collective.
+        tied=True (agz_trainer_create_sharded_tied): the tied trainer at the global batch — every rank holds every tied tensor whole, their
+        gradients are the ranks' double partials added in rank order, and the replicas step alike"""
         assert comm.ctx is ctx, "the communicator belongs to another context"
         self = cls.__new__(cls)
         self.ctx, self.comm = ctx, comm
         self.conf = NetConf(K, SharedLayers, FC, BatchSize, Width, Height, Features, ActionSpace, 0, bn_eps)
         self.h = C.c_void_p()
-        _check(lib().agz_trainer_create_sharded(comm.h, C.byref(self.conf), C.byref(self.h)), "agz_trainer_create_sharded")
+        if tied:
+            _check(lib().agz_trainer_create_sharded_tied(comm.h, C.byref(self.conf), C.byref(self.h)), "agz_trainer_create_sharded_tied")
+        else:
+            _check(lib().agz_trainer_create_sharded(comm.h, C.byref(self.conf), C.byref(self.h)), "agz_trainer_create_sharded")
         ctx._adopt(self)
         return self
 

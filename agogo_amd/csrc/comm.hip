@@ -300,10 +300,12 @@ static int sh_step(agz_comm* c, agz_trainer* t, const Rccl* R, const std::functi
   return sh_agree(c, R, r, "sharded training step");
 }
 
-int agz_trainer_create_sharded(agz_comm* c, const agz_net_conf* conf, agz_trainer** out) {
-  AGZ_REQUIRE(c && conf && out, AGZ_E_INVALID, "agz_trainer_create_sharded: NULL argument");
+// tied: the local trainer is a tied one (agz_trainer_create_tied) of B = BatchSize / n rows; the hooks are the same — its backward gathers
+// are longer (agz_trainer_exchange_plan) and carry the tied tensors' partials, nothing else is exchanged
+static int create_sharded(agz_comm* c, const agz_net_conf* conf, agz_trainer** out, bool tied, const char* who) {
+  AGZ_REQUIRE(c && conf && out, AGZ_E_INVALID, "%s: NULL argument", who);
   AGZ_REQUIRE(conf->BatchSize >= 1 && conf->BatchSize % c->size == 0, AGZ_E_INVALID,
-              "agz_trainer_create_sharded: the global BatchSize %d is not a multiple of the %d ranks", conf->BatchSize, c->size);
+              "%s: the global BatchSize %d is not a multiple of the %d ranks", who, conf->BatchSize, c->size);
   const Rccl* R = rccl();
   if (!R) return AGZ_E_UNSUPPORTED;
   AGZ_HIP_TRY(hipSetDevice(c->ctx->device));
@@ -311,7 +313,7 @@ int agz_trainer_create_sharded(agz_comm* c, const agz_net_conf* conf, agz_traine
   agz_net_conf local = *conf;
   local.BatchSize = conf->BatchSize / c->size;
   agz_trainer* t = nullptr;
-  int r = agz_trainer_create(c->ctx, &local, &t);
+  int r = tied ? agz_trainer_create_tied(c->ctx, &local, &t) : agz_trainer_create(c->ctx, &local, &t);
   if (r != AGZ_OK) return r;
   agz_shard_hooks h;
   h.gather = [c, R](int site, const double* send, double* recv, size_t count) -> int {
@@ -342,6 +344,13 @@ int agz_trainer_create_sharded(agz_comm* c, const agz_net_conf* conf, agz_traine
   if ((r = agz_trainer_bind_shard(t, c->rank, c->size, std::move(h))) != AGZ_OK) { agz_trainer_destroy(t); return r; }
   *out = t;
   return AGZ_OK;
+}
+int agz_trainer_create_sharded(agz_comm* c, const agz_net_conf* conf, agz_trainer** out) {
+  return create_sharded(c, conf, out, false, "agz_trainer_create_sharded");
+}
+// dual.Train at the global batch with gamma / beta and the FC biases stored once (include/agz.h; DESIGN §2 `tied-affine`, §7)
+int agz_trainer_create_sharded_tied(agz_comm* c, const agz_net_conf* conf, agz_trainer** out) {
+  return create_sharded(c, conf, out, true, "agz_trainer_create_sharded_tied");
 }
 
 int agz_comm_debug_fail_layer(agz_comm* c, int layer) {

@@ -416,6 +416,11 @@ __global__ void k_bn_bwd1(TGeo g, const float* __restrict__ z, float* gamma, flo
 // both moments at the same index) through tied_step (= solver_step / adam_step, out of line); no tied gradient is materialised.  Otherwise it stores dgamma, dbeta.
 // The channel sums leave as per-pixel partial sums part[which][p][cc] (double) and k_bn_tied_sums adds them in a fixed order: s1 / s2 do not
 // depend on the order workgroups finish in either (k_bn_bwd1 adds its blocks' sums with double atomics).
+// SHARDED (agz_trainer_create_sharded_tied; a template parameter: the <KIND, false> instantiations are the kernels that ran before the form
+// existed): the rank's rows are B of the n * B the gradient runs over, so nothing is rounded or stepped here.  dgamma / dbeta leave as this
+// rank's DOUBLE partials — the very sum the plain form rounds — in the send buffer that follows the a1 / a2 partials in `part`:
+// part = [a1 | a2] ([2][HW][2 Kp]) | s1 | s2 (2 x 1024, k_bn_tied_sums) | dgamma [HW][C] | dbeta [HW][C]; k_tied_ranks finishes them
+// after the gather.  dz is computed from the gamma of before the step as in the plain form (k_tied_ranks steps later on the same stream).
 constexpr int TB_RS = 4;
 // The solver step of ONE tied gamma / beta element, compiled ONCE and out of line: solver_step's `mu * v + (-lr) * g` and adam_step's
 // `b1 * m + (1 - b1) * g` each have two multiply-adds the compiler may contract them into, and it chooses per call site (inlined into
@@ -445,7 +450,7 @@ __global__ __launch_bounds__(256) void k_tied_sweep(float* __restrict__ p, const
     if (KIND == SK_ADAM) m2[i] = r.b;
   }
 }
-template <int KIND>
+template <int KIND, bool SHARDED = false>
 __global__ __launch_bounds__(256) void k_bn_bwd1_tied(TGeo g, const float* __restrict__ z, float* gamma, float* beta,
                                                       const float* __restrict__ mean, const float* __restrict__ inv, const float* __restrict__ out,
                                                       const float* __restrict__ dout, float* __restrict__ dgamma, float* __restrict__ dbeta,
@@ -490,6 +495,12 @@ __global__ __launch_bounds__(256) void k_bn_bwd1_tied(TGeo g, const float* __res
   for (int k = 0; k < TB_RS - 1; k++) { dg += red[0][k][lane]; db += red[1][k][lane]; a1 += red[2][k][lane]; a2 += red[3][k][lane]; }
   part[e] = a1;
   part[(size_t)g.HW * C + e] = a2;
+  if (SHARDED) {   // (not rounded: the ranks' partials are added first)
+    double* send = part + (size_t)4 * g.HW * Kp + 2048;
+    send[e] = dg;
+    send[(size_t)g.HW * C + e] = db;
+    return;
+  }
   const float fg = (float)dg, fb = (float)db;   // (rounded once)
   if (KIND == SK_ADAM) {  // (fused steps only: fuse_lr != 0)
     const TiedSt rg = tied_step<SK_ADAM>(gm, sv.m1gamma[e], sv.m2gamma[e], fg, fuse_lr, 0.f, sv.l2, sv.clip, sv.ak);
@@ -544,14 +555,62 @@ __global__ __launch_bounds__(256) void k_bn_tied_sums(const double* __restrict__
 }
 // Tied head gamma / beta and FC biases: the head kernels write the untied trainer's per-row gradients into a scratch of the untied shapes;
 // dst[i] = sum over the B rows, in row order, in double, rounded once, for up to five tensors in one launch (n[k] elements per row each)
+// PART (tied sharded trainer): the sums leave unrounded, as doubles, one after the other in `part` (the tail of the heads' send buffer);
+// k_rows_ranks adds the ranks' partials and rounds.  The <false> instantiation is the kernel that ran before the form existed.
 struct RowSum { const float* src[5]; float* dst[5]; int n[5]; };
-__global__ __launch_bounds__(256) void k_rows_sum(RowSum a, int B) {
+template <bool PART>
+__global__ __launch_bounds__(256) void k_rows_sum(RowSum a, int B, double* __restrict__ part) {
   int i = blockIdx.x * 256 + threadIdx.x;
+  const int i0 = i;
 #pragma unroll
   for (int k = 0; k < 5; k++) {
     if (i < a.n[k]) {
       double s = -0.0;   // (the identity of IEEE addition: one row is copied with its sign of zero)
       for (int b = 0; b < B; b++) s += (double)a.src[k][(size_t)b * a.n[k] + i];
+      if (PART) part[i0] = s; else a.dst[k][i] = (float)s;
+      return;
+    }
+    i -= a.n[k];
+  }
+}
+// ---- tied sharded trainer (agz_trainer_create_sharded_tied; DESIGN §2 `tied-affine`): the gradient of a tied tensor from the n ranks' partials
+// xg [n][stride] holds every rank's send buffer after the gather; `xg` points at the first partial of rank 0.  Per element the n double
+// partials are added in RANK order, starting from rank 0's, and rounded once: no atomics, the same bits on every rank, and with n = 1 the
+// tied trainer's bits.  k_tied_ranks: cnt elements of a tower layer's [gamma | beta] (contiguous in P / G / V / M1 / M2).  fuse_lr == 0
+// (KIND = SK_VANILLA): the gradient is stored; a fused step takes the solver step of its KIND in place — the vanilla step with k_axpy's
+// expression, the others through tied_step, the body k_bn_bwd1_tied and k_tied_sweep call — identically on every rank: the replicas of
+// the parameters, the velocity and the moments stay equal without a broadcast.
+template <int KIND>
+__global__ __launch_bounds__(256) void k_tied_ranks(const double* __restrict__ xg, int n, size_t stride, size_t cnt, float* __restrict__ p,
+                                                    float* __restrict__ gout, float* __restrict__ v, float* __restrict__ m2, float fuse_lr,
+                                                    float mu, float l2, float clip, AdamK ak) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < cnt; i += (size_t)gridDim.x * 256) {
+    double s = xg[i];
+    for (int r = 1; r < n; r++) s += xg[(size_t)r * stride + i];
+    const float fg = (float)s;   // (rounded once)
+    if (KIND == SK_VANILLA) {
+      if (fuse_lr != 0.f) p[i] = p[i] + (-fuse_lr) * fg;   // (uniform) exactly k_axpy's expression
+      else gout[i] = fg;
+    } else {   // (fused steps only: fuse_lr != 0)
+      const float a = KIND == SK_OPTIONS ? 0.f : v[i], b = KIND == SK_ADAM ? m2[i] : 0.f;
+      const TiedSt r = tied_step<KIND>(p[i], a, b, fg, fuse_lr, mu, l2, clip, ak);
+      p[i] = r.w;
+      if (KIND != SK_OPTIONS) v[i] = r.a;
+      if (KIND == SK_ADAM) m2[i] = r.b;
+    }
+  }
+}
+// the same finish for the five tied head tensors (head gamma / beta [3][HW], bp, b1, b2), whose partials k_rows_sum<true> left one after the
+// other: always stored into G (the head region goes through the solver sweep of agz_trainer_apply on a fused step as well)
+struct RowDst { float* dst[5]; int n[5]; };
+__global__ __launch_bounds__(256) void k_rows_ranks(const double* __restrict__ xg, int n, size_t stride, RowDst a) {
+  int i = blockIdx.x * 256 + threadIdx.x;
+  const int i0 = i;
+#pragma unroll
+  for (int k = 0; k < 5; k++) {
+    if (i < a.n[k]) {
+      double s = xg[i0];
+      for (int r = 1; r < n; r++) s += xg[(size_t)r * stride + i0];
       a.dst[k][i] = (float)s;
       return;
     }
@@ -2216,7 +2275,9 @@ struct agz_trainer {
   // tied affine (agz_trainer_create_tied; DESIGN §2 `tied-affine`): every batch-shaped learnable is stored ONCE, at its row-0 shape (Bp = 1
   // parameter rows instead of B), in the same flat P / G / V / M1 / M2 layout.  tied_rows: the head kernels' per-row gradients of the head
   // gamma / beta and the FC biases (untied shapes: dhg, dhb [B][3][HW], dbp [B][A], db1 [B][FC], db2 [B]), summed into G by k_rows_sum;
-  // tied_part [2][HW][2 Kp]: the per-pixel channel sums of k_bn_bwd1_tied.
+  // tied_part [2][HW][2 Kp]: the per-pixel channel sums of k_bn_bwd1_tied.  On a tied sharded trainer (agz_trainer_bind_shard) it is followed
+  // by the send buffer of a layer (s1 | s2 | dgamma | dbeta partials: tied_send()) and head_acc by the 6 HW + A + FC + 1 partials of the tied
+  // head tensors.
   bool tied = false;
   int Bp = 0;               // parameter rows of a batch-shaped learnable: B, or 1 on a tied trainer
   float* tied_rows = nullptr;
@@ -2229,7 +2290,10 @@ struct agz_trainer {
   bool sharded = false;
   int rank = 0, n_ranks = 1;
   agz_shard_hooks shard;
-  double* xg = nullptr;     // [n_ranks][2048] the partial sums of one exchange, rank-major
+  double* xg = nullptr;     // [n_ranks][largest count of the exchange plan] the partial sums of one exchange, rank-major
+  bool tied_sharded() const { return tied && sharded; }
+  double* tied_send() const { return tied_part + (size_t)4 * g.HW * Kp; }
+  size_t tied_head_n() const { return (size_t)6 * g.HW + A + FC + 1; }
   int m_glob() const { return g.M * n_ranks; }
   int exchange(int site, const double* send, size_t count) { return shard.gather(site, send, xg, count); }
   bool bn_single_pass(int C) const { return C % 4 == 0 && C <= 1024 && g.M >= 4096; }
@@ -2455,7 +2519,17 @@ int agz_trainer::forward_backward_dev(const float* planes, const float* pi, cons
     hipLaunchKernelGGL(k_fc_bwd_small, dim3(nblk((size_t)B * A + (size_t)B * FC + FC + B)), dim3(256), 0, s, h);
     hipLaunchKernelGGL(k_fc_bwd_y, dim3(nblk(2 * g.HW), nblk(B, 8), 2), dim3(256), (size_t)8 * fcJ * sizeof(float), s, h);
     hipLaunchKernelGGL(tied ? k_head_bn_bwd_a<true> : k_head_bn_bwd_a<false>, dim3(std::min(nblk(g.M), ctx->num_cus)), dim3(256), 0, s, g, zh, yh, dyh, P + o_hg, hmean, hinv, dhg, dhb, dzh, head_acc);
-    if (sharded) {
+    if (tied_sharded()) {
+      // the five tied head tensors' partials over this rank's rows ride the same gather, behind the 16 words; summed in rank order into G
+      const size_t nt = tied_head_n(), cnt = 16 + nt;
+      RowSum rs{{dhg, dhb, h.dbp, h.db1, h.db2}, {nullptr, nullptr, nullptr, nullptr, nullptr}, {3 * g.HW, 3 * g.HW, A, FC, 1}};
+      hipLaunchKernelGGL(k_rows_sum<true>, dim3(nblk(nt)), dim3(256), 0, s, rs, B, head_acc + 16);
+      int r = exchange(L + 1, head_acc, cnt);
+      if (r != AGZ_OK) return r;
+      hipLaunchKernelGGL(k_sum_ranks, dim3(1), dim3(64), 0, s, xg, n_ranks, (int)cnt, head_acc, 8, 6);
+      RowDst rd{{G + o_hg, G + o_hb, G + o_bp, G + o_b1, G + o_b2}, {3 * g.HW, 3 * g.HW, A, FC, 1}};
+      hipLaunchKernelGGL(k_rows_ranks, dim3(nblk(nt)), dim3(256), 0, s, xg + 16, n_ranks, cnt, rd);
+    } else if (sharded) {
       int r = exchange(L + 1, head_acc, 16);
       if (r != AGZ_OK) return r;
       hipLaunchKernelGGL(k_sum_ranks, dim3(1), dim3(64), 0, s, xg, n_ranks, 16, head_acc, 8, 6);
@@ -2467,9 +2541,9 @@ int agz_trainer::forward_backward_dev(const float* planes, const float* pi, cons
   hipLaunchKernelGGL(tied ? k_head_bn_bwd<true> : k_head_bn_bwd<false>, dim3(3), dim3(256), 0, s, g, zh, yh, dyh, P + o_hg, hmean, hinv, dhg, dhb, dzh);
   hipLaunchKernelGGL(k_head_conv_bwd_w, dim3(nblk(g.M, RPB)), dim3(256), 0, s, g, cur, dzh, G + o_hc, Kp, RPB);
   }
-  if (tied) {
+  if (tied && !sharded) {
     RowSum rs{{dhg, dhb, h.dbp, h.db1, h.db2}, {G + o_hg, G + o_hb, G + o_bp, G + o_b1, G + o_b2}, {3 * g.HW, 3 * g.HW, A, FC, 1}};
-    hipLaunchKernelGGL(k_rows_sum, dim3(nblk((size_t)6 * g.HW + A + FC + 1)), dim3(256), 0, s, rs, B);
+    hipLaunchKernelGGL(k_rows_sum<false>, dim3(nblk((size_t)6 * g.HW + A + FC + 1)), dim3(256), 0, s, rs, B, (double*)nullptr);
   }
   float* dcur = dA;
   float* dnext = dB;
@@ -2508,7 +2582,11 @@ int agz_trainer::forward_backward_dev(const float* planes, const float* pi, cons
         sd.ak = adam_k(adam_t + 1);
         sd.m1gamma = M1 + ly.o_gamma; sd.m1beta = M1 + ly.o_beta; sd.m2gamma = M2 + ly.o_gamma; sd.m2beta = M2 + ly.o_beta;
       }
-      if (tied) {   // one workgroup per (pixel, 64 channels) owns the element for all B boards; then the channel sums in a fixed pixel order
+      if (tied_sharded()) {   // this rank's double partials and channel sums into the layer's send buffer (nothing rounded, nothing stepped)
+        hipLaunchKernelGGL((k_bn_bwd1_tied<SK_VANILLA, true>), dim3(g.HW * ceil_div(C, 64)), dim3(256), 0, s, g, ly.z, P + ly.o_gamma, P + ly.o_beta, ly.mean,
+                           ly.inv, ly.out, dcur, G + ly.o_gamma, G + ly.o_beta, dz, tied_part, Kp, ly.nbr, 0.f, sd);
+        hipLaunchKernelGGL(k_bn_tied_sums, dim3(nblk((size_t)2 * C, 16)), dim3(256), 0, s, tied_part, g.HW, C, tied_send(), tied_send() + 1024);
+      } else if (tied) {   // one workgroup per (pixel, 64 channels) owns the element for all B boards; then the channel sums in a fixed pixel order
         auto* bwd1t = sv_adam ? k_bn_bwd1_tied<SK_ADAM> : sv_mom ? k_bn_bwd1_tied<SK_MOMENTUM> : sv_on ? k_bn_bwd1_tied<SK_OPTIONS> : k_bn_bwd1_tied<SK_VANILLA>;
         hipLaunchKernelGGL(bwd1t, dim3(g.HW * ceil_div(C, 64)), dim3(256), 0, s, g, ly.z, P + ly.o_gamma, P + ly.o_beta, ly.mean, ly.inv,
                            ly.out, dcur, G + ly.o_gamma, G + ly.o_beta, dz, tied_part, Kp, ly.nbr, fuse_lr, sd);
@@ -2519,7 +2597,23 @@ int agz_trainer::forward_backward_dev(const float* planes, const float* pi, cons
                          ly.out, dcur, G + ly.o_gamma, G + ly.o_beta, dz, s1, s2, Kp, ly.nbr, RPB, fuse_lr, sd);
       }
     }
-    if (sharded) {   // the two channel sums over the global batch (in place: acc_b of this layer holds the ranks' sum afterwards)
+    if (tied_sharded()) {
+      // ONE gather of s1 | s2 | dgamma | dbeta partials; the channel sums into acc_b of this layer, where step 2 reads them, and the tied
+      // gradient in rank order: stored (two-pass) or stepped in place with the solver of the fused step (the constants of adam_t + 1)
+      const size_t nt = (size_t)2 * g.HW * C, cnt = 2048 + nt;
+      int r = exchange(l, tied_send(), cnt);
+      if (r != AGZ_OK) return r;
+      // (k_bn_tied_sums wrote words [0, C) of each half of the send buffer; the rest of the 2 x 1024 is whatever a wider layer left there,
+      // summed into acc_b as well and never read: step 2 reads channels < C, and acc_b is cleared at the start of a step)
+      hipLaunchKernelGGL(k_sum_ranks, dim3(nblk(2048)), dim3(256), 0, s, xg, n_ranks, (int)cnt, s1, 0, 2048);
+      const bool sv_adam = fuse_lr != 0.f && adam.on, sv_on = fuse_lr != 0.f && solver_on(), sv_mom = sv_on && solver.momentum != 0.f;
+      const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>(nblk(nt), (size_t)ctx->num_cus * 8));
+      const size_t og = ly.o_gamma;   // [gamma | beta], contiguous
+      if (sv_adam) hipLaunchKernelGGL(k_tied_ranks<SK_ADAM>, dim3(grid), dim3(256), 0, s, xg + 2048, n_ranks, cnt, nt, P + og, G + og, M1 + og, M2 + og, fuse_lr, 0.f, solver.l2reg, solver.clip, adam_k(adam_t + 1));
+      else if (sv_mom) hipLaunchKernelGGL(k_tied_ranks<SK_MOMENTUM>, dim3(grid), dim3(256), 0, s, xg + 2048, n_ranks, cnt, nt, P + og, G + og, V + og, (float*)nullptr, fuse_lr, solver.momentum, solver.l2reg, solver.clip, AdamK{});
+      else if (sv_on) hipLaunchKernelGGL(k_tied_ranks<SK_OPTIONS>, dim3(grid), dim3(256), 0, s, xg + 2048, n_ranks, cnt, nt, P + og, G + og, (float*)nullptr, (float*)nullptr, fuse_lr, solver.momentum, solver.l2reg, solver.clip, AdamK{});
+      else hipLaunchKernelGGL(k_tied_ranks<SK_VANILLA>, dim3(grid), dim3(256), 0, s, xg + 2048, n_ranks, cnt, nt, P + og, G + og, (float*)nullptr, (float*)nullptr, fuse_lr, 0.f, 0.f, 0.f, AdamK{});
+    } else if (sharded) {   // the two channel sums over the global batch (in place: acc_b of this layer holds the ranks' sum afterwards)
       int r = exchange(l, s1, 2048);
       if (r != AGZ_OK) return r;
       hipLaunchKernelGGL(k_sum_ranks, dim3(nblk(2048)), dim3(256), 0, s, xg, n_ranks, 2048, s1, 0, 2048);
@@ -2646,9 +2740,29 @@ int agz_trainer_bind_shard(agz_trainer* t, int rank, int n, agz_shard_hooks hook
   AGZ_REQUIRE((size_t)8 * (2 * t->g.HW) * 4 <= 60000 && (size_t)t->B * 8 * 4 <= 60000 && (size_t)8 * fcJ * 4 <= 60000, AGZ_E_UNSUPPORTED,
               "sharded trainer: board, batch or action space too large for the head kernels it runs");
   AGZ_HIP_TRY(hipSetDevice(t->ctx->device));
-  int r = t->alloc(&t->xg, (size_t)n * 2048);
-  if (r != AGZ_OK) return r;
+  // Everything is allocated first and the handle changed last: a failure leaves it the unbound trainer it was.
+  // The gather buffer holds n slices of the largest exchange of the plan: 2048 doubles, or on a tied trainer the largest backward gather,
+  // which carries the tied tensors' partials as well (agz_trainer_exchange_plan).  A gather that a failed step never issued is entered
+  // in place from slice `rank` of it (comm.hip).  A tied trainer's tied_part and head_acc are replaced by ones with room for the send
+  // buffers behind them (tied_send(); the head partials): agz_trainer_create_tied itself allocates what it always did.
+  size_t mx = 2048;
+  double *xg = nullptr, *part = nullptr, *hacc = nullptr;
+  int r = AGZ_OK;
+  if (t->tied) {
+    for (const auto& ly : t->layers) mx = std::max(mx, 2048 + (size_t)2 * t->g.HW * ly.Cout_p);
+    mx = std::max(mx, 16 + t->tied_head_n());
+    if ((r = t->alloc(&part, (size_t)4 * t->g.HW * 2 * t->Kp + 2048)) != AGZ_OK || (r = t->alloc(&hacc, 16 + t->tied_head_n())) != AGZ_OK) return r;
+  }
+  if ((r = t->alloc(&xg, (size_t)n * mx)) != AGZ_OK) return r;
   AGZ_HIP_TRY(hipStreamSynchronize(t->ctx->stream));
+  if (t->tied) {
+    for (void* old : {(void*)t->tied_part, (void*)t->head_acc}) {
+      t->allocs.erase(std::find(t->allocs.begin(), t->allocs.end(), old));
+      hipFree(old);
+    }
+    t->tied_part = part; t->head_acc = hacc;
+  }
+  t->xg = xg;
   t->sharded = true; t->rank = rank; t->n_ranks = n; t->shard = std::move(hooks);
   return AGZ_OK;
 }
@@ -2662,8 +2776,10 @@ void agz_trainer_exchange_plan(const agz_trainer* t, std::vector<size_t>& out, b
     if (t->bn_single_pass(ly.Cout_p)) out.push_back(2048);
     else { out.push_back(1024); out.push_back(1024); }
   }
-  for (int k = 0; k < 3; k++) out.push_back(16);
-  for (size_t l = 0; l < t->layers.size(); l++) out.push_back(2048);
+  // (tied: the heads' backward gather and every layer's carry the double partials of the tied tensors' gradients behind the sums)
+  const bool ts = t->tied && t->sharded;
+  for (int k = 0; k < 3; k++) out.push_back(k == 2 && ts ? 16 + t->tied_head_n() : 16);
+  for (int l = t->L; l >= 0; l--) out.push_back(2048 + (ts ? (size_t)2 * t->g.HW * t->layers[l].Cout_p : 0));
 }
 double* agz_trainer_gather_buf(agz_trainer* t) { return t->xg; }
 void agz_trainer_shared_ranges(const agz_trainer* t, std::vector<std::pair<size_t, size_t>>& out) {
@@ -3065,10 +3181,11 @@ int agz_trainer_init_random(agz_trainer* t, uint64_t seed) {  // same recipe as 
     std::vector<float> v(pref_size(p));
     // this rank's slice: elements [g0, g0 + v.size()) of a tensor of n elements.  A tied trainer draws row 0 of the BatchSize rows a plain
     // trainer draws (the same stream positions, the Glorot deviation of the batch-shaped tensor): the slice of "rank 0 of B"
-    const int nr = pref_batch_shaped(p) ? (t->tied ? t->B : t->n_ranks) : 1;
+    // (a tied sharded trainer draws that row at the GLOBAL batch, whole and the same on every rank)
+    const int nr = pref_batch_shaped(p) ? (t->tied ? t->B * t->n_ranks : t->n_ranks) : 1;
     double field = 1; for (size_t k = 2; k < p.shape.size(); k++) field *= p.shape[k];
     const double stdev = std::sqrt(2.0 / ((double)(p.shape[0] * nr + p.shape[1]) * field));
-    const size_t n = v.size() * nr, g0 = v.size() * (nr > 1 ? t->rank : 0);
+    const size_t n = v.size() * nr, g0 = v.size() * (nr > 1 && !t->tied ? t->rank : 0);
     const uint64_t d0 = draws;
     if (p.kind == 0) {           // GlorotU: one draw per element
       const double lim = stdev * std::sqrt(3.0);
@@ -3467,11 +3584,15 @@ int agz_trainer_eval(agz_trainer* t, const float* planes, const float* pi, const
 // carries.
 namespace ckpt = agz::ckpt;
 
-// BatchSize and the batch-shaped tensors are the GLOBAL batch's on a sharded trainer: its file is the plain trainer's at that batch size
+// BatchSize and the batch-shaped tensors are the GLOBAL batch's on a sharded trainer: its file is the plain trainer's at that batch size.
+// A tied sharded trainer holds every tied tensor whole on every rank: its file is the tied trainer's at the global batch size
 static ckpt::Layout ckpt_layout(const agz_trainer* t) {
   ckpt::Layout lay{t->conf, t->tied, {}, {}};
   lay.conf.BatchSize = t->B * t->n_ranks;
-  for (const auto& p : t->prefs) lay.tensors.push_back({(uint64_t)pref_size(p) * (pref_batch_shaped(p) ? t->n_ranks : 1), pref_batch_shaped(p)});
+  for (const auto& p : t->prefs) {
+    const bool split = pref_batch_shaped(p) && !t->tied;   // its rows are spread over the ranks
+    lay.tensors.push_back({(uint64_t)pref_size(p) * (split ? t->n_ranks : 1), split});
+  }
   for (int i = 0; i < t->bn_num(); i++) lay.bn_C.push_back((uint64_t)(i >= 2 * t->L + 1 ? (i == 2 * t->L + 1 ? 2 : 1) : t->K));
   return lay;
 }
@@ -3533,7 +3654,8 @@ int agz_trainer_save(const agz_trainer* t, const char* path) {
   FILE* f = nullptr;
   if (t->rank == 0 && !(f = fopen(path, "wb"))) { agz::set_error("agz_trainer_save: cannot open %s", path); rc = AGZ_E_INVALID; }
   size_t mx = 0;
-  for (const auto& p : t->prefs) if (t->sharded && pref_batch_shaped(p)) mx = std::max(mx, pref_size(p));
+  const bool split = t->sharded && !t->tied;   // (tied sharded: rank 0 holds every tensor whole and writes the tied trainer's file; the call stays collective)
+  for (const auto& p : t->prefs) if (split && pref_batch_shaped(p)) mx = std::max(mx, pref_size(p));
   float* d = nullptr;   // (sharded) [n][mx] gathered slices, then this rank's slice
   if (mx && hipMalloc(&d, (size_t)(n + 1) * mx * 4) != hipSuccess) { d = nullptr; if (rc == AGZ_OK) { agz::set_error("agz_trainer_save: out of device memory for the gather"); rc = AGZ_E_NOMEM; } }
   const int a = agree(rc);
@@ -3546,7 +3668,7 @@ int agz_trainer_save(const agz_trainer* t, const char* path) {
     const TParamRef& p = t->prefs[i];
     v.assign(pref_size(p), 0.f);
     if (xfer_param(t, group_buf(t, g), (int)i, v.data(), 1) != AGZ_OK && rc == AGZ_OK) rc = AGZ_E_HIP;
-    if (!t->sharded || !pref_batch_shaped(p)) return std::make_pair((const float*)v.data(), (uint64_t)v.size());
+    if (!split || !pref_batch_shaped(p)) return std::make_pair((const float*)v.data(), (uint64_t)v.size());
     float* mine = d + (size_t)n * mx;
     if (hipMemcpy(mine, v.data(), v.size() * 4, hipMemcpyHostToDevice) != hipSuccess && rc == AGZ_OK) rc = AGZ_E_HIP;
     const int r = t->shard.allgather_bytes(mine, d, v.size() * 4);
@@ -3572,8 +3694,9 @@ int agz_trainer_load(agz_trainer* t, const char* path) {
   const ckpt::Status st = ckpt::scan(f, lay, &sc);
   if (st != ckpt::OK) {
     fclose(f);
-    if (st == ckpt::KIND)   // (also a tied file offered to a sharded trainer: there is no tied sharded trainer)
-      agz::set_error("agz_trainer_load: %s is the checkpoint of a %s trainer, this trainer is %s", path, sc.form.tied ? "tied (agz_trainer_create_tied)" : "plain",
+    if (st == ckpt::KIND)   // (sharded handles alike: a tied file loads into agz_trainer_create_sharded_tied, a plain one into agz_trainer_create_sharded)
+      agz::set_error("agz_trainer_load: %s is the checkpoint of a %s trainer, this trainer is %s", path,
+                     sc.form.tied ? "tied (agz_trainer_create_tied / agz_trainer_create_sharded_tied)" : "plain (agz_trainer_create / agz_trainer_create_sharded)",
                      t->tied ? "tied" : "plain");
     else if (st == ckpt::NOT_THIS) agz::set_error("agz_trainer_load: %s is not a checkpoint of this trainer configuration (batch size %d)", path, lay.conf.BatchSize);
     else agz::set_error("agz_trainer_load: %s is truncated or mismatched", path);

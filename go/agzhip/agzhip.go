@@ -776,7 +776,7 @@ func NewTrainer(ctx *Ctx, d *dual.Dual) (*Trainer, error) {
 // [rows, ActionSpace], values [rows] as flat float32 slices (tensor.Dense.Data()).
 func (t *Trainer) Train(Xs, policies, values []float32, batches, iterations int, seed uint64) error {
 	if t.d == nil {
-		return fmt.Errorf("agzhip: Train: a sharded or tied trainer (NewShardedTrainer, NewTrainerTied) has no dual.Dual to copy back into: use TrainDev")
+		return fmt.Errorf("agzhip: Train: a sharded or tied trainer (NewShardedTrainer, NewTrainerTied, NewShardedTrainerTied) has no dual.Dual to copy back into: use TrainDev")
 	}
 	rows := batches * t.d.BatchSize
 	if batches < 1 || len(Xs) < rows*t.d.Features*t.d.Height*t.d.Width || len(policies) < rows*t.d.ActionSpace || len(values) < rows {
@@ -1040,6 +1040,16 @@ func (c *Comm) BatchStep(t *Trainer, planes, pi, v []float32, lr float32) (cost 
 
 func (c *Comm) Close() error { defer c.ctx.enter()(); C.agz_comm_destroy(c.h); c.h = nil; return nil }
 
+// trainerConf is the agz_net_conf of a trainer over conf: the one place that sets bn_mode and bn_eps for NewShardedTrainer, NewShardedTrainerTied
+// and NewTrainerTied.
+func trainerConf(conf dual.Config) C.agz_net_conf {
+	return C.agz_net_conf{
+		K: C.int32_t(conf.K), SharedLayers: C.int32_t(conf.SharedLayers), FC: C.int32_t(conf.FC), BatchSize: C.int32_t(conf.BatchSize),
+		Width: C.int32_t(conf.Width), Height: C.int32_t(conf.Height), Features: C.int32_t(conf.Features),
+		ActionSpace: C.int32_t(conf.ActionSpace), bn_mode: C.AGZ_BN_DEGENERATE_EPS, bn_eps: 1e-5,
+	}
+}
+
 // NewShardedTrainer is dual.Train at the GLOBAL batch conf.BatchSize split over the ranks of comm (agz_trainer_create_sharded): this rank
 // holds rows Shard() of the batch-shaped BatchNorm gamma / beta and FC biases (dualnet/dual.go:105-132), the shared tensors whole; the
 // BatchNorm statistics and the loss are the global batch's, so the run IS dual.Train (dualnet/meta.go:16-54) at conf.BatchSize.
@@ -1049,13 +1059,24 @@ func (c *Comm) Close() error { defer c.ctx.enter()(); C.agz_comm_destroy(c.h); c
 // available (there is no dual.Dual to copy back into).
 func NewShardedTrainer(comm *Comm, conf dual.Config) (*Trainer, error) {
 	defer comm.ctx.enter()()
-	cc := C.agz_net_conf{
-		K: C.int32_t(conf.K), SharedLayers: C.int32_t(conf.SharedLayers), FC: C.int32_t(conf.FC), BatchSize: C.int32_t(conf.BatchSize),
-		Width: C.int32_t(conf.Width), Height: C.int32_t(conf.Height), Features: C.int32_t(conf.Features),
-		ActionSpace: C.int32_t(conf.ActionSpace), bn_mode: C.AGZ_BN_DEGENERATE_EPS, bn_eps: 1e-5,
-	}
+	cc := trainerConf(conf)
 	t := &Trainer{ctx: comm.ctx}
 	if err := lastErr(C.agz_trainer_create_sharded(comm.h, &cc, &t.h)); err != nil {
+		return nil, err
+	}
+	return t, nil
+}
+
+// NewShardedTrainerTied is NewTrainerTied at the GLOBAL batch conf.BatchSize split over the ranks of comm (agz_trainer_create_sharded_tied):
+// every rank holds every tied tensor whole and conf.BatchSize / ranks rows of a step; the BatchNorm statistics and the loss are the global
+// batch's, the gradient of a tied tensor is the ranks' partial sums added in rank order, and the replicas take the same solver step.  Start
+// the learnables with InitRandom (the same seed everywhere) or Load (a tied checkpoint of the global conf); TrainDev, Export and Save are
+// collective as on NewShardedTrainer; Train is not available.
+func NewShardedTrainerTied(comm *Comm, conf dual.Config) (*Trainer, error) {
+	defer comm.ctx.enter()()
+	cc := trainerConf(conf)
+	t := &Trainer{ctx: comm.ctx}
+	if err := lastErr(C.agz_trainer_create_sharded_tied(comm.h, &cc, &t.h)); err != nil {
 		return nil, err
 	}
 	return t, nil
@@ -1068,11 +1089,7 @@ func NewShardedTrainer(comm *Comm, conf dual.Config) (*Trainer, error) {
 // holds the batch-shaped tensors: there is nothing of the tied shapes to copy back into).
 func NewTrainerTied(ctx *Ctx, conf dual.Config) (*Trainer, error) {
 	defer ctx.enter()()
-	cc := C.agz_net_conf{
-		K: C.int32_t(conf.K), SharedLayers: C.int32_t(conf.SharedLayers), FC: C.int32_t(conf.FC), BatchSize: C.int32_t(conf.BatchSize),
-		Width: C.int32_t(conf.Width), Height: C.int32_t(conf.Height), Features: C.int32_t(conf.Features),
-		ActionSpace: C.int32_t(conf.ActionSpace), bn_mode: C.AGZ_BN_DEGENERATE_EPS, bn_eps: 1e-5,
-	}
+	cc := trainerConf(conf)
 	t := &Trainer{ctx: ctx}
 	if err := lastErr(C.agz_trainer_create_tied(ctx.h, &cc, &t.h)); err != nil {
 		return nil, err
@@ -1080,7 +1097,7 @@ func NewTrainerTied(ctx *Ctx, conf dual.Config) (*Trainer, error) {
 	return t, nil
 }
 
-// IsTied reports whether the trainer was made by NewTrainerTied (agz_trainer_is_tied).
+// IsTied reports whether the trainer was made by NewTrainerTied or NewShardedTrainerTied (agz_trainer_is_tied).
 func (t *Trainer) IsTied() (bool, error) {
 	defer t.ctx.enter()()
 	var v C.int

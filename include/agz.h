@@ -195,8 +195,8 @@ int agz_trainer_create(agz_ctx* ctx, const agz_net_conf* conf, agz_trainer** out
  * once, with that sum.  conf->BatchSize stays the number of rows of a step; it also still feeds the Glorot fans of
  * agz_trainer_init_random, so that a tied trainer draws row 0 of what a plain trainer of the same conf and seed draws.  Every entry
  * point of a plain trainer works on a tied handle (velocity and moments take the tied shapes; agz_trainer_allreduce reduces the now
- * small flat buffer in one call), except agz_trainer_forward_backward_allreduce(_dev), which return AGZ_E_STATE; there is no tied
- * sharded trainer.  Checkpoints are "AGZTRN05" (agz_trainer_save below) and load only into a tied trainer.  A trainer made by
+ * small flat buffer in one call), except agz_trainer_forward_backward_allreduce(_dev), which return AGZ_E_STATE; the sharded
+ * form is agz_trainer_create_sharded_tied below.  Checkpoints are "AGZTRN05" (agz_trainer_save below) and load only into a tied trainer.  A trainer made by
  * agz_trainer_create / agz_trainer_create_sharded runs exactly the kernels it ran before this option existed. */
 int agz_trainer_create_tied(agz_ctx* ctx, const agz_net_conf* conf, agz_trainer** out);
 int agz_trainer_is_tied(const agz_trainer* t, int* tied);   /* *tied = 1 for a handle of agz_trainer_create_tied, else 0 */
@@ -719,6 +719,31 @@ int agz_trainer_forward_backward_allreduce_dev(agz_comm* comm, agz_trainer* t, c
  * the call fails on EVERY rank (AGZ_E_PEER on the ranks that were fine), nobody hangs, and the next call is an ordinary one.  After a
  * failed step the learnables are undefined (see agz_trainer_batch). */
 int agz_trainer_create_sharded(agz_comm* comm, const agz_net_conf* conf, agz_trainer** out);
+/* Tied sharded training (DESIGN §2 `tied-affine`, §7): the handle computes what agz_trainer_create_tied computes at BatchSize = n * B, over the n
+ * ranks of the communicator, each holding B = BatchSize / n rows of the step and EVERY tied tensor whole.
+ *   Forward, cost and BatchNorm statistics are those of the agz_trainer_create_sharded handle whose batch-shaped tensors hold the tied tensor
+ *     in every row — for the same n bit for bit.
+ *   The gradient of a tied tensor is built from one double partial per rank.  Each rank forms its partial over its own B rows exactly as the
+ *     tied trainer does: fp32 per-row terms accumulated in double, four interleaved row slices added in slice order (the head tensors: the
+ *     rows in row order), NOT rounded.  The n partials are added in rank order in double, starting from rank 0's, and rounded once.  No float
+ *     atomics; every rank gets the same bits; with n = 1 the result is the tied trainer's bits.  The partials ride the backward gathers the
+ *     sharded step already issues (one per tower layer, one for the heads): no collective is added.
+ *   The solver step of the configured kind (vanilla, L2 / clip, momentum, Adam) is taken once per element with that sum, by the same code on
+ *     every rank: parameters, velocity, moments and t stay replicated, nothing is broadcast.
+ * agz_trainer_is_tied reports 1, agz_trainer_shard this rank's rows.  On such a handle:
+ *   forward_backward(_dev), batch, train, train_dev, eval(_dev), export, save are COLLECTIVE as on an agz_trainer_create_sharded handle
+ *     (planes / pi / v: this rank's B rows; train / train_dev: the global tensors).  save: rank 0 writes, byte for byte, the "AGZTRN05" file a
+ *     single-process tied trainer with the global conf writes in the same state.
+ *   init_random, set / get_param, get_grad, set / get_velocity, set / get_moments, apply, set_solver, set_adam, set_bn_tracking, load are
+ *     local and take or give whole tied tensors, identical on every rank (every rank makes the same calls).  init_random(seed) draws what
+ *     agz_trainer_create_tied with the global conf draws (the Glorot fans use the global BatchSize); load reads a tied file whose conf carries
+ *     the global BatchSize (a plain trainer's file is AGZ_E_INVALID and leaves the handle untouched, as a tied file does on a plain sharded
+ *     handle).
+ *   agz_trainer_allreduce and agz_trainer_forward_backward_allreduce(_dev) return AGZ_E_STATE.
+ * Errors of a collective call: as agz_trainer_create_sharded.  After a FUSED step (batch, train, train_dev) that fails part-way the ranks may
+ * have stepped different layers: the replicated state may then differ between the ranks, and EVERY rank must reload a checkpoint before it
+ * trains on.  Tests: tests/test_tied_sharded_cpu.py, tests/test_tied_sharded_gpu.py. */
+int agz_trainer_create_sharded_tied(agz_comm* comm, const agz_net_conf* conf, agz_trainer** out);
 /* this rank's rows of the global batch: [*row0, *row0 + *rows) of *n_ranks * *rows; a plain trainer reports 0, BatchSize, 1 */
 int agz_trainer_shard(const agz_trainer* t, int* row0, int* rows, int* n_ranks);
 
