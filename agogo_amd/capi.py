@@ -248,6 +248,7 @@ def lib():
     sig("agz_wino_h2_tile", i32, i32, i32)
     sig("agz_net_set_wino_h2_form", i32, vp, i32)
     sig("agz_net_set_wino_h2_gemm", i32, vp, i32)
+    sig("agz_net_wino_h2_last_rows", i32, vp, C.POINTER(C.c_int), C.POINTER(C.c_int))
     sig("agz_net_min_same_batch", i32, vp, i32, i32, C.POINTER(C.c_int))
     sig("agz_arena_set_prep_compact", i32, vp, i32)
     sig("agz_arena_set_split", i32, vp, i32)
@@ -456,8 +457,15 @@ class Net:
         _check(lib().agz_net_set_wino_h2_form(self.h, int(form)), "agz_net_set_wino_h2_form")
 
     def set_wino_h2_gemm(self, variant):
-        """agz_debug.h A/B hook: 0 default, 1 wino_gemm_h2g_kernel, 2 wino_gemm_h2p_kernel (persistent; K = 256)"""
+        """agz_debug.h A/B hook: 0 default, 1 wino_gemm_h2g_kernel, 2 wino_gemm_h2p_kernel (persistent; K = 256); + 64: round 4's
+        store policy; + 128: every transform-domain row kept (no short positions)"""
         _check(lib().agz_net_set_wino_h2_gemm(self.h, int(variant)), "agz_net_set_wino_h2_gemm")
+
+    def wino_h2_last_rows(self):
+        """agz_debug.h: (live_r, live_c) of the last chained WINO_H2 block — live rows per 128-row slot at the short positions, 0 = every row kept"""
+        r, c = C.c_int(0), C.c_int(0)
+        _check(lib().agz_net_wino_h2_last_rows(self.h, C.byref(r), C.byref(c)), "agz_net_wino_h2_last_rows")
+        return r.value, c.value
 
     def min_same_batch(self, n, G):
         """agz_debug.h: the smallest batch >= n whose per-board outputs equal those of a G-board batch bit for bit"""

@@ -18,6 +18,9 @@
 //   V2c[T/128][pos][C/32][128 rows][hi 32 fp16 | lo 32 fp16]      a GEMM K step of a 128-row tile = one 16 KB chunk
 //   U2c[pos][C/32][Ntot/256][256 cols][hi | lo]                    a K step of a 256-column tile = one 32 KB chunk
 //   Mc [T/128][pos][C/32 slices][128 rows][64 cols] fp32           column 2j + br of slice s = branch br of channel 32 s + j
+// Short positions (gemm_maps.hpp, rows_*; wino_h2c_rows below): where the tiles hang over the board's edge, the rows of V2c and Mc that
+// only feed off-board outputs — last transform point x last tile row / column — are not stored, multiplied or read: at those positions
+// a 128-row slot holds its live tiles packed into rows 0 .. live - 1 (19x19: 96 of 128 at 13 of the 49 positions, 2.33 GB per block).
 // LDS image of a staged chunk: row r, 16-byte slot q (0..3 hi, 4..7 lo) at r * 128 + ((q ^ ((r >> 1) & 7)) << 4): conflict-free
 // for the 128-byte row writes and for the MFMA fragment reads (ds_read_b128: even and odd rows are the two halves of the
 // 64-bank period, and the 8 even / 8 odd rows of a 16-lane group get 8 distinct slots).
@@ -184,40 +187,60 @@ __global__ __launch_bounds__(256, 3) void wino_gemm_h2g_kernel(WinoH2Args h) {
 #pragma unroll
       for (int r = 0; r < 16; r++) acc[i][j][r] = 0.f;
 
+  // Short positions (gemm_maps.hpp): the slot's live rows are its first `live` = 32, 64 or 96; the 32-row blocks at or past them are
+  // neither fetched (wave w's A part is rows 32 w ..) nor multiplied nor stored.  Everything below is uniform per WAVE: a_on (one
+  // branch around the A-DMA per K step), and ni = how many of this wave's two 32-row MFMA blocks are live, which picks one of three
+  // copies of the K loop per wave, so no branch sits between the MFMAs.  At live = 96 the waves of ONE workgroup run different copies
+  // (wm = 0: NI = 2, wm = 1: NI = 1) and meet at barriers that are different instructions.  That is safe here, and relied on: every
+  // copy executes exactly the same 2 NK barriers in the same order relative to its DMA and its LDS reads, and the hardware barrier
+  // (s_barrier) counts the workgroup's arriving waves, whichever instruction each arrives at.
+  const int live = maps::rows_pos_live(h.live_r, h.live_c, h.tm + 2, pos);
+  const bool a_on = maps::h2c_wave_row0(wid, 128) < live;
+  const int ni = (maps::h2c_mfma_row0(wm, 0) < live ? 1 : 0) + (maps::h2c_mfma_row0(wm, 1) < live ? 1 : 0);
+  auto k_loop = [&](auto ni_c) {
+    constexpr int NI = decltype(ni_c)::value;
 #pragma nounroll
-  for (int it = 0; it < NK; it++) {
+    for (int it = 0; it < NK; it++) {
+      if (a_on) {
 #pragma unroll
-    for (int j = 0; j < maps::h2c_wave_instrs(128); j++)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(ar, (h2c_lds_ptr_t)(la + maps::h2c_dma_dst(0, j)), 16, (j & 1) ? vo_o : vo_e,
-                                               a_so + (maps::h2c_dma_src(0, j) - maps::h2c_dma_src(0, j & 1)), 0, 0);
-#pragma unroll
-    for (int j = 0; j < maps::h2c_wave_instrs(256); j++)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(br, (h2c_lds_ptr_t)(lb + maps::h2c_dma_dst(0, j)), 16, (j & 1) ? vo_o : vo_e,
-                                               b_so + (maps::h2c_dma_src(0, j) - maps::h2c_dma_src(0, j & 1)), 0, 0);
-    a_so += SA; b_so += b_step;
-    __syncthreads();                                  // (its fence waits vmcnt(0): this wave's DMA has landed; then every wave's)
-#pragma unroll
-    for (int ks = 0; ks < 2; ks++) {
-      f16x8_t A_[2][2];
-#pragma unroll
-      for (int i = 0; i < 2; i++) {
-        A_[i][0] = *reinterpret_cast<const f16x8_t*>(lds + maps::h2c_frag(wm * 64 + i * 32, lane, 0, ks));
-        A_[i][1] = *reinterpret_cast<const f16x8_t*>(lds + maps::h2c_frag(wm * 64 + i * 32, lane, 1, ks));
+        for (int j = 0; j < maps::h2c_wave_instrs(128); j++)
+          __builtin_amdgcn_raw_ptr_buffer_load_lds(ar, (h2c_lds_ptr_t)(la + maps::h2c_dma_dst(0, j)), 16, (j & 1) ? vo_o : vo_e,
+                                                   a_so + (maps::h2c_dma_src(0, j) - maps::h2c_dma_src(0, j & 1)), 0, 0);
       }
 #pragma unroll
-      for (int j = 0; j < 4; j++) {                   // B fragments just in time: 8 registers live instead of 32
-        const f16x8_t b0 = *reinterpret_cast<const f16x8_t*>(lds + SA + maps::h2c_frag(wn * 128 + j * 32, lane, 0, ks));
-        const f16x8_t b1 = *reinterpret_cast<const f16x8_t*>(lds + SA + maps::h2c_frag(wn * 128 + j * 32, lane, 1, ks));
+      for (int j = 0; j < maps::h2c_wave_instrs(256); j++)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(br, (h2c_lds_ptr_t)(lb + maps::h2c_dma_dst(0, j)), 16, (j & 1) ? vo_o : vo_e,
+                                                 b_so + (maps::h2c_dma_src(0, j) - maps::h2c_dma_src(0, j & 1)), 0, 0);
+      a_so += SA; b_so += b_step;
+      __syncthreads();                                  // (its fence waits vmcnt(0): this wave's DMA has landed; then every wave's)
+      if (NI > 0) {
 #pragma unroll
-        for (int i = 0; i < 2; i++) {                 // small terms first: lo*hi, hi*lo, hi*hi
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A_[i][1], b0, acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A_[i][0], b1, acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A_[i][0], b0, acc[i][j], 0, 0, 0);
+        for (int ks = 0; ks < 2; ks++) {
+          f16x8_t A_[2][2];
+#pragma unroll
+          for (int i = 0; i < NI; i++) {
+            A_[i][0] = *reinterpret_cast<const f16x8_t*>(lds + maps::h2c_frag(maps::h2c_mfma_row0(wm, i), lane, 0, ks));
+            A_[i][1] = *reinterpret_cast<const f16x8_t*>(lds + maps::h2c_frag(maps::h2c_mfma_row0(wm, i), lane, 1, ks));
+          }
+#pragma unroll
+          for (int j = 0; j < 4; j++) {                   // B fragments just in time: 8 registers live instead of 32
+            const f16x8_t b0 = *reinterpret_cast<const f16x8_t*>(lds + SA + maps::h2c_frag(wn * 128 + j * 32, lane, 0, ks));
+            const f16x8_t b1 = *reinterpret_cast<const f16x8_t*>(lds + SA + maps::h2c_frag(wn * 128 + j * 32, lane, 1, ks));
+#pragma unroll
+            for (int i = 0; i < NI; i++) {                // small terms first: lo*hi, hi*lo, hi*hi
+              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A_[i][1], b0, acc[i][j], 0, 0, 0);
+              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A_[i][0], b1, acc[i][j], 0, 0, 0);
+              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A_[i][0], b0, acc[i][j], 0, 0, 0);
+            }
+          }
         }
       }
+      __syncthreads();                                  // every wave has read the stage before the next DMA overwrites it
     }
-    __syncthreads();                                  // every wave has read the stage before the next DMA overwrites it
-  }
+  };
+  if (ni == 2) k_loop(std::integral_constant<int, 2>{});
+  else if (ni == 1) k_loop(std::integral_constant<int, 1>{});
+  else k_loop(std::integral_constant<int, 0>{});
 
   // M: after v_permlane32_swap of two neighbouring column tiles a register holds all 64 columns of one row (lanes = columns): w0 = row
   // mfma_row(r), w1 = that row + 4; every store instruction writes one 256-byte run of Mc
@@ -225,7 +248,8 @@ __global__ __launch_bounds__(256, 3) void wino_gemm_h2g_kernel(WinoH2Args h) {
 #pragma unroll
   for (int qq = 0; qq < 2; qq++)
 #pragma unroll
-    for (int i = 0; i < 2; i++)
+    for (int i = 0; i < 2; i++) {
+      if (i >= ni) continue;                            // (uniform) a 32-row block past the live rows
 #pragma unroll
       for (int r = 0; r < 16; r++) {
         const unsigned x0 = __float_as_uint(acc[i][2 * qq][r]), x1 = __float_as_uint(acc[i][2 * qq + 1][r]);
@@ -240,6 +264,7 @@ __global__ __launch_bounds__(256, 3) void wino_gemm_h2g_kernel(WinoH2Args h) {
           d[maps::mc_index(0, 0, 0, 0, 0, 4, 0)] = __uint_as_float(w1);
         }
       }
+    }
 }
 
 // (Measured and dropped, profiles/r04/gemm_256x256_pipelined_ab.log: a 256 x 256 tile — 1.6 instead of 2.4 GB of operands from L2 — on 512
@@ -488,6 +513,18 @@ __global__ __launch_bounds__(256, 2) void wino_oi_h2c_kernel(WinoH2Args h) {
   const __amdgpu_buffer_rsrc_t mr = h2_rsrc(a.Mb + ((size_t)(t0 >> 7) * h.npos * NS + s) * 8192);
   const unsigned m_lane = (unsigned)(((tc & 127) * 64 + pr * 4) * 4);
   const unsigned m_pos = (unsigned)NS * 32768u;        // bytes between positions
+  // short positions (gemm_maps.hpp; h.live_r / h.live_c, 0 = off): M is read through the class's row map; a dead (position, tile) reads
+  // zeros from past the descriptor's range, which reach off-board outputs only
+  const int bpt = 128 / a.TPB;
+  auto m_row = [&](int cls) -> unsigned {
+    const int r = maps::rows_row(cls, a.nty, a.ntx, b % bpt, ty, tx);
+    return r < 0 ? 0x80000000u : (unsigned)((r * 64 + pr * 4) * 4);
+  };
+  const unsigned m_lane_r = h.live_r ? m_row(maps::ROWS_R) : m_lane, m_lane_c = h.live_c ? m_row(maps::ROWS_C) : m_lane;
+  auto m_voff = [&](int xi, int nu) -> unsigned {        // (the class is a constant after unrolling)
+    const int cls = maps::rows_class(true, true, AL, xi, nu);
+    return cls == maps::ROWS_R ? m_lane_r : (cls == maps::ROWS_C ? m_lane_c : m_lane);
+  };
   float Y[TM][TM][4];
 #pragma unroll
   for (int k = 0; k < TM; k++)
@@ -497,12 +534,12 @@ __global__ __launch_bounds__(256, 2) void wino_oi_h2c_kernel(WinoH2Args h) {
       for (int e = 0; e < 4; e++) Y[k][l][e] = 0.f;
   float4 m[2][AL];
 #pragma unroll
-  for (int xi = 0; xi < AL; xi++) m[0][xi] = h2_ldf4(mr, m_lane, (unsigned)(xi * AL) * m_pos);
+  for (int xi = 0; xi < AL; xi++) m[0][xi] = h2_ldf4(mr, m_voff(xi, 0), (unsigned)(xi * AL) * m_pos);
 #pragma unroll
   for (int nu = 0; nu < AL; nu++) {
     if (nu + 1 < AL) {
 #pragma unroll
-      for (int xi = 0; xi < AL; xi++) m[(nu + 1) & 1][xi] = h2_ldf4(mr, m_lane, (unsigned)(xi * AL + nu + 1) * m_pos);
+      for (int xi = 0; xi < AL; xi++) m[(nu + 1) & 1][xi] = h2_ldf4(mr, m_voff(xi, nu + 1), (unsigned)(xi * AL + nu + 1) * m_pos);
     }
     float mm[4][AL], oo[4][TM];
 #pragma unroll
@@ -717,6 +754,25 @@ __global__ __launch_bounds__(256, 2) void wino_oip_h2c_kernel(WinoH2Args h) {
   const unsigned m_lane = (unsigned)((tl * 64 + pr * 4) * 4);
   const unsigned v_lane = (unsigned)((((tid >> 6) * 4) * 128) + lane * 4);
   const unsigned e_pix = (unsigned)a.Cout_p * 16u;
+  // Short positions (gemm_maps.hpp; h.live_r / h.live_c, 0 = off): at a class R / class C position a group's live tiles are packed into
+  // gr_r / gr_c rows instead of 16, and the thread's M row and its lanes' two V2c store rows are the class's own.  A dead (position,
+  // tile) gets an offset past the descriptor's range: the load returns zeros (they reach discarded outputs only), the store moves nothing.
+  // The class of a position is a constant after unrolling; with the short map off the class values ARE the full ones.
+  constexpr unsigned OOB = 0x80000000u;
+  const unsigned gr_r = h.live_r ? (unsigned)(bpg * maps::rows_per_board(maps::ROWS_R, a.nty, a.ntx)) : 16u;
+  const unsigned gr_c = h.live_c ? (unsigned)(bpg * maps::rows_per_board(maps::ROWS_C, a.nty, a.ntx)) : 16u;
+  auto m_row = [&](int cls) -> unsigned {
+    const int r = maps::rows_row(cls, a.nty, a.ntx, bl, ty, tx);
+    return r < 0 ? OOB : (unsigned)((r * 64 + pr * 4) * 4);
+  };
+  auto v_row = [&](int cls, int k) -> unsigned {           // store k of the wave: lanes 0..31 tile 4 w + 2 k, lanes 32..63 the next one
+    const int tv = (tid >> 6) * 4 + 2 * k + (lane >> 5), ttv = tv % a.TPB;
+    const int r = maps::rows_row(cls, a.nty, a.ntx, tv / a.TPB, ttv / a.ntx, ttv % a.ntx);
+    return r < 0 ? OOB : (unsigned)(r * 128 + (lane & 31) * 4);
+  };
+  const unsigned m_lane_r = h.live_r ? m_row(maps::ROWS_R) : m_lane, m_lane_c = h.live_c ? m_row(maps::ROWS_C) : m_lane;
+  const unsigned v0_r = h.live_r ? v_row(maps::ROWS_R, 0) : v_lane, v1_r = h.live_r ? v_row(maps::ROWS_R, 1) : v_lane + 256u;
+  const unsigned v0_c = h.live_c ? v_row(maps::ROWS_C, 0) : v_lane, v1_c = h.live_c ? v_row(maps::ROWS_C, 1) : v_lane + 256u;
   // this thread's tile origin in the haloed LDS board (floats): output pixel (k, l) at yo + ((k + 1) * PW + l + 1) * 32, input patch (i, j) at yi + (i * PW + j) * 32
   float* const ybase = ys + ((size_t)bl * PH * PW + (size_t)(TM * ty) * PW + TM * tx) * 32 + 2 * pr;
   unsigned okmask = 0;                                       // bit k * TM + l: output pixel (k, l) of this thread's tile lies on the board
@@ -726,14 +782,22 @@ __global__ __launch_bounds__(256, 2) void wino_oip_h2c_kernel(WinoH2Args h) {
     for (int l = 0; l < TM; l++) okmask |= (TM * ty + k < a.H && TM * tx + l < a.W) ? 1u << (k * TM + l) : 0u;
   const __amdgpu_buffer_rsrc_t er = h2_rsrc(a.ep);
   float4 m[NPRE][AL];
-  auto m_soff = [&](int g, int s, int pos) -> unsigned { return (unsigned)((((g >> 3) * h.npos + pos) * NS + s)) * 32768u + (unsigned)(g & 7) * 4096u; };
+  auto m_soff = [&](int g, int s, int xi, int nu) -> unsigned {
+    const int cls = maps::rows_class(true, true, AL, xi, nu);
+    const unsigned gr = cls == maps::ROWS_R ? gr_r : (cls == maps::ROWS_C ? gr_c : 16u);
+    return (unsigned)((((g >> 3) * h.npos + xi * AL + nu) * NS + s)) * 32768u + (unsigned)(g & 7) * (gr * 256u);
+  };
+  auto m_voff = [&](int xi, int nu) -> unsigned {
+    const int cls = maps::rows_class(true, true, AL, xi, nu);
+    return cls == maps::ROWS_R ? m_lane_r : (cls == maps::ROWS_C ? m_lane_c : m_lane);
+  };
   int item = blockIdx.x;
   {
     const int g = __builtin_amdgcn_readfirstlane(item / NS), s = __builtin_amdgcn_readfirstlane(item - (item / NS) * NS);
 #pragma unroll
     for (int nu = 0; nu < NPRE; nu++)
 #pragma unroll
-      for (int xi = 0; xi < AL; xi++) m[nu][xi] = h2_ldf4<MAUX>(mr, m_lane, m_soff(g, s, xi * AL + nu));
+      for (int xi = 0; xi < AL; xi++) m[nu][xi] = h2_ldf4<MAUX>(mr, m_voff(xi, nu), m_soff(g, s, xi, nu));
   }
   __syncthreads();
   for (; item < n_items; item += gridDim.x) {
@@ -759,7 +823,7 @@ __global__ __launch_bounds__(256, 2) void wino_oip_h2c_kernel(WinoH2Args h) {
       }
       if (nu + NPRE < AL) {
 #pragma unroll
-        for (int xi = 0; xi < AL; xi++) m[nu % NPRE][xi] = h2_ldf4<MAUX>(mr, m_lane, m_soff(g, s, xi * AL + nu + NPRE));
+        for (int xi = 0; xi < AL; xi++) m[nu % NPRE][xi] = h2_ldf4<MAUX>(mr, m_voff(xi, nu + NPRE), m_soff(g, s, xi, nu + NPRE));
       }
       wino_atv_p<TM>(c0, o0);
       wino_atv_p<TM>(c1, o1);
@@ -839,11 +903,12 @@ __global__ __launch_bounds__(256, 2) void wino_oip_h2c_kernel(WinoH2Args h) {
 #pragma unroll
       for (int nu = 0; nu < NPRE; nu++)
 #pragma unroll
-        for (int xi = 0; xi < AL; xi++) m[nu][xi] = h2_ldf4<MAUX>(mr, m_lane, m_soff(g2, s2, xi * AL + nu));
+        for (int xi = 0; xi < AL; xi++) m[nu][xi] = h2_ldf4<MAUX>(mr, m_voff(xi, nu), m_soff(g2, s2, xi, nu));
     }
     __builtin_amdgcn_sched_barrier(0);
     // ---- input transform of the next block, one output row at a time (column pass recomputed per row from LDS)
-    const unsigned v_base = (unsigned)((((g >> 3) * h.npos) * NS + s)) * 16384u + (unsigned)(g & 7) * 2048u;
+    const unsigned v_base = (unsigned)((((g >> 3) * h.npos) * NS + s)) * 16384u;
+    const unsigned v_g = (unsigned)(g & 7) * 2048u, v_g_r = (unsigned)(g & 7) * (gr_r * 128u), v_g_c = (unsigned)(g & 7) * (gr_c * 128u);
     const unsigned v_pos = (unsigned)NS * 16384u;
     const float* yr = ybase;
     asm volatile("" : "+v"(yr));
@@ -880,8 +945,10 @@ __global__ __launch_bounds__(256, 2) void wino_oip_h2c_kernel(WinoH2Args h) {
           const unsigned e0 = s16[0], e1 = s16[1];
           const auto s32 = __builtin_amdgcn_permlane32_swap(e0, e1, false, false);
           const unsigned w0 = s32[0], w1 = s32[1];
-          __builtin_amdgcn_raw_buffer_store_b32(w0, vr, v_lane, v_base + (unsigned)(i * AL + j) * v_pos, VAUX);
-          __builtin_amdgcn_raw_buffer_store_b32(w1, vr, v_lane + 256u, v_base + (unsigned)(i * AL + j) * v_pos, VAUX);
+          const int cls = maps::rows_class(true, true, AL, i, j);
+          const unsigned v_so = v_base + (cls == maps::ROWS_R ? v_g_r : (cls == maps::ROWS_C ? v_g_c : v_g)) + (unsigned)(i * AL + j) * v_pos;
+          __builtin_amdgcn_raw_buffer_store_b32(w0, vr, cls == maps::ROWS_R ? v0_r : (cls == maps::ROWS_C ? v0_c : v_lane), v_so, VAUX);
+          __builtin_amdgcn_raw_buffer_store_b32(w1, vr, cls == maps::ROWS_R ? v1_r : (cls == maps::ROWS_C ? v1_c : v_lane + 256u), v_so, VAUX);
         }
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -924,6 +991,40 @@ static void wino_h2c_geometry(WinoH2Args& h) {
   a.n_mtiles = ceil_div(a.T, 128); a.n_ntiles = ceil_div(a.Ntot, 128);
   h.in_swap = 1; h.cform = 1; h.wm_per_board = 0;
 }
+constexpr int WINO_H2_GEMM_DEFAULT = 1;   // 1: wino_gemm_h2g_kernel (three workgroups per CU), 2: wino_gemm_h2p_kernel (persistent)
+// gemm_variant (0 = the default) -> the kernel and its decomposition mode: what BOTH the launch (wino_h2c_gemm) and the short-row
+// decision (wino_h2c_rows) go by (the environment switch is resolved by the caller: net.hip)
+static inline int wino_h2c_gemm_variant(const WinoH2Args& h) { return h.gemm_variant > 0 ? h.gemm_variant : WINO_H2_GEMM_DEFAULT; }
+// the 31-bit buffer offsets of the DMA GEMM (V, U2c) and of the pipelined out->in kernel (M, V)
+static inline bool wino_h2c_dma_ok(const WinoH2Args& h) {
+  return wino_h2_rows(h.npos, (size_t)h.w.T) * h.w.C * 4 < ((size_t)1 << 31) && (size_t)h.npos * h.w.C * h.w.Ntot * 4 < ((size_t)1 << 31);
+}
+static inline bool wino_h2c_fits31(const WinoH2Args& h) { return wino_h2_rows(h.npos, (size_t)h.w.T) * h.w.Ntot * 4 < ((size_t)1 << 31); }
+// The pipelined out->in kernel takes up to 80 KB of dynamic LDS (wino_h2c_ok): a function attribute of the CURRENT DEVICE — kept per
+// context (several contexts / devices in one process: agz_comm_init_all), its result checked; where it cannot be set the plain
+// out->in kernel runs instead
+static bool wino_h2c_oip_ready(agz_ctx* ctx) {
+  if (!(ctx->func_attr_state & 2u)) {
+    const bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_oip_h2c_kernel<5>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) == hipSuccess &&
+                    hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_oip_h2c_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) == hipSuccess;
+    if (!ok) (void)hipGetLastError();
+    ctx->func_attr_state |= 2u | (ok ? 1u : 0u);
+  }
+  return (ctx->func_attr_state & 1u) != 0;
+}
+// Short positions (gemm_maps.hpp): sets h.live_r / h.live_c for a block of the tower.  The three stages of every block of a forward must
+// agree on the layout, so the answer depends only on the shape and on which kernels run — asked before block 0's input transform and
+// the same for every block: the tower's default kernels (DMA GEMM wino_gemm_h2g_kernel, pipelined out->in kernel; oi_variant 4) and
+// live counts of whole 32-row MFMA blocks.  keep_all (agz_net_set_wino_h2_gemm + 128): the A/B hook, every row kept.
+static void wino_h2c_rows(agz_ctx* ctx, WinoH2Args& h, int oi_variant, bool keep_all) {
+  wino_h2c_geometry(h);
+  h.live_r = h.live_c = 0;
+  const int gemm = wino_h2c_gemm_variant(h) & 15;
+  const maps::WinoRows g = maps::wino_rows(h.w.H, h.w.W, h.tm);
+  if (keep_all || gemm != 1 || oi_variant != 4 || !wino_h2c_dma_ok(h) || !wino_h2c_fits31(h) || !maps::rows_short_ok(g) || !wino_h2c_oip_ready(ctx)) return;
+  h.live_r = g.dead_y ? maps::rows_slot_live(g, maps::ROWS_R) : 0;
+  h.live_c = g.dead_x ? maps::rows_slot_live(g, maps::ROWS_C) : 0;
+}
 static void wino_h2c_in(agz_ctx* ctx, WinoH2Args& h, hipStream_t st) {     // block 0: x -> V2c (exact range: h.amax_in, fuse_prev = 0)
   wino_h2c_geometry(h);
   h.fuse_prev = 0; h.amax_self = const_cast<unsigned*>(h.amax_in);
@@ -932,15 +1033,14 @@ static void wino_h2c_in(agz_ctx* ctx, WinoH2Args& h, hipStream_t st) {     // bl
   if (h.tm == 5) hipLaunchKernelGGL(wino_in_h2_kernel<5>, dim3((unsigned)((n_in + 255) / 256)), dim3(256), 0, st, h);
   else hipLaunchKernelGGL(wino_in_h2_kernel<4>, dim3((unsigned)((n_in + 255) / 256)), dim3(256), 0, st, h);
 }
-constexpr int WINO_H2_GEMM_DEFAULT = 1;   // 1: wino_gemm_h2g_kernel (three workgroups per CU), 2: wino_gemm_h2p_kernel (persistent)
 static void wino_h2c_gemm(agz_ctx* ctx, WinoH2Args& h, hipStream_t st) {
   wino_h2c_geometry(h);
   ProfScopeOn ps(ctx, AGZ_PROF_WINO_GEMM, st == ctx->stream.raw());
   const dim3 g(h.npos * h.w.n_mtiles * (h.w.Ntot >> 8));
   // (the DMA form addresses V and U2c through buffer descriptors: 31-bit byte offsets)
-  const bool dma_ok = wino_h2_rows(h.npos, (size_t)h.w.T) * h.w.C * 4 < ((size_t)1 << 31) && (size_t)h.npos * h.w.C * h.w.Ntot * 4 < ((size_t)1 << 31);
+  const bool dma_ok = wino_h2c_dma_ok(h);
   // persistent form (wino_gemm_h2p_kernel; gemm_variant 2, AGZ_WINO_H2_GEMM=2): K = 256, whole 128-column slabs, one workgroup per CU
-  const int variant_all = h.gemm_variant > 0 ? h.gemm_variant : WINO_H2_GEMM_DEFAULT;   // (the environment switch is resolved by the caller: net.hip)
+  const int variant_all = wino_h2c_gemm_variant(h);
   const int variant = variant_all & 15, mode = (variant_all >> 4) & 3;   // (mode: agz_debug.h decomposition runs — results are then NOT valid)
   const int n_slabs = h.w.Ntot >> 7;
   if (variant == 2 && dma_ok && (h.w.C >> 5) == 8 && h.w.Ntot % 256 == 0 && ctx->num_cus / 8 >= n_slabs) {
@@ -977,16 +1077,8 @@ static void wino_h2c_oi(agz_ctx* ctx, WinoH2Args& h, bool last, hipStream_t st, 
   const dim3 g((unsigned)ceil_div(a.T, 16), (unsigned)(a.C >> 5));
   const size_t shm = last ? 0 : (size_t)(16 / a.TPB) * a.H * a.W * 32 * sizeof(float);
   // (the pipelined kernel addresses M and V through one buffer descriptor each: 31-bit byte offsets)
-  const bool fits31 = wino_h2_rows(h.npos, (size_t)a.T) * a.Ntot * 4 < ((size_t)1 << 31);
-  // up to 80 KB of dynamic LDS (wino_h2c_ok): a function attribute of the CURRENT DEVICE — kept per context (several contexts / devices in
-  // one process: agz_comm_init_all), its result checked; where it cannot be set the plain out->in kernel below runs instead
-  if (variant == 4 && !last && fits31 && !(ctx->func_attr_state & 2u)) {
-    const bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_oip_h2c_kernel<5>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) == hipSuccess &&
-                    hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_oip_h2c_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) == hipSuccess;
-    if (!ok) (void)hipGetLastError();
-    ctx->func_attr_state |= 2u | (ok ? 1u : 0u);
-  }
-  if (variant == 4 && !last && fits31 && (ctx->func_attr_state & 1u)) {   // persistent, software-pipelined
+  const bool fits31 = wino_h2c_fits31(h);
+  if (variant == 4 && !last && fits31 && wino_h2c_oip_ready(ctx)) {   // persistent, software-pipelined
     const size_t shp = (size_t)(16 / a.TPB) * (h.tm * a.nty + 2) * (h.tm * a.ntx + 2) * 32 * sizeof(float);
     const int items = ceil_div(a.T, 16) * (a.C >> 5);
     const dim3 gp((unsigned)std::min(items, 2 * ctx->num_cus));

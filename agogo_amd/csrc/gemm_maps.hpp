@@ -45,6 +45,60 @@ AGZ_MAPS_HD constexpr size_t mc_index(int m_tile, int npos, int pos, int n_slice
   return ((((size_t)m_tile * npos + pos) * (size_t)n_slices + (size_t)slice) * 128 + (size_t)row) * 64 + (size_t)col;
 }
 
+// the four waves of a workgroup: first row of wave w's part of a stage, and of the 32-row MFMA block i of the waves wm (64 rows each)
+AGZ_MAPS_HD constexpr int h2c_wave_row0(int wid, int stage_rows) { return wid * (stage_rows / 4); }
+AGZ_MAPS_HD constexpr int h2c_mfma_row0(int wm, int i) { return wm * 64 + i * 32; }
+
+// ---- short positions (tests/cpp/wino_rows_check.cpp, tests/test_wino_dead_rows_cpu.py) --------------------------------------------
+// F(TM x TM, 3x3) covers H pixels with nty = ceil(H / TM) tiles; where TM * nty > H the last output row of the last tile row lies
+// off the board, and the last transform point (index AL - 1, the "infinity" point) feeds that output only.  So the V2c / GEMM / Mc
+// row of (position (xi, nu), tile (ty, tx)) is dead — it reaches no kept pixel — when xi == AL - 1 and ty == nty - 1, and likewise
+// with nu / tx for the columns.  A short position packs its live tiles into the first rows of its 128-row slot:
+//   class R (dead_y, xi == AL - 1, every nu): live ty < nty - 1, local index tt,                    lr = TPB - ntx per board
+//   class C (dead_x, nu == AL - 1, xi != AL - 1): live tx < ntx - 1, local index ty * (ntx - 1) + tx, lc = TPB - nty per board
+// row in the slot = (b % bpt) * l + local index, bpt = 128 / TPB boards per slot; rows bpt * l .. 127 are neither written nor read.
+// (At the corner class R keeps the tx == ntx - 1 rows although they are dead too: one rule per position.)
+enum { ROWS_FULL = 0, ROWS_R = 1, ROWS_C = 2 };
+struct WinoRows { int TM, AL, nty, ntx, TPB, bpt; bool dead_y, dead_x; };
+AGZ_MAPS_HD constexpr WinoRows wino_rows(int H, int W, int TM) {
+  const int nty = (H + TM - 1) / TM, ntx = (W + TM - 1) / TM;
+  return WinoRows{TM, TM + 2, nty, ntx, nty * ntx, 128 / (nty * ntx), TM * nty > H, TM * ntx > W};
+}
+AGZ_MAPS_HD constexpr int rows_class(bool dead_y, bool dead_x, int AL, int xi, int nu) {
+  return xi == AL - 1 ? (dead_y ? ROWS_R : ROWS_FULL) : ((dead_x && nu == AL - 1) ? ROWS_C : ROWS_FULL);   // (the corner is never class C)
+}
+// live tiles per board at a position of class cls
+AGZ_MAPS_HD constexpr int rows_per_board(int cls, int nty, int ntx) {
+  return cls == ROWS_R ? nty * ntx - ntx : (cls == ROWS_C ? nty * ntx - nty : nty * ntx);
+}
+// local index of tile (ty, tx) among its board's live tiles; -1: dead
+AGZ_MAPS_HD constexpr int rows_local(int cls, int nty, int ntx, int ty, int tx) {
+  return cls == ROWS_R ? (ty < nty - 1 ? ty * ntx + tx : -1) : (cls == ROWS_C ? (tx < ntx - 1 ? ty * (ntx - 1) + tx : -1) : ty * ntx + tx);
+}
+// row of (board bs = b % bpt of the slot, tile (ty, tx)) inside the 128-row slot; -1: dead
+AGZ_MAPS_HD constexpr int rows_row(int cls, int nty, int ntx, int bs, int ty, int tx) {
+  return rows_local(cls, nty, ntx, ty, tx) < 0 ? -1 : bs * rows_per_board(cls, nty, ntx) + rows_local(cls, nty, ntx, ty, tx);
+}
+// live rows of a slot at a position of class cls
+AGZ_MAPS_HD constexpr int rows_slot_live(const WinoRows& g, int cls) { return g.bpt * rows_per_board(cls, g.nty, g.ntx); }
+// the short map is taken when a class exists and every class that does leaves whole 32-row MFMA blocks: 32, 64 or 96 live rows
+AGZ_MAPS_HD constexpr bool rows_live_ok(int live) { return live == 32 || live == 64 || live == 96; }
+AGZ_MAPS_HD constexpr bool rows_short_ok(const WinoRows& g) {
+  return 128 % g.TPB == 0 && (g.dead_y || g.dead_x) && (!g.dead_y || rows_live_ok(rows_slot_live(g, ROWS_R))) &&
+         (!g.dead_x || rows_live_ok(rows_slot_live(g, ROWS_C)));
+}
+// what the GEMM needs: the live rows of position pos's slots (live_r / live_c: the two classes' counts, 0 = no such class)
+AGZ_MAPS_HD constexpr int rows_pos_live(int live_r, int live_c, int AL, int pos) {
+  return pos / AL == AL - 1 ? (live_r ? live_r : 128) : ((live_c && pos % AL == AL - 1) ? live_c : 128);
+}
+// stored rows per board over all positions
+AGZ_MAPS_HD constexpr int rows_stored_per_board(const WinoRows& g) {
+  int n = 0;
+  for (int xi = 0; xi < g.AL; xi++)
+    for (int nu = 0; nu < g.AL; nu++) n += rows_per_board(rows_class(g.dead_y, g.dead_x, g.AL, xi, nu), g.nty, g.ntx);
+  return n;
+}
+
 // ---- persistent kernel (wino_gemm_h2p_kernel): 8 KB stages of 64 rows, ring of 16, DMA 10 stages ahead
 constexpr int H2P_D = 10, H2P_R = 16, H2P_NK = 8;
 // byte offset in V2c of K step 0 of half tile hm (rows 64 (hm & 1) .. of m-tile hm >> 1) of position pos

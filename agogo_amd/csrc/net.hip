@@ -1239,18 +1239,21 @@ void agz_net::wino_h2c_block(int l, int B, int b0, int ci, const H2Tower& t, hip
   hh.wm_prev = d_wave_max + ((size_t)((l + 1) & 1) * B + b0) * wmb;
   hh.wm_out = d_wave_max + ((size_t)(l & 1) * B + b0) * wmb;
   hh.g1 = wino_g1[l]; hh.g0 = wino_g0[l];
-  {   // which GEMM kernel / store policy: agz_net_set_wino_h2_gemm, else AGZ_WINO_H2_GEMM (1 | 2, + 64 = round 4's stores), else the default
-    // (the environment reaches the two product kernels only: 1 | 2, + 64; anything else — 2 + 16 * mode are the persistent kernel's
+  {   // which GEMM kernel / store policy: agz_net_set_wino_h2_gemm, else AGZ_WINO_H2_GEMM (1 | 2, + 64 = round 4's stores, + 128 = every row kept), else the default
+    // (the environment reaches the two product kernels only: 1 | 2, + 64, + 128; anything else — 2 + 16 * mode are the persistent kernel's
     //  timing-only decomposition instances, wrong results by design, agz_debug.h — is ignored with one line on stderr)
     static const int gemm_env = [] {
       const char* e = getenv("AGZ_WINO_H2_GEMM");
       const int v = e ? atoi(e) : 0;
-      if (v == 0 || (((v & 63) == 1 || (v & 63) == 2) && (v >> 6) <= 1)) return v;
-      fprintf(stderr, "libagz: AGZ_WINO_H2_GEMM=%s ignored (want 1 or 2, optionally + 64)\n", e);
+      if (v == 0 || (((v & 63) == 1 || (v & 63) == 2) && (v >> 6) <= 3)) return v;
+      fprintf(stderr, "libagz: AGZ_WINO_H2_GEMM=%s ignored (want 1 or 2, optionally + 64 and / or + 128)\n", e);
       return 0;
     }();
     const int gv = wino_gemm > 0 ? wino_gemm : gemm_env;
     hh.gemm_variant = gv & 63; hh.temporal_stores = (gv >> 6) & 1;
+    // short positions (gemm_maps.hpp): decided from the shape and the kernel choice alone, the same for every block of the forward
+    agz::wino_h2c_rows(ctx, hh, t.form_want == 1 ? 1 : 4, ((gv >> 7) & 1) != 0);
+    wino_live_r = hh.live_r; wino_live_c = hh.live_c;
   }
   if (l == 0) agz::wino_h2c_in(ctx, hh, st);
   agz::wino_h2c_gemm(ctx, hh, st);
@@ -1953,9 +1956,15 @@ int agz_net_min_same_batch(agz_net* n, int k, int G, int* batch) {
   return AGZ_OK;
 }
 
+int agz_net_wino_h2_last_rows(agz_net* n, int* live_r, int* live_c) {
+  AGZ_REQUIRE(n && live_r && live_c, AGZ_E_INVALID, "agz_net_wino_h2_last_rows: null argument");
+  *live_r = n->wino_live_r; *live_c = n->wino_live_c;
+  return AGZ_OK;
+}
+
 int agz_net_set_wino_h2_gemm(agz_net* n, int variant) {
   AGZ_REQUIRE(n, AGZ_E_INVALID, "agz_net_set_wino_h2_gemm: null net");
-  AGZ_REQUIRE(((variant & 63) <= 2 && (variant >> 6) <= 1) || ((variant & 15) == 2 && (variant >> 4) <= 3), AGZ_E_INVALID, "agz_net_set_wino_h2_gemm: variant %d (want 0, 1, 2, + 64, or 2 + 16 * mode)", variant);
+  AGZ_REQUIRE(((variant & 63) <= 2 && (variant >> 6) <= 3) || ((variant & 15) == 2 && (variant >> 4) <= 3), AGZ_E_INVALID, "agz_net_set_wino_h2_gemm: variant %d (want 0, 1, 2, + 64, + 128, or 2 + 16 * mode)", variant);
   n->wino_gemm = variant;
   return AGZ_OK;
 }

@@ -83,6 +83,7 @@ struct agz_net {
   std::vector<_Float16*> d_u2c_dual;
   std::vector<float> wino_g1, wino_g0;
   int wino_gemm = 0;                       // agz_net_set_wino_h2_gemm (agz_debug.h): 0 default, 1 wino_gemm_h2g_kernel, 2 wino_gemm_h2p_kernel
+  int wino_live_r = 0, wino_live_c = 0;    // agz_net_wino_h2_last_rows (agz_debug.h): what the last chained block ran with (WinoH2Args::live_r / live_c)
   int wino_form = -1;                      // agz_net_set_wino_h2_form (agz_debug.h): -1 auto (chained where the shape allows), 0 three-kernel block, 1 chained
   void free_u2c() { for (auto& p : d_u2c_dual) if (p) hipFree(p); d_u2c_dual.clear(); wino_g1.clear(); wino_g0.clear(); }
   int build_wino_h2_weights();

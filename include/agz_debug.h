@@ -54,8 +54,16 @@ int agz_net_set_wino_h2_form(agz_net* net, int form);
  * registers, M stores under the next tile's arithmetic; K = 256 only, other shapes keep kernel 1).  Results are bit-identical.  The
  * environment switch AGZ_WINO_H2_GEMM=1|2 (agz.h) does the same for a whole process.  Decomposition runs (timing only, the results are
  * NOT valid): 2 + 16 * mode with mode bit 0 = kernel 2 without its M stores, bit 1 = without its operand DMA (profiles/r05).
- * + 64 (with 0, 1 or 2): M and V2c stored with the default cache policy, as in round 4, instead of non-temporally (bit-identical; A/B). */
+ * + 64 (with 0, 1 or 2): M and V2c stored with the default cache policy, as in round 4, instead of non-temporally (bit-identical; A/B).
+ * + 128 (with 0, 1 or 2, and with + 64): every transform-domain row is kept — by default the tower's default kernels neither store,
+ * multiply nor read the rows that only feed off-board outputs (the last transform point of the tiles that hang over the board's
+ * edge: DESIGN 4a, gemm_maps.hpp); kernel 2 and the other forms always keep every row (bit-identical; A/B). */
 int agz_net_set_wino_h2_gemm(agz_net* net, int variant);
+
+/* What the last chained AGZ_COMPUTE_WINO_H2 block this net launched ran with: the live rows per 128-row slot at the class R (xi == AL-1)
+ * and class C (nu == AL-1) positions, 0 = no such class / every row kept (19x19: 96, 96; with + 128 above, the persistent GEMM or the
+ * other forms: 0, 0).  Lets a test see that the short positions are on, which identical results alone cannot show. */
+int agz_net_wino_h2_last_rows(agz_net* net, int* live_r, int* live_c);
 
 /* prepareRoot (mcts/search.go:392-408) evaluates the network only for roots without children.  agz_arena_begin_move packs those roots to
  * the front of the batch and runs the forward on the smallest batch that takes the same kernels as the arena's whole batch (per board the
