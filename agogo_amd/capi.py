@@ -260,6 +260,9 @@ def lib():
     sig("agz_wino_h2_chained", i32, i32, i32, i32)
     sig("agz_arena_random_moves", i32, vp, pi, u64)
     sig("agz_arena_set_state", i32, vp, i32, C.POINTER(State))
+    sig("agz_arena_save", i32, vp, C.c_char_p)
+    sig("agz_arena_load", i32, vp, C.c_char_p)
+    sig("agz_arena_set_ckpt_staging", i32, vp, C.c_size_t)
     sig("agz_arena_examples_labelled_dev", i32, vp, pvp)
     sig("agz_mcts_create", i32, vp, C.POINTER(GameConf), C.POINTER(MctsConf), u64, i32, pvp)
     sig("agz_mcts_destroy", None, vp)
@@ -829,6 +832,19 @@ class Arena:
         st, keep = make_state(self.m * self.n, **kw)
         _check(lib().agz_arena_set_state(self.h, g, C.byref(st)), "agz_arena_set_state")
         del keep
+
+    def save(self, path):
+        """checkpoint of the running arena, between moves (agz_arena_save): games, trees, RNG states, counters, examples"""
+        _check(lib().agz_arena_save(self.h, os.fsencode(path)), "agz_arena_save")
+
+    def load(self, path):
+        """a checkpoint of an arena of the same game, search configuration and n_games (agz_arena_load); inferencers, lanes and the pool
+        policy are the caller's to set again"""
+        _check(lib().agz_arena_load(self.h, os.fsencode(path)), "agz_arena_load")
+
+    def set_ckpt_staging(self, nbytes):
+        """agz_debug.h: bytes of each staging buffer save / load stream the nodes and examples through"""
+        _check(lib().agz_arena_set_ckpt_staging(self.h, int(nbytes)), "agz_arena_set_ckpt_staging")
 
     def results(self):
         a, b, d = C.c_int64(0), C.c_int64(0), C.c_int64(0)

@@ -22,8 +22,12 @@
 #include <chrono>
 #include <climits>
 #include <cstring>
+#include <string>
 #include <vector>
 
+#include <unistd.h>
+
+#include "arena_ckpt.hpp"
 #include "engine_dev.hpp"
 #include "net.hpp"
 
@@ -1350,6 +1354,7 @@ struct agz_arena {
   long long room_sims = 0, sims_this_move = 0;   // simulations the current capacity is guaranteed for / enqueued since begin_move
   int pool_grows = 0;       // how often the pools were re-allocated
   int ensure_pool_room(long long sims);
+  int pool_room_for(long long most, long long sims);   // the same for a given fullest tree (ensure_pool_room reads it from the device)
   bool pool_stop = false;   // agz_arena_set_pool_policy: a full node pool stops that tree's search for the move (the reference's MAXTREESIZE rule) instead of failing the call
   size_t h_pk_policy_cap = 0, h_policy_cap[2] = {0, 0}, h_value_cap[2] = {0, 0};
 
@@ -1381,6 +1386,14 @@ struct agz_arena {
   int64_t split_steps = 0, joined_steps = 0;
   bool split_eligible() const;
   int nn_step_split();
+  // checkpoints (agz_arena_save / agz_arena_load): the configuration as the file stores and compares it, and the staging size
+  agz_game_conf conf_game{};           // max_moves resolved
+  agz_mcts_conf conf_mcts{};
+  size_t ckpt_staging = 256u << 20;    // bytes of the device buffer and of each of the two page-locked host buffers (agz_arena_set_ckpt_staging)
+  arena_ckpt::Shape ckpt_shape() const;
+  template <class Sm, class Fn> int ckpt_small(Sm& sm, Fn xfer);
+  int ckpt_write(FILE* f, const arena_ckpt::Shape& h, const arena_ckpt::Small& sm, const arena_ckpt::Layout& l);
+  int ckpt_apply(FILE* f, const arena_ckpt::Scan& sc);
 };
 
 // prepareRoot evaluates only roots without children (search.go:392-408): with tree reuse a minority of an arena's games (19x19, 512
@@ -1426,6 +1439,12 @@ int agz_arena::ensure_pool_room(long long sims) {
   AGZ_HIP_TRY(hipStreamSynchronize(s));
   long long most = 0;
   for (int t = 0; t < T; t++) most = std::max<long long>(most, nn[t]);
+  return pool_room_for(most, sims);
+}
+
+int agz_arena::pool_room_for(long long most, long long sims) {
+  hipStream_t s = ctx->stream;
+  const int T = d.T;
   const long long need = most + (sims + 2) * (long long)(gc.A + 1) + 16;
   if (need <= d.cap) return AGZ_OK;
   long long ncap = std::max(need + need / 2, 2ll * d.cap);
@@ -1770,6 +1789,8 @@ int agz_arena_create(agz_ctx* ctx, const agz_game_conf* game, const agz_mcts_con
   c.pass_legal = (c.kind == AGZ_GAME_WQ || c.kind == AGZ_GAME_C4);
   c.go_like = (c.kind == AGZ_GAME_KOMI || c.kind == AGZ_GAME_WQ);
   c.has_passes = c.kind == AGZ_GAME_WQ;
+  a->conf_game = *game; a->conf_game.max_moves = c.max_moves;
+  a->conf_mcts = *mcts;
   MctsCfg& m = a->mc;
   m.PUCT = mcts->PUCT; m.maxDepth = mcts->M * mcts->N; m.RandomCount = mcts->RandomCount; m.Budget = mcts->Budget;
   m.RandomMinVisits = mcts->RandomMinVisits; m.RandomTemperature = mcts->RandomTemperature; m.DumbPass = mcts->DumbPass;
@@ -2388,6 +2409,322 @@ int agz_arena_set_state(agz_arena* a, int g, const agz_state* st) {
   AGZ_HIP_TRY(hipMemcpyAsync(d.cap_w + g, &st->captures_white, 4, hipMemcpyHostToDevice, s));
   AGZ_HIP_TRY(hipMemcpyAsync(d.zhash + g, &st->hash, 4, hipMemcpyHostToDevice, s));
   AGZ_HIP_TRY(hipStreamSynchronize(s));   // the staging vectors and *st are the caller's / locals
+  return AGZ_OK;
+}
+
+}  // extern "C"
+
+// ---- arena checkpoints (agz_arena_save / agz_arena_load) ------------------------------------------------------------------------------
+// The bytes are arena_ckpt.hpp's; this side describes the arena, moves the small state as whole arrays, and streams the two large
+// sections through ONE device staging buffer and TWO page-locked host buffers of ckpt_staging bytes each: the copy of chunk i + 1 between
+// device and host runs while the file system has chunk i.  The trees' nodes lie [T][2][cap]; what is live at a move boundary is the prefix
+// [0, n_nodes[t]) of pool cur_pool[t], so k_ckpt_pack gathers those prefixes into per-field runs (the file's node order: tree by tree)
+// and k_ckpt_unpack scatters them back at the loading arena's own stride.  A chunk is a range of whole trees; a tree larger than the
+// staging buffer is cut by node range.  Example rows are contiguous already and take the same double buffer without a kernel.
+// Nothing here is on the step path: no existing kernel and no existing field of Dev changes.
+namespace agz {
+
+struct CkptRuns { float* prior; uint32_t* visits; float* bsum; int32_t* kids_off; int16_t* kids_n; int16_t* nmove; };
+// the six runs of a chunk of cnt nodes inside the staging buffer (every run starts on a 4-byte boundary)
+__host__ __device__ inline CkptRuns ckpt_runs(void* staging, size_t cnt) {
+  char* p = (char*)staging;
+  const size_t even = (cnt + 1) & ~(size_t)1;
+  return {(float*)p, (uint32_t*)(p + 4 * cnt), (float*)(p + 8 * cnt), (int32_t*)(p + 12 * cnt), (int16_t*)(p + 16 * cnt), (int16_t*)(p + 16 * cnt + 2 * even)};
+}
+inline size_t ckpt_chunk_nodes(size_t staging_bytes) { return (staging_bytes - 4) / 20; }
+
+// n 16-bit words, src -> dst, by threads tid, tid + nth, ...  A tree's run may start at an odd element on either side; the body is written as
+// aligned 32-bit words of the DESTINATION (one full-width store per lane instead of a half-width one), the odd element at either end alone.
+__device__ __forceinline__ void ckpt_copy16(int16_t* dst, const int16_t* src, int n, int tid, int nth) {
+  const int head = (n > 0 && ((uintptr_t)dst & 2)) ? 1 : 0;
+  if (head && tid == 0) dst[0] = src[0];
+  const int pairs = (n - head) / 2;
+  uint32_t* d32 = reinterpret_cast<uint32_t*>(dst + head);
+  const uint16_t* s16 = reinterpret_cast<const uint16_t*>(src + head);
+  for (int w = tid; w < pairs; w += nth) d32[w] = (uint32_t)s16[2 * w] | ((uint32_t)s16[2 * w + 1] << 16);
+  if (((n - head) & 1) && tid == 0) dst[n - 1] = src[n - 1];
+}
+
+// nodes [n0, n1) of the file's node order <-> the staging runs.  first[t]: exclusive prefix sum of the trees' node counts (T + 1 words, the
+// counts the HOST read or validated: no count is taken from the device here).  Grid (blocks, trees of the chunk), tree t0 + blockIdx.y.
+template <bool PACK>
+__device__ __forceinline__ void ckpt_move(const Dev& d, const long long* __restrict__ first, int t0, long long n0, long long n1, void* staging) {
+  const int t = t0 + blockIdx.y;
+  const long long a = first[t] > n0 ? first[t] : n0, b = first[t + 1] < n1 ? first[t + 1] : n1;
+  if (a >= b) return;
+  const int cnt = (int)(b - a);
+  const size_t p = ((size_t)t * 2 + d.cur_pool[t]) * d.cap + (size_t)(a - first[t]), q = (size_t)(a - n0);
+  const CkptRuns r = ckpt_runs(staging, (size_t)(n1 - n0));
+  const int tid = blockIdx.x * 256 + threadIdx.x, nth = gridDim.x * 256;
+  if (PACK) {
+    for (int i = tid; i < cnt; i += nth) {
+      r.prior[q + i] = d.prior[p + i]; r.visits[q + i] = d.visits[p + i]; r.bsum[q + i] = d.bsum[p + i]; r.kids_off[q + i] = d.kids_off[p + i];
+    }
+    ckpt_copy16(r.kids_n + q, d.kids_n + p, cnt, tid, nth);
+    ckpt_copy16(r.nmove + q, d.nmove + p, cnt, tid, nth);
+  } else {
+    for (int i = tid; i < cnt; i += nth) {
+      d.prior[p + i] = r.prior[q + i]; d.visits[p + i] = r.visits[q + i]; d.bsum[p + i] = r.bsum[q + i]; d.kids_off[p + i] = r.kids_off[q + i];
+    }
+    ckpt_copy16(d.kids_n + p, r.kids_n + q, cnt, tid, nth);
+    ckpt_copy16(d.nmove + p, r.nmove + q, cnt, tid, nth);
+  }
+}
+__global__ __launch_bounds__(256) void k_ckpt_pack(Dev d, const long long* __restrict__ first, int t0, long long n0, long long n1, void* staging) {
+  ckpt_move<true>(d, first, t0, n0, n1, staging);
+}
+__global__ __launch_bounds__(256) void k_ckpt_unpack(Dev d, const long long* __restrict__ first, int t0, long long n0, long long n1, void* staging) {
+  ckpt_move<false>(d, first, t0, n0, n1, staging);
+}
+
+// the staging of one save or load; released (after the queue has drained) when the call returns, whatever happened
+struct CkptStaging {
+  hipStream_t s = nullptr;
+  void* dev = nullptr;
+  void* host[2] = {nullptr, nullptr};
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  long long* first = nullptr;   // device copy of the node prefix sums
+  size_t bytes = 0;
+  int init(hipStream_t stream, size_t want, const std::vector<uint64_t>& tree_first) {
+    s = stream; bytes = want;
+    AGZ_HIP_TRY(hipMalloc(&dev, bytes));
+    for (int i = 0; i < 2; i++) { AGZ_HIP_TRY(hipHostMalloc(&host[i], bytes, hipHostMallocDefault)); AGZ_HIP_TRY(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming)); }
+    AGZ_HIP_TRY(hipMalloc(&first, tree_first.size() * 8));
+    AGZ_HIP_TRY(hipMemcpyAsync(first, tree_first.data(), tree_first.size() * 8, hipMemcpyHostToDevice, s));
+    AGZ_HIP_TRY(hipStreamSynchronize(s));
+    return AGZ_OK;
+  }
+  ~CkptStaging() {
+    if (s) hipStreamSynchronize(s);
+    if (dev) hipFree(dev);
+    if (first) hipFree(first);
+    for (int i = 0; i < 2; i++) { if (host[i]) hipHostFree(host[i]); if (ev[i]) hipEventDestroy(ev[i]); }
+  }
+};
+
+// one step of a section: nodes [a, b) of the file's order (trees t0 .. t0 + nt - 1), or bytes [a, b) of example run `field`
+struct CkptChunk { int field; uint64_t a, b; int t0, nt; };   // field < 0: nodes
+
+// whole trees while they fit the staging buffer; a tree that does not fit alone is cut by node range
+static std::vector<CkptChunk> ckpt_chunks(const arena_ckpt::Shape& h, const arena_ckpt::Layout& l, size_t staging, bool nodes) {
+  std::vector<CkptChunk> out;
+  if (nodes) {
+    const std::vector<uint64_t>& f = l.tree_first;
+    const uint64_t capn = ckpt_chunk_nodes(staging);
+    const int T = (int)f.size() - 1;
+    for (uint64_t n0 = 0; n0 < l.nodes;) {
+      const int t0 = (int)(std::upper_bound(f.begin(), f.end(), n0) - f.begin()) - 1;   // the tree that holds node n0 (empty trees before it skipped)
+      uint64_t n1 = std::min(n0 + capn, l.nodes);
+      int t1 = (int)(std::upper_bound(f.begin(), f.end(), n1) - f.begin()) - 1;          // largest t with first[t] <= n1
+      if (t1 > t0 + 65535) t1 = t0 + 65535;                                                // (a launch's grid holds so many trees)
+      if (f[t1] > n0) n1 = f[t1];                                                          // end on a tree boundary when one lies inside
+      const int last = (int)(std::lower_bound(f.begin(), f.end(), n1) - f.begin()) - 1;    // the tree that holds node n1 - 1
+      out.push_back({-1, n0, n1, t0, std::min(last, T - 1) - t0 + 1});
+      n0 = n1;
+    }
+  } else {
+    uint64_t es[arena_ckpt::EX_FIELDS];
+    arena_ckpt::ex_sizes(h, es);
+    const uint64_t step = staging & ~(uint64_t)15;
+    for (int k = 0; k < arena_ckpt::EX_FIELDS; k++)
+      for (uint64_t a = 0; a < l.examples * es[k]; a += step) out.push_back({k, a, std::min(a + step, l.examples * es[k]), 0, 0});
+  }
+  return out;
+}
+
+}  // namespace agz
+
+arena_ckpt::Shape agz_arena::ckpt_shape() const {
+  return {conf_game, conf_mcts, (uint32_t)G, (uint32_t)d.V, (uint32_t)CELLS_PAD, (uint32_t)RING, (uint32_t)d.moves_stride};
+}
+
+// every per-game and per-tree array with its device pointer and element count, handed to xfer(host vector, device pointer, count)
+template <class Sm, class Fn>
+int agz_arena::ckpt_small(Sm& sm, Fn xfer) {
+  const size_t g = (size_t)G, t = (size_t)d.T, P = CELLS_PAD, S = (size_t)d.moves_stride;
+  int r;
+#define AGZ_CK(name, n) if ((r = xfer(sm.name, d.name, (size_t)(n))) != AGZ_OK) return r;
+  AGZ_CK(board, g * P) AGZ_CK(ring, g * RING * P) AGZ_CK(to_move, g) AGZ_CK(ply, g) AGZ_CK(passes, g) AGZ_CK(pass_count, g) AGZ_CK(ended, g)
+  AGZ_CK(winner, g) AGZ_CK(a_is_black, g) AGZ_CK(last_move, g) AGZ_CK(cap_b, g) AGZ_CK(cap_w, g) AGZ_CK(zhash, g) AGZ_CK(moves, g * S)
+  AGZ_CK(amoves, g * S) AGZ_CK(n_amoves, g) AGZ_CK(hist_from, g) AGZ_CK(rng_game, g) AGZ_CK(ex_last, g) AGZ_CK(best_out, g)
+  AGZ_CK(n_nodes, t) AGZ_CK(cur_pool, t) AGZ_CK(has_root, t) AGZ_CK(has_prev, t) AGZ_CK(prev_ply, t) AGZ_CK(stalled, t) AGZ_CK(overflow, t)
+  AGZ_CK(pc_n, t) AGZ_CK(prev_board, t * P) AGZ_CK(rng, t) AGZ_CK(pc_hash, t * S) AGZ_CK(pc_move, t * S)
+#undef AGZ_CK
+  return AGZ_OK;
+}
+
+// everything behind the head: nodes, counters, examples, end marker.  AGZ_E_INVALID: the file system refused a write.
+int agz_arena::ckpt_write(FILE* f, const arena_ckpt::Shape& h, const arena_ckpt::Small& sm, const arena_ckpt::Layout& l) {
+  hipStream_t s = ctx->stream;
+  uint64_t es[arena_ckpt::EX_FIELDS], ex_most = 0;
+  arena_ckpt::ex_sizes(h, es);
+  for (uint64_t e : es) ex_most = std::max(ex_most, l.examples * e);
+  const size_t staging = (size_t)std::max<uint64_t>(std::min<uint64_t>(ckpt_staging, std::max<uint64_t>(l.nodes * 20 + 4, ex_most)), 64);
+  CkptStaging st;
+  int r = st.init(s, staging, l.tree_first);
+  if (r != AGZ_OK) return r;
+  const char* ex_base[arena_ckpt::EX_FIELDS] = {(const char*)d.ex_planes, (const char*)d.ex_policy, (const char*)d.ex_value, (const char*)d.ex_game, (const char*)d.ex_prev, (const char*)d.ex_labelled};
+  for (int section = 0; section < 2; section++) {
+    const std::vector<CkptChunk> ch = ckpt_chunks(h, l, staging, section == 0);
+    auto issue = [&](size_t i) -> int {   // chunk i -> host[i & 1], asynchronously
+      const CkptChunk& c = ch[i];
+      if (c.field < 0) {
+        const size_t cnt = (size_t)(c.b - c.a);
+        hipLaunchKernelGGL(k_ckpt_pack, dim3((unsigned)std::min<size_t>(64, (cnt + 255) / 256), (unsigned)c.nt), dim3(256), 0, s, d, (const long long*)st.first, c.t0, (long long)c.a, (long long)c.b, st.dev);
+        AGZ_HIP_TRY(hipGetLastError());
+        AGZ_HIP_TRY(hipMemcpyAsync(st.host[i & 1], st.dev, 20 * cnt + 4, hipMemcpyDeviceToHost, s));
+      } else {
+        AGZ_HIP_TRY(hipMemcpyAsync(st.host[i & 1], ex_base[c.field] + c.a, (size_t)(c.b - c.a), hipMemcpyDeviceToHost, s));
+      }
+      AGZ_HIP_TRY(hipEventRecord(st.ev[i & 1], s));
+      return AGZ_OK;
+    };
+    if (!ch.empty() && (r = issue(0)) != AGZ_OK) return r;
+    for (size_t i = 0; i < ch.size(); i++) {
+      if (i + 1 < ch.size() && (r = issue(i + 1)) != AGZ_OK) return r;   // the next chunk's copy runs under this chunk's write
+      AGZ_HIP_TRY(hipEventSynchronize(st.ev[i & 1]));
+      const CkptChunk& c = ch[i];
+      bool ok;
+      if (c.field < 0) {
+        const CkptRuns q = ckpt_runs(st.host[i & 1], (size_t)(c.b - c.a));
+        const void* runs[arena_ckpt::NODE_FIELDS] = {q.prior, q.visits, q.bsum, q.kids_off, q.kids_n, q.nmove};
+        ok = arena_ckpt::write_nodes(f, l, c.a, c.b - c.a, runs);
+      } else {
+        ok = arena_ckpt::write_examples(f, l, c.field, c.a, c.b - c.a, st.host[i & 1]);
+      }
+      AGZ_REQUIRE(ok, AGZ_E_INVALID, "agz_arena_save: write failed");
+    }
+    if (section == 0) AGZ_REQUIRE(arena_ckpt::write_counters(f, l, sm), AGZ_E_INVALID, "agz_arena_save: write failed");
+  }
+  AGZ_REQUIRE(arena_ckpt::write_end(f, l), AGZ_E_INVALID, "agz_arena_save: write failed");
+  return AGZ_OK;
+}
+
+// a file scan() has accepted and the capacity checks have passed -> the arena.  A device error from here on leaves the state undefined.
+int agz_arena::ckpt_apply(FILE* f, const arena_ckpt::Scan& sc) {
+  hipStream_t s = ctx->stream;
+  const arena_ckpt::Shape h = ckpt_shape();
+  const arena_ckpt::Layout& l = sc.lay;
+  const arena_ckpt::Small& sm = sc.small;
+  int r = ckpt_small(sm, [&](auto& v, auto* dev, size_t n) -> int {
+    AGZ_REQUIRE(v.size() == n, AGZ_E_INVALID, "agz_arena_load: internal size mismatch");
+    AGZ_HIP_TRY(hipMemcpyAsync(dev, v.data(), n * sizeof(v[0]), hipMemcpyHostToDevice, s));
+    return AGZ_OK;
+  });
+  if (r != AGZ_OK) return r;
+  const int32_t exc = (int32_t)sm.ex_count;
+  AGZ_HIP_TRY(hipMemcpyAsync(d.counters, sm.counters, sizeof(sm.counters), hipMemcpyHostToDevice, s));
+  AGZ_HIP_TRY(hipMemcpyAsync(d.ex_count, &exc, 4, hipMemcpyHostToDevice, s));
+  // virtual-loss flags are not in the file: every round clears what it set, so they are all clear at a move boundary
+  AGZ_HIP_TRY(hipMemsetAsync(d.vl, 0, (size_t)d.T * 2 * (size_t)d.cap, s));
+  AGZ_HIP_TRY(hipStreamSynchronize(s));
+  uint64_t es[arena_ckpt::EX_FIELDS], ex_most = 0;
+  arena_ckpt::ex_sizes(h, es);
+  for (uint64_t e : es) ex_most = std::max(ex_most, l.examples * e);
+  const size_t staging = (size_t)std::max<uint64_t>(std::min<uint64_t>(ckpt_staging, std::max<uint64_t>(l.nodes * 20 + 4, ex_most)), 64);
+  CkptStaging st;
+  if ((r = st.init(s, staging, l.tree_first)) != AGZ_OK) return r;
+  char* ex_base[arena_ckpt::EX_FIELDS] = {(char*)d.ex_planes, (char*)d.ex_policy, (char*)d.ex_value, (char*)d.ex_game, (char*)d.ex_prev, (char*)d.ex_labelled};
+  for (int section = 0; section < 2; section++) {
+    const std::vector<CkptChunk> ch = ckpt_chunks(h, l, staging, section == 0);
+    for (size_t i = 0; i < ch.size(); i++) {   // the file read of chunk i runs under the copy and scatter of chunk i - 1
+      const CkptChunk& c = ch[i];
+      if (i >= 2) AGZ_HIP_TRY(hipEventSynchronize(st.ev[i & 1]));   // host[i & 1] has left for the device
+      if (c.field < 0) {
+        const size_t cnt = (size_t)(c.b - c.a);
+        const CkptRuns q = ckpt_runs(st.host[i & 1], cnt);
+        void* runs[arena_ckpt::NODE_FIELDS] = {q.prior, q.visits, q.bsum, q.kids_off, q.kids_n, q.nmove};
+        AGZ_REQUIRE(arena_ckpt::read_nodes(f, l, c.a, cnt, runs), AGZ_E_INVALID, "agz_arena_load: reading the nodes failed");
+        AGZ_HIP_TRY(hipMemcpyAsync(st.dev, st.host[i & 1], 20 * cnt + 4, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_ckpt_unpack, dim3((unsigned)std::min<size_t>(64, (cnt + 255) / 256), (unsigned)c.nt), dim3(256), 0, s, d, (const long long*)st.first, c.t0, (long long)c.a, (long long)c.b, st.dev);
+        AGZ_HIP_TRY(hipGetLastError());
+      } else {
+        AGZ_REQUIRE(arena_ckpt::read_examples(f, l, c.field, c.a, c.b - c.a, st.host[i & 1]), AGZ_E_INVALID, "agz_arena_load: reading the examples failed");
+        AGZ_HIP_TRY(hipMemcpyAsync(ex_base[c.field] + c.a, st.host[i & 1], (size_t)(c.b - c.a), hipMemcpyHostToDevice, s));
+      }
+      AGZ_HIP_TRY(hipEventRecord(st.ev[i & 1], s));
+    }
+    AGZ_HIP_TRY(hipStreamSynchronize(s));
+  }
+  seed = sc.host.seed; seed0 = sc.host.seed0; prep_expand_seen = sc.host.prep_expand_seen; moves_done = sc.host.moves_done; restart = sc.host.restart != 0;
+  for (int g = 0; g < G; g++) a_is_black[g] = (uint8_t)sm.a_is_black[g];
+  in_move = false; sims_this_move = 0; room_sims = 0;
+  return update_slots();
+}
+
+extern "C" {
+
+int agz_arena_save(agz_arena* a, const char* path) {
+  AGZ_REQUIRE(a && path, AGZ_E_INVALID, "agz_arena_save: NULL argument");
+  AGZ_REQUIRE(!a->in_move, AGZ_E_STATE, "agz_arena_save: a move is in progress (a checkpoint is taken between agz_arena_end_move and the next agz_arena_begin_move)");
+  AGZ_HIP_TRY(hipSetDevice(a->ctx->device));
+  hipStream_t s = a->ctx->stream;   // (the conversion joins an open split step)
+  const arena_ckpt::Shape h = a->ckpt_shape();
+  const arena_ckpt::Host host = {a->seed, a->seed0, a->prep_expand_seen, a->moves_done, a->restart ? 1u : 0u};
+  arena_ckpt::Small sm;
+  int r = a->ckpt_small(sm, [&](auto& v, auto* dev, size_t n) -> int {
+    v.resize(n);
+    AGZ_HIP_TRY(hipMemcpyAsync(v.data(), dev, n * sizeof(v[0]), hipMemcpyDeviceToHost, s));
+    return AGZ_OK;
+  });
+  if (r != AGZ_OK) return r;
+  int32_t exc = 0;
+  static_assert(arena_ckpt::N_COUNTERS == CNT_N && sizeof(unsigned long long) == 8, "the file holds every counter");
+  AGZ_HIP_TRY(hipMemcpyAsync(sm.counters, a->d.counters, sizeof(sm.counters), hipMemcpyDeviceToHost, s));
+  AGZ_HIP_TRY(hipMemcpyAsync(&exc, a->d.ex_count, 4, hipMemcpyDeviceToHost, s));
+  AGZ_HIP_TRY(hipStreamSynchronize(s));
+  sm.ex_count = std::min(exc, a->d.ex_cap);
+  for (int t = 0; t < a->d.T; t++) AGZ_REQUIRE(sm.n_nodes[t] <= a->d.cap, AGZ_E_STATE, "agz_arena_save: tree %d holds %d nodes, its pool %d", t, sm.n_nodes[t], a->d.cap);
+  const std::string why = arena_ckpt::check_small(h, sm);
+  AGZ_REQUIRE(why.empty(), AGZ_E_STATE, "agz_arena_save: the arena is in a state a checkpoint cannot hold (%s)", why.c_str());
+  const arena_ckpt::Layout l = arena_ckpt::layout(h, sm);
+  const std::string tmp = std::string(path) + ".tmp";
+  FILE* f = fopen(tmp.c_str(), "wb");
+  AGZ_REQUIRE(f, AGZ_E_INVALID, "agz_arena_save: cannot open %s", tmp.c_str());
+  r = AGZ_OK;
+  if (!arena_ckpt::write_head(f, h, host, sm, l)) { agz::set_error("agz_arena_save: write to %s failed", tmp.c_str()); r = AGZ_E_INVALID; }
+  if (r == AGZ_OK) r = a->ckpt_write(f, h, sm, l);
+  const bool flushed = fflush(f) == 0 && fsync(fileno(f)) == 0;
+  const bool closed = fclose(f) == 0;
+  if (r == AGZ_OK && !(flushed && closed)) { agz::set_error("agz_arena_save: write to %s failed", tmp.c_str()); r = AGZ_E_INVALID; }
+  if (r == AGZ_OK && rename(tmp.c_str(), path) != 0) { agz::set_error("agz_arena_save: cannot rename %s to %s", tmp.c_str(), path); r = AGZ_E_INVALID; }
+  if (r != AGZ_OK) remove(tmp.c_str());
+  return r;
+}
+
+int agz_arena_load(agz_arena* a, const char* path) {
+  AGZ_REQUIRE(a && path, AGZ_E_INVALID, "agz_arena_load: NULL argument");
+  AGZ_REQUIRE(!a->in_move, AGZ_E_STATE, "agz_arena_load: a move is in progress");
+  AGZ_HIP_TRY(hipSetDevice(a->ctx->device));
+  hipStream_t s = a->ctx->stream;
+  AGZ_HIP_TRY(hipStreamSynchronize(s));
+  FILE* f = fopen(path, "rb");
+  AGZ_REQUIRE(f, AGZ_E_INVALID, "agz_arena_load: cannot open %s", path);
+  arena_ckpt::Scan sc;
+  std::string why;
+  const arena_ckpt::Status st = arena_ckpt::scan(f, a->ckpt_shape(), &sc, &why);
+  int r = AGZ_OK;
+  if (st != arena_ckpt::OK) {
+    agz::set_error("agz_arena_load: %s %s: %s", path, st == arena_ckpt::MISMATCH ? "belongs to another arena configuration" : st == arena_ckpt::NOT_ARENA ? "is not an arena checkpoint of this build" : "is truncated or inconsistent", why.c_str());
+    r = AGZ_E_INVALID;
+  } else if ((long long)sc.lay.examples > a->d.ex_cap) {
+    agz::set_error("agz_arena_load: %s holds %llu example rows, this arena's buffer %d", path, (unsigned long long)sc.lay.examples, a->d.ex_cap);
+    r = AGZ_E_NOMEM;
+  } else if (a->pool_grow) {   // room for the fullest tree and the next search, as before every move (AGZ_POOL_GROW)
+    r = a->pool_room_for((long long)sc.most, a->mc.Budget > 0 ? a->mc.Budget : 0);
+  } else if ((long long)sc.most > a->d.cap) {
+    agz::set_error("agz_arena_load: the fullest tree of %s holds %llu nodes, this arena's pools %d (a larger max_nodes, or AGZ_POOL_GROW)", path, (unsigned long long)sc.most, a->d.cap);
+    r = AGZ_E_NOMEM;
+  }
+  if (r == AGZ_OK) r = a->ckpt_apply(f, sc);
+  fclose(f);
+  return r;
+}
+
+int agz_arena_set_ckpt_staging(agz_arena* a, size_t bytes) {
+  AGZ_REQUIRE(a, AGZ_E_INVALID, "arena is NULL");
+  AGZ_REQUIRE(bytes >= 64 && bytes <= ((size_t)4 << 30), AGZ_E_INVALID, "agz_arena_set_ckpt_staging: %zu bytes (64 bytes .. 4 GiB)", bytes);
+  a->ckpt_staging = bytes;
   return AGZ_OK;
 }
 

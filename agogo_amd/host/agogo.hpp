@@ -176,6 +176,10 @@ struct Arena {
   }
   void SetParallel(int lanes) { agz::check(agz_arena_set_parallel(h, lanes), "SetParallel"); }  // lane-ordered tree-parallel rounds
   void Opponent(const std::vector<int32_t>& moves) { agz::check(agz_arena_apply_moves(h, moves.data()), "opponent move"); }
+  // Checkpoint of the running arena between two moves, and the continuation from one (agz_arena_save / agz_arena_load): games, trees, RNG
+  // states, counters, examples.  The agents, the lanes and the pool policy are not in the file: set them again as they were.
+  void Save(const std::string& path) { agz::check(agz_arena_save(h, path.c_str()), "Arena.Save"); }
+  void Load(const std::string& path) { agz::check(agz_arena_load(h, path.c_str()), "Arena.Load"); }
   // Play every game to the end, leaving the recorded examples on the device (see Examples::Append)
   void PlayOnDevice(bool record) {
     agz::check(agz_arena_reset(h, nullptr), "Arena.Play");

@@ -361,6 +361,24 @@ func (a *BatchedArena) SetParallel(lanes int) error {
 	return lastErr(C.agz_arena_set_parallel(a.h, C.int(lanes)))
 }
 
+// Save writes a checkpoint of the running arena — games, both trees of every game, RNG states, counters, recorded examples — between two
+// moves (agz_arena_save).  The file replaces `path` only once it is complete.
+func (a *BatchedArena) Save(path string) error {
+	defer a.ctx.enter()()
+	p := C.CString(path)
+	defer C.free(unsafe.Pointer(p))
+	return lastErr(C.agz_arena_save(a.h, p))
+}
+
+// Load continues from a checkpoint of an arena of the same game, search configuration and number of games (agz_arena_load).  The agents
+// (SetAgents), the lanes and the pool policy are not in the file: set them as they were for a bit-identical continuation.
+func (a *BatchedArena) Load(path string) error {
+	defer a.ctx.enter()()
+	p := C.CString(path)
+	defer C.free(unsafe.Pointer(p))
+	return lastErr(C.agz_arena_load(a.h, p))
+}
+
 // Opponent applies the outside player's moves (one per game; ignored for finished games).
 func (a *BatchedArena) Opponent(moves []game.Single) error {
 	defer a.ctx.enter()()

@@ -526,6 +526,32 @@ typedef struct agz_state {
 /* overwrite game g of an arena with a host-side state (trees are kept: the next search re-roots or starts fresh) */
 int agz_arena_set_state(agz_arena* arena, int g, const agz_state* st);
 
+/* Checkpoint of a running arena: every game, both search trees of every game, every RNG state, the counters and the recorded examples, so
+ * that self-play interrupted after a move continues EXACTLY as the uninterrupted arena would — bit for bit, trees and examples included
+ * (the format is specified in agogo_amd/csrc/arena_ckpt.hpp, the one place that reads, writes and validates it).
+ * save: only between moves; inside agz_arena_begin_move .. agz_arena_end_move it returns AGZ_E_STATE.  It enqueues on, and waits for, the
+ * context's main queue, so an open split step is joined first.  It writes `path` + ".tmp" and renames that over `path` once every byte is
+ * written and flushed: a crash during a save never destroys the previous checkpoint; on failure the temporary file is removed.  The arena
+ * is never changed by a save.  Only the live prefix of every tree is written (20 bytes a node) plus 27.5 KB an example row at 19x19.
+ * load: into an arena created with the same agz_game_conf, agz_mcts_conf and n_games; the file stores them and they are compared field by
+ * field, a mismatch is AGZ_E_INVALID and agz_last_error() names the field (max_moves = 0 and its resolved value 2 * m * n are the same).  The
+ * create-time seed need NOT match: every RNG state comes from the file.  The WHOLE file is validated before anything in the arena
+ * changes — lengths, constants, configuration, and every index a kernel would follow (node counts, child blocks, moves, example links) — so a
+ * truncated, overlong or inconsistent file is AGZ_E_INVALID with the arena exactly as it was, and never reaches a kernel.  After a device
+ * error while the accepted file is applied (AGZ_E_HIP) the state is undefined.
+ * NOT in the file, because they are the caller's configuration as lr is for a trainer: the inferencers (kind, net, callback), the lane
+ * count (agz_arena_set_parallel), the pool policy, the split mode, timers and debug hooks.  The caller re-attaches them on the new arena
+ * before or after the load; a bit-identical continuation needs the same ones (the same network parameters, the same lanes).
+ * Capacity: node indices do not depend on the pool capacity, so a file loads into an arena of any max_nodes that holds its fullest tree.
+ * An AGZ_POOL_GROW arena re-allocates its pools for the fullest tree plus the next search, as it does before every move
+ * (agz_arena_pool_capacity, agz_debug.h, shows the growth); an AGZ_POOL_STRICT or AGZ_POOL_STOP_SEARCH arena whose pools are smaller than
+ * the fullest tree fails with AGZ_E_NOMEM and stays unchanged, and so does any arena whose example buffer is smaller than the file's rows.
+ * I/O failures (a path that cannot be opened, a failed write or rename) are AGZ_E_INVALID, as for agz_trainer_save / agz_trainer_load.
+ * Not covered: the single-tree agz_mcts handle, the agz_examples store, a save inside a move.
+ * Tests: tests/test_arena_ckpt_cpu.py (the format and every refusal, without a GPU), tests/test_arena_ckpt_gpu.py (continuations). */
+int agz_arena_save(agz_arena* arena, const char* path);
+int agz_arena_load(agz_arena* arena, const char* path);
+
 /* --- observers (all copy into caller buffers) --- */
 typedef struct agz_arena_stats {
   int64_t sims_total;    /* pipeline invocations (iter, search.go:181) */

@@ -110,6 +110,11 @@ int agz_arena_debug_counter(agz_arena* arena, int which, int64_t* value);
 /* Measurement: the node-pool capacity of an arena's trees and how often AGZ_POOL_GROW has re-allocated them */
 int agz_arena_pool_capacity(agz_arena* arena, int* nodes_per_pool, int* grows);
 
+/* Tests: the size of the device staging buffer and of each of the two page-locked host buffers agz_arena_save / agz_arena_load stream the
+ * nodes and example rows through (default 256 MB; 64 bytes .. 4 GiB).  A few hundred bytes force many chunks, and trees cut across chunks,
+ * at tiny shapes.  The file does not depend on it. */
+int agz_arena_set_ckpt_staging(agz_arena* arena, size_t bytes);
+
 /* Failure injection (tests): the data-parallel step of this communicator fails on THIS rank right before it would enter the collective of
  * slice k (0 = the heads, 1 .. = layer L .. 0; k < 0: off).  One shot: cleared by the step it hits.  What the test checks is the rule of
  * agz_trainer_forward_backward_allreduce: the failing rank still enters every collective, every rank's call fails (AGZ_E_PEER on the
