@@ -22,6 +22,7 @@ PROF_CONV, PROF_HEADS, PROF_SELECT, PROF_EXPAND, PROF_MOVE, PROF_CONV_INIT = 0, 
 PROF_WINO_IN, PROF_WINO_GEMM, PROF_WINO_OUT = 6, 7, 8
 DONT_PREFER_PASS, PREFER_PASS, DONT_RESIGN = 0, 1, 2
 POOL_STRICT, POOL_STOP_SEARCH, POOL_GROW = 0, 1, 2
+SYM_OFF, SYM_RANDOM, SYM_FIXED = 0, 1, 8   # set_leaf_symmetry: SYM_FIXED + k applies S_k at every leaf
 
 
 class AgzError(RuntimeError):
@@ -214,6 +215,13 @@ def lib():
     sig("agz_arena_play", i32, vp, i32, i32)
     sig("agz_arena_selfplay", i32, vp, C.c_int64, i32)
     sig("agz_arena_set_parallel", i32, vp, i32)
+    sig("agz_arena_set_leaf_symmetry", i32, vp, i32, u64)
+    sig("agz_mcts_set_leaf_symmetry", i32, vp, i32, u64)
+    sig("agz_symmetry_map", i32, i32, i32, pi)
+    sig("agz_symmetry_inverse", i32, i32)
+    sig("agz_leaf_symmetry_of", i32, u64, pi, i32, i32, C.POINTER(C.c_int))
+    sig("agz_examples_augment_dihedral", i32, vp)
+    sig("agz_symmetry_boards", i32, vp, pf, i32, i32, i32, pf)
     sig("agz_arena_begin_move", i32, vp)
     sig("agz_arena_simulate", i32, vp, i32)
     sig("agz_arena_end_move", i32, vp, i32)
@@ -802,6 +810,10 @@ class Arena:
     def set_parallel(self, lanes):
         _check(lib().agz_arena_set_parallel(self.h, int(lanes)), "agz_arena_set_parallel")
 
+    def set_leaf_symmetry(self, mode, seed=0):
+        """SYM_OFF / SYM_RANDOM / SYM_FIXED + k: leaves of AGZ_INF_NET agents are evaluated under a board symmetry"""
+        _check(lib().agz_arena_set_leaf_symmetry(self.h, int(mode), int(seed) & (2 ** 64 - 1)), "agz_arena_set_leaf_symmetry")
+
     def begin_move(self):
         _check(lib().agz_arena_begin_move(self.h), "agz_arena_begin_move")
 
@@ -994,6 +1006,9 @@ class Mcts:
 
     def set_parallel(self, lanes):
         _check(lib().agz_mcts_set_parallel(self.h, int(lanes)), "agz_mcts_set_parallel")
+
+    def set_leaf_symmetry(self, mode, seed=0):
+        _check(lib().agz_mcts_set_leaf_symmetry(self.h, int(mode), int(seed) & (2 ** 64 - 1)), "agz_mcts_set_leaf_symmetry")
 
     def set_game(self, **kw):
         st, keep = make_state(self.m * self.n, **kw)
@@ -1207,6 +1222,10 @@ class Examples:
     def augment_rotate(self):
         _check(lib().agz_examples_augment_rotate(self.h), "agz_examples_augment_rotate")
 
+    def augment_dihedral(self):
+        """every example e -> [S_0 e .. S_7 e] (the eight board symmetries, symmetry_map)"""
+        _check(lib().agz_examples_augment_dihedral(self.h), "agz_examples_augment_dihedral")
+
     def prepare(self, BatchSize, maxExamples=0, seed=1337):
         b = C.c_int32(0)
         _check(lib().agz_examples_prepare(self.h, BatchSize, maxExamples, seed, C.byref(b)), "agz_examples_prepare")
@@ -1258,3 +1277,34 @@ def rotate_boards(ctx, boards, m, n):
     out = np.zeros_like(b)
     _check(lib().agz_rotate_boards(ctx.h, _pf(b), count, m, n, _pf(out)), "agz_rotate_boards")
     return out
+
+
+def symmetry_boards(ctx, boards, m, k):
+    """S_k (symmetry_map) on a stack of m x m boards, on the device"""
+    b = np.ascontiguousarray(boards, np.float32)
+    count = b.size // (m * m)
+    out = np.zeros_like(b)
+    _check(lib().agz_symmetry_boards(ctx.h, _pf(b), count, m, int(k), _pf(out)), "agz_symmetry_boards")
+    return out
+
+
+def symmetry_map(m, k):
+    """src_k: (S_k x).flat[c] == x.flat[src[c]] for an m x m board x (host only)"""
+    src = np.zeros(m * m, np.int32)
+    _check(lib().agz_symmetry_map(int(m), int(k), _pi(src)), "agz_symmetry_map")
+    return src
+
+
+def symmetry_inverse(k):
+    """inv(k): S_inv(k) o S_k = id (host only)"""
+    r = lib().agz_symmetry_inverse(int(k))
+    _check(min(r, 0), "agz_symmetry_inverse")
+    return r
+
+
+def leaf_symmetry_of(seed, board, to_move):
+    """SYM_RANDOM's k for a position: board = cells of NONE / BLACK / WHITE, row-major (host only)"""
+    b = np.ascontiguousarray(board, np.int32).reshape(-1)
+    k = C.c_int(0)
+    _check(lib().agz_leaf_symmetry_of(int(seed) & (2 ** 64 - 1), _pi(b), b.size, int(to_move), C.byref(k)), "agz_leaf_symmetry_of")
+    return k.value

@@ -231,14 +231,26 @@ __device__ void legal_mask(const GameCfg& c, const Sh& s, int player, uint8_t* o
   if (lane == 0) out[c.A] = c.pass_legal ? 1 : 0;
 }
 
+// The leaf symmetry (sym.hpp, agz_arena_set_leaf_symmetry) of the position in s.board: one pass over the board and a wave reduction,
+// the same value in every lane.  Only called while d.sym_mode != 0.
+__device__ __forceinline__ int leaf_symmetry(const GameCfg& c, const Dev& d, const Sh& s, int to_move, int lane) {
+  if (d.sym_mode >= AGZ_SYM_FIXED) return d.sym_mode - AGZ_SYM_FIXED;
+  uint32_t h = 0;
+  for (int i = lane; i < c.cells; i += WAVE) h += sym::cell_term(i, s.board[i]);
+  for (int o = 32; o > 0; o >>= 1) h += __shfl_xor(h, o, 64);
+  return sym::of_key(h + sym::mover_term(to_move), d.sym_seed);
+}
+
 // Encoders.  Output is the network's input tile for this leaf: padded NHWC [Hp][Wp][32].
-__device__ void encode_nhwc(const GameCfg& c, const Sh& s, const St& st, float* out, int lane) {
+// sk: the leaf symmetry (wave-uniform; 0 = identity).  Cell i of the tile holds the encoding of board cell src_sk(i), in every plane.
+__device__ void encode_nhwc(const GameCfg& c, const Sh& s, const St& st, float* out, int lane, int sk) {
   const int Wp = c.n + 2;
   for (int i = lane; i < c.cells; i += WAVE) {
     int h = i / c.n, w = i - h * c.n;
     float* o = out + ((size_t)(h + 1) * Wp + (w + 1)) * 32;
+    const int sc = sk ? sym::src_ij(c.n, sk, h, w) : i;
     if (c.encoder == AGZ_ENC_TWOPLANE) {  // cmd/tictactoe/main.go:26-47
-      int v = s.board[i];
+      int v = s.board[sc];
       o[0] = v == AGZ_BLACK ? 1.f : (v == AGZ_WHITE ? -1.f : 0.001f);
       o[1] = st.to_move == AGZ_BLACK ? 1.f : (st.to_move == AGZ_WHITE ? -1.f : 0.f);
     } else {  // WQEncoder, encoding_helper.go:29-68
@@ -249,7 +261,7 @@ __device__ void encode_nhwc(const GameCfg& c, const Sh& s, const St& st, float* 
       for (int k = 1; k < 8; k++) {
         int j = mn - k;  // board after move j (Historical(h), h = mn-1-k, needs h > 0)
         float e = 0.f;
-        if (j >= 2) { int v = s.ring[j % RING][i]; e = v == AGZ_BLACK ? 1.f : (v == AGZ_WHITE ? -1.f : 0.f); }
+        if (j >= 2) { int v = s.ring[j % RING][sc]; e = v == AGZ_BLACK ? 1.f : (v == AGZ_WHITE ? -1.f : 0.f); }
         vb[k - 1] = e;
         vw[k - 1] = j >= 2 ? -e : 0.f;  // vecf32.Scale(retVal, -1): empty cells become -0.0
       }
@@ -509,8 +521,14 @@ __global__ __launch_bounds__(64) void k_select(Dev d, GameCfg c, MctsCfg mc, flo
       legal_mask(c, s, st.to_move, d.leaf_legal + q * CELLS_PAD, lane);
       for (int i = lane; i < c.cells; i += WAVE) d.leaf_board[q * CELLS_PAD + i] = s.board[i];
       float* act = agent == 0 ? act_in0 : act_in1;
+      // leaf symmetry: a network agent's input goes through S_sk, k_expand maps the policy row back (callback agents: sk = 0)
+      int sk = 0;
+      if (d.sym_mode) {
+        if (act) sk = leaf_symmetry(c, d, s, st.to_move, lane);
+        if (lane == 0) d.leaf_sym[q] = (uint8_t)sk;
+      }
       // NN slots are lane-major ([lane][game slot]) so that a round of nl lanes is one dense batch of nl*G rows
-      if (act) encode_nhwc(c, s, st, act + ((size_t)l * d.G + d.slot_of_game[g]) * (c.m + 2) * (c.n + 2) * 32, lane);
+      if (act) encode_nhwc(c, s, st, act + ((size_t)l * d.G + d.slot_of_game[g]) * (c.m + 2) * (c.n + 2) * 32, lane, sk);
       if (d.cb_planes && ((d.cb_mask >> agent) & 1)) encode_nchw(c, s, st, d.cb_planes + q * (size_t)c.F * c.cells, lane);   // AGZ_INF_CALLBACK
     }
     if (lane == 0) {
@@ -619,7 +637,12 @@ __global__ __launch_bounds__(64) void k_leaf(Dev d, GameCfg c, MctsCfg mc, float
   legal_mask(c, s, st.to_move, d.leaf_legal + q * CELLS_PAD, lane);
   for (int i = lane; i < c.cells; i += WAVE) d.leaf_board[q * CELLS_PAD + i] = s.board[i];
   float* act = agent == 0 ? act_in0 : act_in1;
-  if (act) encode_nhwc(c, s, st, act + ((size_t)l * d.G + d.slot_of_game[g]) * (c.m + 2) * (c.n + 2) * 32, lane);
+  int sk = 0;   // leaf symmetry, as k_select
+  if (d.sym_mode) {
+    if (act) sk = leaf_symmetry(c, d, s, st.to_move, lane);
+    if (lane == 0) d.leaf_sym[q] = (uint8_t)sk;
+  }
+  if (act) encode_nhwc(c, s, st, act + ((size_t)l * d.G + d.slot_of_game[g]) * (c.m + 2) * (c.n + 2) * 32, lane, sk);
   if (d.cb_planes && ((d.cb_mask >> agent) & 1)) encode_nchw(c, s, st, d.cb_planes + q * (size_t)c.F * c.cells, lane);
 }
 
@@ -672,6 +695,7 @@ __global__ __launch_bounds__(64) void k_expand_prep(Dev d, GameCfg c, MctsCfg mc
     }
   };
   if (player == AGZ_WHITE) value = __fsub_rn(1.f, value);
+  const int sk = d.sym_mode ? d.leaf_sym[q] : 0;   // the network saw S_sk of the position: cell i's prior is row entry dst_sk(i)
   int n = 0;
   for (int b0 = 0; b0 < c.A; b0 += WAVE) {
     const int i = b0 + lane;
@@ -679,7 +703,7 @@ __global__ __launch_bounds__(64) void k_expand_prep(Dev d, GameCfg c, MctsCfg mc
     const unsigned long long m = __ballot(ok);
     if (ok) {
       const int pos = n + __popcll(m & ((1ull << lane) - 1ull));
-      s.fscore[pos] = policy_at(i);
+      s.fscore[pos] = policy_at(sk ? sym::dst(c.n, sk, i) : i);
       s.fmove[pos] = i;
     }
     n += __popcll(m);
@@ -869,6 +893,7 @@ __global__ __launch_bounds__(64) void k_expand(Dev d, GameCfg c, MctsCfg mc, Inf
         }
       };
       if (player == AGZ_WHITE) value = __fsub_rn(1.f, value);  // search.go:278-280
+      const int sk = d.sym_mode ? d.leaf_sym[q] : 0;   // the network saw S_sk of the position: cell i's prior is row entry dst_sk(i)
       // nodelist in move order, Pass last (search.go:285-296)
       int n = 0;
       {
@@ -881,7 +906,7 @@ __global__ __launch_bounds__(64) void k_expand(Dev d, GameCfg c, MctsCfg mc, Inf
           const int i = lane + k * WAVE;
           const bool in = i < c.A;
           lg[k] = in ? legal[i] : 0;
-          pr[k] = (ik == AGZ_INF_NET && in) ? pol[i] : 0.f;
+          pr[k] = (ik == AGZ_INF_NET && in) ? pol[sk ? sym::dst(c.n, sk, i) : i] : 0.f;
         }
 #pragma unroll
         for (int k = 0; k < PER; k++) {
@@ -1827,7 +1852,7 @@ int agz_arena_create(agz_ctx* ctx, const agz_game_conf* game, const agz_mcts_con
   d.V = 1;
   AL(vl, pool)
   AL(slot_of_game, G) AL(prep_slot, G) AL(leaf_kind, G) AL(leaf_player, G) AL(leaf_ply, G) AL(leaf_result, G) AL(leaf_board, (size_t)G * CELLS_PAD)
-  AL(leaf_legal, (size_t)G * CELLS_PAD) AL(path, (size_t)G * MAXPATH) AL(path_len, G) AL(counters, CNT_N)
+  AL(leaf_legal, (size_t)G * CELLS_PAD) AL(path, (size_t)G * MAXPATH) AL(path_len, G) AL(leaf_sym, G) AL(counters, CNT_N)
   {
     size_t per_ex = (size_t)c.F * c.cells + (c.A + 1) + 3;
     size_t want = std::max<size_t>((size_t)G * c.max_moves * 2, 16384);  // room for restarted games (agz_arena_selfplay)
@@ -1942,7 +1967,7 @@ int agz_arena_set_parallel(agz_arena* a, int lanes) {
   // the previous (smaller) scratch arrays stay on the arena's allocation list and are released with it
 #define RL(p, cnt) if ((r = a->alloc(&d.p, (size_t)(cnt))) != AGZ_OK) return r;
   RL(leaf_kind, n) RL(leaf_player, n) RL(leaf_ply, n) RL(leaf_result, n) RL(leaf_board, n * CELLS_PAD) RL(leaf_legal, n * CELLS_PAD)
-  RL(path, n * MAXPATH) RL(path_len, n)
+  RL(path, n * MAXPATH) RL(path_len, n) RL(leaf_sym, n)
   RL(exp_score, n * CELLS_PAD) RL(exp_move, n * CELLS_PAD) RL(exp_n, n) RL(exp_value, n)
 #undef RL
   d.V = lanes;
@@ -1950,6 +1975,37 @@ int agz_arena_set_parallel(agz_arena* a, int lanes) {
   for (int agent = 0; agent < 2; agent++)   // network batch and output buffers grow to G*lanes rows
     if (a->inf_kind[agent] == AGZ_INF_NET) { r = agz_arena_set_inferencer(a, agent, AGZ_INF_NET, a->net[agent]); if (r != AGZ_OK) return r; }
   if (a->d.cb_mask) { r = a->cb_setup(); if (r != AGZ_OK) return r; }   // host-callback agents: staging for G * lanes leaves
+  return AGZ_OK;
+}
+
+// Leaf symmetry (BUILD EXTENSION): the setting lives in the Dev block every kernel receives; nothing is allocated,
+// nothing in a tree changes.  It is not part of an arena checkpoint: the caller re-applies it after agz_arena_load.
+int agz_arena_set_leaf_symmetry(agz_arena* a, int mode, uint64_t seed) {
+  AGZ_REQUIRE(a, AGZ_E_INVALID, "arena is NULL");
+  AGZ_REQUIRE(mode == AGZ_SYM_OFF || mode == AGZ_SYM_RANDOM || (mode >= AGZ_SYM_FIXED && mode < AGZ_SYM_FIXED + 8), AGZ_E_INVALID,
+              "agz_arena_set_leaf_symmetry: mode %d (AGZ_SYM_OFF, AGZ_SYM_RANDOM or AGZ_SYM_FIXED + k, k in [0,8))", mode);
+  AGZ_REQUIRE(a->gc.kind != AGZ_GAME_C4 && a->gc.m == a->gc.n, AGZ_E_UNSUPPORTED,
+              "agz_arena_set_leaf_symmetry: the eight maps are those of a square board whose actions are its cells (%s, %dx%d)",
+              a->gc.kind == AGZ_GAME_C4 ? "c4: actions are columns" : "not square", a->gc.m, a->gc.n);
+  AGZ_REQUIRE(!a->in_move, AGZ_E_STATE, "agz_arena_set_leaf_symmetry: a search is in progress");
+  a->d.sym_mode = mode;
+  a->d.sym_seed = sym::fold_seed(seed);
+  return AGZ_OK;
+}
+
+// Host-only helpers over sym.hpp: what a host inferencer needs to do the same on its side.  No context, no device.
+int agz_symmetry_map(int m, int k, int32_t* src) {
+  AGZ_REQUIRE(src && m >= 1 && m <= 19 && k >= 0 && k < 8, AGZ_E_INVALID, "agz_symmetry_map: m %d (1..19), k %d (0..7)", m, k);
+  for (int c = 0; c < m * m; c++) src[c] = sym::src(m, k, c);
+  return AGZ_OK;
+}
+int agz_symmetry_inverse(int k) {
+  AGZ_REQUIRE(k >= 0 && k < 8, AGZ_E_INVALID, "agz_symmetry_inverse: k %d (0..7)", k);
+  return sym::inv(k);
+}
+int agz_leaf_symmetry_of(uint64_t seed, const int32_t* board, int cells, int to_move, int* k) {
+  AGZ_REQUIRE(board && k && cells >= 1 && cells <= 361, AGZ_E_INVALID, "agz_leaf_symmetry_of: bad argument (cells %d)", cells);
+  *k = sym::of_key(sym::position_key(board, cells, to_move), sym::fold_seed(seed));
   return AGZ_OK;
 }
 
@@ -2805,6 +2861,11 @@ int agz_mcts_set_pool_policy(agz_mcts* m, int policy) {
 int agz_mcts_set_parallel(agz_mcts* m, int lanes) {
   AGZ_REQUIRE(m, AGZ_E_INVALID, "mcts is NULL");
   return agz_arena_set_parallel(m->arena, lanes);
+}
+
+int agz_mcts_set_leaf_symmetry(agz_mcts* m, int mode, uint64_t seed) {
+  AGZ_REQUIRE(m, AGZ_E_INVALID, "mcts is NULL");
+  return agz_arena_set_leaf_symmetry(m->arena, mode, seed);
 }
 
 int agz_mcts_set_game(agz_mcts* m, const agz_state* st) {

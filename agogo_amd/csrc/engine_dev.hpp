@@ -15,6 +15,7 @@
 #include <cstdint>
 
 #include "../../include/agz.h"
+#include "sym.hpp"
 
 namespace agz {
 
@@ -105,6 +106,8 @@ struct Dev {
   uint8_t* leaf_legal;    // [G*V][CELLS_PAD]  (index A = pass)
   int32_t* path;          // [G*V][MAXPATH]
   int32_t* path_len;      // [G*V]
+  uint8_t* leaf_sym;      // [G*V] the symmetry k this leaf's network input was written through (k_select / k_leaf), read back by
+                          //        k_expand / k_expand_prep; 0 for a leaf of an agent without a network.  Only touched while sym_mode != 0
   // lane rounds (V > 1): the expansion list of every lane, prepared in parallel (k_expand_prep) and committed in lane order
   float* exp_score;       // [G*V][CELLS_PAD] renormalised priors in child order (sorted)
   int16_t* exp_move;      // [G*V][CELLS_PAD]
@@ -127,6 +130,9 @@ struct Dev {
   // ---- AGZ_INF_CALLBACK: the leaf states a host inferencer is handed between k_select and k_expand
   float* cb_planes;       // [G*V][F*cells] the encoder's NCHW tensor of leaf q (what Agent.Infer encodes, agent.go:60-74); nullptr: no callback agent
   int cb_mask;            // bit a set: agent a holds a callback inferencer
+  // ---- leaf symmetry (agz_arena_set_leaf_symmetry, sym.hpp): AGZ_SYM_OFF, AGZ_SYM_RANDOM or AGZ_SYM_FIXED + k
+  int sym_mode;
+  uint32_t sym_seed;      // sym::fold_seed(seed)
 };
 
 enum { CNT_SIMS = 0, CNT_NONNULL = 1, CNT_EVALS = 2, CNT_MOVES = 3, CNT_GAMES = 4, CNT_EXAMPLES = 5, CNT_FULL = 6, CNT_A_WINS = 7, CNT_B_WINS = 8,
@@ -142,11 +148,6 @@ struct InfDesc {
 };
 
 __device__ __forceinline__ int opp(int p) { return p == AGZ_BLACK ? AGZ_WHITE : AGZ_BLACK; }
-
-__device__ __forceinline__ uint32_t mix32(uint32_t x) {
-  x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16;
-  return x;
-}
 
 // ---------------------------------------------------------------------------------------------------
 // Shared-memory working set of one game

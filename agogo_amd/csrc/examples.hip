@@ -9,6 +9,7 @@
 #include <numeric>
 
 #include "comm.hpp"
+#include "sym.hpp"
 
 namespace agz {
 
@@ -24,18 +25,13 @@ __global__ void k_gather_rows(const float* __restrict__ src, const int32_t* __re
 }
 
 // RotateBoard composed q times as an index map: one application is new[i][j] = old[j][m-1-i]
-// (encoding_helper.go:92-103: it[i][j] <- it[j][mi1] <- it[mi1][mj1] <- it[mj1][i] <- it[i][j]).
-__device__ __forceinline__ int rot_src(int i, int j, int m, int q) {
-  switch (q & 3) {
-    case 0: return i * m + j;
-    case 1: return j * m + (m - 1 - i);
-    case 2: return (m - 1 - i) * m + (m - 1 - j);
-    default: return (m - 1 - j) * m + i;
-  }
-}
+// (encoding_helper.go:92-103: it[i][j] <- it[j][mi1] <- it[mi1][mj1] <- it[mj1][i] <- it[i][j]) — sym::src_ij with k = q < 4;
+// k = 4..7 are the same rotations of the transposed board (sym.hpp), the other half of the dihedral augmenter.
+__device__ __forceinline__ int rot_src(int i, int j, int m, int q) { return sym::src_ij(m, q & 7, i, j); }
 
-// out row reps*e+q = rot^(q0+q)(in row e): `planes` rows are nplanes boards of m*m followed by `tail` untouched floats
-// (Board: nplanes = F, tail = 0; Policy: nplanes = 1, tail = pass entry; Value: nplanes = 0, tail = 1).
+// out row reps*e+q = S_(q0+q)(in row e): `planes` rows are nplanes boards of m*m followed by `tail` untouched floats
+// (Board: nplanes = F, tail = 0; Policy: nplanes = 1, tail = pass entry; Value: nplanes = 0, tail = 1).  reps = 4: the rotation
+// augmenter, reps = 8: the dihedral one, in the same single pass.
 __global__ void k_augment_rot(const float* __restrict__ in, float* __restrict__ out, int nplanes, int m, int tail, int reps,
                               int q0, size_t total_out) {
   const int mm = m * m, row = nplanes * mm + tail;
@@ -307,30 +303,34 @@ int agz_examples_get(agz_examples* e, float* planes, float* policy, float* value
 // The rotation Augmenter over the whole set: every example e becomes [e, rot e, rot^2 e, rot^3 e] in place of e
 // (same multiset and order as applying it per example at record time, arena.go:115-120).  RotateBoard's error for
 // non-square boards (encoding_helper.go:81-83) is AGZ_E_INVALID.
-int agz_examples_augment_rotate(agz_examples* e) {
+// reps = 4: e -> [S_0 e .. S_3 e]; reps = 8: e -> [S_0 e .. S_7 e].  One launch per array, whatever reps is.
+static int augment(agz_examples* e, int reps, const char* who) {
   AGZ_REQUIRE(e, AGZ_E_INVALID, "NULL argument");
   AGZ_REQUIRE(e->H == e->W, AGZ_E_INVALID, "Cannot handle m %d, n %d. This function only takes square boards", e->H, e->W);
-  AGZ_REQUIRE(e->A1 >= e->H * e->W, AGZ_E_INVALID, "agz_examples_augment_rotate: policy shorter than the board");
+  AGZ_REQUIRE(e->A1 >= e->H * e->W, AGZ_E_INVALID, "%s: policy shorter than the board", who);
   if (e->n == 0) return AGZ_OK;
   AGZ_HIP_TRY(hipSetDevice(e->ctx->device));
-  const size_t n4 = e->n * 4;
+  const size_t n4 = e->n * (size_t)reps;
   float *p = nullptr, *q = nullptr, *v = nullptr;
   if (hipMalloc(&p, n4 * e->xs * 4) != hipSuccess || hipMalloc(&q, n4 * e->A1 * 4) != hipSuccess || hipMalloc(&v, n4 * 4) != hipSuccess) {
     hipFree(p); hipFree(q); hipFree(v);
-    agz::set_error("agz_examples_augment_rotate: out of device memory for %zu examples", n4);
+    agz::set_error("%s: out of device memory for %zu examples", who, n4);
     return AGZ_E_HIP;
   }
   hipStream_t s = e->ctx->stream;
   const int m = e->H;
-  hipLaunchKernelGGL(k_augment_rot, dim3(grid_for(n4 * e->xs)), dim3(256), 0, s, e->planes, p, e->F, m, 0, 4, 0, n4 * e->xs);
-  hipLaunchKernelGGL(k_augment_rot, dim3(grid_for(n4 * e->A1)), dim3(256), 0, s, e->policy, q, 1, m, e->A1 - m * m, 4, 0, n4 * (size_t)e->A1);
-  hipLaunchKernelGGL(k_augment_rot, dim3(grid_for(n4)), dim3(256), 0, s, e->value, v, 0, m, 1, 4, 0, n4);
+  hipLaunchKernelGGL(k_augment_rot, dim3(grid_for(n4 * e->xs)), dim3(256), 0, s, e->planes, p, e->F, m, 0, reps, 0, n4 * e->xs);
+  hipLaunchKernelGGL(k_augment_rot, dim3(grid_for(n4 * e->A1)), dim3(256), 0, s, e->policy, q, 1, m, e->A1 - m * m, reps, 0, n4 * (size_t)e->A1);
+  hipLaunchKernelGGL(k_augment_rot, dim3(grid_for(n4)), dim3(256), 0, s, e->value, v, 0, m, 1, reps, 0, n4);
   AGZ_HIP_TRY(hipGetLastError());
   AGZ_HIP_TRY(hipStreamSynchronize(s));
   hipFree(e->planes); hipFree(e->policy); hipFree(e->value);
   e->planes = p; e->policy = q; e->value = v; e->n = n4; e->cap = n4;
   return AGZ_OK;
 }
+int agz_examples_augment_rotate(agz_examples* e) { return augment(e, 4, "agz_examples_augment_rotate"); }
+// the dihedral Augmenter (BUILD EXTENSION): the four rotations and the four rotations of the transposed board
+int agz_examples_augment_dihedral(agz_examples* e) { return augment(e, 8, "agz_examples_augment_dihedral"); }
 
 // agogo.go:118-121 (maxExamples cut) + prepareExamples (agogo.go:211-249): shuffle, batches = n / BatchSize, keep
 // batches*BatchSize rows as Xs [rows,F,H,W], Policies [rows,PolicyLen], Values [rows] — device tensors.
@@ -391,25 +391,38 @@ int agz_examples_get_tensors(agz_examples* e, float* Xs, float* Policies, float*
   return AGZ_OK;
 }
 
-// RotateBoard (encoding_helper.go:80-107) for `count` boards of m x n floats, host buffers in and out.
-int agz_rotate_boards(agz_ctx* ctx, const float* boards, int count, int m, int n, float* out) {
-  AGZ_REQUIRE(ctx && boards && out && count >= 0 && m >= 1, AGZ_E_INVALID, "agz_rotate_boards: bad argument");
-  AGZ_REQUIRE(m == n, AGZ_E_INVALID, "Cannot handle m %d, n %d. This function only takes square boards", m, n);
+// S_k on `count` boards of m x m floats, host buffers in and out
+static int map_boards(agz_ctx* ctx, const float* boards, int count, int m, int k, float* out) {
   if (count == 0) return AGZ_OK;
   AGZ_HIP_TRY(hipSetDevice(ctx->device));
   size_t tot = (size_t)count * m * m;
   float *a = nullptr, *b = nullptr;
   AGZ_HIP_TRY(hipMalloc(&a, tot * 4));
-  AGZ_HIP_TRY(hipMalloc(&b, tot * 4));
-  AGZ_HIP_TRY(hipMemcpyAsync(a, boards, tot * 4, hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(k_augment_rot, dim3(grid_for(tot)), dim3(256), 0, ctx->stream, a, b, 1, m, 0, 1, 1, tot);
-  hipError_t le = hipGetLastError();
-  hipError_t ce = le == hipSuccess ? hipMemcpyAsync(out, b, tot * 4, hipMemcpyDeviceToHost, ctx->stream) : le;
+  if (hipMalloc(&b, tot * 4) != hipSuccess) { hipFree(a); agz::set_error("out of device memory for %d boards", count); return AGZ_E_HIP; }
+  hipError_t ce = hipMemcpyAsync(a, boards, tot * 4, hipMemcpyHostToDevice, ctx->stream);
+  if (ce == hipSuccess) {
+    hipLaunchKernelGGL(k_augment_rot, dim3(grid_for(tot)), dim3(256), 0, ctx->stream, a, b, 1, m, 0, 1, k, tot);
+    ce = hipGetLastError();
+  }
+  if (ce == hipSuccess) ce = hipMemcpyAsync(out, b, tot * 4, hipMemcpyDeviceToHost, ctx->stream);
   hipError_t se = hipStreamSynchronize(ctx->stream);
   hipFree(a); hipFree(b);
   AGZ_HIP_TRY(ce);
   AGZ_HIP_TRY(se);
   return AGZ_OK;
+}
+
+// RotateBoard (encoding_helper.go:80-107) for `count` boards of m x n floats, host buffers in and out.
+int agz_rotate_boards(agz_ctx* ctx, const float* boards, int count, int m, int n, float* out) {
+  AGZ_REQUIRE(ctx && boards && out && count >= 0 && m >= 1, AGZ_E_INVALID, "agz_rotate_boards: bad argument");
+  AGZ_REQUIRE(m == n, AGZ_E_INVALID, "Cannot handle m %d, n %d. This function only takes square boards", m, n);
+  return map_boards(ctx, boards, count, m, 1, out);
+}
+
+int agz_symmetry_boards(agz_ctx* ctx, const float* boards, int count, int m, int k, float* out) {
+  AGZ_REQUIRE(ctx && boards && out && count >= 0 && m >= 1, AGZ_E_INVALID, "agz_symmetry_boards: bad argument");
+  AGZ_REQUIRE(k >= 0 && k < 8, AGZ_E_INVALID, "agz_symmetry_boards: k %d (0..7)", k);
+  return map_boards(ctx, boards, count, m, k, out);
 }
 
 }  // extern "C"

@@ -175,6 +175,9 @@ struct Arena {
     agz::check(agz_arena_end_move(h, 0), "Agent.Search");
   }
   void SetParallel(int lanes) { agz::check(agz_arena_set_parallel(h, lanes), "SetParallel"); }  // lane-ordered tree-parallel rounds
+  // build extension: leaves of network agents evaluated under a board symmetry — AGZ_SYM_OFF (default), AGZ_SYM_RANDOM (one of the eight
+  // per position, a function of board, mover and seed) or AGZ_SYM_FIXED + k.  Square boards, not c4.  Not in a checkpoint: set it again.
+  void SetLeafSymmetry(int mode, uint64_t seed = 0) { agz::check(agz_arena_set_leaf_symmetry(h, mode, seed), "SetLeafSymmetry"); }
   void Opponent(const std::vector<int32_t>& moves) { agz::check(agz_arena_apply_moves(h, moves.data()), "opponent move"); }
   // Checkpoint of the running arena between two moves, and the continuation from one (agz_arena_save / agz_arena_load): games, trees, RNG
   // states, counters, examples.  The agents, the lanes and the pool policy are not in the file: set them again as they were.
@@ -212,6 +215,7 @@ struct Examples {
   size_t size() const { int64_t n = 0; agz::check(agz_examples_count(h, &n), "len(ex)"); return (size_t)n; }
   void Append(Arena& a) { agz::check(agz_examples_append_arena(h, a.h), "append(ex, SelfPlay()...)"); }
   void AugmentRotate() { agz::check(agz_examples_augment_rotate(h), "RotateBoard"); }
+  void AugmentDihedral() { agz::check(agz_examples_augment_dihedral(h), "AugmentDihedral"); }   // all eight board symmetries, one pass
   int Prepare(int BatchSize, int maxExamples, uint64_t seed) {  // agogo.go:118-121 + prepareExamples
     int b = 0;
     agz::check(agz_examples_prepare(h, BatchSize, maxExamples, seed, &b), "prepareExamples");
@@ -227,6 +231,9 @@ struct Config {
   int MaxExamples = 0;
   int Encoder = AGZ_ENC_TWOPLANE;
   bool AugmentRotate = false;  // Augmenter (datatypes.go:24): the RotateBoard-based rotation augmenter, or none
+  bool AugmentDihedral = false;  // build extension: the four rotations and the four reflections (takes precedence over AugmentRotate)
+  // build extension: leaf symmetry of the self-play and evaluation arenas (Arena::SetLeafSymmetry); AGZ_SYM_OFF = the reference's search
+  int LeafSymmetry = AGZ_SYM_OFF;
   // build extension: the arithmetic of the inference networks (agz_net_set_compute_mode) and, through it, of the trainer: AGZ_COMPUTE_F32_MFMA
   // (default), AGZ_COMPUTE_BF16X3, AGZ_COMPUTE_WINO (training then uses BF16X3), AGZ_COMPUTE_WINO_H2 / AGZ_COMPUTE_AUTO (the measured mode;
   // training takes the trainer's AGZ_COMPUTE_WINO_H2)
@@ -291,10 +298,12 @@ struct AZ {
         Arena sp(ctx, game.kind, game.m, game.n, game.k, game.komi, conf.Encoder, conf.MCTSConf, episodes, seed + 1000 * epoch);
         if (epoch == 0 && useDummy) sp.SetAgents(nullptr, nullptr);
         else sp.SetAgentKinds(conf.SelfPlayInferencer[0], infA.get(), conf.SelfPlayInferencer[1], infB.get());
-        sp.PlayOnDevice(true);                                             // episodes x SelfPlay(), agogo.go:110-114
+        if (conf.LeafSymmetry != AGZ_SYM_OFF) sp.SetLeafSymmetry(conf.LeafSymmetry, seed + 1000 * epoch + 1);
+        sp.PlayOnDevice(true);                                            // episodes x SelfPlay(), agogo.go:110-114
         ex.Append(sp);                                                     // device to device, episode after episode
       }
-      if (conf.AugmentRotate) ex.AugmentRotate();                          // Arena.Play's aug(ex), arena.go:115-120
+      if (conf.AugmentDihedral) ex.AugmentDihedral();
+      else if (conf.AugmentRotate) ex.AugmentRotate();                     // Arena.Play's aug(ex), arena.go:115-120
       st.examples = ex.size();
       // maxExamples cut (agogo.go:118-121) + prepareExamples (agogo.go:211-249), tensors stay in HBM
       int batches = ex.Prepare(conf.NNConf.BatchSize, conf.MaxExamples, seed + 13 * epoch + 1);
@@ -307,7 +316,8 @@ struct AZ {
       {
         Arena ev(ctx, game.kind, game.m, game.n, game.k, game.komi, conf.Encoder, conf.MCTSConf, arenaGames, seed + 1000 * epoch + 500);
         ev.SetAgentKinds(conf.EvalInferencer[0], infA.get(), conf.EvalInferencer[1], infB.get());
-        ev.Play(false);                                                    // agogo.go:144-148
+        if (conf.LeafSymmetry != AGZ_SYM_OFF) ev.SetLeafSymmetry(conf.LeafSymmetry, seed + 1000 * epoch + 501);
+        ev.Play(false);                                                   // agogo.go:144-148
         int64_t aw = 0, bw = 0, dr = 0;
         agz::check(agz_arena_get_results(ev.h, &aw, &bw, &dr), "results");
         st.a_wins = aw; st.b_wins = bw; st.draws = dr;

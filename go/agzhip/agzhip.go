@@ -308,6 +308,9 @@ func (a *BatchedArena) SelfPlayInto(ex *Examples) error {
 
 func (e *Examples) AugmentRotate() error { defer e.ctx.enter()(); return lastErr(C.agz_examples_augment_rotate(e.h)) }
 
+// AugmentDihedral replaces every example by its eight images under the symmetries of the square board (four rotations, four reflections).
+func (e *Examples) AugmentDihedral() error { defer e.ctx.enter()(); return lastErr(C.agz_examples_augment_dihedral(e.h)) }
+
 // Prepare returns the number of batches (0: "batches is nil", agogo.go:123-125).
 func (e *Examples) Prepare(batchSize, maxExamples int, seed uint64) (int, error) {
 	defer e.ctx.enter()()
@@ -359,6 +362,21 @@ func (a *BatchedArena) SetPoolPolicy(policy int) error {
 func (a *BatchedArena) SetParallel(lanes int) error {
 	defer a.ctx.enter()()
 	return lastErr(C.agz_arena_set_parallel(a.h, C.int(lanes)))
+}
+
+// Leaf symmetry modes (agz_arena_set_leaf_symmetry): SymFixed + k applies S_k at every leaf.
+const (
+	SymOff    = 0
+	SymRandom = 1
+	SymFixed  = 8
+)
+
+// SetLeafSymmetry evaluates the leaves of network agents under a board symmetry and maps the policy back: SymOff (default),
+// SymRandom (one of the eight per position, a pure function of board, mover and seed) or SymFixed + k.  Square boards, not c4;
+// between moves.  The setting is not part of a checkpoint: set it again after Load.
+func (a *BatchedArena) SetLeafSymmetry(mode int, seed uint64) error {
+	defer a.ctx.enter()()
+	return lastErr(C.agz_arena_set_leaf_symmetry(a.h, C.int(mode), C.uint64_t(seed)))
 }
 
 // Save writes a checkpoint of the running arena — games, both trees of every game, RNG states, counters, recorded examples — between two
@@ -619,6 +637,12 @@ func (t *MCTS) SetPoolPolicy(policy int) error {
 func (t *MCTS) SetParallel(lanes int) error {
 	defer t.ctx.enter()()
 	return lastErr(C.agz_mcts_set_parallel(t.h, C.int(lanes)))
+}
+
+// SetLeafSymmetry: leaf evaluation under a board symmetry (see BatchedArena.SetLeafSymmetry).
+func (t *MCTS) SetLeafSymmetry(mode int, seed uint64) error {
+	defer t.ctx.enter()()
+	return lastErr(C.agz_mcts_set_leaf_symmetry(t.h, C.int(mode), C.uint64_t(seed)))
 }
 
 // ship serialises t.current into an agz_state.

@@ -490,6 +490,29 @@ int agz_arena_selfplay(agz_arena* arena, int64_t n_games_target, int record);
  * 1 (default) is the sequential search, the declared semantics of everything else in this library.  Changes the search
  * result (different, not worse, simulations); call between searches. */
 int agz_arena_set_parallel(agz_arena* arena, int lanes);
+/* BUILD EXTENSION (no mcts.Config field): leaf evaluation under a board symmetry, the AlphaGo Zero remedy for a network
+ * that is not yet equivariant.  Square boards whose actions are their cells (mnk, komi, wq with m == n).
+ * The eight maps: (R x)[i][j] = x[j][m-1-i] (RotateBoard), (T x)[i][j] = x[j][i]; S_k = R^(k&3) o T^(k>>2), k = 0..7, as an index map
+ * (S_k x)[c] = x[src_k(c)]; inv(k): S_inv(k) o S_k = id; dst_k = src_inv(k).  S_0..S_3 are agz_examples_augment_rotate's images.
+ * For a leaf of an agent holding AGZ_INF_NET the network's input is S_k of every plane of the encoder's tensor, the value is used as
+ * returned, the prior of board cell c is policy_row[dst_k(c)], the pass prior policy_row[policy_len-1].  Every other inferencer kind is
+ * unaffected (AGZ_INF_CALLBACK is handed the untransformed planes), and so are the recorded examples.
+ *   AGZ_SYM_OFF        default: everything as without this call, bit for bit
+ *   AGZ_SYM_RANDOM     k = mix32(ph ^ (uint32)seed ^ (uint32)(seed >> 32)) >> 29, ph = the position hash of AGZ_INF_HASH
+ *                      (sum over cells of mix32(4 i + board[i] + 1), plus mix32(0xABCD0000 + to_move), uint32): a pure function of
+ *                      (board, mover, seed) — independent of batch order, lanes, queues and the split step; agz_leaf_symmetry_of
+ *   AGZ_SYM_FIXED + k  S_k at every leaf (tests, A/B runs)
+ * AGZ_E_UNSUPPORTED for c4 or m != n, AGZ_E_STATE inside a move, AGZ_E_INVALID for any other mode.  Not stored in an arena checkpoint:
+ * re-apply it after agz_arena_load and the continuation is bit for bit. */
+#define AGZ_SYM_OFF 0
+#define AGZ_SYM_RANDOM 1
+#define AGZ_SYM_FIXED 8
+int agz_arena_set_leaf_symmetry(agz_arena* arena, int mode, uint64_t seed);
+/* The same definitions for a host inferencer (no context, no device).  agz_symmetry_map: src[c] = src_k(c) for the m*m cells
+ * (1 <= m <= 19, 0 <= k < 8).  agz_symmetry_inverse: inv(k), or AGZ_E_INVALID.  agz_leaf_symmetry_of: AGZ_SYM_RANDOM's k of a position. */
+int agz_symmetry_map(int m, int k, int32_t* src);
+int agz_symmetry_inverse(int k);
+int agz_leaf_symmetry_of(uint64_t seed, const int32_t* board, int cells, int to_move, int* k);
 int agz_arena_begin_move(agz_arena* arena);
 int agz_arena_simulate(agz_arena* arena, int k);
 int agz_arena_end_move(agz_arena* arena, int record);
@@ -620,6 +643,8 @@ int agz_mcts_set_inferencer_callback(agz_mcts* mcts, agz_infer_fn fn, void* user
 int agz_mcts_set_pool_policy(agz_mcts* mcts, int policy);
 /* lanes per round (BUILD EXTENSION, see agz_arena_set_parallel) */
 int agz_mcts_set_parallel(agz_mcts* mcts, int lanes);
+/* leaf symmetry of a single tree (BUILD EXTENSION, see agz_arena_set_leaf_symmetry) */
+int agz_mcts_set_leaf_symmetry(agz_mcts* mcts, int mode, uint64_t seed);
 /* (*MCTS).SetGame (tree.go:120-124) */
 int agz_mcts_set_game(agz_mcts* mcts, const agz_state* st);
 /* (*MCTS).Search(player) (search.go:92-164): SetToMove(player), updateRoot, prepareRoot, Budget simulations, bestMove,
@@ -680,6 +705,10 @@ int agz_examples_get(agz_examples* ex, float* planes, float* policy, float* valu
  * and the m*n board part of Policy rotated, the pass entry and Value kept.  Non-square boards: AGZ_E_INVALID with
  * RotateBoard's message. */
 int agz_examples_augment_rotate(agz_examples* ex);
+/* BUILD EXTENSION: the dihedral Augmenter — every example e is replaced by [S_0 e .. S_7 e] (the eight maps of
+ * agz_arena_set_leaf_symmetry; rows 0..3 of each group are agz_examples_augment_rotate's, bit for bit): planes and the board part
+ * of Policy mapped, the pass entry and Value copied.  One pass over the store.  Same preconditions as agz_examples_augment_rotate. */
+int agz_examples_augment_dihedral(agz_examples* ex);
 /* `if maxExamples > 0 && len(ex) > maxExamples { shuffleExamples(ex); ex = ex[:maxExamples] }` (agogo.go:118-121;
  * maxExamples <= 0: skipped) followed by prepareExamples (agogo.go:211-249): shuffleExamples (agogo.go:251-257, build
  * RNG), batches = len/BatchSize, the first batches*BatchSize rows tensorised.  *batches may be 0 ("batches is nil",
@@ -690,6 +719,8 @@ int agz_examples_tensors_dev(agz_examples* ex, float** Xs, float** Policies, flo
 int agz_examples_get_tensors(agz_examples* ex, float* Xs, float* Policies, float* Values);
 /* RotateBoard (encoding_helper.go:80-107) on `count` boards of m x n floats (host buffers; runs on the device). */
 int agz_rotate_boards(agz_ctx* ctx, const float* boards, int count, int m, int n, float* out);
+/* S_k (agz_arena_set_leaf_symmetry) on `count` boards of m x m floats (host buffers; runs on the device). k < 4: RotateBoard k times. */
+int agz_symmetry_boards(agz_ctx* ctx, const float* boards, int count, int m, int k, float* out);
 
 /* ---- multi-GPU exchange over RCCL / xGMI -------------------------------------------------------------------
  * Self-play games shard across GPUs with NO data-path collective (one agz_ctx + arena set per GPU).  The path has exactly
