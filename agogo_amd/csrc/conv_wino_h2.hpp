@@ -119,6 +119,8 @@ struct WinoH2Args {
   int temporal_stores;       // A/B (agz_net_set_wino_h2_gemm + 64): 1 = M and V2c stored with the default cache policy (round 4); 0: non-temporal
   int live_r, live_c;        // chained form, short positions (gemm_maps.hpp, wino_h2c_rows): live rows per 128-row slot at the class R / class C
                              // positions; 0: no such class here / the short map is off (every position keeps its 128 rows)
+  maps::PackGrid pk;         // ... and their packing (gemm_maps.hpp "packed short positions"; wino_h2c_geometry sets it from live_r / live_c): the live
+                             // rows of S slots fill whole slots, the DMA GEMM launches a workgroup per USED slot only
   int row_pad;               // three-kernel form: extra rows after every position's 128 tile rows of V and M (wino_h2_launch: rB = 128 + row_pad)
 };
 __device__ __forceinline__ size_t h2_row(const WinoH2Args& h, int pos, int t) {
@@ -211,10 +213,14 @@ __global__ __launch_bounds__(256) void wino_in_h2_kernel(WinoH2Args h) {
   // register: per instruction ONE 256-byte run (lanes 0..63 = 64 consecutive words of the row).
   const int lane = threadIdx.x & 63;
   const size_t swap_word = (size_t)((c2 >> 6) * 4) * 32 + lane;           // chunks 4q, 4q+1 of the wave's 4 chunks; the others 64 words on
-  // chained layout, short positions (gemm_maps.hpp; h.live_r / h.live_c, 0 = off): the tile's row in its 128-row slot at the class R
-  // and class C positions; -1: dead there (nothing is stored)
-  const int row_r = (h.cform && h.live_r) ? maps::rows_row(maps::ROWS_R, a.nty, a.ntx, b % (128 / a.TPB), ty, tx) : (t & 127);
-  const int row_c = (h.cform && h.live_c) ? maps::rows_row(maps::ROWS_C, a.nty, a.ntx, b % (128 / a.TPB), ty, tx) : (t & 127);
+  // chained layout, short positions (gemm_maps.hpp; h.live_r / h.live_c, 0 = off): the tile's packed (physical slot * 128 + row) at the
+  // class R and class C positions; -1: dead there (nothing is stored).  rows_row's row inside the board's own slot is the packed map with S = 1.
+  auto packed = [&](int cls, int S) -> int {
+    const int idx = maps::rows_row(cls, a.nty, a.ntx, 0, ty, tx);
+    return idx < 0 ? -1 : maps::pack_slot_row(S, 128 / a.TPB, maps::rows_per_board(cls, a.nty, a.ntx), b, idx);
+  };
+  const int row_r = (h.cform && h.live_r) ? packed(maps::ROWS_R, h.pk.S_r) : t;
+  const int row_c = (h.cform && h.live_c) ? packed(maps::ROWS_C, h.pk.S_c) : t;
 #pragma unroll
   for (int i = 0; i < AL; i++) {
     float ox[AL], oy[AL];
@@ -228,11 +234,11 @@ __global__ __launch_bounds__(256) void wino_in_h2_kernel(WinoH2Args h) {
         const auto s16 = __builtin_amdgcn_permlane16_swap(hi, lo, false, false);   // [hi k0, lo k0, hi k2, lo k2], [hi k1, lo k1, hi k3, lo k3]
         const unsigned e0 = s16[0], e1 = s16[1];
         const int NS = a.C >> 5;
-        const size_t chunk0 = ((size_t)(t >> 7) * h.npos + (size_t)(i * AL + j)) * NS + (size_t)((c2 >> 6) * 4 + 2 * (lane >> 5));   // K step of e0's half
         const int cls = maps::rows_class(true, true, AL, i, j);   // (a constant after unrolling; an absent class has the full row)
-        const int row = cls == maps::ROWS_R ? row_r : (cls == maps::ROWS_C ? row_c : (t & 127));
+        const int row = cls == maps::ROWS_R ? row_r : (cls == maps::ROWS_C ? row_c : t);
         if (row < 0) continue;                                    // a wave is one tile: a dead (position, tile) is a wave-uniform skip
-        unsigned* p0 = V2 + chunk0 * 4096 + (size_t)row * 32 + (lane & 31);
+        const size_t chunk0 = ((size_t)(row >> 7) * h.npos + (size_t)(i * AL + j)) * NS + (size_t)((c2 >> 6) * 4 + 2 * (lane >> 5));   // K step of e0's half
+        unsigned* p0 = V2 + chunk0 * 4096 + (size_t)(row & 127) * 32 + (lane & 31);
         p0[0] = e0;
         p0[4096] = e1;                                                              // the next K step's chunk
         continue;

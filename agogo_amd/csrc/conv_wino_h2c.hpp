@@ -19,8 +19,9 @@
 //   U2c[pos][C/32][Ntot/256][256 cols][hi | lo]                    a K step of a 256-column tile = one 32 KB chunk
 //   Mc [T/128][pos][C/32 slices][128 rows][64 cols] fp32           column 2j + br of slice s = branch br of channel 32 s + j
 // Short positions (gemm_maps.hpp, rows_*; wino_h2c_rows below): where the tiles hang over the board's edge, the rows of V2c and Mc that
-// only feed off-board outputs — last transform point x last tile row / column — are not stored, multiplied or read: at those positions
-// a 128-row slot holds its live tiles packed into rows 0 .. live - 1 (19x19: 96 of 128 at 13 of the 49 positions, 2.33 GB per block).
+// only feed off-board outputs — last transform point x last tile row / column — are not stored, multiplied or read (19x19: 96 of a
+// slot's 128 at 13 of the 49 positions, 2.33 GB per block), and the live rows of S consecutive slots are packed into S * live / 128 FULL
+// slots (19x19: 32 boards' 384 rows into three slots of four): the GEMM launches no workgroup for the slots left empty, every tile is full.
 // LDS image of a staged chunk: row r, 16-byte slot q (0..3 hi, 4..7 lo) at r * 128 + ((q ^ ((r >> 1) & 7)) << 4): conflict-free
 // for the 128-byte row writes and for the MFMA fragment reads (ds_read_b128: even and odd rows are the two halves of the
 // 64-bank period, and the 8 even / 8 odd rows of a 16-lane group get 8 distinct slots).
@@ -155,15 +156,14 @@ __global__ __launch_bounds__(256, 3) void wino_gemm_h2g_kernel(WinoH2Args h) {
   constexpr int SA = 128 * 128, SB = 256 * 128;
   __shared__ __attribute__((aligned(16))) unsigned char lds[SA + SB];
 
+  // one workgroup per (position, USED 128-row slot, column tile) — maps::pack_tile: at a short position the live rows are packed into
+  // whole slots and the slots they leave empty get no workgroup, so every tile here is a full one.  XCD x takes a contiguous range of tiles.
   const int n_nt = a.Ntot >> 8;
-  const int per_pos = a.n_mtiles * n_nt;
-  const int nblk = h.npos * per_pos;
+  const int nblk = maps::pack_grid_tiles(h.pk);
   const int id = blockIdx.x;
   int q = nblk >> 3, rr = nblk & 7, xcd = id & 7, slot = id >> 3;
-  int tile = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + slot;
-  const int pos = tile / per_pos;
-  const int rem = tile - pos * per_pos;
-  const int m_tile = rem / n_nt, n_tile = rem - m_tile * n_nt;
+  const maps::PackTile pt = maps::pack_tile(h.pk, (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + slot);
+  const int pos = pt.pos, m_tile = pt.slot, n_tile = pt.n_tile;
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -187,60 +187,40 @@ __global__ __launch_bounds__(256, 3) void wino_gemm_h2g_kernel(WinoH2Args h) {
 #pragma unroll
       for (int r = 0; r < 16; r++) acc[i][j][r] = 0.f;
 
-  // Short positions (gemm_maps.hpp): the slot's live rows are its first `live` = 32, 64 or 96; the 32-row blocks at or past them are
-  // neither fetched (wave w's A part is rows 32 w ..) nor multiplied nor stored.  Everything below is uniform per WAVE: a_on (one
-  // branch around the A-DMA per K step), and ni = how many of this wave's two 32-row MFMA blocks are live, which picks one of three
-  // copies of the K loop per wave, so no branch sits between the MFMAs.  At live = 96 the waves of ONE workgroup run different copies
-  // (wm = 0: NI = 2, wm = 1: NI = 1) and meet at barriers that are different instructions.  That is safe here, and relied on: every
-  // copy executes exactly the same 2 NK barriers in the same order relative to its DMA and its LDS reads, and the hardware barrier
-  // (s_barrier) counts the workgroup's arriving waves, whichever instruction each arrives at.
-  const int live = maps::rows_pos_live(h.live_r, h.live_c, h.tm + 2, pos);
-  const bool a_on = maps::h2c_wave_row0(wid, 128) < live;
-  const int ni = (maps::h2c_mfma_row0(wm, 0) < live ? 1 : 0) + (maps::h2c_mfma_row0(wm, 1) < live ? 1 : 0);
-  auto k_loop = [&](auto ni_c) {
-    constexpr int NI = decltype(ni_c)::value;
 #pragma nounroll
-    for (int it = 0; it < NK; it++) {
-      if (a_on) {
+  for (int it = 0; it < NK; it++) {
 #pragma unroll
-        for (int j = 0; j < maps::h2c_wave_instrs(128); j++)
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(ar, (h2c_lds_ptr_t)(la + maps::h2c_dma_dst(0, j)), 16, (j & 1) ? vo_o : vo_e,
-                                                   a_so + (maps::h2c_dma_src(0, j) - maps::h2c_dma_src(0, j & 1)), 0, 0);
+    for (int j = 0; j < maps::h2c_wave_instrs(128); j++)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(ar, (h2c_lds_ptr_t)(la + maps::h2c_dma_dst(0, j)), 16, (j & 1) ? vo_o : vo_e,
+                                               a_so + (maps::h2c_dma_src(0, j) - maps::h2c_dma_src(0, j & 1)), 0, 0);
+#pragma unroll
+    for (int j = 0; j < maps::h2c_wave_instrs(256); j++)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(br, (h2c_lds_ptr_t)(lb + maps::h2c_dma_dst(0, j)), 16, (j & 1) ? vo_o : vo_e,
+                                               b_so + (maps::h2c_dma_src(0, j) - maps::h2c_dma_src(0, j & 1)), 0, 0);
+    a_so += SA; b_so += b_step;
+    __syncthreads();                                  // (its fence waits vmcnt(0): this wave's DMA has landed; then every wave's)
+#pragma unroll
+    for (int ks = 0; ks < 2; ks++) {
+      f16x8_t A_[2][2];
+#pragma unroll
+      for (int i = 0; i < 2; i++) {
+        A_[i][0] = *reinterpret_cast<const f16x8_t*>(lds + maps::h2c_frag(maps::h2c_mfma_row0(wm, i), lane, 0, ks));
+        A_[i][1] = *reinterpret_cast<const f16x8_t*>(lds + maps::h2c_frag(maps::h2c_mfma_row0(wm, i), lane, 1, ks));
       }
 #pragma unroll
-      for (int j = 0; j < maps::h2c_wave_instrs(256); j++)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(br, (h2c_lds_ptr_t)(lb + maps::h2c_dma_dst(0, j)), 16, (j & 1) ? vo_o : vo_e,
-                                                 b_so + (maps::h2c_dma_src(0, j) - maps::h2c_dma_src(0, j & 1)), 0, 0);
-      a_so += SA; b_so += b_step;
-      __syncthreads();                                  // (its fence waits vmcnt(0): this wave's DMA has landed; then every wave's)
-      if (NI > 0) {
+      for (int j = 0; j < 4; j++) {                   // B fragments just in time: 8 registers live instead of 32
+        const f16x8_t b0 = *reinterpret_cast<const f16x8_t*>(lds + SA + maps::h2c_frag(wn * 128 + j * 32, lane, 0, ks));
+        const f16x8_t b1 = *reinterpret_cast<const f16x8_t*>(lds + SA + maps::h2c_frag(wn * 128 + j * 32, lane, 1, ks));
 #pragma unroll
-        for (int ks = 0; ks < 2; ks++) {
-          f16x8_t A_[2][2];
-#pragma unroll
-          for (int i = 0; i < NI; i++) {
-            A_[i][0] = *reinterpret_cast<const f16x8_t*>(lds + maps::h2c_frag(maps::h2c_mfma_row0(wm, i), lane, 0, ks));
-            A_[i][1] = *reinterpret_cast<const f16x8_t*>(lds + maps::h2c_frag(maps::h2c_mfma_row0(wm, i), lane, 1, ks));
-          }
-#pragma unroll
-          for (int j = 0; j < 4; j++) {                   // B fragments just in time: 8 registers live instead of 32
-            const f16x8_t b0 = *reinterpret_cast<const f16x8_t*>(lds + SA + maps::h2c_frag(wn * 128 + j * 32, lane, 0, ks));
-            const f16x8_t b1 = *reinterpret_cast<const f16x8_t*>(lds + SA + maps::h2c_frag(wn * 128 + j * 32, lane, 1, ks));
-#pragma unroll
-            for (int i = 0; i < NI; i++) {                // small terms first: lo*hi, hi*lo, hi*hi
-              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A_[i][1], b0, acc[i][j], 0, 0, 0);
-              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A_[i][0], b1, acc[i][j], 0, 0, 0);
-              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A_[i][0], b0, acc[i][j], 0, 0, 0);
-            }
-          }
+        for (int i = 0; i < 2; i++) {                 // small terms first: lo*hi, hi*lo, hi*hi
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A_[i][1], b0, acc[i][j], 0, 0, 0);
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A_[i][0], b1, acc[i][j], 0, 0, 0);
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A_[i][0], b0, acc[i][j], 0, 0, 0);
         }
       }
-      __syncthreads();                                  // every wave has read the stage before the next DMA overwrites it
     }
-  };
-  if (ni == 2) k_loop(std::integral_constant<int, 2>{});
-  else if (ni == 1) k_loop(std::integral_constant<int, 1>{});
-  else k_loop(std::integral_constant<int, 0>{});
+    __syncthreads();                                  // every wave has read the stage before the next DMA overwrites it
+  }
 
   // M: after v_permlane32_swap of two neighbouring column tiles a register holds all 64 columns of one row (lanes = columns): w0 = row
   // mfma_row(r), w1 = that row + 4; every store instruction writes one 256-byte run of Mc
@@ -249,7 +229,6 @@ __global__ __launch_bounds__(256, 3) void wino_gemm_h2g_kernel(WinoH2Args h) {
   for (int qq = 0; qq < 2; qq++)
 #pragma unroll
     for (int i = 0; i < 2; i++) {
-      if (i >= ni) continue;                            // (uniform) a 32-row block past the live rows
 #pragma unroll
       for (int r = 0; r < 16; r++) {
         const unsigned x0 = __float_as_uint(acc[i][2 * qq][r]), x1 = __float_as_uint(acc[i][2 * qq + 1][r]);
@@ -510,17 +489,22 @@ __global__ __launch_bounds__(256, 2) void wino_oi_h2c_kernel(WinoH2Args h) {
   float s_, un0;
   wino_h2_scales(h.amax_in[b], WT::VSHIFT, &s_, &un0);
   // ---- output transform: stream the AL columns of the position grid (AL float4 {a c0, b c0, a c1, b c1} each), column pass, accumulate the row pass
-  const __amdgpu_buffer_rsrc_t mr = h2_rsrc(a.Mb + ((size_t)(t0 >> 7) * h.npos * NS + s) * 8192);
-  const unsigned m_lane = (unsigned)(((tc & 127) * 64 + pr * 4) * 4);
+  // (the descriptor starts at a slot every packing group — 1, 2 or 4 slots — starts at: a packed row may lie in an earlier slot than t0's own)
+  const int sl0 = (t0 >> 7) & ~3;
+  const __amdgpu_buffer_rsrc_t mr = h2_rsrc(a.Mb + ((size_t)sl0 * h.npos * NS + s) * 8192);
   const unsigned m_pos = (unsigned)NS * 32768u;        // bytes between positions
-  // short positions (gemm_maps.hpp; h.live_r / h.live_c, 0 = off): M is read through the class's row map; a dead (position, tile) reads
-  // zeros from past the descriptor's range, which reach off-board outputs only
+  const unsigned m_slot = (unsigned)h.npos * m_pos;    // ... between slots (at most 3 of them go into an offset: far inside 31 bits)
+  const unsigned m_lane = (unsigned)((t0 >> 7) - sl0) * m_slot + (unsigned)(((tc & 127) * 64 + pr * 4) * 4);
+  // short positions (gemm_maps.hpp; h.live_r / h.live_c, 0 = off): M is read through the class's packed row map; a dead (position, tile)
+  // reads zeros from past the descriptor's range, which reach off-board outputs only
   const int bpt = 128 / a.TPB;
-  auto m_row = [&](int cls) -> unsigned {
-    const int r = maps::rows_row(cls, a.nty, a.ntx, b % bpt, ty, tx);
-    return r < 0 ? 0x80000000u : (unsigned)((r * 64 + pr * 4) * 4);
+  auto m_row = [&](int cls, int S) -> unsigned {
+    const int idx = maps::rows_row(cls, a.nty, a.ntx, 0, ty, tx);
+    if (idx < 0) return 0x80000000u;
+    const int p = maps::pack_slot_row(S, bpt, maps::rows_per_board(cls, a.nty, a.ntx), b, idx);
+    return (unsigned)((p >> 7) - sl0) * m_slot + (unsigned)(((p & 127) * 64 + pr * 4) * 4);
   };
-  const unsigned m_lane_r = h.live_r ? m_row(maps::ROWS_R) : m_lane, m_lane_c = h.live_c ? m_row(maps::ROWS_C) : m_lane;
+  const unsigned m_lane_r = h.live_r ? m_row(maps::ROWS_R, h.pk.S_r) : m_lane, m_lane_c = h.live_c ? m_row(maps::ROWS_C, h.pk.S_c) : m_lane;
   auto m_voff = [&](int xi, int nu) -> unsigned {        // (the class is a constant after unrolling)
     const int cls = maps::rows_class(true, true, AL, xi, nu);
     return cls == maps::ROWS_R ? m_lane_r : (cls == maps::ROWS_C ? m_lane_c : m_lane);
@@ -758,7 +742,14 @@ __global__ __launch_bounds__(256, 2) void wino_oip_h2c_kernel(WinoH2Args h) {
   // gr_r / gr_c rows instead of 16, and the thread's M row and its lanes' two V2c store rows are the class's own.  A dead (position,
   // tile) gets an offset past the descriptor's range: the load returns zeros (they reach discarded outputs only), the store moves nothing.
   // The class of a position is a constant after unrolling; with the short map off the class values ARE the full ones.
+  // Packed (gemm_maps.hpp "packed short positions"): the live rows of S slots fill whole slots, so a group's rows start at the uniform
+  // row rg0 = (g % (8 S)) * gr of its packing group and may cross into the group's next slot.  The six per-thread values below stay what
+  // they were — offsets inside the GROUP'S rows — and the slot a row falls into, q = ((rg0 + row) >> 7) & (S - 1), is recomputed at every
+  // use (m_voff / v_voff: nothing more is carried through the item loop) and adds q * (slot stride - one slot's rows).  Every address
+  // stays inside the tensor (31 bits: wino_h2c_fits31 / wino_h2c_dma_ok); a dead lane's 2^31 plus at most 3 slot strides stays out of range.
   constexpr unsigned OOB = 0x80000000u;
+  const int S_r = h.pk.S_r, S_c = h.pk.S_c;
+  const unsigned m_dq = (unsigned)(h.npos * NS - 1) * 32768u, v_dq = (unsigned)(h.npos * NS - 1) * 16384u;
   const unsigned gr_r = h.live_r ? (unsigned)(bpg * maps::rows_per_board(maps::ROWS_R, a.nty, a.ntx)) : 16u;
   const unsigned gr_c = h.live_c ? (unsigned)(bpg * maps::rows_per_board(maps::ROWS_C, a.nty, a.ntx)) : 16u;
   auto m_row = [&](int cls) -> unsigned {
@@ -785,11 +776,14 @@ __global__ __launch_bounds__(256, 2) void wino_oip_h2c_kernel(WinoH2Args h) {
   auto m_soff = [&](int g, int s, int xi, int nu) -> unsigned {
     const int cls = maps::rows_class(true, true, AL, xi, nu);
     const unsigned gr = cls == maps::ROWS_R ? gr_r : (cls == maps::ROWS_C ? gr_c : 16u);
-    return (unsigned)((((g >> 3) * h.npos + xi * AL + nu) * NS + s)) * 32768u + (unsigned)(g & 7) * (gr * 256u);
+    const int S = cls == maps::ROWS_R ? S_r : (cls == maps::ROWS_C ? S_c : 1);
+    return (unsigned)(((maps::pack_group_slot0(S, g) * h.npos + xi * AL + nu) * NS + s)) * 32768u + maps::pack_group_rg0(S, g, gr) * 256u;
   };
-  auto m_voff = [&](int xi, int nu) -> unsigned {
+  auto m_voff = [&](int g, int xi, int nu) -> unsigned {
     const int cls = maps::rows_class(true, true, AL, xi, nu);
-    return cls == maps::ROWS_R ? m_lane_r : (cls == maps::ROWS_C ? m_lane_c : m_lane);
+    if (cls == maps::ROWS_R) return m_lane_r + maps::pack_q(S_r, maps::pack_group_rg0(S_r, g, gr_r), m_lane_r, 8) * m_dq;
+    if (cls == maps::ROWS_C) return m_lane_c + maps::pack_q(S_c, maps::pack_group_rg0(S_c, g, gr_c), m_lane_c, 8) * m_dq;
+    return m_lane;
   };
   int item = blockIdx.x;
   {
@@ -797,7 +791,7 @@ __global__ __launch_bounds__(256, 2) void wino_oip_h2c_kernel(WinoH2Args h) {
 #pragma unroll
     for (int nu = 0; nu < NPRE; nu++)
 #pragma unroll
-      for (int xi = 0; xi < AL; xi++) m[nu][xi] = h2_ldf4<MAUX>(mr, m_voff(xi, nu), m_soff(g, s, xi, nu));
+      for (int xi = 0; xi < AL; xi++) m[nu][xi] = h2_ldf4<MAUX>(mr, m_voff(g, xi, nu), m_soff(g, s, xi, nu));
   }
   __syncthreads();
   for (; item < n_items; item += gridDim.x) {
@@ -823,7 +817,7 @@ __global__ __launch_bounds__(256, 2) void wino_oip_h2c_kernel(WinoH2Args h) {
       }
       if (nu + NPRE < AL) {
 #pragma unroll
-        for (int xi = 0; xi < AL; xi++) m[nu % NPRE][xi] = h2_ldf4<MAUX>(mr, m_voff(xi, nu + NPRE), m_soff(g, s, xi, nu + NPRE));
+        for (int xi = 0; xi < AL; xi++) m[nu % NPRE][xi] = h2_ldf4<MAUX>(mr, m_voff(g, xi, nu + NPRE), m_soff(g, s, xi, nu + NPRE));
       }
       wino_atv_p<TM>(c0, o0);
       wino_atv_p<TM>(c1, o1);
@@ -903,13 +897,21 @@ __global__ __launch_bounds__(256, 2) void wino_oip_h2c_kernel(WinoH2Args h) {
 #pragma unroll
       for (int nu = 0; nu < NPRE; nu++)
 #pragma unroll
-        for (int xi = 0; xi < AL; xi++) m[nu][xi] = h2_ldf4<MAUX>(mr, m_voff(xi, nu), m_soff(g2, s2, xi, nu));
+        for (int xi = 0; xi < AL; xi++) m[nu][xi] = h2_ldf4<MAUX>(mr, m_voff(g2, xi, nu), m_soff(g2, s2, xi, nu));
     }
     __builtin_amdgcn_sched_barrier(0);
     // ---- input transform of the next block, one output row at a time (column pass recomputed per row from LDS)
-    const unsigned v_base = (unsigned)((((g >> 3) * h.npos) * NS + s)) * 16384u;
-    const unsigned v_g = (unsigned)(g & 7) * 2048u, v_g_r = (unsigned)(g & 7) * (gr_r * 128u), v_g_c = (unsigned)(g & 7) * (gr_c * 128u);
     const unsigned v_pos = (unsigned)NS * 16384u;
+    const unsigned v_slot = (unsigned)h.npos * v_pos;
+    const unsigned rg0_r = maps::pack_group_rg0(S_r, g, gr_r), rg0_c = maps::pack_group_rg0(S_c, g, gr_c);
+    const unsigned v_g = (unsigned)(g >> 3) * v_slot + (unsigned)s * 16384u + (unsigned)(g & 7) * 2048u;
+    const unsigned v_g_r = maps::pack_group_slot0(S_r, g) * v_slot + (unsigned)s * 16384u + rg0_r * 128u;
+    const unsigned v_g_c = maps::pack_group_slot0(S_c, g) * v_slot + (unsigned)s * 16384u + rg0_c * 128u;
+    auto v_voff = [&](int cls, int k) -> unsigned {           // store k (0 / 1) of the wave at a position of class cls (a constant)
+      if (cls == maps::ROWS_R) { const unsigned o = k ? v1_r : v0_r; return o + maps::pack_q(S_r, rg0_r, o, 7) * v_dq; }
+      if (cls == maps::ROWS_C) { const unsigned o = k ? v1_c : v0_c; return o + maps::pack_q(S_c, rg0_c, o, 7) * v_dq; }
+      return k ? v_lane + 256u : v_lane;
+    };
     const float* yr = ybase;
     asm volatile("" : "+v"(yr));
     // rows in passes of <= 3: per pass every patch column is read once (AL ds_read_b64 with immediate offsets) and gives the pass's rows
@@ -946,9 +948,9 @@ __global__ __launch_bounds__(256, 2) void wino_oip_h2c_kernel(WinoH2Args h) {
           const auto s32 = __builtin_amdgcn_permlane32_swap(e0, e1, false, false);
           const unsigned w0 = s32[0], w1 = s32[1];
           const int cls = maps::rows_class(true, true, AL, i, j);
-          const unsigned v_so = v_base + (cls == maps::ROWS_R ? v_g_r : (cls == maps::ROWS_C ? v_g_c : v_g)) + (unsigned)(i * AL + j) * v_pos;
-          __builtin_amdgcn_raw_buffer_store_b32(w0, vr, cls == maps::ROWS_R ? v0_r : (cls == maps::ROWS_C ? v0_c : v_lane), v_so, VAUX);
-          __builtin_amdgcn_raw_buffer_store_b32(w1, vr, cls == maps::ROWS_R ? v1_r : (cls == maps::ROWS_C ? v1_c : v_lane + 256u), v_so, VAUX);
+          const unsigned v_so = (cls == maps::ROWS_R ? v_g_r : (cls == maps::ROWS_C ? v_g_c : v_g)) + (unsigned)(i * AL + j) * v_pos;
+          __builtin_amdgcn_raw_buffer_store_b32(w0, vr, v_voff(cls, 0), v_so, VAUX);
+          __builtin_amdgcn_raw_buffer_store_b32(w1, vr, v_voff(cls, 1), v_so, VAUX);
         }
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -990,6 +992,15 @@ static void wino_h2c_geometry(WinoH2Args& h) {
   h.rsh = 7; h.rmask = 127; h.rA = (unsigned)h.npos * 128u; h.rB = 128u;
   a.n_mtiles = ceil_div(a.T, 128); a.n_ntiles = ceil_div(a.Ntot, 128);
   h.in_swap = 1; h.cform = 1; h.wm_per_board = 0;
+  // packing of the short positions' live rows (live_r / live_c = 0: every position full); a caller that changes them calls this again
+  h.pk = maps::pack_grid(tm + 2, a.nty, a.ntx, a.B, a.Ntot >> 8, h.live_r, h.live_c);
+}
+// workgroups of the DMA GEMM: one per (position, used slot, column tile).  A position whose slots hold maps::rows_pos_live = 128 rows
+// uses every slot, a short one S * live / 128 of every S.
+static int wino_h2c_gemm_tiles(const WinoH2Args& h) {
+  int n = 0;
+  for (int pos = 0; pos < h.npos; pos++) n += maps::pack_pos_used(h.pk, pos);
+  return n * h.pk.n_nt;
 }
 constexpr int WINO_H2_GEMM_DEFAULT = 1;   // 1: wino_gemm_h2g_kernel (three workgroups per CU), 2: wino_gemm_h2p_kernel (persistent)
 // gemm_variant (0 = the default) -> the kernel and its decomposition mode: what BOTH the launch (wino_h2c_gemm) and the short-row
@@ -1015,7 +1026,8 @@ static bool wino_h2c_oip_ready(agz_ctx* ctx) {
 // Short positions (gemm_maps.hpp): sets h.live_r / h.live_c for a block of the tower.  The three stages of every block of a forward must
 // agree on the layout, so the answer depends only on the shape and on which kernels run — asked before block 0's input transform and
 // the same for every block: the tower's default kernels (DMA GEMM wino_gemm_h2g_kernel, pipelined out->in kernel; oi_variant 4) and
-// live counts of whole 32-row MFMA blocks.  keep_all (agz_net_set_wino_h2_gemm + 128): the A/B hook, every row kept.
+// live counts of whole 32-row MFMA blocks.  Where the map is on its live rows are PACKED into whole slots (h.pk; one mode, decided here for
+// every block and every chunk alike).  keep_all (agz_net_set_wino_h2_gemm + 128): the A/B hook, every row kept.
 static void wino_h2c_rows(agz_ctx* ctx, WinoH2Args& h, int oi_variant, bool keep_all) {
   wino_h2c_geometry(h);
   h.live_r = h.live_c = 0;
@@ -1024,6 +1036,7 @@ static void wino_h2c_rows(agz_ctx* ctx, WinoH2Args& h, int oi_variant, bool keep
   if (keep_all || gemm != 1 || oi_variant != 4 || !wino_h2c_dma_ok(h) || !wino_h2c_fits31(h) || !maps::rows_short_ok(g) || !wino_h2c_oip_ready(ctx)) return;
   h.live_r = g.dead_y ? maps::rows_slot_live(g, maps::ROWS_R) : 0;
   h.live_c = g.dead_x ? maps::rows_slot_live(g, maps::ROWS_C) : 0;
+  wino_h2c_geometry(h);   // (h.pk: where the short map is on its live rows are packed into whole slots — there is no unpacked short mode)
 }
 static void wino_h2c_in(agz_ctx* ctx, WinoH2Args& h, hipStream_t st) {     // block 0: x -> V2c (exact range: h.amax_in, fuse_prev = 0)
   wino_h2c_geometry(h);
@@ -1053,13 +1066,15 @@ static void wino_h2c_gemm(agz_ctx* ctx, WinoH2Args& h, hipStream_t st) {
     }
     return;
   }
-  if (dma_ok && h.temporal_stores && (h.w.C >> 5) == 8) { hipLaunchKernelGGL((wino_gemm_h2g_kernel<8, false>), g, dim3(256), 0, st, h); return; }   // (A/B: round 4's stores)
+  // the DMA form launches a workgroup per USED slot (short positions packed: gemm_maps.hpp), the others one per slot
+  const dim3 gd((unsigned)wino_h2c_gemm_tiles(h));
+  if (dma_ok && h.temporal_stores && (h.w.C >> 5) == 8) { hipLaunchKernelGGL((wino_gemm_h2g_kernel<8, false>), gd, dim3(256), 0, st, h); return; }   // (A/B: round 4's stores)
   if (dma_ok) {
     switch (h.w.C >> 5) {
-      case 4: hipLaunchKernelGGL((wino_gemm_h2g_kernel<4>), g, dim3(256), 0, st, h); return;
-      case 8: hipLaunchKernelGGL((wino_gemm_h2g_kernel<8>), g, dim3(256), 0, st, h); return;
-      case 12: hipLaunchKernelGGL((wino_gemm_h2g_kernel<12>), g, dim3(256), 0, st, h); return;
-      default: hipLaunchKernelGGL((wino_gemm_h2g_kernel<16>), g, dim3(256), 0, st, h); return;
+      case 4: hipLaunchKernelGGL((wino_gemm_h2g_kernel<4>), gd, dim3(256), 0, st, h); return;
+      case 8: hipLaunchKernelGGL((wino_gemm_h2g_kernel<8>), gd, dim3(256), 0, st, h); return;
+      case 12: hipLaunchKernelGGL((wino_gemm_h2g_kernel<12>), gd, dim3(256), 0, st, h); return;
+      default: hipLaunchKernelGGL((wino_gemm_h2g_kernel<16>), gd, dim3(256), 0, st, h); return;
     }
   }
   switch (h.w.C >> 5) {

@@ -99,6 +99,60 @@ AGZ_MAPS_HD constexpr int rows_stored_per_board(const WinoRows& g) {
   return n;
 }
 
+// ---- packed short positions (tests/cpp/wino_pack_check.cpp, tests/test_wino_packed_rows_cpu.py) ------------------------------------
+// Where the short map is on, a class with `live` rows per slot does not leave the last 128 - live rows of every slot empty: the live
+// rows of S = 128 / gcd(128, live) consecutive slots (a packing group: S * bpt boards, S * live rows; 96 -> 4 slots, 64 -> 2, 32 -> 4)
+// fill the group's first S * live / 128 slots COMPLETELY, and the group's remaining slots are neither written, read nor multiplied at
+// that position.  Board b, live tile of local index idx (rows_local), l = rows_per_board live tiles per board:
+//   rg = (b % (S * bpt)) * l + idx        physical slot (b / (S * bpt)) * S + (rg >> 7), row rg & 127
+// (a board's rows may straddle two slots).  A partly filled last group uses ceil(rows / 128) slots; its rows past the last board are
+// unwritten, the GEMM may multiply them and nothing reads the result.  A full position is the same map with S = 1, l = TPB.
+AGZ_MAPS_HD constexpr int pack_slots(int live) { return live == 96 || live == 32 ? 4 : (live == 64 ? 2 : 1); }
+AGZ_MAPS_HD constexpr int pack_used_per_group(int live) { return live == 96 ? 3 : 1; }                 // S * live / 128 (1 for a full position)
+AGZ_MAPS_HD constexpr int pack_rg(int S, int bpt, int l, int b, int idx) { return (b % (S * bpt)) * l + idx; }
+// physical slot * 128 + row of (board b, local index idx)
+AGZ_MAPS_HD constexpr int pack_slot_row(int S, int bpt, int l, int b, int idx) { return (b / (S * bpt)) * S * 128 + pack_rg(S, bpt, l, b, idx); }
+// slots that hold rows at a position of B boards
+AGZ_MAPS_HD constexpr int pack_used_slots(int S, int bpt, int l, int B) {
+  return (B / (S * bpt)) * (S * bpt * l / 128) + ((B % (S * bpt)) * l + 127) / 128;
+}
+// The out->in kernels work on groups of 16 tile rows (16 / TPB whole boards, gr = live rows of the group at the class; 8 S groups per
+// packing group).  Group g's first packed row rg0 = (g % (8 S)) * gr is uniform, and with off = (row of the tile inside its group) *
+// row_bytes + (the lane's bytes inside the row) — what the unpacked map held per thread — the packed address is
+//   base(slot (g / (8 S)) * S) + rg0 * row_bytes + off + q * (slot_stride - 128 * row_bytes),   q = ((rg0 + off / row_bytes) >> 7) & (S - 1)
+// (q = the slot of the group the row falls into).  A dead lane's off is 2^31: q stays below S, so its offset stays past the descriptor's range.
+AGZ_MAPS_HD constexpr unsigned pack_group_rg0(int S, int g, int gr) { return (unsigned)((g & (8 * S - 1)) * gr); }
+AGZ_MAPS_HD constexpr int pack_log2(int S) { return S >> 1; }                                           // S is 1, 2 or 4 (no division in a kernel)
+AGZ_MAPS_HD constexpr unsigned pack_group_slot0(int S, int g) { return (unsigned)((g >> (3 + pack_log2(S))) << pack_log2(S)); }
+AGZ_MAPS_HD constexpr unsigned pack_q(int S, unsigned rg0, unsigned off, int row_shift) { return ((rg0 + (off >> row_shift)) >> 7) & (unsigned)(S - 1); }
+// GEMM grid: one workgroup per (position, USED slot, column tile), position-major as before.  per / S = 1 and u = u_full where a class
+// is absent or the short map is off.
+struct PackGrid { int AL, n_nt, u_full, u_r, u_c, S_r, S_c, per_r, per_c; };
+AGZ_MAPS_HD constexpr PackGrid pack_grid(int AL, int nty, int ntx, int B, int n_nt, int live_r, int live_c) {
+  const int TPB = nty * ntx, bpt = 128 / TPB, u_full = pack_used_slots(1, bpt, TPB, B);
+  return PackGrid{AL, n_nt, u_full,
+                  live_r ? pack_used_slots(pack_slots(live_r), bpt, rows_per_board(ROWS_R, nty, ntx), B) : u_full,
+                  live_c ? pack_used_slots(pack_slots(live_c), bpt, rows_per_board(ROWS_C, nty, ntx), B) : u_full,
+                  pack_slots(live_r), pack_slots(live_c), pack_used_per_group(live_r), pack_used_per_group(live_c)};
+}
+// used slots of position pos; workgroups of the launch
+AGZ_MAPS_HD constexpr int pack_pos_used(const PackGrid& g, int pos) {
+  return pos / g.AL == g.AL - 1 ? g.u_r : (pos % g.AL == g.AL - 1 ? g.u_c : g.u_full);
+}
+AGZ_MAPS_HD constexpr int pack_grid_tiles(const PackGrid& g) {
+  return ((g.AL - 1) * ((g.AL - 1) * g.u_full + g.u_c) + g.AL * g.u_r) * g.n_nt;
+}
+struct PackTile { int pos, slot, n_tile; };
+AGZ_MAPS_HD constexpr PackTile pack_tile(const PackGrid& g, int tile) {
+  const int u = tile / g.n_nt, row_u = (g.AL - 1) * g.u_full + g.u_c;
+  const int xi = u / row_u < g.AL - 1 ? u / row_u : g.AL - 1, r = u - xi * row_u;
+  const bool last = xi == g.AL - 1;
+  const int nu = last ? r / g.u_r : (r / g.u_full < g.AL - 1 ? r / g.u_full : g.AL - 1);
+  const int k = r - nu * (last ? g.u_r : g.u_full);
+  const int per = last ? g.per_r : (nu == g.AL - 1 ? g.per_c : 1), S = last ? g.S_r : (nu == g.AL - 1 ? g.S_c : 1);
+  return PackTile{xi * g.AL + nu, (k / per) * S + k % per, tile - u * g.n_nt};
+}
+
 // ---- persistent kernel (wino_gemm_h2p_kernel): 8 KB stages of 64 rows, ring of 16, DMA 10 stages ahead
 constexpr int H2P_D = 10, H2P_R = 16, H2P_NK = 8;
 // byte offset in V2c of K step 0 of half tile hm (rows 64 (hm & 1) .. of m-tile hm >> 1) of position pos
