@@ -58,6 +58,11 @@ class MctsConf(C.Structure):
                 ("DumbPass", C.c_int32), ("ResignPercentage", C.c_float), ("PassPreference", C.c_int32)]
 
 
+class NoiseConf(C.Structure):
+    """agz_noise_conf (include/agz.h): root noise P = (1 - eps) p + eps eta, eta ~ Dir(alpha); 16 bytes"""
+    _fields_ = [("eps", C.c_float), ("alpha", C.c_float), ("on", C.c_int32), ("reserved", C.c_int32)]
+
+
 class ArenaStats(C.Structure):
     _fields_ = [("sims_total", C.c_int64), ("sims_nonnull", C.c_int64), ("nn_evals", C.c_int64),
                 ("moves_played", C.c_int64), ("games_finished", C.c_int64), ("examples", C.c_int64),
@@ -222,6 +227,13 @@ def lib():
     sig("agz_leaf_symmetry_of", i32, u64, pi, i32, i32, C.POINTER(C.c_int))
     sig("agz_examples_augment_dihedral", i32, vp)
     sig("agz_symmetry_boards", i32, vp, pf, i32, i32, i32, pf)
+    pnc, pu64 = C.POINTER(NoiseConf), C.POINTER(C.c_uint64)
+    sig("agz_arena_set_root_noise", i32, vp, pnc)
+    sig("agz_arena_get_root_noise", i32, vp, pnc)
+    sig("agz_arena_root_noise", i32, vp, i32, i32, pu64, pi, pf, i32, C.POINTER(C.c_int))
+    sig("agz_mcts_set_root_noise", i32, vp, pnc)
+    sig("agz_mcts_root_noise", i32, vp, pu64, pi, pf, i32, C.POINTER(C.c_int))
+    sig("agz_root_noise_of", i32, u64, i32, C.c_float, pf)
     sig("agz_arena_begin_move", i32, vp)
     sig("agz_arena_simulate", i32, vp, i32)
     sig("agz_arena_end_move", i32, vp, i32)
@@ -814,6 +826,25 @@ class Arena:
         """SYM_OFF / SYM_RANDOM / SYM_FIXED + k: leaves of AGZ_INF_NET agents are evaluated under a board symmetry"""
         _check(lib().agz_arena_set_leaf_symmetry(self.h, int(mode), int(seed) & (2 ** 64 - 1)), "agz_arena_set_leaf_symmetry")
 
+    def set_root_noise(self, eps=0.25, alpha=0.3, on=True):
+        """Dirichlet noise on the root priors of every search: P = (1 - eps) p + eps eta, eta ~ Dir(alpha) (include/agz.h); default off"""
+        conf = NoiseConf(eps, alpha, int(on), 0)
+        _check(lib().agz_arena_set_root_noise(self.h, C.byref(conf)), "agz_arena_set_root_noise")
+
+    def get_root_noise(self):
+        conf = NoiseConf()
+        _check(lib().agz_arena_get_root_noise(self.h, C.byref(conf)), "agz_arena_get_root_noise")
+        return {"eps": conf.eps, "alpha": conf.alpha, "on": bool(conf.on)}
+
+    def root_noise(self, g, agent, cap=None):
+        """the last draw of `agent`'s tree in game g: (key, moves, eta, n) — n children, min(cap, n) of them copied; n = 0: no draw yet"""
+        cap = self.m * self.n + 2 if cap is None else int(cap)
+        mv, eta = np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.float32)
+        key, n = C.c_uint64(0), C.c_int(0)
+        _check(lib().agz_arena_root_noise(self.h, int(g), int(agent), C.byref(key), _pi(mv), _pf(eta), cap, C.byref(n)), "agz_arena_root_noise")
+        k = min(cap, n.value)
+        return key.value, mv[:k].copy(), eta[:k].copy(), n.value
+
     def begin_move(self):
         _check(lib().agz_arena_begin_move(self.h), "agz_arena_begin_move")
 
@@ -1009,6 +1040,19 @@ class Mcts:
 
     def set_leaf_symmetry(self, mode, seed=0):
         _check(lib().agz_mcts_set_leaf_symmetry(self.h, int(mode), int(seed) & (2 ** 64 - 1)), "agz_mcts_set_leaf_symmetry")
+
+    def set_root_noise(self, eps=0.25, alpha=0.3, on=True):
+        conf = NoiseConf(eps, alpha, int(on), 0)
+        _check(lib().agz_mcts_set_root_noise(self.h, C.byref(conf)), "agz_mcts_set_root_noise")
+
+    def root_noise(self, cap=None):
+        """the tree's last draw: (key, moves, eta, n), as Arena.root_noise"""
+        cap = self.m * self.n + 2 if cap is None else int(cap)
+        mv, eta = np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.float32)
+        key, n = C.c_uint64(0), C.c_int(0)
+        _check(lib().agz_mcts_root_noise(self.h, C.byref(key), _pi(mv), _pf(eta), cap, C.byref(n)), "agz_mcts_root_noise")
+        k = min(cap, n.value)
+        return key.value, mv[:k].copy(), eta[:k].copy(), n.value
 
     def set_game(self, **kw):
         st, keep = make_state(self.m * self.n, **kw)
@@ -1308,3 +1352,10 @@ def leaf_symmetry_of(seed, board, to_move):
     k = C.c_int(0)
     _check(lib().agz_leaf_symmetry_of(int(seed) & (2 ** 64 - 1), _pi(b), b.size, int(to_move), C.byref(k)), "agz_leaf_symmetry_of")
     return k.value
+
+
+def root_noise_of(key, n, alpha):
+    """eta[0..n) of the root-noise draw `key` (noise.hpp; host only): what the device mixes into n root children"""
+    eta = np.zeros(max(int(n), 1), np.float32)
+    _check(lib().agz_root_noise_of(int(key) & (2 ** 64 - 1), int(n), float(alpha), _pf(eta)), "agz_root_noise_of")
+    return eta[:int(n)]

@@ -437,7 +437,7 @@ __global__ __launch_bounds__(64) void k_begin_move(Dev d, GameCfg c, MctsCfg mc)
         __syncthreads();
         scan = hi;
       }
-      if (lane == 0) { d.cur_pool[t] = pool ^ 1; d.n_nodes[t] = new_n; }
+      if (lane == 0) { d.cur_pool[t] = pool ^ 1; d.n_nodes[t] = new_n; if (d.noised) d.noised[t] = 0; }   // another root: no root noise on it yet
     }
   } else {
     // fresh root: Pass if legal, else the first legal move (search.go:476-487); pool restarts empty
@@ -455,9 +455,48 @@ __global__ __launch_bounds__(64) void k_begin_move(Dev d, GameCfg c, MctsCfg mc)
     if (lane == 0) {
       d.prior[base] = 0.f; d.visits[base] = 1; d.bsum[base] = 0.f; d.kids_off[base] = -1; d.kids_n[base] = 0;
       d.nmove[base] = (int16_t)rootmv; d.n_nodes[t] = 1; d.has_root[t] = 1;
+      if (d.noised) d.noised[t] = 0;
     }
   }
   if (lane == 0) d.has_prev[t] = 0;  // t.searchState.prev = nil (search.go:490)
+}
+
+// Root noise (BUILD EXTENSION, DESIGN.md §2 root-noise; noise.hpp holds the definition): after prepareRoot, the priors of the children of
+// the root this move searches become (1 - eps) p + eps eta, eta ~ Dir(alpha).  Only launched while the setting is on.  The key of the
+// draw is one output of the tree's own stream d.rng[t] (randomizeChildren's); child i = position i of the root's block as it stands now.
+// A root without children and a root that already carries noise (a depth-0 re-search of the same root) are left alone, no key is drawn.
+__global__ __launch_bounds__(64) void k_root_noise(Dev d, GameCfg c, float eps, float alpha) {
+  __shared__ double gam[CELLS_PAD];
+  __shared__ unsigned long long skey;
+  const int g = blockIdx.x, lane = threadIdx.x;
+  if (d.ended[g]) return;
+  const int t = agent_of(d, g) * d.G + g;
+  const size_t base = pool_base(d, t, d.cur_pool[t]);
+  const int off = d.kids_off[base];
+  int n = off >= 0 ? d.kids_n[base] : 0;
+  n = n < d.noise_stride ? n : d.noise_stride;           // (a block never holds more than A + 1 children)
+  if (n <= 0) { if (lane == 0) d.noise_n[t] = 0; return; }
+  if (d.noised[t]) return;                                // every lane has read the mark before lane 0 sets it behind the barriers
+  if (lane == 0) {
+    uint64_t s = d.rng[t];
+    skey = noise::next(s);
+    d.rng[t] = s;
+  }
+  __syncthreads();
+  const uint64_t key = skey;
+  const double a = (double)alpha;
+  for (int i = lane; i < n; i += WAVE) gam[i] = noise::gamma_of(key, i, a);
+  __syncthreads();
+  double S = 0.0;
+  for (int i = 0; i < n; i++) S = S + gam[i];             // index order, the same sum in every lane
+  for (int i = lane; i < n; i += WAVE) {
+    const float eta = noise::eta_of(gam[i], S, n);
+    const size_t o = base + off + i, r = (size_t)t * d.noise_stride + i;
+    d.prior[o] = noise::mix(eps, d.prior[o], eta);
+    d.noise_eta[r] = eta;
+    d.noise_move[r] = d.nmove[o];
+  }
+  if (lane == 0) { d.noise_key[t] = key; d.noise_n[t] = n; d.noised[t] = 1; }
 }
 
 // pipeline() descent: mcts/search.go:209-257 up to (and excluding) the network call.
@@ -1359,6 +1398,7 @@ struct agz_arena {
   int last_prep_batch = 0, last_prep_roots = 0;   // boards in / roots evaluated by the last prepareRoot forward (0: skipped)
   int nA_slots = 0, nB_slots = 0;
   bool in_move = false;
+  agz_noise_conf noise{0.25f, 0.3f, 0, 0};   // agz_arena_set_root_noise; the caller's configuration, not in a checkpoint
   bool restart = false;  // continuous self-play: finished games restart immediately
   int moves_done = 0;
   // AGZ_INF_CALLBACK (mcts.Inferencer as a host function, mcts/mcts.go:15-18): the callee, its policy width, page-locked staging
@@ -2009,6 +2049,67 @@ int agz_leaf_symmetry_of(uint64_t seed, const int32_t* board, int cells, int to_
   return AGZ_OK;
 }
 
+// Root noise (BUILD EXTENSION): the setting lives in the arena; the record buffers and the per-tree marks are allocated
+// when it is first turned on.  It is not part of an arena checkpoint: the caller re-applies it after agz_arena_load.
+static bool noise_conf_ok(const agz_noise_conf* c) {
+  return c && (c->on == 0 || c->on == 1) && c->reserved == 0 && c->eps >= 0.f && c->eps <= 1.f && c->alpha > 0.f && c->alpha <= 1.f;   // (NaN fails every comparison)
+}
+int agz_arena_set_root_noise(agz_arena* a, const agz_noise_conf* conf) {
+  AGZ_REQUIRE(a, AGZ_E_INVALID, "arena is NULL");
+  AGZ_REQUIRE(noise_conf_ok(conf), AGZ_E_INVALID, "agz_arena_set_root_noise: on in {0,1}, 0 <= eps <= 1, 0 < alpha <= 1, reserved == 0 (on %d, eps %g, alpha %g, reserved %d)",
+              conf ? conf->on : -1, conf ? (double)conf->eps : 0.0, conf ? (double)conf->alpha : 0.0, conf ? conf->reserved : -1);
+  AGZ_REQUIRE(!a->in_move, AGZ_E_STATE, "agz_arena_set_root_noise: a search is in progress");
+  if (conf->on && !a->d.noised) {
+    AGZ_HIP_TRY(hipSetDevice(a->ctx->device));
+    Dev& d = a->d;
+    const size_t T = (size_t)d.T, stride = (size_t)a->gc.A + 1;
+    int r;
+    if ((r = a->alloc(&d.noise_key, T)) != AGZ_OK || (r = a->alloc(&d.noise_n, T)) != AGZ_OK || (r = a->alloc(&d.noise_move, T * stride)) != AGZ_OK ||
+        (r = a->alloc(&d.noise_eta, T * stride)) != AGZ_OK)
+      return r;
+    d.noise_stride = (int)stride;
+    if ((r = a->alloc(&d.noised, T)) != AGZ_OK) return r;   // last: the kernels take it as "the buffers exist"
+  }
+  a->noise = *conf;
+  return AGZ_OK;
+}
+int agz_arena_get_root_noise(agz_arena* a, agz_noise_conf* out) {
+  AGZ_REQUIRE(a && out, AGZ_E_INVALID, "agz_arena_get_root_noise: NULL argument");
+  *out = a->noise;
+  return AGZ_OK;
+}
+int agz_arena_root_noise(agz_arena* a, int g, int agent, uint64_t* key, int32_t* moves, float* eta, int cap, int* n) {
+  AGZ_REQUIRE(a && n, AGZ_E_INVALID, "agz_arena_root_noise: NULL argument");
+  AGZ_REQUIRE(g >= 0 && g < a->G && (agent == 0 || agent == 1) && cap >= 0, AGZ_E_INVALID, "agz_arena_root_noise: game %d (of %d), agent %d, cap %d", g, a->G, agent, cap);
+  *n = 0;
+  if (key) *key = 0;
+  if (!a->d.noised) return AGZ_OK;   // the setting was never on: no draw, nothing to read back
+  AGZ_HIP_TRY(hipSetDevice(a->ctx->device));
+  hipStream_t s = a->ctx->stream;
+  const Dev& d = a->d;
+  const size_t t = (size_t)agent * d.G + g;
+  int32_t cnt = 0;
+  uint64_t k = 0;
+  AGZ_HIP_TRY(hipMemcpyAsync(&cnt, d.noise_n + t, 4, hipMemcpyDeviceToHost, s));
+  AGZ_HIP_TRY(hipMemcpyAsync(&k, d.noise_key + t, 8, hipMemcpyDeviceToHost, s));
+  AGZ_HIP_TRY(hipStreamSynchronize(s));
+  const int copy = std::min(cap, (int)cnt);
+  if (copy > 0 && moves) AGZ_HIP_TRY(hipMemcpyAsync(moves, d.noise_move + t * d.noise_stride, (size_t)copy * 4, hipMemcpyDeviceToHost, s));
+  if (copy > 0 && eta) AGZ_HIP_TRY(hipMemcpyAsync(eta, d.noise_eta + t * d.noise_stride, (size_t)copy * 4, hipMemcpyDeviceToHost, s));
+  AGZ_HIP_TRY(hipStreamSynchronize(s));
+  *n = cnt;
+  if (key) *key = cnt > 0 ? k : 0;
+  return AGZ_OK;
+}
+// The same definition without a context or a device.
+int agz_root_noise_of(uint64_t key, int n, float alpha, float* eta) {
+  AGZ_REQUIRE(eta && n >= 1 && n <= noise::MAX_N && alpha > 0.f && alpha <= 1.f, AGZ_E_INVALID,
+              "agz_root_noise_of: 1 <= n <= %d, 0 < alpha <= 1, eta != NULL (n %d, alpha %g)", noise::MAX_N, n, (double)alpha);
+  std::vector<double> g((size_t)n);
+  noise::eta_all(key, n, (double)alpha, g.data(), eta);
+  return AGZ_OK;
+}
+
 int agz_arena_reset(agz_arena* a, const uint8_t* a_is_black) {
   AGZ_REQUIRE(a, AGZ_E_INVALID, "arena is NULL");
   AGZ_HIP_TRY(hipSetDevice(a->ctx->device));
@@ -2049,7 +2150,13 @@ int agz_arena_begin_move(agz_arena* a) {
     if (r != AGZ_OK) { a->in_move = false; return r; }
     a->room_sims = sims;
   }
-  return a->nn_step(1);  // prepareRoot
+  int r = a->nn_step(1);  // prepareRoot
+  if (r == AGZ_OK && a->noise.on) {   // root noise on the priors prepareRoot left (or tree reuse kept): one launch, only while the setting is on
+    ProfScope ps(a->ctx, AGZ_PROF_MOVE);
+    hipLaunchKernelGGL(k_root_noise, dim3(a->G), dim3(64), 0, a->ctx->stream, a->d, a->gc, a->noise.eps, a->noise.alpha);
+    AGZ_HIP_TRY(hipGetLastError());
+  }
+  return r;
 }
 
 int agz_arena_debug_counter(agz_arena* a, int which, int64_t* value) {
@@ -2705,6 +2812,10 @@ int agz_arena::ckpt_apply(FILE* f, const arena_ckpt::Scan& sc) {
   seed = sc.host.seed; seed0 = sc.host.seed0; prep_expand_seen = sc.host.prep_expand_seen; moves_done = sc.host.moves_done; restart = sc.host.restart != 0;
   for (int g = 0; g < G; g++) a_is_black[g] = (uint8_t)sm.a_is_black[g];
   in_move = false; sims_this_move = 0; room_sims = 0;
+  if (d.noised) {   // root noise: the marks and the records are not in the file — a loaded arena starts with none
+    AGZ_HIP_TRY(hipMemsetAsync(d.noised, 0, (size_t)d.T * sizeof(int32_t), s));
+    AGZ_HIP_TRY(hipMemsetAsync(d.noise_n, 0, (size_t)d.T * sizeof(int32_t), s));
+  }
   return update_slots();
 }
 
@@ -2866,6 +2977,16 @@ int agz_mcts_set_parallel(agz_mcts* m, int lanes) {
 int agz_mcts_set_leaf_symmetry(agz_mcts* m, int mode, uint64_t seed) {
   AGZ_REQUIRE(m, AGZ_E_INVALID, "mcts is NULL");
   return agz_arena_set_leaf_symmetry(m->arena, mode, seed);
+}
+
+int agz_mcts_set_root_noise(agz_mcts* m, const agz_noise_conf* conf) {
+  AGZ_REQUIRE(m, AGZ_E_INVALID, "mcts is NULL");
+  return agz_arena_set_root_noise(m->arena, conf);
+}
+
+int agz_mcts_root_noise(agz_mcts* m, uint64_t* key, int32_t* moves, float* eta, int cap, int* n) {
+  AGZ_REQUIRE(m, AGZ_E_INVALID, "mcts is NULL");
+  return agz_arena_root_noise(m->arena, 0, 0, key, moves, eta, cap, n);
 }
 
 int agz_mcts_set_game(agz_mcts* m, const agz_state* st) {

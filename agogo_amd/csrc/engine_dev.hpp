@@ -15,6 +15,7 @@
 #include <cstdint>
 
 #include "../../include/agz.h"
+#include "noise.hpp"
 #include "sym.hpp"
 
 namespace agz {
@@ -133,6 +134,14 @@ struct Dev {
   // ---- leaf symmetry (agz_arena_set_leaf_symmetry, sym.hpp): AGZ_SYM_OFF, AGZ_SYM_RANDOM or AGZ_SYM_FIXED + k
   int sym_mode;
   uint32_t sym_seed;      // sym::fold_seed(seed)
+  // ---- root noise (agz_arena_set_root_noise, noise.hpp): all nullptr until the setting is first turned on
+  int32_t* noised;        // [T] the root of tree t carries noise (k_root_noise sets it, k_begin_move clears it when the search gets a
+                          //     different root); not in a checkpoint: a loaded arena starts with every mark clear
+  uint64_t* noise_key;    // [T] the record of the tree's last draw: its key,
+  int32_t* noise_n;       // [T] the number of root children it covered (0: none yet),
+  int32_t* noise_move;    // [T][noise_stride] their moves in the block order of that moment
+  float* noise_eta;       // [T][noise_stride] and their eta
+  int noise_stride;       // A + 1
 };
 
 enum { CNT_SIMS = 0, CNT_NONNULL = 1, CNT_EVALS = 2, CNT_MOVES = 3, CNT_GAMES = 4, CNT_EXAMPLES = 5, CNT_FULL = 6, CNT_A_WINS = 7, CNT_B_WINS = 8,

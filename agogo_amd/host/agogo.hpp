@@ -178,6 +178,12 @@ struct Arena {
   // build extension: leaves of network agents evaluated under a board symmetry — AGZ_SYM_OFF (default), AGZ_SYM_RANDOM (one of the eight
   // per position, a function of board, mover and seed) or AGZ_SYM_FIXED + k.  Square boards, not c4.  Not in a checkpoint: set it again.
   void SetLeafSymmetry(int mode, uint64_t seed = 0) { agz::check(agz_arena_set_leaf_symmetry(h, mode, seed), "SetLeafSymmetry"); }
+  // build extension: Dirichlet noise on the root priors of every search, P = (1 - eps) p + eps eta, eta ~ Dir(alpha) (agz_arena_set_root_noise);
+  // default off.  Not in a checkpoint: set it again after Load.
+  void SetRootNoise(float eps = 0.25f, float alpha = 0.3f, bool on = true) {
+    const agz_noise_conf conf = {eps, alpha, on ? 1 : 0, 0};
+    agz::check(agz_arena_set_root_noise(h, &conf), "SetRootNoise");
+  }
   void Opponent(const std::vector<int32_t>& moves) { agz::check(agz_arena_apply_moves(h, moves.data()), "opponent move"); }
   // Checkpoint of the running arena between two moves, and the continuation from one (agz_arena_save / agz_arena_load): games, trees, RNG
   // states, counters, examples.  The agents, the lanes and the pool policy are not in the file: set them again as they were.
@@ -234,6 +240,10 @@ struct Config {
   bool AugmentDihedral = false;  // build extension: the four rotations and the four reflections (takes precedence over AugmentRotate)
   // build extension: leaf symmetry of the self-play and evaluation arenas (Arena::SetLeafSymmetry); AGZ_SYM_OFF = the reference's search
   int LeafSymmetry = AGZ_SYM_OFF;
+  // build extension: root noise of the SELF-PLAY arena (Arena::SetRootNoise): RootNoiseEps = 0 means off.  The evaluation arena that gates
+  // a new network always plays without noise
+  float RootNoiseEps = 0.f;
+  float RootNoiseAlpha = 0.3f;
   // build extension: the arithmetic of the inference networks (agz_net_set_compute_mode) and, through it, of the trainer: AGZ_COMPUTE_F32_MFMA
   // (default), AGZ_COMPUTE_BF16X3, AGZ_COMPUTE_WINO (training then uses BF16X3), AGZ_COMPUTE_WINO_H2 / AGZ_COMPUTE_AUTO (the measured mode;
   // training takes the trainer's AGZ_COMPUTE_WINO_H2)
@@ -299,6 +309,7 @@ struct AZ {
         if (epoch == 0 && useDummy) sp.SetAgents(nullptr, nullptr);
         else sp.SetAgentKinds(conf.SelfPlayInferencer[0], infA.get(), conf.SelfPlayInferencer[1], infB.get());
         if (conf.LeafSymmetry != AGZ_SYM_OFF) sp.SetLeafSymmetry(conf.LeafSymmetry, seed + 1000 * epoch + 1);
+        if (conf.RootNoiseEps > 0.f) sp.SetRootNoise(conf.RootNoiseEps, conf.RootNoiseAlpha);
         sp.PlayOnDevice(true);                                            // episodes x SelfPlay(), agogo.go:110-114
         ex.Append(sp);                                                     // device to device, episode after episode
       }

@@ -379,6 +379,66 @@ func (a *BatchedArena) SetLeafSymmetry(mode int, seed uint64) error {
 	return lastErr(C.agz_arena_set_leaf_symmetry(a.h, C.int(mode), C.uint64_t(seed)))
 }
 
+// RootNoise is one Dirichlet draw at a root: the key of the draw and, per root child in the block order of that moment, its move and eta.
+type RootNoise struct {
+	Key   uint64
+	Moves []int32
+	Eta   []float32
+}
+
+// SetRootNoise mixes Dirichlet noise into the root priors of every search of this arena: P = (1-eps)·p + eps·eta, eta ~ Dir(alpha)
+// (agz_arena_set_root_noise; 0 <= eps <= 1, 0 < alpha <= 1).  Off by default; between moves.  The setting is not part of a checkpoint:
+// set it again after Load.
+func (a *BatchedArena) SetRootNoise(eps, alpha float32, on bool) error {
+	defer a.ctx.enter()()
+	conf := C.agz_noise_conf{eps: C.float(eps), alpha: C.float(alpha)}
+	if on {
+		conf.on = 1
+	}
+	return lastErr(C.agz_arena_set_root_noise(a.h, &conf))
+}
+
+// RootNoiseConf returns the arena's root-noise setting (agz_arena_get_root_noise).
+func (a *BatchedArena) RootNoiseConf() (eps, alpha float32, on bool, err error) {
+	defer a.ctx.enter()()
+	var conf C.agz_noise_conf
+	if err = lastErr(C.agz_arena_get_root_noise(a.h, &conf)); err != nil {
+		return 0, 0, false, err
+	}
+	return float32(conf.eps), float32(conf.alpha), conf.on != 0, nil
+}
+
+// RootNoise returns the last draw of agent's tree in game g (no draw yet: no moves).
+func (a *BatchedArena) RootNoise(g, agent int) (RootNoise, error) {
+	defer a.ctx.enter()()
+	capacity := a.m*a.n + 2
+	out := RootNoise{Moves: make([]int32, capacity), Eta: make([]float32, capacity)}
+	var key C.uint64_t
+	var n C.int
+	if err := lastErr(C.agz_arena_root_noise(a.h, C.int(g), C.int(agent), &key, (*C.int32_t)(unsafe.Pointer(&out.Moves[0])),
+		(*C.float)(unsafe.Pointer(&out.Eta[0])), C.int(capacity), &n)); err != nil {
+		return RootNoise{}, err
+	}
+	k := int(n)
+	if k > capacity {
+		k = capacity
+	}
+	out.Key, out.Moves, out.Eta = uint64(key), out.Moves[:k], out.Eta[:k]
+	return out, nil
+}
+
+// RootNoiseOf is the same definition on the host: eta of the draw `key` over n children (agz_root_noise_of).
+func RootNoiseOf(key uint64, n int, alpha float32) ([]float32, error) {
+	if n < 1 {
+		n = 0
+	}
+	eta := make([]float32, n+1)
+	if err := lastErr(C.agz_root_noise_of(C.uint64_t(key), C.int(n), C.float(alpha), (*C.float)(unsafe.Pointer(&eta[0])))); err != nil {
+		return nil, err
+	}
+	return eta[:n], nil
+}
+
 // Save writes a checkpoint of the running arena — games, both trees of every game, RNG states, counters, recorded examples — between two
 // moves (agz_arena_save).  The file replaces `path` only once it is complete.
 func (a *BatchedArena) Save(path string) error {
@@ -643,6 +703,36 @@ func (t *MCTS) SetParallel(lanes int) error {
 func (t *MCTS) SetLeafSymmetry(mode int, seed uint64) error {
 	defer t.ctx.enter()()
 	return lastErr(C.agz_mcts_set_leaf_symmetry(t.h, C.int(mode), C.uint64_t(seed)))
+}
+
+// SetRootNoise: Dirichlet noise on the root priors of this tree's searches (see BatchedArena.SetRootNoise).  A second Search of the same
+// position with no move between keeps its priors and draws no new key.
+func (t *MCTS) SetRootNoise(eps, alpha float32, on bool) error {
+	defer t.ctx.enter()()
+	conf := C.agz_noise_conf{eps: C.float(eps), alpha: C.float(alpha)}
+	if on {
+		conf.on = 1
+	}
+	return lastErr(C.agz_mcts_set_root_noise(t.h, &conf))
+}
+
+// RootNoise returns the tree's last draw (no draw yet: no moves).
+func (t *MCTS) RootNoise() (RootNoise, error) {
+	defer t.ctx.enter()()
+	capacity := t.cells + 2
+	out := RootNoise{Moves: make([]int32, capacity), Eta: make([]float32, capacity)}
+	var key C.uint64_t
+	var n C.int
+	if err := lastErr(C.agz_mcts_root_noise(t.h, &key, (*C.int32_t)(unsafe.Pointer(&out.Moves[0])), (*C.float)(unsafe.Pointer(&out.Eta[0])),
+		C.int(capacity), &n)); err != nil {
+		return RootNoise{}, err
+	}
+	k := int(n)
+	if k > capacity {
+		k = capacity
+	}
+	out.Key, out.Moves, out.Eta = uint64(key), out.Moves[:k], out.Eta[:k]
+	return out, nil
 }
 
 // ship serialises t.current into an agz_state.

@@ -513,6 +513,45 @@ int agz_arena_set_leaf_symmetry(agz_arena* arena, int mode, uint64_t seed);
 int agz_symmetry_map(int m, int k, int32_t* src);
 int agz_symmetry_inverse(int k);
 int agz_leaf_symmetry_of(uint64_t seed, const int32_t* board, int cells, int to_move, int* k);
+/* BUILD EXTENSION (no mcts.Config field; DESIGN.md §2 root-noise): Dirichlet noise mixed into the ROOT priors of every search, the
+ * AlphaGo Zero exploration rule P(a) = (1 - eps) p(a) + eps eta(a), eta ~ Dir(alpha).  Opt-in, default off; off (or never called) is
+ * everything as without this call, bit for bit: no launch, no allocation, no read-back.  While on, every path that runs prepareRoot
+ * (agz_arena_begin_move, agz_arena_play, agz_arena_selfplay, agz_mcts_search) is followed by one launch that, per unfinished game and
+ * for the tree of the agent that searches this move, rewrites the priors of the root's children — only those: noise never reaches
+ * below a root.  Any inferencer kind, any game kind (c4 included), any lane count.
+ * The definition (one copy, csrc/noise.hpp; IEEE double + - * /, integer and bit operations only — no libm — so host, device and a
+ * restatement in any language with IEEE doubles agree bit for bit):
+ *   RNG       SplitMix64: s += 0x9E3779B97F4A7C15; z = s; z = (z^(z>>30))*0xBF58476D1CE4E5B9; z = (z^(z>>27))*0x94D049BB133111EB; z ^= z>>31
+ *   u01(z)    ((double)(z >> 12) + 0.5) * 2^-52
+ *   ln_b(x)   x = m 2^e from the bits, m in [1,2); if m > 1.4142135623730951: m *= 0.5, e += 1; s = (m-1)/(m+1), s2 = s*s;
+ *             acc = 0; for k = 12..0: acc = acc*s2 + 1.0/(2k+1); result e*0.6931471805599453 + (2.0*s)*acc
+ *   exp_b(y)  y <= 0: 0.0 if y < -700; t = y*1.4426950408889634 + 0.5, k = floor(t), r = y - k*0.6931471805599453;
+ *             acc = 1; for j = 16..1: acc = 1.0 + (acc*r)/j; result acc * 2^k
+ *   key       one SplitMix64 output of the tree's own stream (the one randomizeChildren draws from: seeded per tree, re-seeded when a
+ *             slot restarts, stored in arena checkpoints)
+ *   gamma_i   child i = position i of the root's child block as it stands after prepareRoot; stream: SplitMix64 from state
+ *             key + (i+1)*0xD1B54A32D192ED03.  Ahrens-Dieter GS (0 < alpha < 1): b = 1.0 + alpha/2.718281828459045; per round two
+ *             outputs u1, u2, p = b*u1; p <= 1: x = exp_b(ln_b(p)/alpha), accept if u2 <= exp_b(-x); else x = -ln_b((b-p)/alpha), accept
+ *             if u2 <= exp_b((alpha-1.0)*ln_b(x)); at most 64 rounds, then gamma_i = 0.  alpha == 1: gamma_i = -ln_b(u1), one output.
+ *             alpha is the double obtained from the float passed in
+ *   eta_i     (float)(gamma_i / S), S = gamma_0 + ... + gamma_{n-1} added in index order in double; S == 0: (float)(1.0/n)
+ *   prior'    fadd(fmul(1.0f - eps, prior), fmul(eps, eta_i)) in float, one rounding per operation
+ * A root without children gets nothing (no key is drawn; the observer reports n = 0).  A tree whose root already carries noise — a
+ * second agz_mcts_search of the same position with no move between — keeps its priors and draws no second key; the mark is cleared
+ * when a search gets a different root (re-rooted below the old one, or fresh).  Neither the setting nor the marks are stored in an arena
+ * checkpoint (AGZARN01 unchanged; a loaded arena starts with every mark clear and no recorded draw): re-apply the setting after
+ * agz_arena_load and the continuation is bit for bit.
+ * AGZ_E_INVALID, with the setting unchanged, unless on is 0 or 1, 0 <= eps <= 1, 0 < alpha <= 1 (both finite) and reserved == 0;
+ * AGZ_E_STATE inside a move. */
+typedef struct agz_noise_conf { float eps, alpha; int32_t on, reserved; } agz_noise_conf;  /* 16 bytes; defaults 0.25, 0.3, on = 0 */
+int agz_arena_set_root_noise(agz_arena* arena, const agz_noise_conf* conf);
+int agz_arena_get_root_noise(agz_arena* arena, agz_noise_conf* out);
+/* The last draw of `agent`'s tree in game g: its key and, per root child in the block order of that moment, the child's move and eta.
+ * *n = the number of children (0: no draw yet; key is then 0); min(cap, *n) entries are copied (moves / eta may be NULL). */
+int agz_arena_root_noise(agz_arena* arena, int g, int agent, uint64_t* key, int32_t* moves, float* eta, int cap, int* n);
+/* The same definition without a context or a device: eta[0..n) of the draw `key`.  AGZ_E_INVALID unless 1 <= n <= 4096,
+ * 0 < alpha <= 1 and eta != NULL. */
+int agz_root_noise_of(uint64_t key, int n, float alpha, float* eta);
 int agz_arena_begin_move(agz_arena* arena);
 int agz_arena_simulate(agz_arena* arena, int k);
 int agz_arena_end_move(agz_arena* arena, int record);
@@ -645,6 +684,9 @@ int agz_mcts_set_pool_policy(agz_mcts* mcts, int policy);
 int agz_mcts_set_parallel(agz_mcts* mcts, int lanes);
 /* leaf symmetry of a single tree (BUILD EXTENSION, see agz_arena_set_leaf_symmetry) */
 int agz_mcts_set_leaf_symmetry(agz_mcts* mcts, int mode, uint64_t seed);
+/* root noise of a single tree (BUILD EXTENSION, see agz_arena_set_root_noise); the observer reads THE tree's last draw */
+int agz_mcts_set_root_noise(agz_mcts* mcts, const agz_noise_conf* conf);
+int agz_mcts_root_noise(agz_mcts* mcts, uint64_t* key, int32_t* moves, float* eta, int cap, int* n);
 /* (*MCTS).SetGame (tree.go:120-124) */
 int agz_mcts_set_game(agz_mcts* mcts, const agz_state* st);
 /* (*MCTS).Search(player) (search.go:92-164): SetToMove(player), updateRoot, prepareRoot, Budget simulations, bestMove,
