@@ -7,11 +7,11 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-functi
 # engine.hip holds the bit-exact MCTS arithmetic: no fused multiply-add contraction (Go/amd64 never fuses)
 ENGINE_FLAGS := -ffp-contract=off
 
-SRCS := $(CS)/ctx.hip $(CS)/net.hip $(CS)/engine.hip $(CS)/train.hip $(CS)/examples.hip $(CS)/comm.hip
-OBJS := $(OUT)/ctx.o $(OUT)/net.o $(OUT)/engine.o $(OUT)/train.o $(OUT)/examples.o $(OUT)/comm.o
+SRCS := $(CS)/ctx.hip $(CS)/net.hip $(CS)/engine.hip $(CS)/train.hip $(CS)/examples.hip $(CS)/comm.hip $(CS)/replay.hip
+OBJS := $(OUT)/ctx.o $(OUT)/net.o $(OUT)/engine.o $(OUT)/train.o $(OUT)/examples.o $(OUT)/comm.o $(OUT)/replay.o
 HDRS := $(wildcard $(CS)/*.hpp) include/agz.h
 
-all: $(OUT)/libagz.so oracle tests/cpp/az_learn_ttt tests/cpp/gtp_main tests/fake_rccl/librccl_fake.so
+all: $(OUT)/libagz.so oracle tests/cpp/az_learn_ttt tests/cpp/az_learn_replay tests/cpp/gtp_main tests/fake_rccl/librccl_fake.so
 
 # TEST INFRASTRUCTURE: a process-per-rank stand-in for librccl (AGZ_RCCL_LIB) so the N > 1 exchange executes on a one-GPU box
 tests/fake_rccl/librccl_fake.so: tests/fake_rccl/fake_rccl.cpp
@@ -19,6 +19,10 @@ tests/fake_rccl/librccl_fake.so: tests/fake_rccl/fake_rccl.cpp
 
 # host-side C++ mirror of the reference API (agogo_amd/host/agogo.hpp) exercised over the C ABI
 tests/cpp/az_learn_ttt: tests/cpp/az_learn_ttt.cpp agogo_amd/host/agogo.hpp include/agz.h $(OUT)/libagz.so
+	g++ -std=c++17 -O1 -Iinclude $< -o $@ -L$(OUT) -lagz -Wl,-rpath,'$$ORIGIN/../../agogo_amd/lib'
+
+# AZ.Learn with a replay window (Config::ReplayWindow) over the C ABI
+tests/cpp/az_learn_replay: tests/cpp/az_learn_replay.cpp agogo_amd/host/agogo.hpp include/agz.h $(OUT)/libagz.so
 	g++ -std=c++17 -O1 -Iinclude $< -o $@ -L$(OUT) -lagz -Wl,-rpath,'$$ORIGIN/../../agogo_amd/lib'
 
 # GTP front end over the C ABI (agogo_amd/host/gtp.hpp)
@@ -38,6 +42,9 @@ $(OUT)/examples.o: $(CS)/examples.hip $(HDRS)
 	@mkdir -p $(OUT)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 $(OUT)/comm.o: $(CS)/comm.hip $(HDRS)
+	@mkdir -p $(OUT)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+$(OUT)/replay.o: $(CS)/replay.hip $(HDRS)
 	@mkdir -p $(OUT)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 $(OUT)/engine.o: $(CS)/engine.hip $(HDRS)

@@ -4,5 +4,5 @@ The product is the C-ABI shared library built from agogo_amd/csrc (see include/a
 package only binds it (ctypes) for tests and bench.py; there is no CPU fallback: without the HIP
 library and a GPU every compute entry point raises.
 """
-from .capi import (AgzError, Arena, Comm, Ctx, Examples, GameConf, Mcts, MctsConf, Net, NetConf, State, Trainer, lib, lib_path,  # noqa: F401
-                   rotate_boards, wino_h2_tile, wino_stages)
+from .capi import (AgzError, Arena, Comm, Ctx, Examples, GameConf, Mcts, MctsConf, Net, NetConf, Replay, State, Trainer, lib, lib_path,  # noqa: F401
+                   replay_draw, rotate_boards, wino_h2_tile, wino_stages)

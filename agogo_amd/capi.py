@@ -262,6 +262,18 @@ def lib():
     sig("agz_examples_tensors_dev", i32, vp, pvp, pvp, pvp, pi64, pi)
     sig("agz_examples_get_tensors", i32, vp, pf, pf, pf)
     sig("agz_examples_raw_dev", i32, vp, pvp, pvp, pvp)
+    sig("agz_replay_create", i32, vp, i32, i32, i32, i32, i64, pvp)
+    sig("agz_replay_destroy", None, vp)
+    sig("agz_replay_count", i32, vp, pi64, C.POINTER(C.c_uint64), pi64)
+    sig("agz_replay_clear", i32, vp)
+    sig("agz_replay_append_examples", i32, vp, vp)
+    sig("agz_replay_append_dev", i32, vp, vp, vp, vp, i64)
+    sig("agz_replay_append_host", i32, vp, pf, pf, pf, i64)
+    sig("agz_replay_get", i32, vp, i64, i64, pf, pf, pf)
+    sig("agz_replay_sample_dev", i32, vp, i32, u64, u64, i32, vp, vp, vp)
+    sig("agz_replay_sample", i32, vp, i32, u64, u64, i32, pf, pf, pf)
+    sig("agz_replay_draw", i32, u64, u64, i32, i64, i32, pi64, pi)
+    sig("agz_train_replay", i32, vp, vp, i32, u64, i32, pf)
     sig("agz_rotate_boards", i32, vp, pf, i32, i32, i32, pf)
     sig("agz_ctx_prof_set_stride", i32, vp, i32, i32)
     sig("agz_wino_stages", i32, vp, pf, pf, i32, i32, i32, i32, i32, pf, pf)
@@ -745,6 +757,14 @@ class Trainer:
         c = C.c_float(0)
         _check(lib().agz_train_dev(self.h, C.c_void_p(Xs_ptr), C.c_void_p(policies_ptr), C.c_void_p(values_ptr), batches,
                                    iterations, seed, C.byref(c)), "agz_train_dev")
+        return c.value
+
+    def train_replay(self, replay, steps, seed=1337, symmetric=False):
+        """dual.Train's loop over `steps` minibatches sampled from a Replay window (replay_draw(seed, step, BatchSize, len(replay))), each
+        sampled straight into the trainer's batch buffers on the device; returns the last step's cost"""
+        c = C.c_float(0)
+        _check(lib().agz_train_replay(self.h, replay.h if replay is not None else None, int(steps), int(seed) & (2 ** 64 - 1),
+                                      1 if symmetric else 0, C.byref(c)), "agz_train_replay")
         return c.value
 
     def export(self, net):
@@ -1289,6 +1309,98 @@ class Examples:
         v = np.zeros(rows, np.float32)
         _check(lib().agz_examples_get_tensors(self.h, _pf(x), _pf(p), _pf(v)), "agz_examples_get_tensors")
         return x, p, v
+
+
+class Replay:
+    """A sliding window over the most recent `capacity` examples on the device, and its sampler: minibatches drawn uniformly with
+    replacement, each row under a random board symmetry applied as it is drawn (agz_replay, include/agz.h).  Logical row 0 is the oldest."""
+
+    def __init__(self, ctx, Features, Height, Width, PolicyLen, capacity):
+        self.ctx = ctx
+        self.F, self.H, self.W, self.A1 = Features, Height, Width, PolicyLen
+        self.h = C.c_void_p()
+        _check(lib().agz_replay_create(ctx.h, Features, Height, Width, PolicyLen, int(capacity), C.byref(self.h)), "agz_replay_create")
+        ctx._adopt(self)
+
+    def close(self):
+        if self.h and self.ctx.h:
+            lib().agz_replay_destroy(self.h)
+        self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _count(self):
+        live, total, cap = C.c_int64(0), C.c_uint64(0), C.c_int64(0)
+        _check(lib().agz_replay_count(self.h, C.byref(live), C.byref(total), C.byref(cap)), "agz_replay_count")
+        return live.value, total.value, cap.value
+
+    def __len__(self):
+        """live rows: min(total, capacity)"""
+        return self._count()[0]
+
+    def total(self):
+        """rows ever appended"""
+        return self._count()[1]
+
+    @property
+    def capacity(self):
+        return self._count()[2]
+
+    def clear(self):
+        _check(lib().agz_replay_clear(self.h), "agz_replay_clear")
+
+    def append_examples(self, ex):
+        """the raw store of an Examples set, in append order, device to device; `ex` is unchanged"""
+        _check(lib().agz_replay_append_examples(self.h, ex.h), "agz_replay_append_examples")
+
+    def append_dev(self, planes_ptr, policy_ptr, value_ptr, n):
+        _check(lib().agz_replay_append_dev(self.h, C.c_void_p(planes_ptr), C.c_void_p(policy_ptr), C.c_void_p(value_ptr), n),
+               "agz_replay_append_dev")
+
+    def append_host(self, planes, policy, value):
+        p = np.ascontiguousarray(planes, np.float32)
+        q = np.ascontiguousarray(policy, np.float32)
+        v = np.ascontiguousarray(value, np.float32)
+        n = v.size
+        assert p.size == n * self.F * self.H * self.W and q.size == n * self.A1
+        _check(lib().agz_replay_append_host(self.h, _pf(p), _pf(q), _pf(v), n), "agz_replay_append_host")
+
+    def get(self, j0=0, cnt=None):
+        """logical rows [j0, j0 + cnt), oldest first (default: every live row)"""
+        if cnt is None:
+            cnt = len(self) - j0
+        p = np.zeros((max(cnt, 0), self.F * self.H * self.W), np.float32)
+        q = np.zeros((max(cnt, 0), self.A1), np.float32)
+        v = np.zeros(max(cnt, 0), np.float32)
+        _check(lib().agz_replay_get(self.h, int(j0), int(cnt), _pf(p), _pf(q), _pf(v)), "agz_replay_get")
+        return p, q, v
+
+    def sample(self, rows, seed, step=0, symmetric=False):
+        """minibatch `step` on the host: X [rows, F, H, W], Pi [rows, PolicyLen], V [rows]"""
+        x = np.zeros((max(rows, 1), self.F, self.H, self.W), np.float32)
+        p = np.zeros((max(rows, 1), self.A1), np.float32)
+        v = np.zeros(max(rows, 1), np.float32)
+        _check(lib().agz_replay_sample(self.h, int(rows), int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1), 1 if symmetric else 0,
+                                       _pf(x), _pf(p), _pf(v)), "agz_replay_sample")
+        return x, p, v
+
+    def sample_dev(self, rows, seed, step, symmetric, X_ptr, Pi_ptr, V_ptr):
+        """minibatch `step` into device buffers, asynchronous on the context's queue"""
+        _check(lib().agz_replay_sample_dev(self.h, int(rows), int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1), 1 if symmetric else 0,
+                                           C.c_void_p(X_ptr), C.c_void_p(Pi_ptr), C.c_void_p(V_ptr)), "agz_replay_sample_dev")
+
+
+def replay_draw(seed, step, rows, n, symmetric=True):
+    """(j [rows], k [rows]) of minibatch `step` over n live rows (replay.hpp; host only): the rows and symmetries Replay.sample draws"""
+    j = np.zeros(max(int(rows), 1), np.int64)
+    k = np.zeros(max(int(rows), 1), np.int32)
+    _check(lib().agz_replay_draw(int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1), int(rows), int(n), 1 if symmetric else 0,
+                                 j.ctypes.data_as(C.POINTER(C.c_int64)), _pi(k)), "agz_replay_draw")
+    return j[:int(rows)], k[:int(rows)]
 
 
 def wino_h2_chained(H, W, K):

@@ -9,6 +9,7 @@
 #include <numeric>
 
 #include "comm.hpp"
+#include "replay_win.hpp"
 #include "sym.hpp"
 
 namespace agz {
@@ -116,6 +117,10 @@ struct agz_examples {
     return AGZ_OK;
   }
 };
+
+agz::ExamplesInfo agz::examples_info(const agz_examples* e) {
+  return agz::ExamplesInfo{e->ctx, e->F, e->H, e->W, e->A1, e->planes, e->policy, e->value, (uint64_t)e->n};
+}
 
 extern "C" {
 

@@ -1,0 +1,29 @@
+// What train.hip needs of a replay window (replay.hip): its context, row shape and ring counters, and one sampler launch.
+#pragma once
+#include "common.hpp"
+
+struct agz_replay;
+struct agz_examples;
+
+namespace agz {
+struct ReplayInfo {
+  agz_ctx* ctx;
+  int F, H, W, A1;
+  uint64_t total, cap;
+};
+ReplayInfo replay_info(const agz_replay* rp);
+// enqueue ONE k_replay_sample on the window's context stream: minibatch `step` of `rows` rows drawn from the n live rows of the ring state
+// (total, cap), written to the device buffers X [rows, F*H*W], Pi [rows, A1], V [rows].  No synchronisation, nothing uploaded.
+int replay_sample_launch(agz_replay* rp, int rows, uint64_t seed, uint64_t step, int symmetric, uint64_t n, uint64_t total, float* X,
+                         float* Pi, float* V);
+// symmetric sampling needs a square board whose policy row holds every cell (the augmenter's preconditions and wording)
+int replay_check_symmetric(const agz_replay* rp, int symmetric, const char* who);
+// (examples.hip) the raw store of an example set as the window's agz_replay_append_examples reads it: rows in append order
+struct ExamplesInfo {
+  agz_ctx* ctx;
+  int F, H, W, A1;
+  const float *planes, *policy, *value;
+  uint64_t n;
+};
+ExamplesInfo examples_info(const agz_examples* ex);
+}  // namespace agz

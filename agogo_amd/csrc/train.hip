@@ -35,6 +35,7 @@
 #include "net.hpp"
 #include "conv_maps.hpp"
 #include "ckpt.hpp"
+#include "replay_win.hpp"
 #include "shard.hpp"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -3408,6 +3409,17 @@ int agz_train(agz_trainer* t, float* Xs, float* policies, float* values, int bat
   return AGZ_OK;
 }
 
+// one batch of dual.Train's loop (meta.go:33-40) on the trainer's own batch buffers, already filled on its stream: the fused step at
+// dual.Train's learn rate, then the solver on what the backward did not step itself.  Nothing is synchronised.
+static int train_step_on_batch(agz_trainer* t) {
+  t->fuse_lr = DUAL_TRAIN_LR;
+  int rc = t->step(t->d_planes, t->d_pi, t->d_v);
+  t->fused_done = rc == AGZ_OK;
+  t->fuse_lr = 0.f;
+  if (rc == AGZ_OK) rc = agz_trainer_apply(t, DUAL_TRAIN_LR, 1.0f);
+  return rc;
+}
+
 // dual.Train over DEVICE tensors (Xs [rows,F,H,W], policies [rows,A], values [rows], rows = batches*BatchSize — e.g.
 // agz_examples_tensors_dev).  Same loop and the same shuffleBatch stream as agz_train, but the shuffle permutes a row
 // index (4 B/row) instead of swapping rows, each batch is gathered device to device, and the cost is read back once at
@@ -3440,11 +3452,7 @@ int agz_train_dev(agz_trainer* t, const float* Xs_dev, const float* policies_dev
       hipLaunchKernelGGL(k_gather_rows_t, dim3(nblk((size_t)t->B * xs)), dim3(256), 0, s, Xs_dev, ib, t->d_planes, (int)xs, (size_t)t->B * xs);
       hipLaunchKernelGGL(k_gather_rows_t, dim3(nblk((size_t)t->B * ps)), dim3(256), 0, s, policies_dev, ib, t->d_pi, (int)ps, (size_t)t->B * ps);
       hipLaunchKernelGGL(k_gather_rows_t, dim3(nblk((size_t)t->B)), dim3(256), 0, s, values_dev, ib, t->d_v, 1, (size_t)t->B);
-      t->fuse_lr = DUAL_TRAIN_LR;
-      rc = t->step(t->d_planes, t->d_pi, t->d_v);
-      t->fused_done = rc == AGZ_OK;
-      t->fuse_lr = 0.f;
-      if (rc == AGZ_OK) rc = agz_trainer_apply(t, DUAL_TRAIN_LR, 1.0f);
+      rc = train_step_on_batch(t);
     }
     for (size_t i = 0; i < n; i++) {  // shuffleBatch (meta.go:57-102) on the row index
       size_t j = (size_t)(rng.next() % (uint64_t)(i + 1));
@@ -3461,6 +3469,36 @@ int agz_train_dev(agz_trainer* t, const float* Xs_dev, const float* policies_dev
   return AGZ_OK;
 }
 
+// dual.Train's loop over minibatches SAMPLED from a replay window (replay.hip; BUILD EXTENSION, DESIGN.md §2 replay-window): step s of the
+// run draws the trainer's BatchSize rows with replay::draw(seed, s, BatchSize, r, n, symmetric) straight into the trainer's batch buffers
+// (one k_replay_sample launch where agz_train_dev has three gathers) and takes the step agz_train_dev takes per batch.  n is read once, at
+// entry; nothing is uploaded and nothing waited for between steps; the cost is read back once at the end.
+int agz_train_replay(agz_trainer* t, agz_replay* rp, int steps, uint64_t seed, int symmetric, float* last_cost) {
+  AGZ_REQUIRE(t && rp && steps >= 0, AGZ_E_INVALID, "agz_train_replay: bad argument");
+  AGZ_REQUIRE(!t->sharded, AGZ_E_UNSUPPORTED, "agz_train_replay: a sharded trainer cannot train from a replay window yet");
+  const agz::ReplayInfo w = agz::replay_info(rp);
+  AGZ_REQUIRE(w.ctx == t->ctx, AGZ_E_INVALID, "agz_train_replay: the trainer and the window belong to different contexts");
+  AGZ_REQUIRE(w.F == t->conf.Features && w.H == t->conf.Height && w.W == t->conf.Width && w.A1 == t->conf.ActionSpace, AGZ_E_INVALID,
+              "agz_train_replay: the window's rows are [%d, %d, %d] + %d, the trainer's [%d, %d, %d] + %d", w.F, w.H, w.W, w.A1,
+              t->conf.Features, t->conf.Height, t->conf.Width, t->conf.ActionSpace);
+  int rc = agz::replay_check_symmetric(rp, symmetric, "agz_train_replay");
+  if (rc != AGZ_OK) return rc;
+  AGZ_REQUIRE(w.total > 0, AGZ_E_STATE, "agz_train_replay: the window is empty");
+  AGZ_HIP_TRY(hipSetDevice(t->ctx->device));
+  hipStream_t s = t->ctx->stream;
+  const uint64_t n = w.total < w.cap ? w.total : w.cap;
+  for (int st = 0; st < steps && rc == AGZ_OK; st++) {
+    rc = agz::replay_sample_launch(rp, t->B, seed, (uint64_t)st, symmetric, n, w.total, t->d_planes, t->d_pi, t->d_v);
+    if (rc == AGZ_OK) rc = train_step_on_batch(t);
+  }
+  float c[2] = {0, 0};
+  hipError_t e = hipMemcpyAsync(c, t->cost, 8, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (rc != AGZ_OK) return rc;
+  AGZ_HIP_TRY(e);
+  if (last_cost) *last_cost = steps > 0 ? c[0] + c[1] : 0.f;
+  return AGZ_OK;
+}
 
 // ---- running BatchNorm statistics (BnTrack above; include/agz.h) --------------------------------------------------------------------------
 using agz::ckpt::bn_momentum_valid;

@@ -124,6 +124,12 @@ inline float TrainDev(Trainable& d, const float* Xs_dev, const float* policies_d
   agz::check(agz_train_dev(d.h, Xs_dev, policies_dev, values_dev, batches, iterations, seed, &cost), "dual.Train");
   return cost;
 }
+// build extension: dual.Train's loop over `steps` minibatches sampled from a replay window (agogo::Replay), on the device
+inline float TrainReplay(Trainable& d, agz_replay* window, int steps, uint64_t seed, bool symmetric) {
+  float cost = 0;
+  agz::check(agz_train_replay(d.h, window, steps, seed, symmetric ? 1 : 0, &cost), "dual.Train");
+  return cost;
+}
 }  // namespace dual
 
 namespace mcts {
@@ -228,6 +234,19 @@ struct Examples {
     return b;
   }
 };
+// build extension: a sliding window over the most recent `capacity` examples, kept on the device across epochs (agz_replay): minibatches
+// are drawn from it uniformly, each row under a random board symmetry applied as it is drawn (dual::TrainReplay)
+struct Replay {
+  agz_replay* h = nullptr;
+  Replay(agz::Ctx& ctx, int F, int H, int W, int policyLen, int64_t capacity) {
+    agz::check(agz_replay_create(ctx.h, F, H, W, policyLen, capacity, &h), "Replay");
+  }
+  ~Replay() { agz_replay_destroy(h); }
+  Replay(const Replay&) = delete;
+  Replay& operator=(const Replay&) = delete;
+  size_t size() const { int64_t n = 0; agz::check(agz_replay_count(h, &n, nullptr, nullptr), "len(window)"); return (size_t)n; }   // live rows
+  void Append(Examples& ex) { agz::check(agz_replay_append_examples(h, ex.h), "append(window, ex...)"); }
+};
 // agogo.Config (datatypes.go:14-25)
 struct Config {
   std::string Name;
@@ -251,6 +270,13 @@ struct Config {
   // build extension: the options of the solver dual.Train builds (agz_trainer_set_solver); all 0 (default) = the reference's vanilla solver.
   // Applied to A, B and every newB.
   agz_solver_conf Solver = {0.f, 0.f, 0.f, 0};
+  // build extension: train from a replay window instead of one epoch's examples.  ReplayWindow = rows the window keeps across epochs; 0
+  // (default) = off, AZ.Learn exactly as the reference has it.  ReplaySteps = minibatches per epoch; 0 = (live rows / BatchSize) * nniters.
+  // ReplaySymmetric = every sampled row under one of the eight board symmetries, chosen per draw; the materialising augmenters
+  // (AugmentRotate / AugmentDihedral) are then not applied.  MaxExamples is not applied either: the window is the cut.
+  int64_t ReplayWindow = 0;
+  int ReplaySteps = 0;
+  bool ReplaySymmetric = false;
   // test hooks (not in the reference): inferencers of the self-play games once the dummy is no longer in use, and of the evaluation
   // games — AGZ_INF_NET plays the networks as the reference does; the synthetic kinds make an epoch's games independent of fp32 rounding
   // in a network evaluation (tests/test_learn_parity_gpu.py compares the epoch log with oracle/learn.hpp)
@@ -279,7 +305,9 @@ struct AZ {
   std::unique_ptr<dual::Dual> infA, infB;     // SwitchToInference products (agent.go:42-57)
   bool useDummy = true;
   uint64_t seed;
-  struct EpochStats { int epoch; size_t examples; int batches; float cost; long a_wins, b_wins, draws; bool killedA; int a_id; };
+  // (window, steps: the replay window's live rows after this epoch's append and the minibatches trained on; 0 without a window)
+  struct EpochStats { int epoch; size_t examples; int batches; float cost; long a_wins, b_wins, draws; bool killedA; int a_id; size_t window; int steps; };
+  std::unique_ptr<Replay> window;              // Config::ReplayWindow > 0: one window across epochs
   std::vector<EpochStats> log;
   Statistics stats;
   int a_id = 1, b_id = 2, next_id = 3;         // network identities (the reference's %p of Agent.NN)
@@ -290,6 +318,7 @@ struct AZ {
     A.reset(new dual::Trainable(ctx, cf.NNConf)); A->Init(seed * 3 + 1); applySolver(*A);
     B.reset(new dual::Trainable(ctx, cf.NNConf)); B->Init(seed * 3 + 2); applySolver(*B);
     infA.reset(new dual::Dual(ctx, cf.NNConf)); infB.reset(new dual::Dual(ctx, cf.NNConf));
+    if (cf.ReplayWindow > 0) window.reset(new Replay(ctx, cf.NNConf.Features, cf.NNConf.Height, cf.NNConf.Width, cf.NNConf.ActionSpace, cf.ReplayWindow));
   }
   void applySolver(dual::Trainable& t) const {   // (the default options leave the trainer untouched: no call)
     if (conf.Solver.momentum != 0.f || conf.Solver.l2reg != 0.f || conf.Solver.clip != 0.f) t.SetSolver(conf.Solver.momentum, conf.Solver.l2reg, conf.Solver.clip);
@@ -313,16 +342,26 @@ struct AZ {
         sp.PlayOnDevice(true);                                            // episodes x SelfPlay(), agogo.go:110-114
         ex.Append(sp);                                                     // device to device, episode after episode
       }
-      if (conf.AugmentDihedral) ex.AugmentDihedral();
-      else if (conf.AugmentRotate) ex.AugmentRotate();                     // Arena.Play's aug(ex), arena.go:115-120
+      const bool sampled_sym = window && conf.ReplaySymmetric;             // the sampler applies the symmetries: nothing is materialised
+      if (conf.AugmentDihedral && !sampled_sym) ex.AugmentDihedral();
+      else if (conf.AugmentRotate && !sampled_sym) ex.AugmentRotate();     // Arena.Play's aug(ex), arena.go:115-120
       st.examples = ex.size();
-      // maxExamples cut (agogo.go:118-121) + prepareExamples (agogo.go:211-249), tensors stay in HBM
-      int batches = ex.Prepare(conf.NNConf.BatchSize, conf.MaxExamples, seed + 13 * epoch + 1);
-      if (batches == 0) throw agz::Error("batches is nil, probably too few examples regarding the batchsize");  // agogo.go:123-125
-      st.batches = batches;
-      float *Xs = nullptr, *Pi = nullptr, *V = nullptr;
-      agz::check(agz_examples_tensors_dev(ex.h, &Xs, &Pi, &V, nullptr, nullptr), "prepareExamples");
-      st.cost = dual::TrainDev(*B, Xs, Pi, V, batches, nniters, seed + 17 * epoch);  // agogo.go:133
+      if (window) {
+        window->Append(ex);                                                // the epoch's examples join the window, the oldest rows leave it
+        st.window = window->size();
+        st.batches = (int)(st.window / (size_t)conf.NNConf.BatchSize);
+        st.steps = conf.ReplaySteps > 0 ? conf.ReplaySteps : st.batches * nniters;
+        if (st.steps == 0) throw agz::Error("batches is nil, probably too few examples regarding the batchsize");
+        st.cost = dual::TrainReplay(*B, window->h, st.steps, seed + 17 * epoch, conf.ReplaySymmetric);
+      } else {
+        // maxExamples cut (agogo.go:118-121) + prepareExamples (agogo.go:211-249), tensors stay in HBM
+        int batches = ex.Prepare(conf.NNConf.BatchSize, conf.MaxExamples, seed + 13 * epoch + 1);
+        if (batches == 0) throw agz::Error("batches is nil, probably too few examples regarding the batchsize");  // agogo.go:123-125
+        st.batches = batches;
+        float *Xs = nullptr, *Pi = nullptr, *V = nullptr;
+        agz::check(agz_examples_tensors_dev(ex.h, &Xs, &Pi, &V, nullptr, nullptr), "prepareExamples");
+        st.cost = dual::TrainDev(*B, Xs, Pi, V, batches, nniters, seed + 17 * epoch);  // agogo.go:133
+      }
       B->SwitchToInference(*infB);                                         // agogo.go:137
       {
         Arena ev(ctx, game.kind, game.m, game.n, game.k, game.komi, conf.Encoder, conf.MCTSConf, arenaGames, seed + 1000 * epoch + 500);

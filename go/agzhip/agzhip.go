@@ -321,6 +321,38 @@ func (e *Examples) Prepare(batchSize, maxExamples int, seed uint64) (int, error)
 
 func (e *Examples) Close() error { defer e.ctx.enter()(); C.agz_examples_destroy(e.h); e.h = nil; return nil }
 
+// Replay is a sliding window over the most recent `capacity` examples, kept in HBM across epochs (agz_replay): TrainReplay draws its
+// minibatches from it uniformly with replacement, each row under a random board symmetry applied as it is drawn.
+type Replay struct {
+	ctx *Ctx
+	h   *C.agz_replay
+}
+
+func NewReplay(ctx *Ctx, features, height, width, policyLen int, capacity int64) (*Replay, error) {
+	defer ctx.enter()()
+	r := &Replay{ctx: ctx}
+	if err := lastErr(C.agz_replay_create(ctx.h, C.int(features), C.int(height), C.int(width), C.int(policyLen), C.int64_t(capacity), &r.h)); err != nil {
+		return nil, err
+	}
+	return r, nil
+}
+
+// AppendExamples appends the raw rows of an Examples set in their order, device to device; the oldest rows leave a full window.
+func (r *Replay) AppendExamples(ex *Examples) error {
+	defer r.ctx.enter()()
+	return lastErr(C.agz_replay_append_examples(r.h, ex.h))
+}
+
+// Len is the number of live rows: min(rows ever appended, capacity).
+func (r *Replay) Len() (int64, error) {
+	defer r.ctx.enter()()
+	var live C.int64_t
+	err := lastErr(C.agz_replay_count(r.h, &live, nil, nil))
+	return int64(live), err
+}
+
+func (r *Replay) Close() error { defer r.ctx.enter()(); C.agz_replay_destroy(r.h); r.h = nil; return nil }
+
 // ---- tournament use: Agent.Search against an outside opponent (agent.go:76-81, BASELINE configs[4]) ----
 // The game state and both trees live on the device.  Search() = mcts.Search for the side to move (begin_move, Budget
 // simulations, end_move): it returns the chosen move and plays it.  Opponent(move) applies the outside player's reply
@@ -941,6 +973,18 @@ func (t *Trainer) TrainDev(ex *Examples, iterations int, seed uint64) error {
 	}
 	var cost C.float
 	return lastErr(C.agz_train_dev(t.h, xs, pi, v, batches, C.int(iterations), C.uint64_t(seed), &cost))
+}
+
+// TrainReplay is dual.Train's loop over `steps` minibatches sampled from a Replay window on the device; symmetric: every sampled row under
+// one of the eight board symmetries.  Not available on a sharded trainer.
+func (t *Trainer) TrainReplay(w *Replay, steps int, seed uint64, symmetric bool) error {
+	defer t.ctx.enter()()
+	sym := C.int(0)
+	if symmetric {
+		sym = 1
+	}
+	var cost C.float
+	return lastErr(C.agz_train_replay(t.h, w.h, C.int(steps), C.uint64_t(seed), sym, &cost))
 }
 
 // Export is dual.Infer's copy loop (meta.go:141-146): row 0 of every learnable into an inference Net.

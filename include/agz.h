@@ -764,6 +764,55 @@ int agz_rotate_boards(agz_ctx* ctx, const float* boards, int count, int m, int n
 /* S_k (agz_arena_set_leaf_symmetry) on `count` boards of m x m floats (host buffers; runs on the device). k < 4: RotateBoard k times. */
 int agz_symmetry_boards(agz_ctx* ctx, const float* boards, int count, int m, int k, float* out);
 
+/* ---- replay window on device (BUILD EXTENSION, DESIGN.md §2 replay-window) --------------------------------------------------
+ * The standard AlphaZero arrangement around dual.Train, which AZ.Learn (agogo.go:100-172) does not have: a sliding window over the most
+ * recent `capacity` examples, minibatches drawn uniformly from it with replacement, each row under a random board symmetry applied as it
+ * is drawn (nothing is materialised: agz_examples_augment_dihedral holds eight copies of every row).  Off unless used; agz_examples_* and
+ * agz_train_dev are untouched by it.
+ * Storage: a ring of `capacity` rows in the row format of agz_examples (planes [F*H*W], policy [PolicyLen], value; fp32), three device
+ * arrays allocated once at create.  total = rows ever appended, live = min(total, capacity); logical row j (0 = the oldest live row) sits in
+ * slot (total - live + j) mod capacity; an append writes slot total mod capacity, then total++.
+ * The draw (agogo_amd/csrc/replay.hpp, one host/device definition): out(seed, i) = the i-th output (from 0) of the build's SplitMix64
+ * seeded with `seed`.  Row r of minibatch `step` (every minibatch `rows` rows) is draw q = step * rows + r (uint64) and uses z0 =
+ * out(seed, 2q), z1 = out(seed, 2q + 1): j = (z0 * live) >> 64 (128-bit product), k = z1 >> 61 if symmetric else 0.  A whole run is one
+ * sequential SplitMix64 stream, two outputs per row; symmetric on or off draws the same rows.
+ * Tests: tests/test_replay_cpu.py, tests/test_replay_gpu.py, tests/test_replay_learn_gpu.py. */
+typedef struct agz_replay agz_replay;
+/* capacity < 1 or a bad shape: AGZ_E_INVALID.  The device cannot hold the ring: AGZ_E_NOMEM, nothing stays allocated. */
+int agz_replay_create(agz_ctx* ctx, int Features, int Height, int Width, int PolicyLen, int64_t capacity, agz_replay** out);
+void agz_replay_destroy(agz_replay* rp);
+/* any of the three may be NULL */
+int agz_replay_count(const agz_replay* rp, int64_t* live, uint64_t* total, int64_t* capacity);
+/* empties the window (total = 0); the storage stays */
+int agz_replay_clear(agz_replay* rp);
+/* Appends.  n rows are n single-row appends in order: with n > capacity only the last `capacity` rows survive (total still grows by n).
+ * append_examples: the raw store of `ex` in append order, device to device on the context's queue; `ex` is unchanged and must live on the
+ * window's context with the window's shape (AGZ_E_INVALID otherwise).  append_dev: device buffers, asynchronous.  append_host: host
+ * buffers, returns when they have been read. */
+int agz_replay_append_examples(agz_replay* rp, agz_examples* ex);
+int agz_replay_append_dev(agz_replay* rp, const float* planes_dev, const float* policy_dev, const float* value_dev, int64_t n);
+int agz_replay_append_host(agz_replay* rp, const float* planes, const float* policy, const float* value, int64_t n);
+/* read back logical rows [j0, j0 + cnt), oldest first (tests / host-side consumers); any buffer may be NULL.  AGZ_E_INVALID unless
+ * 0 <= j0, 0 <= cnt, j0 + cnt <= live. */
+int agz_replay_get(agz_replay* rp, int64_t j0, int64_t cnt, float* planes, float* policy, float* value);
+/* Minibatch `step` of `rows` rows, ONE kernel launch that computes (j, k) of every row itself — no index array, no synchronisation:
+ * X [rows, F, H, W] = S_k of the planes of window row j, Pi [rows, PolicyLen] = S_k of its policy's board part with the pass entry (and
+ * anything after it) copied, V [rows] = its value; S_k as in agz_symmetry_map.  sample_dev: device buffers, asynchronous on the context's
+ * queue.  sample: host buffers.  rows < 1: AGZ_E_INVALID.  symmetric != 0 needs Height == Width and PolicyLen >= Height * Width
+ * (AGZ_E_INVALID with agz_examples_augment_rotate's messages).  An empty window: AGZ_E_STATE. */
+int agz_replay_sample_dev(agz_replay* rp, int rows, uint64_t seed, uint64_t step, int symmetric, float* X_dev, float* Pi_dev, float* V_dev);
+int agz_replay_sample(agz_replay* rp, int rows, uint64_t seed, uint64_t step, int symmetric, float* X, float* Pi, float* V);
+/* The same draw without a context or a device: j[r] in [0, n) and k[r] for the `rows` rows of minibatch `step` over n live rows (either
+ * array may be NULL, not both).  AGZ_E_INVALID unless rows >= 1 and n >= 1. */
+int agz_replay_draw(uint64_t seed, uint64_t step, int rows, int64_t n, int symmetric, int64_t* j, int32_t* k);
+/* dual.Train's loop over sampled minibatches: for step = 0 .. steps - 1, minibatch `step` of BatchSize rows is sampled straight into the
+ * trainer's batch buffers and the trainer takes exactly the step agz_train_dev takes per batch (learn rate 0.1, the solver options / Adam
+ * that are set).  live is read once at entry; no host synchronisation between steps; the cost of the last step is read back at the end
+ * (last_cost may be NULL; 0 when steps == 0).  The trainer and the window must share a context and a shape (AGZ_E_INVALID); an empty
+ * window is AGZ_E_STATE; a SHARDED trainer (agz_trainer_create_sharded / _sharded_tied) is AGZ_E_UNSUPPORTED: multi-GPU windows are not
+ * built yet. */
+int agz_train_replay(agz_trainer* t, agz_replay* rp, int steps, uint64_t seed, int symmetric, float* last_cost);
+
 /* ---- multi-GPU exchange over RCCL / xGMI -------------------------------------------------------------------
  * Self-play games shard across GPUs with NO data-path collective (one agz_ctx + arena set per GPU).  The path has exactly
  * two exchange steps, both around dual.Train: the union of all ranks' examples (agogo.go:110-133: `ex` holds every episode
