@@ -263,6 +263,10 @@ def lib():
     sig("agz_examples_get_tensors", i32, vp, pf, pf, pf)
     sig("agz_examples_raw_dev", i32, vp, pvp, pvp, pvp)
     sig("agz_replay_create", i32, vp, i32, i32, i32, i32, i64, pvp)
+    sig("agz_replay_create_packed", i32, vp, i32, i32, i32, i32, i64, pf, i32, pvp)
+    sig("agz_encoder_palette", i32, i32, pf, pi)
+    sig("agz_replay_pack_host", i32, pf, i64, i32, i32, pf, i32, pu, pi64)
+    sig("agz_replay_storage", i32, vp, pi, pi64, pi64)
     sig("agz_replay_destroy", None, vp)
     sig("agz_replay_count", i32, vp, pi64, C.POINTER(C.c_uint64), pi64)
     sig("agz_replay_clear", i32, vp)
@@ -1313,14 +1317,27 @@ class Examples:
 
 class Replay:
     """A sliding window over the most recent `capacity` examples on the device, and its sampler: minibatches drawn uniformly with
-    replacement, each row under a random board symmetry applied as it is drawn (agz_replay, include/agz.h).  Logical row 0 is the oldest."""
+    replacement, each row under a random board symmetry applied as it is drawn (agz_replay, include/agz.h).  Logical row 0 is the oldest.
+    With a `palette` (1 to 4 float32 values taken as bit patterns, e.g. encoder_palette(enc)) the planes are kept as 2-bit codes
+    (agz_replay_create_packed): appends then take all rows or none, a cell outside the palette raises AgzError."""
 
-    def __init__(self, ctx, Features, Height, Width, PolicyLen, capacity):
+    def __init__(self, ctx, Features, Height, Width, PolicyLen, capacity, palette=None):
         self.ctx = ctx
         self.F, self.H, self.W, self.A1 = Features, Height, Width, PolicyLen
         self.h = C.c_void_p()
-        _check(lib().agz_replay_create(ctx.h, Features, Height, Width, PolicyLen, int(capacity), C.byref(self.h)), "agz_replay_create")
+        if palette is None:
+            _check(lib().agz_replay_create(ctx.h, Features, Height, Width, PolicyLen, int(capacity), C.byref(self.h)), "agz_replay_create")
+        else:
+            pal = np.ascontiguousarray(palette, np.float32).ravel()
+            _check(lib().agz_replay_create_packed(ctx.h, Features, Height, Width, PolicyLen, int(capacity), _pf(pal), int(pal.size),
+                                                  C.byref(self.h)), "agz_replay_create_packed")
         ctx._adopt(self)
+
+    def storage(self):
+        """(packed, row_bytes, device_bytes): the kind of the window, the bytes of one stored row and of the whole ring on the device"""
+        packed, row, dev = C.c_int32(0), C.c_int64(0), C.c_int64(0)
+        _check(lib().agz_replay_storage(self.h, C.byref(packed), C.byref(row), C.byref(dev)), "agz_replay_storage")
+        return bool(packed.value), row.value, dev.value
 
     def close(self):
         if self.h and self.ctx.h:
@@ -1401,6 +1418,30 @@ def replay_draw(seed, step, rows, n, symmetric=True):
     _check(lib().agz_replay_draw(int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1), int(rows), int(n), 1 if symmetric else 0,
                                  j.ctypes.data_as(C.POINTER(C.c_int64)), _pi(k)), "agz_replay_draw")
     return j[:int(rows)], k[:int(rows)]
+
+
+def encoder_palette(encoder):
+    """the bit patterns an encoder's planes hold, as float32 (agz_encoder_palette; host only): a packed Replay's palette"""
+    pal = np.zeros(4, np.float32)
+    n = C.c_int32(0)
+    _check(lib().agz_encoder_palette(int(encoder), _pf(pal), C.byref(n)), "agz_encoder_palette")
+    return pal[:n.value]
+
+
+def replay_pack_host(planes, Features, cells, palette, validate_only=False):
+    """(words [n, Features * ((cells + 15) // 16)] uint32 or None, first_bad) of n rows of planes under a palette (replay_pack.hpp through
+    agz_replay_pack_host; host only).  first_bad is -1, or the smallest linear element index outside the palette; words is then None."""
+    p = np.ascontiguousarray(planes, np.float32)
+    pal = np.ascontiguousarray(palette, np.float32).ravel()
+    n = p.size // (Features * cells)
+    assert p.size == n * Features * cells
+    words = None if validate_only else np.zeros((n, Features * ((cells + 15) // 16)), np.uint32)
+    bad = C.c_int64(-1)
+    r = lib().agz_replay_pack_host(_pf(p), n, int(Features), int(cells), _pf(pal), int(pal.size),
+                                   None if words is None else words.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(bad))
+    if r != 0 and bad.value < 0:
+        _check(r, "agz_replay_pack_host")
+    return (words if r == 0 else None), bad.value
 
 
 def wino_h2_chained(H, W, K):

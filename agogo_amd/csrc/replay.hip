@@ -2,12 +2,15 @@
 // replay-window).  The standard AlphaZero arrangement around dual.Train: a ring of recent positions, minibatches drawn uniformly from it
 // with replacement, each row under a random board symmetry applied AS IT IS DRAWN — no materialised copies (agz_examples_augment_dihedral
 // holds eight), no index array and no host synchronisation per minibatch.  The draw and the ring arithmetic are replay.hpp's, the eight maps
-// sym.hpp's.  Rows are agz_examples rows: planes [F*H*W], policy [PolicyLen], value, fp32.
+// sym.hpp's.  Rows are agz_examples rows: planes [F*H*W], policy [PolicyLen], value, fp32 — or, in a window made by
+// agz_replay_create_packed, the planes as 2-bit codes under a palette (replay_pack.hpp), decoded by the sampler as it draws.
 #include <algorithm>
+#include <cstring>
 #include <vector>
 
 #include "replay_win.hpp"   // (hip_runtime.h first: replay.hpp's device half uses __umul64hi)
 #include "replay.hpp"
+#include "replay_pack.hpp"
 #include "sym.hpp"
 
 namespace agz {
@@ -57,6 +60,108 @@ __global__ __launch_bounds__(REPLAY_THREADS) void k_replay_sample(const float* _
   }
 }
 
+// ---- packed windows (agz_replay_create_packed, DESIGN.md §2 replay-packed; the layout is replay_pack.hpp's) -----------------------------
+
+constexpr uint64_t PACK_NONE = ~0ull;   // "no bad cell" in chk[1]
+constexpr size_t PACK_STAGING_BYTES = (size_t)8 << 20;   // host rows go up to the device through at most this much staging (at least one row)
+
+// Validation of an append: chk[0] += the elements of src[0, n) whose bit pattern is not in the palette, chk[1] = min(chk[1], the first
+// such element).  A lane touches chk only if it met a bad element, so a clean append costs no atomic at all.
+__global__ __launch_bounds__(REPLAY_THREADS) void k_replay_pack_check(const uint32_t* __restrict__ src, uint64_t n, uint32_t p0, uint32_t p1,
+                                                                      uint32_t p2, uint32_t p3, int n_pal,
+                                                                      unsigned long long* __restrict__ chk) {
+  unsigned long long bad = 0, first = PACK_NONE;
+  const uint64_t stride = (uint64_t)gridDim.x * REPLAY_THREADS;
+  for (uint64_t i = (uint64_t)blockIdx.x * REPLAY_THREADS + threadIdx.x; i < n; i += stride) {
+    if (replay_pack::code_of(p0, p1, p2, p3, n_pal, src[i]) < 0) {
+      bad++;
+      if (i < first) first = i;
+    }
+  }
+  if (bad) {
+    atomicAdd(&chk[0], bad);
+    atomicMin(&chk[1], first);
+  }
+}
+
+// Source rows [0, rows) of `src` ([rows][F * mm] bit patterns, every one in the palette) into the ring slots (slot0 + r) mod cap: at most
+// two contiguous slot ranges.  A row is walked in its PADDED index t = (f * wpp + w) * 16 + i, cell c = w * 16 + i of plane f: lanes read
+// consecutive cells of a plane (coalesced), the 16 lanes of a word OR their shifted codes together by four xor-shuffles and lane i == 0
+// writes the word whole — no atomics on the store, the same words whatever the launch geometry.  Cells past mm contribute zero bits.
+// Every lane of a wavefront runs every iteration (the loop bound is the workgroup's), as the shuffles need.
+__global__ __launch_bounds__(REPLAY_THREADS) void k_replay_pack(const uint32_t* __restrict__ src, uint32_t* __restrict__ packed, int F,
+                                                                int mm, int wpp, int rows, uint64_t slot0, uint64_t cap, uint32_t p0,
+                                                                uint32_t p1, uint32_t p2, uint32_t p3, int n_pal) {
+  const int row_words = F * wpp;
+  const int64_t padded = (int64_t)row_words * replay_pack::CODES_PER_WORD;
+  const size_t xs = (size_t)F * mm;
+  for (int r = (int)blockIdx.y; r < rows; r += (int)gridDim.y) {
+    const uint32_t* in = src + (size_t)r * xs;
+    uint32_t* out = packed + (size_t)((slot0 + (uint64_t)r) % cap) * row_words;
+    for (int64_t base = (int64_t)blockIdx.x * REPLAY_THREADS; base < padded; base += (int64_t)gridDim.x * REPLAY_THREADS) {
+      const int64_t t = base + threadIdx.x;
+      const int word = (int)(t >> 4), i = (int)(t & 15);
+      const int f = word / wpp, c = (word - f * wpp) * replay_pack::CODES_PER_WORD + i;
+      uint32_t bits = 0;
+      if (t < padded && c < mm) {
+        const int code = replay_pack::code_of(p0, p1, p2, p3, n_pal, in[(size_t)f * mm + c]);
+        bits = (uint32_t)(code < 0 ? 0 : code) << replay_pack::shift_of(c);   // (validated before the launch: never < 0)
+      }
+      bits |= (uint32_t)__shfl_xor((int)bits, 1);
+      bits |= (uint32_t)__shfl_xor((int)bits, 2);
+      bits |= (uint32_t)__shfl_xor((int)bits, 4);
+      bits |= (uint32_t)__shfl_xor((int)bits, 8);
+      if (i == 0 && t < padded) out[word] = bits;
+    }
+  }
+}
+
+// k_replay_sample on a packed window: the same contract, grid and draw.  A plane element is one LDS read (the symmetry's source cell),
+// one read of the source cell's word — word (src >> 4) of the SAME plane, straight from global memory: 16 neighbouring cells share a word
+// and a 19x19 plane is 92 bytes, so the reads of a wavefront fall into one or two cache lines — a shift, two levels of selects on the
+// code bits over the palette (four uint32 kernel arguments, no table in memory) and one coalesced write.  Every output goes through a
+// uint32 view of the float buffers: a NaN entry arrives with its payload.  Algorithmic bytes per row: F * wpp * 4 + (A1 + 1) * 4 read,
+// (F * mm + A1 + 1) * 4 written.
+__global__ __launch_bounds__(REPLAY_THREADS) void k_replay_sample_packed(const uint32_t* __restrict__ packed,
+                                                                         const uint32_t* __restrict__ policy,
+                                                                         const uint32_t* __restrict__ value, uint32_t* __restrict__ X,
+                                                                         uint32_t* __restrict__ Pi, uint32_t* __restrict__ V, int F, int m,
+                                                                         int mm, int wpp, int A1, int rows, uint64_t seed, uint64_t step,
+                                                                         int symmetric, uint64_t n, uint64_t total, uint64_t cap,
+                                                                         uint32_t p0, uint32_t p1, uint32_t p2, uint32_t p3) {
+  __shared__ int tab[REPLAY_TAB];
+  const int xs = F * mm, row = xs + A1 + 1;
+  const int e0 = (int)blockIdx.x * REPLAY_SEG;
+  const int e1 = min(e0 + REPLAY_SEG, row);
+  for (int r = (int)blockIdx.y; r < rows; r += (int)gridDim.y) {
+    const replay::Draw d = replay::draw(seed, step, rows, r, n, symmetric != 0);
+    const size_t s = (size_t)replay::slot(total, cap, d.j);
+    const bool mapped = d.k != 0;     // (the host refuses symmetric sampling unless the board is square and mm <= REPLAY_TAB)
+    if (mapped) {
+      for (int c = (int)threadIdx.x; c < mm; c += REPLAY_THREADS) tab[c] = sym::src(m, d.k, c);
+      __syncthreads();
+    }
+    const uint32_t* in_w = packed + s * (size_t)F * wpp;
+    const uint32_t* in_p = policy + s * (size_t)A1;
+    uint32_t* out_x = X + (size_t)r * xs;
+    uint32_t* out_p = Pi + (size_t)r * A1;
+    for (int e = e0 + (int)threadIdx.x; e < e1; e += REPLAY_THREADS) {
+      if (e < xs) {
+        const int pl = e / mm, c = e - pl * mm;
+        const int src = mapped ? tab[c] : c;
+        const uint32_t code = in_w[pl * wpp + (src >> 4)] >> replay_pack::shift_of(src);
+        out_x[e] = replay_pack::decode(p0, p1, p2, p3, code);
+      } else if (e < xs + A1) {
+        const int c = e - xs;
+        out_p[c] = in_p[(mapped && c < mm) ? tab[c] : c];
+      } else {
+        V[r] = value[s];
+      }
+    }
+    if (mapped) __syncthreads();      // the table is rewritten for the next row of this workgroup
+  }
+}
+
 }  // namespace agz
 
 using namespace agz;
@@ -67,19 +172,110 @@ struct agz_replay {
   size_t xs = 0;
   float *planes = nullptr, *policy = nullptr, *value = nullptr;   // [cap][xs], [cap][A1], [cap]
   uint64_t cap = 0, total = 0;
+  // a packed window (agz_replay_create_packed): `planes` stays NULL, the planes live in `words` [cap][F * wpp] under `pal`
+  bool is_packed = false;
+  uint32_t* words = nullptr;
+  int wpp = 0;
+  replay_pack::Palette pal{};
 
   uint64_t live() const { return replay::live(total, cap); }
+  size_t row_words() const { return (size_t)F * wpp; }
+  size_t row_bytes() const { return ((is_packed ? row_words() : xs) + (size_t)A1 + 1) * 4; }
+
+  // A packed append takes all rows or none: every one of the c rows of p (device memory unless kind is host to device) is checked against
+  // the palette before anything is written.  One 16-byte read-back: the context's queue is synchronised once.
+  int validate(const float* p, uint64_t c, hipMemcpyKind kind, const char* who) {
+    const uint64_t nel = c * xs;
+    uint64_t first = PACK_NONE;
+    uint32_t bits = 0;
+    if (kind == hipMemcpyHostToDevice) {
+      const uint32_t* u = reinterpret_cast<const uint32_t*>(p);
+      for (uint64_t i = 0; i < nel && first == PACK_NONE; i++)
+        if (replay_pack::code_of(pal, u[i]) < 0) { first = i; bits = u[i]; }
+    } else {
+      hipStream_t s = ctx->stream;
+      unsigned long long* chk = nullptr;
+      unsigned long long got[2] = {0, PACK_NONE};
+      AGZ_HIP_TRY(hipMalloc(&chk, sizeof(got)));
+      hipError_t e = hipMemsetAsync(chk, 0, 8, s);
+      if (e == hipSuccess) e = hipMemsetAsync(chk + 1, 0xFF, 8, s);   // PACK_NONE
+      if (e == hipSuccess) {
+        const unsigned grid = (unsigned)std::min<uint64_t>((nel + REPLAY_THREADS - 1) / REPLAY_THREADS, 4096);
+        hipLaunchKernelGGL(k_replay_pack_check, dim3(grid), dim3(REPLAY_THREADS), 0, s, reinterpret_cast<const uint32_t*>(p), nel, pal.e[0],
+                           pal.e[1], pal.e[2], pal.e[3], pal.n, chk);
+        e = hipGetLastError();
+      }
+      if (e == hipSuccess) e = hipMemcpyAsync(got, chk, sizeof(got), hipMemcpyDeviceToHost, s);
+      const hipError_t se = hipStreamSynchronize(s);
+      if (e == hipSuccess && se == hipSuccess && got[0]) e = hipMemcpy(&bits, reinterpret_cast<const uint32_t*>(p) + got[1], 4, hipMemcpyDeviceToHost);
+      hipFree(chk);
+      AGZ_HIP_TRY(e);
+      AGZ_HIP_TRY(se);
+      if (got[0]) first = got[1];
+    }
+    AGZ_REQUIRE(first == PACK_NONE, AGZ_E_INVALID,
+                "%s: row %llu, element %llu (linear element %llu) holds the bit pattern 0x%08X, which is not in the window's palette; "
+                "nothing was appended",
+                who, (unsigned long long)(first / xs), (unsigned long long)(first % xs), (unsigned long long)first, bits);
+    return AGZ_OK;
+  }
+  // cnt validated source rows into the slots from s0 on (wrapping): device rows are packed where they lie, host rows go up through a
+  // bounded staging buffer, chunk after chunk in queue order
+  int pack_rows(const float* p, uint64_t cnt, uint64_t s0, hipMemcpyKind kind) {
+    hipStream_t s = ctx->stream;
+    const int mm = H * W;
+    const unsigned gx = (unsigned)std::min<size_t>((row_words() * replay_pack::CODES_PER_WORD + REPLAY_THREADS - 1) / REPLAY_THREADS, 1024);
+    const bool host = kind == hipMemcpyHostToDevice;
+    const uint64_t chunk = host ? std::min<uint64_t>(cnt, std::max<uint64_t>(1, PACK_STAGING_BYTES / (xs * 4))) : cnt;
+    float* staging = nullptr;
+    if (host && hipMalloc(&staging, chunk * xs * 4) != hipSuccess) {
+      (void)hipGetLastError();
+      agz::set_error("agz_replay_append_host: out of device memory for a staging buffer of %llu rows", (unsigned long long)chunk);
+      return AGZ_E_NOMEM;
+    }
+    hipError_t e = hipSuccess;
+    for (uint64_t a = 0; a < cnt && e == hipSuccess; a += chunk) {
+      const uint64_t len = std::min(chunk, cnt - a);
+      const float* src = p + a * xs;
+      if (host) {
+        e = hipMemcpyAsync(staging, src, len * xs * 4, hipMemcpyHostToDevice, s);
+        src = staging;
+        if (e != hipSuccess) break;
+      }
+      hipLaunchKernelGGL(k_replay_pack, dim3(gx, (unsigned)std::min<uint64_t>(len, 65535)), dim3(REPLAY_THREADS), 0, s,
+                         reinterpret_cast<const uint32_t*>(src), words, F, mm, wpp, (int)len, (s0 + a) % cap, cap, pal.e[0], pal.e[1], pal.e[2],
+                         pal.e[3], pal.n);
+      e = hipGetLastError();
+    }
+    if (host) {
+      const hipError_t se = hipStreamSynchronize(s);   // the staging buffer is read by the kernels enqueued above
+      hipFree(staging);
+      if (e == hipSuccess) e = se;
+    }
+    AGZ_HIP_TRY(e);
+    return AGZ_OK;
+  }
   // c rows from (p, q, v) as c single-row appends in order: at most two contiguous row ranges per array; only the last cap rows of a
   // longer append survive
-  int append(const float* p, const float* q, const float* v, uint64_t c, hipMemcpyKind kind) {
+  int append(const float* p, const float* q, const float* v, uint64_t c, hipMemcpyKind kind, const char* who) {
+    if (is_packed) {
+      AGZ_REQUIRE(c <= (uint64_t)INT32_MAX, AGZ_E_INVALID, "%s: %llu rows in one append to a packed window (at most %d)", who,
+                  (unsigned long long)c, INT32_MAX);
+      int r = validate(p, c, kind, who);
+      if (r != AGZ_OK) return r;
+    }
     const uint64_t skip = c > cap ? c - cap : 0, cnt = c - skip;
     const uint64_t s0 = replay::head(total + skip, cap);
     const uint64_t first = std::min<uint64_t>(cnt, cap - s0);
     hipStream_t s = ctx->stream;
+    if (is_packed) {
+      int r = pack_rows(p + skip * xs, cnt, s0, kind);
+      if (r != AGZ_OK) return r;
+    }
     const uint64_t at[2] = {skip, skip + first}, to[2] = {s0, 0}, len[2] = {first, cnt - first};
     for (int i = 0; i < 2; i++) {
       if (!len[i]) continue;
-      AGZ_HIP_TRY(hipMemcpyAsync(planes + to[i] * xs, p + at[i] * xs, len[i] * xs * 4, kind, s));
+      if (!is_packed) AGZ_HIP_TRY(hipMemcpyAsync(planes + to[i] * xs, p + at[i] * xs, len[i] * xs * 4, kind, s));
       AGZ_HIP_TRY(hipMemcpyAsync(policy + to[i] * A1, q + at[i] * A1, len[i] * (size_t)A1 * 4, kind, s));
       AGZ_HIP_TRY(hipMemcpyAsync(value + to[i], v + at[i], len[i] * 4, kind, s));
     }
@@ -103,33 +299,120 @@ int agz::replay_sample_launch(agz_replay* rp, int rows, uint64_t seed, uint64_t 
   const int mm = rp->H * rp->W;
   const int row = (int)rp->xs + rp->A1 + 1;
   const dim3 grid((unsigned)ceil_div(row, REPLAY_SEG), (unsigned)std::min(rows, 65535));
+  if (rp->is_packed) {
+    const replay_pack::Palette& pal = rp->pal;
+    hipLaunchKernelGGL(k_replay_sample_packed, grid, dim3(REPLAY_THREADS), 0, rp->ctx->stream, rp->words,
+                       reinterpret_cast<const uint32_t*>(rp->policy), reinterpret_cast<const uint32_t*>(rp->value),
+                       reinterpret_cast<uint32_t*>(X), reinterpret_cast<uint32_t*>(Pi), reinterpret_cast<uint32_t*>(V), rp->F, rp->H, mm, rp->wpp,
+                       rp->A1, rows, seed, step, symmetric, n, total, rp->cap, pal.e[0], pal.e[1], pal.e[2], pal.e[3]);
+    AGZ_HIP_TRY(hipGetLastError());
+    return AGZ_OK;
+  }
   hipLaunchKernelGGL(k_replay_sample, grid, dim3(REPLAY_THREADS), 0, rp->ctx->stream, rp->planes, rp->policy, rp->value, X, Pi, V, rp->F,
                      rp->H, mm, rp->A1, rows, seed, step, symmetric, n, total, rp->cap);
   AGZ_HIP_TRY(hipGetLastError());
   return AGZ_OK;
 }
 
-extern "C" {
-
-int agz_replay_create(agz_ctx* ctx, int Features, int Height, int Width, int PolicyLen, int64_t capacity, agz_replay** out) {
-  AGZ_REQUIRE(ctx && out, AGZ_E_INVALID, "agz_replay_create: NULL argument");
-  AGZ_REQUIRE(Features >= 1 && Height >= 1 && Width >= 1 && PolicyLen >= 1, AGZ_E_INVALID, "agz_replay_create: bad shape");
-  AGZ_REQUIRE(capacity >= 1, AGZ_E_INVALID, "agz_replay_create: capacity %lld (at least 1 row)", (long long)capacity);
+// the two creates: pal == nullptr keeps the planes as fp32 rows, otherwise as 2-bit codes under *pal
+static int replay_create(const char* who, agz_ctx* ctx, int Features, int Height, int Width, int PolicyLen, int64_t capacity,
+                         const replay_pack::Palette* pal, agz_replay** out) {
+  AGZ_REQUIRE(ctx && out, AGZ_E_INVALID, "%s: NULL argument", who);
+  AGZ_REQUIRE(Features >= 1 && Height >= 1 && Width >= 1 && PolicyLen >= 1, AGZ_E_INVALID, "%s: bad shape", who);
+  AGZ_REQUIRE(capacity >= 1, AGZ_E_INVALID, "%s: capacity %lld (at least 1 row)", who, (long long)capacity);
   const size_t xs = (size_t)Features * Height * Width;
-  AGZ_REQUIRE(xs + (size_t)PolicyLen + 1 <= (size_t)1 << 30, AGZ_E_INVALID, "agz_replay_create: a row of %zu floats is too long", xs + PolicyLen + 1);
+  AGZ_REQUIRE(xs + (size_t)PolicyLen + 1 <= (size_t)1 << 30, AGZ_E_INVALID, "%s: a row of %zu floats is too long", who, xs + PolicyLen + 1);
   AGZ_HIP_TRY(hipSetDevice(ctx->device));
   const size_t cap = (size_t)capacity;
-  float *p = nullptr, *q = nullptr, *v = nullptr;
-  if (hipMalloc(&p, cap * xs * 4) != hipSuccess || hipMalloc(&q, cap * PolicyLen * 4) != hipSuccess || hipMalloc(&v, cap * 4) != hipSuccess) {
+  const int wpp = pal ? replay_pack::wpp(Height * Width) : 0;
+  const size_t plane_bytes = pal ? (size_t)Features * wpp * 4 : xs * 4;      // of one row
+  void* p = nullptr;
+  float *q = nullptr, *v = nullptr;
+  if (hipMalloc(&p, cap * plane_bytes) != hipSuccess || hipMalloc(&q, cap * PolicyLen * 4) != hipSuccess || hipMalloc(&v, cap * 4) != hipSuccess) {
     (void)hipGetLastError();
     hipFree(p); hipFree(q); hipFree(v);
-    agz::set_error("agz_replay_create: out of device memory for a window of %zu rows (%zu bytes)", cap, cap * (xs + PolicyLen + 1) * 4);
+    agz::set_error("%s: out of device memory for a window of %zu rows (%zu bytes)", who, cap, cap * (plane_bytes + ((size_t)PolicyLen + 1) * 4));
     return AGZ_E_NOMEM;
   }
   agz_replay* rp = new agz_replay();
   rp->ctx = ctx; rp->F = Features; rp->H = Height; rp->W = Width; rp->A1 = PolicyLen; rp->xs = xs;
-  rp->planes = p; rp->policy = q; rp->value = v; rp->cap = (uint64_t)cap;
+  rp->policy = q; rp->value = v; rp->cap = (uint64_t)cap;
+  if (pal) {
+    rp->is_packed = true; rp->words = static_cast<uint32_t*>(p); rp->wpp = wpp; rp->pal = *pal;
+  } else {
+    rp->planes = static_cast<float*>(p);
+  }
   *out = rp;
+  return AGZ_OK;
+}
+
+// a palette handed over as floats, taken as bit patterns
+static int palette_of(const char* who, const float* palette, int n_palette, replay_pack::Palette* pal) {
+  AGZ_REQUIRE(n_palette >= 1 && n_palette <= replay_pack::MAX_PALETTE, AGZ_E_INVALID, "%s: a palette of %d entries (1 to %d)", who, n_palette,
+              replay_pack::MAX_PALETTE);
+  AGZ_REQUIRE(palette, AGZ_E_INVALID, "%s: NULL palette", who);
+  uint32_t bits[replay_pack::MAX_PALETTE];
+  memcpy(bits, palette, (size_t)n_palette * 4);
+  AGZ_REQUIRE(replay_pack::palette_ok(bits, n_palette), AGZ_E_INVALID, "%s: two palette entries have the same bit pattern", who);
+  *pal = replay_pack::make_palette(bits, n_palette);
+  return AGZ_OK;
+}
+
+extern "C" {
+
+int agz_replay_create(agz_ctx* ctx, int Features, int Height, int Width, int PolicyLen, int64_t capacity, agz_replay** out) {
+  return replay_create("agz_replay_create", ctx, Features, Height, Width, PolicyLen, capacity, nullptr, out);
+}
+
+int agz_replay_create_packed(agz_ctx* ctx, int Features, int Height, int Width, int PolicyLen, int64_t capacity, const float* palette,
+                             int n_palette, agz_replay** out) {
+  AGZ_REQUIRE(ctx && out, AGZ_E_INVALID, "agz_replay_create_packed: NULL argument");
+  replay_pack::Palette pal;
+  int r = palette_of("agz_replay_create_packed", palette, n_palette, &pal);
+  if (r != AGZ_OK) return r;
+  return replay_create("agz_replay_create_packed", ctx, Features, Height, Width, PolicyLen, capacity, &pal, out);
+}
+
+int agz_encoder_palette(int encoder, float palette[4], int* n) {
+  AGZ_REQUIRE(palette && n, AGZ_E_INVALID, "agz_encoder_palette: NULL argument");
+  AGZ_REQUIRE(encoder == AGZ_ENC_WQ || encoder == AGZ_ENC_TWOPLANE, AGZ_E_INVALID, "agz_encoder_palette: unknown encoder %d", encoder);
+  // the literals encode_nchw (engine.hip) writes; WQ's opponent planes hold -0.0 in empty cells, as vecf32.Scale gives them
+  palette[0] = encoder == AGZ_ENC_WQ ? 0.0f : 0.001f;
+  palette[1] = encoder == AGZ_ENC_WQ ? -0.0f : 0.0f;
+  palette[2] = 1.0f;
+  palette[3] = -1.0f;
+  *n = 4;
+  return AGZ_OK;
+}
+
+int agz_replay_pack_host(const float* planes, int64_t n, int Features, int cells, const float* palette, int n_palette, uint32_t* words,
+                         int64_t* first_bad) {
+  replay_pack::Palette pal;
+  int r = palette_of("agz_replay_pack_host", palette, n_palette, &pal);
+  if (r != AGZ_OK) return r;
+  AGZ_REQUIRE(n >= 0 && Features >= 1 && cells >= 1 && (n == 0 || planes), AGZ_E_INVALID, "agz_replay_pack_host: bad argument");
+  const int64_t xs = (int64_t)Features * cells, rw = (int64_t)Features * replay_pack::wpp(cells);
+  const uint32_t* bits = reinterpret_cast<const uint32_t*>(planes);
+  if (first_bad) *first_bad = -1;
+  for (int64_t row = 0; row < n; row++) {   // validate everything first: `words` is written only if every cell has a code
+    const int64_t bad = replay_pack::pack_row(pal, bits + row * xs, Features, cells, nullptr);
+    if (bad >= 0) {
+      if (first_bad) *first_bad = row * xs + bad;
+      agz::set_error("agz_replay_pack_host: row %lld, element %lld holds the bit pattern 0x%08X, which is not in the palette", (long long)row,
+                     (long long)bad, bits[row * xs + bad]);
+      return AGZ_E_INVALID;
+    }
+  }
+  if (words)
+    for (int64_t row = 0; row < n; row++) replay_pack::pack_row(pal, bits + row * xs, Features, cells, words + row * rw);
+  return AGZ_OK;
+}
+
+int agz_replay_storage(const agz_replay* rp, int32_t* packed, int64_t* row_bytes, int64_t* device_bytes) {
+  AGZ_REQUIRE(rp, AGZ_E_INVALID, "agz_replay_storage: NULL window");
+  if (packed) *packed = rp->is_packed ? 1 : 0;
+  if (row_bytes) *row_bytes = (int64_t)rp->row_bytes();
+  if (device_bytes) *device_bytes = (int64_t)(rp->cap * rp->row_bytes());   // the three arrays of create: nothing else stays allocated
   return AGZ_OK;
 }
 
@@ -137,7 +420,7 @@ void agz_replay_destroy(agz_replay* rp) {
   if (!rp) return;
   hipSetDevice(rp->ctx->device);
   hipStreamSynchronize(rp->ctx->stream);
-  hipFree(rp->planes); hipFree(rp->policy); hipFree(rp->value);
+  hipFree(rp->planes); hipFree(rp->words); hipFree(rp->policy); hipFree(rp->value);
   delete rp;
 }
 
@@ -164,21 +447,21 @@ int agz_replay_append_examples(agz_replay* rp, agz_examples* ex) {
               rp->F, rp->H, rp->W, rp->A1);
   if (e.n == 0) return AGZ_OK;
   AGZ_HIP_TRY(hipSetDevice(rp->ctx->device));
-  return rp->append(e.planes, e.policy, e.value, e.n, hipMemcpyDeviceToDevice);   // (same queue as the set's own appends: ordered after them)
+  return rp->append(e.planes, e.policy, e.value, e.n, hipMemcpyDeviceToDevice, "agz_replay_append_examples");   // (same queue as the set's own appends: ordered after them)
 }
 
 int agz_replay_append_dev(agz_replay* rp, const float* planes_dev, const float* policy_dev, const float* value_dev, int64_t n) {
   AGZ_REQUIRE(rp && n >= 0 && (n == 0 || (planes_dev && policy_dev && value_dev)), AGZ_E_INVALID, "agz_replay_append_dev: bad argument");
   if (n == 0) return AGZ_OK;
   AGZ_HIP_TRY(hipSetDevice(rp->ctx->device));
-  return rp->append(planes_dev, policy_dev, value_dev, (uint64_t)n, hipMemcpyDeviceToDevice);
+  return rp->append(planes_dev, policy_dev, value_dev, (uint64_t)n, hipMemcpyDeviceToDevice, "agz_replay_append_dev");
 }
 
 int agz_replay_append_host(agz_replay* rp, const float* planes, const float* policy, const float* value, int64_t n) {
   AGZ_REQUIRE(rp && n >= 0 && (n == 0 || (planes && policy && value)), AGZ_E_INVALID, "agz_replay_append_host: bad argument");
   if (n == 0) return AGZ_OK;
   AGZ_HIP_TRY(hipSetDevice(rp->ctx->device));
-  int r = rp->append(planes, policy, value, (uint64_t)n, hipMemcpyHostToDevice);
+  int r = rp->append(planes, policy, value, (uint64_t)n, hipMemcpyHostToDevice, "agz_replay_append_host");
   AGZ_HIP_TRY(hipStreamSynchronize(rp->ctx->stream));   // the buffers are the caller's
   return r;
 }
@@ -195,7 +478,15 @@ int agz_replay_get(agz_replay* rp, int64_t j0, int64_t cnt, float* planes, float
   const uint64_t at[2] = {0, first}, from[2] = {s0, 0}, len[2] = {first, (uint64_t)cnt - first};
   for (int i = 0; i < 2; i++) {
     if (!len[i]) continue;
-    if (planes) AGZ_HIP_TRY(hipMemcpy(planes + at[i] * rp->xs, rp->planes + from[i] * rp->xs, len[i] * rp->xs * 4, hipMemcpyDeviceToHost));
+    if (planes && rp->is_packed) {   // the words come down as they are and are decoded here, by the header's definition
+      const size_t rw = rp->row_words();
+      std::vector<uint32_t> w(len[i] * rw);
+      AGZ_HIP_TRY(hipMemcpy(w.data(), rp->words + from[i] * rw, w.size() * 4, hipMemcpyDeviceToHost));
+      for (uint64_t r = 0; r < len[i]; r++)
+        replay_pack::unpack_row(rp->pal, w.data() + r * rw, rp->F, rp->H * rp->W, reinterpret_cast<uint32_t*>(planes + (at[i] + r) * rp->xs));
+    } else if (planes) {
+      AGZ_HIP_TRY(hipMemcpy(planes + at[i] * rp->xs, rp->planes + from[i] * rp->xs, len[i] * rp->xs * 4, hipMemcpyDeviceToHost));
+    }
     if (policy) AGZ_HIP_TRY(hipMemcpy(policy + at[i] * rp->A1, rp->policy + from[i] * rp->A1, len[i] * (size_t)rp->A1 * 4, hipMemcpyDeviceToHost));
     if (value) AGZ_HIP_TRY(hipMemcpy(value + at[i], rp->value + from[i], len[i] * 4, hipMemcpyDeviceToHost));
   }

@@ -12,7 +12,7 @@ struct ReplayInfo {
   uint64_t total, cap;
 };
 ReplayInfo replay_info(const agz_replay* rp);
-// enqueue ONE k_replay_sample on the window's context stream: minibatch `step` of `rows` rows drawn from the n live rows of the ring state
+// enqueue ONE k_replay_sample (k_replay_sample_packed for a packed window) on the window's context stream: minibatch `step` of `rows` rows drawn from the n live rows of the ring state
 // (total, cap), written to the device buffers X [rows, F*H*W], Pi [rows, A1], V [rows].  No synchronisation, nothing uploaded.
 int replay_sample_launch(agz_replay* rp, int rows, uint64_t seed, uint64_t step, int symmetric, uint64_t n, uint64_t total, float* X,
                          float* Pi, float* V);

@@ -337,6 +337,36 @@ func NewReplay(ctx *Ctx, features, height, width, policyLen int, capacity int64)
 	return r, nil
 }
 
+// NewReplayPacked is NewReplay with the planes kept as 2-bit codes under a palette of 1 to 4 bit patterns (EncoderPalette gives an
+// encoder's): 8.8 times fewer bytes a row at 19x19, the same bits sampled.  An append then takes all rows or none; a cell outside the
+// palette is an error that names it.
+func NewReplayPacked(ctx *Ctx, features, height, width, policyLen int, capacity int64, palette []float32) (*Replay, error) {
+	defer ctx.enter()()
+	r := &Replay{ctx: ctx}
+	var pal *C.float
+	if len(palette) > 0 {
+		pal = (*C.float)(unsafe.Pointer(&palette[0]))
+	}
+	if err := lastErr(C.agz_replay_create_packed(ctx.h, C.int(features), C.int(height), C.int(width), C.int(policyLen), C.int64_t(capacity), pal, C.int(len(palette)), &r.h)); err != nil {
+		return nil, err
+	}
+	return r, nil
+}
+
+// EncoderPalette is the set of bit patterns an encoder (AGZ_ENC_*) writes into its planes, as float32: the palette of a packed window.
+func EncoderPalette(encoder int) ([]float32, error) {
+	var pal [4]C.float
+	var n C.int
+	if err := lastErr(C.agz_encoder_palette(C.int(encoder), &pal[0], &n)); err != nil {
+		return nil, err
+	}
+	out := make([]float32, int(n))
+	for i := range out {
+		out[i] = float32(pal[i])
+	}
+	return out, nil
+}
+
 // AppendExamples appends the raw rows of an Examples set in their order, device to device; the oldest rows leave a full window.
 func (r *Replay) AppendExamples(ex *Examples) error {
 	defer r.ctx.enter()()

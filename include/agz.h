@@ -780,6 +780,33 @@ int agz_symmetry_boards(agz_ctx* ctx, const float* boards, int count, int m, int
 typedef struct agz_replay agz_replay;
 /* capacity < 1 or a bad shape: AGZ_E_INVALID.  The device cannot hold the ring: AGZ_E_NOMEM, nothing stays allocated. */
 int agz_replay_create(agz_ctx* ctx, int Features, int Height, int Width, int PolicyLen, int64_t capacity, agz_replay** out);
+/* The same window with its planes kept as 2-bit codes (DESIGN.md §2 replay-packed; the layout is agogo_amd/csrc/replay_pack.hpp's, one
+ * host/device definition).  The planes are 95 % of a row and an encoder writes only four bit patterns into them, so a 19x19 / 18-plane row
+ * falls from 27 444 to 3 108 bytes, losslessly.  `palette` holds n_palette (1..4) floats taken as 32-bit PATTERNS and compared as uint32,
+ * never as floats: +0.0 and -0.0 are different entries, a NaN pattern is a legal one; two equal patterns or an n_palette outside 1..4 are
+ * AGZ_E_INVALID, as is everything agz_replay_create refuses (AGZ_E_NOMEM likewise).  A cell's code is the index of its pattern in the
+ * palette; 16 codes to a uint32, wpp = (H*W + 15) / 16 words per plane, every plane starts a word: cell c of plane f of a row is bits
+ * [2 * (c & 15), +2) of word f * wpp + (c >> 4), unused high bits zero.  Storage: packed [capacity][F * wpp] uint32, policy and value fp32
+ * as before.  The handle is an agz_replay: every agz_replay_* call and agz_train_replay work on it with the meaning documented here, get
+ * and the samplers give back the palette entries' bits exactly (the sampler decodes as it draws, k_replay_sample_packed).
+ * APPENDS to a packed window take ALL ROWS OR NONE: every row handed in is checked against the palette first, including the rows an
+ * append longer than the capacity would skip.  A cell outside the palette: AGZ_E_INVALID, the message names the first bad row, element
+ * and bit pattern (the smallest linear index), and the window is unchanged — total, live and every stored bit.  The check costs one
+ * small read-back, so A PACKED APPEND SYNCHRONISES THE CONTEXT'S QUEUE ONCE (append_dev included); an append happens once per epoch.
+ * Tests: tests/test_replay_pack_cpu.py, tests/test_replay_packed_gpu.py, tests/test_replay_packed_learn_gpu.py. */
+int agz_replay_create_packed(agz_ctx* ctx, int Features, int Height, int Width, int PolicyLen, int64_t capacity, const float* palette,
+                             int n_palette, agz_replay** out);
+/* The four patterns an encoder's planes hold (host only, no context): AGZ_ENC_WQ {+0.0f, -0.0f, 1.0f, -1.0f} (the opponent's empty cells
+ * are -0.0), AGZ_ENC_TWOPLANE {0.001f, 0.0f, 1.0f, -1.0f}; *n = 4.  An unknown encoder: AGZ_E_INVALID. */
+int agz_encoder_palette(int encoder, float palette[4], int* n);
+/* The packing without a context or a device: n rows of Features planes of `cells` floats into n * Features * ((cells + 15) / 16) words.
+ * `words` may be NULL (validate only); first_bad (may be NULL) receives the smallest linear element index row * Features * cells + e
+ * whose pattern is not in the palette, or -1.  A bad cell: AGZ_E_INVALID, `words` untouched.  A bad palette: AGZ_E_INVALID. */
+int agz_replay_pack_host(const float* planes, int64_t n, int Features, int cells, const float* palette, int n_palette, uint32_t* words,
+                         int64_t* first_bad);
+/* What a window holds on the device, either kind: *packed = 1 for agz_replay_create_packed's, row_bytes = the bytes of one row as stored
+ * (planes or words, policy, value), device_bytes = capacity * row_bytes, the three arrays of create.  Any of the three may be NULL. */
+int agz_replay_storage(const agz_replay* rp, int32_t* packed, int64_t* row_bytes, int64_t* device_bytes);
 void agz_replay_destroy(agz_replay* rp);
 /* any of the three may be NULL */
 int agz_replay_count(const agz_replay* rp, int64_t* live, uint64_t* total, int64_t* capacity);
