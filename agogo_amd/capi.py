@@ -18,6 +18,11 @@ INF_NET, INF_DUMMY, INF_SCRIPT, INF_HASH, INF_UNIFORM, INF_CALLBACK = 0, 1, 2, 3
 BN_DEGENERATE_EPS, BN_RUNNING, BN_IDENTITY = 0, 1, 2
 COMPUTE_F32_MFMA, COMPUTE_BF16X3, COMPUTE_FP16X2, COMPUTE_WINO, COMPUTE_AUTO, COMPUTE_WINO_H2 = 0, 1, 2, 3, 4, 5
 COMPUTE_FORCE = 0x100
+# agz_debug.h, agz_trainer_last_paths: the kernel a trainer layer's last step took (0 = none launched)
+PATH_FWD_F32, PATH_FWD_BF16X3, PATH_FWD_H2W, PATH_FWD_H2DMA, PATH_FWD_H2DMA3 = 1, 2, 3, 4, 5
+PATH_WGRAD_F32, PATH_WGRAD_X3, PATH_WGRAD_H2, PATH_WGRAD_H2T3 = 1, 2, 3, 4
+PATH_DGRAD_RAW, PATH_DGRAD_X3, PATH_DGRAD_WINO_H2 = 1, 2, 3
+PATH_BN2_SCALAR, PATH_BN2_V = 1, 2
 PROF_CONV, PROF_HEADS, PROF_SELECT, PROF_EXPAND, PROF_MOVE, PROF_CONV_INIT = 0, 1, 2, 3, 4, 5
 PROF_WINO_IN, PROF_WINO_GEMM, PROF_WINO_OUT = 6, 7, 8
 DONT_PREFER_PASS, PREFER_PASS, DONT_RESIGN = 0, 1, 2
@@ -290,6 +295,7 @@ def lib():
     sig("agz_arena_set_split", i32, vp, i32)
     sig("agz_arena_split_steps", i32, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int))
     sig("agz_trainer_set_dma_forward", i32, vp, i32)
+    sig("agz_trainer_last_paths", i32, vp, i32, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int))
     sig("agz_arena_last_prep_batch", i32, vp, C.POINTER(C.c_int), C.POINTER(C.c_int))
     sig("agz_arena_debug_counter", i32, vp, i32, C.POINTER(C.c_int64))
     sig("agz_arena_pool_capacity", i32, vp, C.POINTER(C.c_int), C.POINTER(C.c_int))
@@ -743,6 +749,12 @@ class Trainer:
         kernel; bit 2 the first form of the head kernels; bit 3 weight images per layer in line instead of at the start of the step;
         bit 4 no side stream; bit 5 k_conv_h2dma instead of k_conv_h2dma3; bits 6, 7 timing-only decomposition of the latter (wrong results)"""
         _check(lib().agz_trainer_set_dma_forward(self.h, int(on)), "agz_trainer_set_dma_forward")
+
+    def last_paths(self, layer):
+        """agz_debug.h test hook: (fwd, wgrad, dgrad, bn_bwd2) — the PATH_* kernels the last step launched for tower layer `layer`"""
+        f, w, d, b = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        _check(lib().agz_trainer_last_paths(self.h, int(layer), C.byref(f), C.byref(w), C.byref(d), C.byref(b)), "agz_trainer_last_paths")
+        return f.value, w.value, d.value, b.value
 
     def grads_dev(self):
         ptr, n = C.c_void_p(), C.c_size_t(0)

@@ -2108,6 +2108,8 @@ struct TLayer {
   agz::RawWeights fw, bw;
   hipEvent_t ev_fw = nullptr;
   bool fw_ready = false, bw_ready = false;         // ... built for THIS step
+  // agz_trainer_last_paths (agz_debug.h): the kernels the last step launched for this layer, written at the launching branches (AGZ_PATH_*)
+  int path_fwd = 0, path_wgrad = 0, path_dgrad = 0, path_bn2 = 0;
 };
 struct TParamRef { std::string name; int kind; std::vector<int> shape; int layer; int sub; };  // sub: 0 filter(a) 1 gamma 2 beta, for dual +10 = branch b
 
@@ -2403,19 +2405,24 @@ int agz_trainer::forward_backward_dev(const float* planes, const float* pi, cons
           case 3: hipLaunchKernelGGL(k_conv_h2dma3<3>, dim3(ca.n_mtiles * ca.n_ntiles), dim3(256), 0, s, ca); break;
           default: hipLaunchKernelGGL(k_conv_h2dma3<0>, dim3(ca.n_mtiles * ca.n_ntiles), dim3(256), 0, s, ca); break;
         }
+        ly.path_fwd = AGZ_PATH_FWD_H2DMA3;
       } else {
         ca.n_mtiles = ceil_div(g.M, 128); ca.n_ntiles = ly.Cout_p / 256;
         hipLaunchKernelGGL(k_conv_h2dma, dim3(ca.n_mtiles * ca.n_ntiles), dim3(256), 0, s, ca);
+        ly.path_fwd = AGZ_PATH_FWD_H2DMA;
       }
       ly.x_planes = true;
       r = AGZ_OK;
     } else if (use_h2_fwd(ly.Cin_p, ly.Cout_p)) {
       r = conv3x3_raw_h2(ctx, cur, P + ly.o_wf, ly.z, B, g.H, g.W, ly.Cin_p, ly.Cout_p, &wsc, xb_ready[l] ? board_words + (size_t)l * B : nullptr);
+      ly.path_fwd = AGZ_PATH_FWD_H2W;
     } else if (use_x3(ly, ly.Cin_p, ly.Cout_p)) {
       if ((r = split_w3(ctx, P + ly.o_wf, ly.w3f, ly.Cout_p, ly.Cin_p)) != AGZ_OK) return r;
       r = conv3x3_raw_x3(ctx, cur, ly.w3f, ly.z, B, g.H, g.W, ly.Cin_p, ly.Cout_p);
+      ly.path_fwd = AGZ_PATH_FWD_BF16X3;
     } else {
       r = conv3x3_raw(ctx, cur, P + ly.o_wf, ly.z, B, g.H, g.W, ly.Cin_p, ly.Cout_p);
+      ly.path_fwd = AGZ_PATH_FWD_F32;
     }
     if (r != AGZ_OK) return r;
     int C = ly.Cout_p;
@@ -2626,8 +2633,11 @@ int agz_trainer::forward_backward_dev(const float* planes, const float* pi, cons
       hipLaunchKernelGGL(k_bn_bwd2_v, dim3(nblk(g.M, rpb)), dim3(256), 0, s, g, ly.z, ly.mean, ly.inv, dz, s1, s2, C, rpb, wg_amax,
                          dzb_ready ? board_words + (size_t)(L + 2 + l) * B : nullptr, (float)m_glob());
       dz_amax_ready = true;
-    } else
+      ly.path_bn2 = AGZ_PATH_BN2_V;
+    } else {
       hipLaunchKernelGGL(k_bn_bwd2, dim3(nblk((size_t)g.M * C)), dim3(256), 0, s, g, ly.z, ly.mean, ly.inv, dz, s1, s2, C, (float)m_glob());
+      ly.path_bn2 = AGZ_PATH_BN2_SCALAR;
+    }
     // weight gradient (on its own stream from here)
     if (sw != s) { AGZ_HIP_TRY(hipEventRecord(ev_dz, s)); AGZ_HIP_TRY(hipStreamWaitEvent(sw, ev_dz, 0)); }
     bool split_recorded = false;
@@ -2663,6 +2673,7 @@ int agz_trainer::forward_backward_dev(const float* planes, const float* pi, cons
         const int slots = ctx->num_cus / 8 * 2;
         w3.n_chunks = std::min(B, 8 * std::max(1, 2 * slots / per_chunk3));
         hipLaunchKernelGGL(k_wgrad_h2t3, dim3((unsigned)(per_chunk3 * round_up(w3.n_chunks, 8))), dim3(256), (size_t)wg_pad_lds, sw, w3);
+        ly.path_wgrad = AGZ_PATH_WGRAD_H2T3;
       } else {
         hipLaunchKernelGGL(k_split_h2, dim3(gs), dim3(256), 0, sw, dz, dz_h2, n_dz / 4, wg_amax);
         if (sw != s) { AGZ_HIP_TRY(hipEventRecord(ev_split, sw)); split_recorded = true; }
@@ -2671,13 +2682,17 @@ int agz_trainer::forward_backward_dev(const float* planes, const float* pi, cons
         wh.dz2 = dz_h2; wh.x2 = x_h2; wh.amax = wg_amax; wh.dw = wa.dw; wh.g = g; wh.N = wa.N; wh.Cin = wa.Cin;
         wh.rows_per_block = wa.rows_per_block; wh.n_tiles = wa.n_tiles; wh.c_tiles = wa.c_tiles; wh.n_chunks = chunks;
         hipLaunchKernelGGL(k_wgrad_h2, dim3(wg_grid), dim3(256), 0, sw, wh);
+        ly.path_wgrad = AGZ_PATH_WGRAD_H2;
       }
     }
     // bf16x3 mode: the weight gradient runs on the bf16 pipe as well
-    else if (x3 && off31 && chip_full)
+    else if (x3 && off31 && chip_full) {
       hipLaunchKernelGGL(k_wgrad_x3, dim3(wg_grid), dim3(256), 0, sw, wa);
-    else
+      ly.path_wgrad = AGZ_PATH_WGRAD_X3;
+    } else {
       hipLaunchKernelGGL(k_wgrad, dim3(wa.n_tiles * wa.c_tiles * 9 * chunks), dim3(256), 0, sw, wa);
+      ly.path_wgrad = AGZ_PATH_WGRAD_F32;
+    }
     if (sw != s && !split_recorded) AGZ_HIP_TRY(hipEventRecord(ev_split, sw));   // (kernels that read dz itself: after the weight gradient)
     // layer l's slice [filter | gamma | beta] is final once its weight gradient has run (sw: it started after this layer's BatchNorm backward)
     if (on_slice) { int r = on_slice(ly.o_wf, (l < L ? layers[l + 1].o_wf : o_hc) - ly.o_wf, sw); if (r != AGZ_OK) return r; }
@@ -2687,11 +2702,14 @@ int agz_trainer::forward_backward_dev(const float* planes, const float* pi, cons
       if (use_wino(C, ly.Cin_p)) {
         r = conv3x3_raw_wino_h2(ctx, dz, ly.wt, dnext, B, g.H, g.W, C, ly.Cin_p, &wsc, dzb_ready ? board_words + (size_t)(L + 2 + l) * B : nullptr,
                                 ly.bw_ready ? &ly.bw : nullptr);
+        ly.path_dgrad = AGZ_PATH_DGRAD_WINO_H2;
       } else if (use_x3(ly, C, ly.Cin_p)) {
         if ((r = split_w3(ctx, ly.wt, ly.w3t, ly.Cin_p, C)) != AGZ_OK) return r;
         r = conv3x3_raw_x3(ctx, dz, ly.w3t, dnext, B, g.H, g.W, C, ly.Cin_p);
+        ly.path_dgrad = AGZ_PATH_DGRAD_X3;
       } else {
         r = conv3x3_raw(ctx, dz, ly.wt, dnext, B, g.H, g.W, C, ly.Cin_p);
+        ly.path_dgrad = AGZ_PATH_DGRAD_RAW;
       }
       if (r != AGZ_OK) return r;
       std::swap(dcur, dnext);
@@ -3367,6 +3385,14 @@ int agz_trainer_set_dma_forward(agz_trainer* t, int on) {
   t->hoist_w = (on & 8) == 0;         // bit 3: weight images per layer in line, not at the start of the step on the side stream (A/B)
   t->wg_pad_lds = (on & 256) ? 0 : 16384;   // bit 8: k_wgrad_h2t3 at two workgroups per CU as in round 5 (default: one, 73.7 KB static + 16 KB dynamic LDS)
   t->wg_low_prio = (on & 512) != 0;     // bit 9: the side stream at the lowest priority (before the first step)
+  return AGZ_OK;
+}
+
+int agz_trainer_last_paths(agz_trainer* t, int layer, int* fwd, int* wgrad, int* dgrad, int* bn_bwd2) {
+  AGZ_REQUIRE(t && fwd && wgrad && dgrad && bn_bwd2, AGZ_E_INVALID, "agz_trainer_last_paths: NULL argument");
+  AGZ_REQUIRE(layer >= 0 && layer <= t->L, AGZ_E_INVALID, "agz_trainer_last_paths: layer %d of 0..%d", layer, t->L);
+  const TLayer& ly = t->layers[layer];
+  *fwd = ly.path_fwd; *wgrad = ly.path_wgrad; *dgrad = ly.path_dgrad; *bn_bwd2 = ly.path_bn2;
   return AGZ_OK;
 }
 

@@ -96,6 +96,27 @@ int agz_arena_split_steps(agz_arena* arena, int64_t* split, int64_t* joined, int
  * the first step; measured no different).  Bits 8 and 9 do not change a single product. */
 int agz_trainer_set_dma_forward(agz_trainer* t, int on);
 
+/* Tests: which kernels the trainer's last step (agz_trainer_forward_backward / _batch / _eval) launched for tower layer `layer`
+ * (0 = the input convolution, 1 .. SharedLayers = the dual blocks).  Every value is written by the launcher at the very branch that
+ * launches the kernel, so a test can see which of the shape-dependent paths a geometry took — identical results cannot show that.
+ * Read-only: it has no effect on any launch.  0 = nothing launched (a layer before its first step; the data gradient of layer 0,
+ * which has none; everything but the forward value after an eval). */
+#define AGZ_PATH_FWD_F32 1      /* conv3x3_raw: the fp32-MFMA convolution */
+#define AGZ_PATH_FWD_BF16X3 2   /* conv3x3_raw_x3 */
+#define AGZ_PATH_FWD_H2W 3      /* conv3x3_raw_h2: conv3x3_h2w_kernel, activations split while staged */
+#define AGZ_PATH_FWD_H2DMA 4    /* k_conv_h2dma: DMA GEMM on pre-split planes, one tap per K step, 128 x 256 tile */
+#define AGZ_PATH_FWD_H2DMA3 5   /* k_conv_h2dma3: nine taps from one x image, 256 x 128 tile */
+#define AGZ_PATH_WGRAD_F32 1    /* k_wgrad */
+#define AGZ_PATH_WGRAD_X3 2     /* k_wgrad_x3 */
+#define AGZ_PATH_WGRAD_H2 3     /* k_wgrad_h2 */
+#define AGZ_PATH_WGRAD_H2T3 4   /* k_wgrad_h2t3: three taps per workgroup from hi / lo planes (boards >= 16 wide) */
+#define AGZ_PATH_DGRAD_RAW 1    /* conv3x3_raw on the transposed filter */
+#define AGZ_PATH_DGRAD_X3 2     /* conv3x3_raw_x3 */
+#define AGZ_PATH_DGRAD_WINO_H2 3 /* conv3x3_raw_wino_h2 */
+#define AGZ_PATH_BN2_SCALAR 1   /* k_bn_bwd2 (the weight gradient then takes dz's range with k_absmax) */
+#define AGZ_PATH_BN2_V 2        /* k_bn_bwd2_v: vector form, writes dz's range itself */
+int agz_trainer_last_paths(agz_trainer* t, int layer, int* fwd, int* wgrad, int* dgrad, int* bn_bwd2);
+
 /* The smallest batch >= n that runs the kernels of a batch of G boards on this net in its current compute mode (agz_net::min_same_batch, what
  * prepareRoot's packed forward uses): per board the outputs of such a batch are those of the G-board batch bit for bit.  The parity tests
  * evaluate single leaves for the oracle with it instead of G copies of the board. */

@@ -5,9 +5,8 @@ import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "..", "tests"))
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", ".."))
 import numpy as np
-import torch
-import torch.nn.functional as Fn
 import oracle_lib as O
+from f64_train import f64_train_of
 
 
 def shape_of(seed):
@@ -34,29 +33,8 @@ def oracle_net(K, L, FC, W, H, F, A, B, seed=5, wscale=3.0):      # tests/test_t
     return ot
 
 
-def f64_grads(t, x, pi, v, K, L, FC, W, H, F, A, B, eps=1e-5):
-    P = [torch.tensor(t.get_param(i).astype(np.float64), requires_grad=True) for i in range(t.num_params())]
-    it = iter(range(len(P)))
-
-    def cbr(z, cin, cout, k):
-        w = P[next(it)].reshape(cout, cin, k, k); g = P[next(it)].reshape(B, cout, H, W); b = P[next(it)].reshape(B, cout, H, W)
-        y = Fn.conv2d(z, w, padding=k // 2)
-        mean = y.mean(dim=(0, 2, 3), keepdim=True)
-        var = ((y - mean) ** 2).mean(dim=(0, 2, 3), keepdim=True)
-        return torch.relu((y - mean) / torch.sqrt(var + eps) * g + b)
-
-    z = cbr(torch.tensor(x.astype(np.float64)), F, K, 3)
-    for _ in range(L):
-        a = cbr(z, K, K, 3); b = cbr(z, K, K, 3); z = torch.relu(a + b)
-    p = cbr(z, K, 2, 1).reshape(B, 2 * H * W)
-    logits = p @ P[next(it)].reshape(2 * H * W, A) + P[next(it)].reshape(B, A)
-    vv = cbr(z, K, 1, 1).reshape(B, H * W)
-    hid = torch.relu(vv @ P[next(it)].reshape(H * W, FC) + P[next(it)].reshape(B, FC))
-    o = (hid @ P[next(it)].reshape(FC, 1) + P[next(it)].reshape(B, 1)).reshape(B)
-    Pi, V = torch.tensor(pi.astype(np.float64)), torch.tensor(v.astype(np.float64))
-    cost = -(Pi * logits + (1 - Pi) * (1 - logits)).mean() + ((o - V) ** 2).mean()
-    cost.backward()
-    return cost.item(), [q.grad.numpy().ravel() for q in P]
+def f64_grads(t, x, pi, v, K, L, FC, W, H, F, A, B, eps=1e-5):      # the float64 autograd restatement: tests/f64_train.py
+    return f64_train_of(t, x, pi, v, K, L, FC, W, H, F, A, B, eps=eps)
 
 
 if __name__ == "__main__":

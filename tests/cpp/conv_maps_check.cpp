@@ -110,6 +110,20 @@ int main() {
   for (int t : {0, 1, 180, 359, 360}) check_tile(gbig, t);
   const Geo g1617 = geo(4, 16, 17);                                       // another board >= 16 wide that fits
   if (max_rows(g1617) <= CD3_IMG) for (int t = 0; t * 256 < g1617.M; t++) check_tile(g1617, t);
+  // the wide boards tests/test_train_wide_gpu.py runs the kernel on, every tile (geo(B, H, W): boards, height, width):
+  // 16x16 (HW = 256: every tile is one board) at B = 1 and 3; 16 wide x 17 high and its transpose; 20 wide x 16 high at B = 2, whose image needs
+  // exactly the limit; 21 wide x 16 high at B = 1 (one board: no crossing, fits); 16 wide x 9 high at B = 3 (two board crossings inside one tile)
+  const Geo wide[] = {geo(1, 16, 16), geo(3, 16, 16), geo(2, 17, 16), geo(2, 16, 17), geo(2, 16, 20), geo(1, 16, 21), geo(3, 9, 16)};
+  for (const Geo& g : wide) {
+    CHECK(max_rows(g) <= CD3_IMG, "%d boards of %d wide x %d high need %d rows", g.B, g.W, g.H, max_rows(g));
+    for (int t = 0; t * 256 < g.M; t++) check_tile(g, t);
+  }
+  CHECK(max_rows(geo(2, 16, 20)) == CD3_IMG, "20 wide x 16 high, B = 2 needs %d rows, not exactly the limit", max_rows(geo(2, 16, 20)));
+  CHECK(max_rows(geo(3, 9, 16)) == 360, "16 wide x 9 high, B = 3 needs %d rows", max_rows(geo(3, 9, 16)));
+  // ... and the ones the launcher must keep on k_conv_h2dma: the same 21-wide board at B = 2, the short boards at B = 5
+  CHECK(max_rows(geo(2, 16, 21)) > CD3_IMG, "21 wide x 16 high, B = 2 fits (%d rows)", max_rows(geo(2, 16, 21)));
+  CHECK(max_rows(geo(5, 9, 16)) > CD3_IMG, "16 wide x 9 high, B = 5 fits (%d rows)", max_rows(geo(5, 9, 16)));
+  CHECK(max_rows(geo(5, 3, 16)) > CD3_IMG, "16 wide x 3 high, B = 5 fits (%d rows)", max_rows(geo(5, 3, 16)));
   // k_conv_h2dma's stage images use the same row / unit / swizzle functions: 16 distinct bank slots for 16 consecutive rows, any alignment
   for (int r0 = 0; r0 < 8; r0++)
     for (int u = 0; u < 4; u++) {

@@ -4,6 +4,7 @@ The exchange itself (agz_examples_allgather / agz_trainer_allreduce) is device c
 (tests/test_comm_fake_gpu.py: n = 2 and 3 ranks on one GPU through tests/fake_rccl; tests/test_comm_gpu.py: real RCCL at n = 1)."""
 import os
 import socket
+import subprocess
 
 import pytest
 import torch
@@ -52,6 +53,8 @@ def test_shard_games_partition():
 
 
 def test_id_exchange_sharding_and_bench_aggregation_world2_gloo():
+    if not os.path.exists(FAKE):   # a product of `make all`; a tests directory laid out after the build gets it here, as tests/cpp's binaries do
+        subprocess.check_call(["make", "-C", ROOT, "tests/fake_rccl/librccl_fake.so"])
     assert os.path.exists(FAKE), "tests/fake_rccl/librccl_fake.so is built by `make`"
     world = 2
     port = _free_port()

@@ -11,6 +11,7 @@ import torch
 import torch.nn.functional as Fn
 
 import oracle_lib as O
+from f64_train import f64_train_of
 
 
 def torch_forward(net, x, bn_mode, stats=None, eps=1e-5):
@@ -108,36 +109,10 @@ def test_oracle_train_forward_backward_matches_torch_autograd():
     v = rng.choice(np.array([-1.0, 0.0, 1.0], np.float32), B)
     cost_o = t.batch(x, pi, v, lr=0.0)
 
-    P = [torch.tensor(t.get_param(i).astype(np.float64), requires_grad=True) for i in range(t.num_params())]
-    it = iter(range(len(P)))
-    eps = 1e-5
-
-    def conv_bn_relu(z, cin, cout, k):
-        w = P[next(it)].reshape(cout, cin, k, k)
-        g = P[next(it)].reshape(B, cout, H, W)
-        b = P[next(it)].reshape(B, cout, H, W)
-        y = Fn.conv2d(z, w, padding=k // 2)
-        mean = y.mean(dim=(0, 2, 3), keepdim=True)
-        var = ((y - mean) ** 2).mean(dim=(0, 2, 3), keepdim=True)
-        return torch.relu((y - mean) / torch.sqrt(var + eps) * g + b)
-
-    z = torch.tensor(x.astype(np.float64))
-    z = conv_bn_relu(z, F, K, 3)
-    for _ in range(L):
-        a = conv_bn_relu(z, K, K, 3)
-        b = conv_bn_relu(z, K, K, 3)
-        z = torch.relu(a + b)
-    p = conv_bn_relu(z, K, 2, 1).reshape(B, 2 * H * W)
-    logits = p @ P[next(it)].reshape(2 * H * W, A) + P[next(it)].reshape(B, A)
-    vv = conv_bn_relu(z, K, 1, 1).reshape(B, H * W)
-    hid = torch.relu(vv @ P[next(it)].reshape(H * W, FC) + P[next(it)].reshape(B, FC))
-    o = (hid @ P[next(it)].reshape(FC, 1) + P[next(it)].reshape(B, 1)).reshape(B)
-    Pi, V = torch.tensor(pi.astype(np.float64)), torch.tensor(v.astype(np.float64))
-    cost = -(Pi * logits + (1 - Pi) * (1 - logits)).mean() + ((o - V) ** 2).mean()
-    cost.backward()
-    assert abs(cost.item() - cost_o) < 1e-5 * max(1.0, abs(cost_o))
+    cost, g64 = f64_train_of(t, x, pi, v, K, L, FC, W, H, F, A, B)   # tests/f64_train.py: the float64 autograd restatement
+    assert abs(cost - cost_o) < 1e-5 * max(1.0, abs(cost_o))
     for i, nm in enumerate(names):
-        g_t = P[i].grad.numpy().ravel()
+        g_t = g64[i]
         g_o = t.get_grad(i)
         scale = max(np.abs(g_t).max(), 1e-8)
         assert np.abs(g_o - g_t).max() <= 2e-5 * scale + 1e-9, (nm, np.abs(g_o - g_t).max(), scale)
