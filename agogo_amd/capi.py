@@ -283,6 +283,11 @@ def lib():
     sig("agz_replay_sample", i32, vp, i32, u64, u64, i32, pf, pf, pf)
     sig("agz_replay_draw", i32, u64, u64, i32, i64, i32, pi64, pi)
     sig("agz_train_replay", i32, vp, vp, i32, u64, i32, pf)
+    sig("agz_replay_sample_slice_dev", i32, vp, i32, i32, i32, u64, u64, i32, vp, vp, vp)
+    sig("agz_replay_sample_slice", i32, vp, i32, i32, i32, u64, u64, i32, pf, pf, pf)
+    sig("agz_replay_digest", i32, vp, C.POINTER(C.c_uint64))
+    sig("agz_replay_digest_host", i32, pf, pf, pf, i64, i32, i32, i32, C.POINTER(C.c_uint64))
+    sig("agz_train_replay_sharded", i32, vp, vp, i32, u64, i32, i32, pf)
     sig("agz_rotate_boards", i32, vp, pf, i32, i32, i32, pf)
     sig("agz_ctx_prof_set_stride", i32, vp, i32, i32)
     sig("agz_wino_stages", i32, vp, pf, pf, i32, i32, i32, i32, i32, pf, pf)
@@ -781,6 +786,15 @@ class Trainer:
         c = C.c_float(0)
         _check(lib().agz_train_replay(self.h, replay.h if replay is not None else None, int(steps), int(seed) & (2 ** 64 - 1),
                                       1 if symmetric else 0, C.byref(c)), "agz_train_replay")
+        return c.value
+
+    def train_replay_sharded(self, replay, steps, seed=1337, symmetric=False, verify=True):
+        """train_replay on a sharded handle (agz_train_replay_sharded), COLLECTIVE: every rank calls it with its own replica of the window
+        and the same arguments; step s trains on minibatch s of n_ranks * BatchSize rows, this rank on its own rows of it.  The replicas'
+        counts are compared at entry, with verify their digests too; a difference raises AgzError on every rank, nothing trained."""
+        c = C.c_float(0)
+        _check(lib().agz_train_replay_sharded(self.h, replay.h if replay is not None else None, int(steps), int(seed) & (2 ** 64 - 1),
+                                              1 if symmetric else 0, 1 if verify else 0, C.byref(c)), "agz_train_replay_sharded")
         return c.value
 
     def export(self, net):
@@ -1421,6 +1435,42 @@ class Replay:
         """minibatch `step` into device buffers, asynchronous on the context's queue"""
         _check(lib().agz_replay_sample_dev(self.h, int(rows), int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1), 1 if symmetric else 0,
                                            C.c_void_p(X_ptr), C.c_void_p(Pi_ptr), C.c_void_p(V_ptr)), "agz_replay_sample_dev")
+
+    def sample_slice(self, rows, row0, cnt, seed, step=0, symmetric=False):
+        """rows [row0, row0 + cnt) of minibatch `step` of `rows` rows on the host: X [cnt, F, H, W], Pi [cnt, PolicyLen], V [cnt]"""
+        x = np.zeros((max(cnt, 1), self.F, self.H, self.W), np.float32)
+        p = np.zeros((max(cnt, 1), self.A1), np.float32)
+        v = np.zeros(max(cnt, 1), np.float32)
+        _check(lib().agz_replay_sample_slice(self.h, int(rows), int(row0), int(cnt), int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1),
+                                             1 if symmetric else 0, _pf(x), _pf(p), _pf(v)), "agz_replay_sample_slice")
+        return x, p, v
+
+    def sample_slice_dev(self, rows, row0, cnt, seed, step, symmetric, X_ptr, Pi_ptr, V_ptr):
+        """the same slice into device buffers of cnt rows, asynchronous on the context's queue"""
+        _check(lib().agz_replay_sample_slice_dev(self.h, int(rows), int(row0), int(cnt), int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1),
+                                                 1 if symmetric else 0, C.c_void_p(X_ptr), C.c_void_p(Pi_ptr), C.c_void_p(V_ptr)),
+               "agz_replay_sample_slice_dev")
+
+    def digest(self):
+        """the uint64 digest of the window's logical content, computed on the device (agz_replay_digest): equal for replicas holding the
+        same rows in the same order, packed or not, wherever their rings sit"""
+        d = C.c_uint64(0)
+        _check(lib().agz_replay_digest(self.h, C.byref(d)), "agz_replay_digest")
+        return d.value
+
+
+def replay_digest_host(planes, policy, value, Features, cells, PolicyLen):
+    """the digest of n rows in host arrays, in logical order (replay.hpp through agz_replay_digest_host; host only):
+    replay_digest_host(*rp.get(), F, H * W, A1) == rp.digest()"""
+    p = np.ascontiguousarray(planes, np.float32)
+    q = np.ascontiguousarray(policy, np.float32)
+    v = np.ascontiguousarray(value, np.float32)
+    n = v.size
+    assert p.size == n * Features * cells and q.size == n * PolicyLen
+    d = C.c_uint64(0)
+    _check(lib().agz_replay_digest_host(_pf(p), _pf(q), _pf(v), n, int(Features), int(cells), int(PolicyLen), C.byref(d)),
+           "agz_replay_digest_host")
+    return d.value
 
 
 def replay_draw(seed, step, rows, n, symmetric=True):

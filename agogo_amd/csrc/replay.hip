@@ -19,22 +19,22 @@ constexpr int REPLAY_THREADS = 256;
 constexpr int REPLAY_SEG = REPLAY_THREADS * 8;   // elements of one output row that one workgroup moves
 constexpr int REPLAY_TAB = 1024;                 // cells of the largest board sampled under a symmetry (32 x 32); 4 KB of LDS
 
-// One minibatch: out row r = S_k(window row j), (j, k) = replay::draw(seed, step, rows, r, n, symmetric) — computed here, the same in every
-// lane of the workgroup.  An output row is the concatenation [planes F*mm | policy A1 | value 1] cut into segments of REPLAY_SEG elements:
-// grid = (segments, rows).  The mm source cells of S_k go to LDS once per workgroup; a plane element then costs one LDS read, one gathered
+// Rows [row0, row0 + cnt) of one minibatch of `rows` rows (the whole of it: row0 = 0, cnt = rows): out row r = S_k(window row j), (j, k) =
+// replay::draw(seed, step, rows, row0 + r, n, symmetric) — computed here, the same in every lane of the workgroup.  An output row is the
+// concatenation [planes F*mm | policy A1 | value 1] cut into segments of REPLAY_SEG elements: grid = (segments, cnt).  The mm source cells of S_k go to LDS once per workgroup; a plane element then costs one LDS read, one gathered
 // global read (within a 4*mm-byte board: the same cache lines whatever k is) and one coalesced write.  k == 0 copies straight through.
 // Pure data movement: algorithmic bytes = 2 x payload of `rows` rows.
 __global__ __launch_bounds__(REPLAY_THREADS) void k_replay_sample(const float* __restrict__ planes, const float* __restrict__ policy,
                                                                   const float* __restrict__ value, float* __restrict__ X,
                                                                   float* __restrict__ Pi, float* __restrict__ V, int F, int m, int mm,
-                                                                  int A1, int rows, uint64_t seed, uint64_t step, int symmetric,
-                                                                  uint64_t n, uint64_t total, uint64_t cap) {
+                                                                  int A1, int rows, int row0, int cnt, uint64_t seed, uint64_t step,
+                                                                  int symmetric, uint64_t n, uint64_t total, uint64_t cap) {
   __shared__ int tab[REPLAY_TAB];
   const int xs = F * mm, row = xs + A1 + 1;
   const int e0 = (int)blockIdx.x * REPLAY_SEG;
   const int e1 = min(e0 + REPLAY_SEG, row);
-  for (int r = (int)blockIdx.y; r < rows; r += (int)gridDim.y) {
-    const replay::Draw d = replay::draw(seed, step, rows, r, n, symmetric != 0);
+  for (int r = (int)blockIdx.y; r < cnt; r += (int)gridDim.y) {
+    const replay::Draw d = replay::draw(seed, step, rows, row0 + r, n, symmetric != 0);
     const size_t s = (size_t)replay::slot(total, cap, d.j);
     const bool mapped = d.k != 0;     // (the host refuses symmetric sampling unless the board is square and mm <= REPLAY_TAB)
     if (mapped) {
@@ -126,15 +126,15 @@ __global__ __launch_bounds__(REPLAY_THREADS) void k_replay_sample_packed(const u
                                                                          const uint32_t* __restrict__ policy,
                                                                          const uint32_t* __restrict__ value, uint32_t* __restrict__ X,
                                                                          uint32_t* __restrict__ Pi, uint32_t* __restrict__ V, int F, int m,
-                                                                         int mm, int wpp, int A1, int rows, uint64_t seed, uint64_t step,
-                                                                         int symmetric, uint64_t n, uint64_t total, uint64_t cap,
+                                                                         int mm, int wpp, int A1, int rows, int row0, int cnt, uint64_t seed,
+                                                                         uint64_t step, int symmetric, uint64_t n, uint64_t total, uint64_t cap,
                                                                          uint32_t p0, uint32_t p1, uint32_t p2, uint32_t p3) {
   __shared__ int tab[REPLAY_TAB];
   const int xs = F * mm, row = xs + A1 + 1;
   const int e0 = (int)blockIdx.x * REPLAY_SEG;
   const int e1 = min(e0 + REPLAY_SEG, row);
-  for (int r = (int)blockIdx.y; r < rows; r += (int)gridDim.y) {
-    const replay::Draw d = replay::draw(seed, step, rows, r, n, symmetric != 0);
+  for (int r = (int)blockIdx.y; r < cnt; r += (int)gridDim.y) {
+    const replay::Draw d = replay::draw(seed, step, rows, row0 + r, n, symmetric != 0);
     const size_t s = (size_t)replay::slot(total, cap, d.j);
     const bool mapped = d.k != 0;     // (the host refuses symmetric sampling unless the board is square and mm <= REPLAY_TAB)
     if (mapped) {
@@ -159,6 +159,58 @@ __global__ __launch_bounds__(REPLAY_THREADS) void k_replay_sample_packed(const u
       }
     }
     if (mapped) __syncthreads();      // the table is rewritten for the next row of this workgroup
+  }
+}
+
+// ---- the digest of a window's logical content (agz_replay_digest, DESIGN.md §2 replay-sharded; the definition is replay.hpp's) ----------
+
+constexpr int DIGEST_ROWS = 4096;   // rows of the grid (y); the live rows are dealt to them round-robin
+
+// *sum += the digest terms of every element of the n live rows (the host adds `live`).  The sampler's geometry: a logical row j is the
+// concatenation [planes F*mm | policy A1 | value 1] cut into segments of REPLAY_SEG elements, grid = (segments, rows), rows strided.  A
+// packed window (packed != NULL) contributes the decoded palette pattern of a cell, so the digest is that of the unpacked rows.  Terms are
+// summed as uint64 in a lane, over the wavefront by shuffles, over the workgroup through LDS, and one atomicAdd per workgroup: an
+// integer sum, the same whatever the order and the launch geometry.  The window is read once.
+__global__ __launch_bounds__(REPLAY_THREADS) void k_replay_digest(const uint32_t* __restrict__ planes, const uint32_t* __restrict__ packed,
+                                                                  const uint32_t* __restrict__ policy, const uint32_t* __restrict__ value,
+                                                                  int F, int mm, int wpp, int A1, uint64_t n, uint64_t total, uint64_t cap,
+                                                                  uint32_t p0, uint32_t p1, uint32_t p2, uint32_t p3,
+                                                                  unsigned long long* __restrict__ sum) {
+  __shared__ unsigned long long part[REPLAY_THREADS / 64];
+  const int xs = F * mm, row = xs + A1 + 1;
+  const int e0 = (int)blockIdx.x * REPLAY_SEG;
+  const int e1 = min(e0 + REPLAY_SEG, row);
+  unsigned long long acc = 0;
+  for (uint64_t j = blockIdx.y; j < n; j += gridDim.y) {
+    const size_t s = (size_t)replay::slot(total, cap, j);
+    const uint32_t* in_x = packed ? packed + s * (size_t)F * wpp : planes + s * (size_t)xs;
+    const uint32_t* in_p = policy + s * (size_t)A1;
+    for (int e = e0 + (int)threadIdx.x; e < e1; e += REPLAY_THREADS) {
+      uint32_t bits;
+      if (e < xs) {
+        if (packed) {
+          const int pl = e / mm, c = e - pl * mm;
+          bits = replay_pack::decode(p0, p1, p2, p3, in_x[pl * wpp + (c >> 4)] >> replay_pack::shift_of(c));
+        } else {
+          bits = in_x[e];
+        }
+      } else if (e < xs + A1) {
+        bits = in_p[e - xs];
+      } else {
+        bits = value[s];
+      }
+      acc += replay::digest_term(j, (uint64_t)row, (uint64_t)e, bits);
+    }
+  }
+  // (every lane arrives here: the loops above have no barrier in them)
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+  const int wave = (int)threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) part[wave] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long t = 0;
+    for (int w = 0; w < REPLAY_THREADS / 64; w++) t += part[w];
+    atomicAdd(sum, t);
   }
 }
 
@@ -284,7 +336,7 @@ struct agz_replay {
   }
 };
 
-ReplayInfo agz::replay_info(const agz_replay* rp) { return ReplayInfo{rp->ctx, rp->F, rp->H, rp->W, rp->A1, rp->total, rp->cap}; }
+ReplayInfo agz::replay_info(const agz_replay* rp) { return ReplayInfo{rp->ctx, rp->F, rp->H, rp->W, rp->A1, rp->total, rp->cap, rp->is_packed}; }
 
 int agz::replay_check_symmetric(const agz_replay* rp, int symmetric, const char* who) {
   if (!symmetric) return AGZ_OK;
@@ -294,23 +346,68 @@ int agz::replay_check_symmetric(const agz_replay* rp, int symmetric, const char*
   return AGZ_OK;
 }
 
-int agz::replay_sample_launch(agz_replay* rp, int rows, uint64_t seed, uint64_t step, int symmetric, uint64_t n, uint64_t total, float* X,
-                              float* Pi, float* V) {
+int agz::replay_sample_launch(agz_replay* rp, int rows, int row0, int cnt, uint64_t seed, uint64_t step, int symmetric, uint64_t n,
+                              uint64_t total, float* X, float* Pi, float* V) {
   const int mm = rp->H * rp->W;
   const int row = (int)rp->xs + rp->A1 + 1;
-  const dim3 grid((unsigned)ceil_div(row, REPLAY_SEG), (unsigned)std::min(rows, 65535));
+  const dim3 grid((unsigned)ceil_div(row, REPLAY_SEG), (unsigned)std::min(cnt, 65535));
   if (rp->is_packed) {
     const replay_pack::Palette& pal = rp->pal;
     hipLaunchKernelGGL(k_replay_sample_packed, grid, dim3(REPLAY_THREADS), 0, rp->ctx->stream, rp->words,
                        reinterpret_cast<const uint32_t*>(rp->policy), reinterpret_cast<const uint32_t*>(rp->value),
                        reinterpret_cast<uint32_t*>(X), reinterpret_cast<uint32_t*>(Pi), reinterpret_cast<uint32_t*>(V), rp->F, rp->H, mm, rp->wpp,
-                       rp->A1, rows, seed, step, symmetric, n, total, rp->cap, pal.e[0], pal.e[1], pal.e[2], pal.e[3]);
+                       rp->A1, rows, row0, cnt, seed, step, symmetric, n, total, rp->cap, pal.e[0], pal.e[1], pal.e[2], pal.e[3]);
     AGZ_HIP_TRY(hipGetLastError());
     return AGZ_OK;
   }
   hipLaunchKernelGGL(k_replay_sample, grid, dim3(REPLAY_THREADS), 0, rp->ctx->stream, rp->planes, rp->policy, rp->value, X, Pi, V, rp->F,
-                     rp->H, mm, rp->A1, rows, seed, step, symmetric, n, total, rp->cap);
+                     rp->H, mm, rp->A1, rows, row0, cnt, seed, step, symmetric, n, total, rp->cap);
   AGZ_HIP_TRY(hipGetLastError());
+  return AGZ_OK;
+}
+
+// rows [row0, row0 + cnt) of a minibatch of `rows` rows: the slice calls' own argument check
+static int check_slice(const char* who, int rows, int row0, int cnt) {
+  AGZ_REQUIRE(rows >= 1 && row0 >= 0 && cnt >= 1 && (int64_t)row0 + cnt <= rows, AGZ_E_INVALID,
+              "%s: rows [%d, %lld) of a minibatch of %d (rows >= 1, row0 >= 0, cnt >= 1 and row0 + cnt <= rows)", who, row0,
+              (long long)row0 + cnt, rows);
+  return AGZ_OK;
+}
+
+// the body of the four public samplers, arguments checked: into device buffers, asynchronous ...
+static int sample_slice_dev(const char* who, agz_replay* rp, int rows, int row0, int cnt, uint64_t seed, uint64_t step, int symmetric,
+                            float* X_dev, float* Pi_dev, float* V_dev) {
+  int r = replay_check_symmetric(rp, symmetric, who);
+  if (r != AGZ_OK) return r;
+  AGZ_REQUIRE(rp->total > 0, AGZ_E_STATE, "%s: the window is empty", who);
+  AGZ_HIP_TRY(hipSetDevice(rp->ctx->device));
+  return replay_sample_launch(rp, rows, row0, cnt, seed, step, symmetric, rp->live(), rp->total, X_dev, Pi_dev, V_dev);
+}
+// ... and into host buffers of cnt rows
+static int sample_slice_host(const char* who, agz_replay* rp, int rows, int row0, int cnt, uint64_t seed, uint64_t step, int symmetric,
+                             float* X, float* Pi, float* V) {
+  int r = replay_check_symmetric(rp, symmetric, who);
+  if (r != AGZ_OK) return r;
+  AGZ_REQUIRE(rp->total > 0, AGZ_E_STATE, "%s: the window is empty", who);
+  AGZ_HIP_TRY(hipSetDevice(rp->ctx->device));
+  const size_t nx = (size_t)cnt * rp->xs, np = (size_t)cnt * rp->A1, nv = (size_t)cnt;
+  float* d = nullptr;
+  if (hipMalloc(&d, (nx + np + nv) * 4) != hipSuccess) {
+    (void)hipGetLastError();
+    agz::set_error("%s: out of device memory for %d rows", who, cnt);
+    return AGZ_E_NOMEM;
+  }
+  hipStream_t s = rp->ctx->stream;
+  r = replay_sample_launch(rp, rows, row0, cnt, seed, step, symmetric, rp->live(), rp->total, d, d + nx, d + nx + np);
+  hipError_t e = hipSuccess;
+  if (r == AGZ_OK) e = hipMemcpyAsync(X, d, nx * 4, hipMemcpyDeviceToHost, s);
+  if (r == AGZ_OK && e == hipSuccess) e = hipMemcpyAsync(Pi, d + nx, np * 4, hipMemcpyDeviceToHost, s);
+  if (r == AGZ_OK && e == hipSuccess) e = hipMemcpyAsync(V, d + nx + np, nv * 4, hipMemcpyDeviceToHost, s);
+  const hipError_t se = hipStreamSynchronize(s);
+  hipFree(d);
+  if (r != AGZ_OK) return r;
+  AGZ_HIP_TRY(e);
+  AGZ_HIP_TRY(se);
   return AGZ_OK;
 }
 
@@ -496,38 +593,64 @@ int agz_replay_get(agz_replay* rp, int64_t j0, int64_t cnt, float* planes, float
 int agz_replay_sample_dev(agz_replay* rp, int rows, uint64_t seed, uint64_t step, int symmetric, float* X_dev, float* Pi_dev, float* V_dev) {
   AGZ_REQUIRE(rp && X_dev && Pi_dev && V_dev, AGZ_E_INVALID, "agz_replay_sample_dev: NULL argument");
   AGZ_REQUIRE(rows >= 1, AGZ_E_INVALID, "agz_replay_sample_dev: rows %d (at least 1)", rows);
-  int r = replay_check_symmetric(rp, symmetric, "agz_replay_sample_dev");
-  if (r != AGZ_OK) return r;
-  AGZ_REQUIRE(rp->total > 0, AGZ_E_STATE, "agz_replay_sample_dev: the window is empty");
-  AGZ_HIP_TRY(hipSetDevice(rp->ctx->device));
-  return replay_sample_launch(rp, rows, seed, step, symmetric, rp->live(), rp->total, X_dev, Pi_dev, V_dev);
+  return sample_slice_dev("agz_replay_sample_dev", rp, rows, 0, rows, seed, step, symmetric, X_dev, Pi_dev, V_dev);
 }
 
 int agz_replay_sample(agz_replay* rp, int rows, uint64_t seed, uint64_t step, int symmetric, float* X, float* Pi, float* V) {
   AGZ_REQUIRE(rp && X && Pi && V, AGZ_E_INVALID, "agz_replay_sample: NULL argument");
   AGZ_REQUIRE(rows >= 1, AGZ_E_INVALID, "agz_replay_sample: rows %d (at least 1)", rows);
-  int r = replay_check_symmetric(rp, symmetric, "agz_replay_sample");
+  return sample_slice_host("agz_replay_sample", rp, rows, 0, rows, seed, step, symmetric, X, Pi, V);
+}
+
+int agz_replay_sample_slice_dev(agz_replay* rp, int rows, int row0, int cnt, uint64_t seed, uint64_t step, int symmetric, float* X_dev,
+                                float* Pi_dev, float* V_dev) {
+  AGZ_REQUIRE(rp && X_dev && Pi_dev && V_dev, AGZ_E_INVALID, "agz_replay_sample_slice_dev: NULL argument");
+  int r = check_slice("agz_replay_sample_slice_dev", rows, row0, cnt);
   if (r != AGZ_OK) return r;
-  AGZ_REQUIRE(rp->total > 0, AGZ_E_STATE, "agz_replay_sample: the window is empty");
+  return sample_slice_dev("agz_replay_sample_slice_dev", rp, rows, row0, cnt, seed, step, symmetric, X_dev, Pi_dev, V_dev);
+}
+
+int agz_replay_sample_slice(agz_replay* rp, int rows, int row0, int cnt, uint64_t seed, uint64_t step, int symmetric, float* X, float* Pi,
+                            float* V) {
+  AGZ_REQUIRE(rp && X && Pi && V, AGZ_E_INVALID, "agz_replay_sample_slice: NULL argument");
+  int r = check_slice("agz_replay_sample_slice", rows, row0, cnt);
+  if (r != AGZ_OK) return r;
+  return sample_slice_host("agz_replay_sample_slice", rp, rows, row0, cnt, seed, step, symmetric, X, Pi, V);
+}
+
+int agz_replay_digest(agz_replay* rp, uint64_t* digest) {
+  AGZ_REQUIRE(rp && digest, AGZ_E_INVALID, "agz_replay_digest: NULL argument");
   AGZ_HIP_TRY(hipSetDevice(rp->ctx->device));
-  const size_t nx = (size_t)rows * rp->xs, np = (size_t)rows * rp->A1, nv = (size_t)rows;
-  float* d = nullptr;
-  if (hipMalloc(&d, (nx + np + nv) * 4) != hipSuccess) {
-    (void)hipGetLastError();
-    agz::set_error("agz_replay_sample: out of device memory for %d rows", rows);
-    return AGZ_E_NOMEM;
-  }
   hipStream_t s = rp->ctx->stream;
-  r = replay_sample_launch(rp, rows, seed, step, symmetric, rp->live(), rp->total, d, d + nx, d + nx + np);
-  hipError_t e = hipSuccess;
-  if (r == AGZ_OK) e = hipMemcpyAsync(X, d, nx * 4, hipMemcpyDeviceToHost, s);
-  if (r == AGZ_OK && e == hipSuccess) e = hipMemcpyAsync(Pi, d + nx, np * 4, hipMemcpyDeviceToHost, s);
-  if (r == AGZ_OK && e == hipSuccess) e = hipMemcpyAsync(V, d + nx + np, nv * 4, hipMemcpyDeviceToHost, s);
+  const uint64_t n = rp->live();
+  unsigned long long* d = nullptr;
+  unsigned long long got = 0;
+  AGZ_HIP_TRY(hipMalloc(&d, 8));
+  hipError_t e = hipMemsetAsync(d, 0, 8, s);
+  if (e == hipSuccess && n) {
+    const int row = (int)rp->xs + rp->A1 + 1;
+    const dim3 grid((unsigned)ceil_div(row, REPLAY_SEG), (unsigned)std::min<uint64_t>(n, DIGEST_ROWS));
+    const replay_pack::Palette& pal = rp->pal;   // (an unpacked window's is all zero and unused)
+    hipLaunchKernelGGL(k_replay_digest, grid, dim3(REPLAY_THREADS), 0, s, reinterpret_cast<const uint32_t*>(rp->planes), rp->words,
+                       reinterpret_cast<const uint32_t*>(rp->policy), reinterpret_cast<const uint32_t*>(rp->value), rp->F, rp->H * rp->W,
+                       rp->wpp, rp->A1, n, rp->total, rp->cap, pal.e[0], pal.e[1], pal.e[2], pal.e[3], d);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(&got, d, 8, hipMemcpyDeviceToHost, s);
   const hipError_t se = hipStreamSynchronize(s);
   hipFree(d);
-  if (r != AGZ_OK) return r;
   AGZ_HIP_TRY(e);
   AGZ_HIP_TRY(se);
+  *digest = n + (uint64_t)got;
+  return AGZ_OK;
+}
+
+int agz_replay_digest_host(const float* planes, const float* policy, const float* value, int64_t n, int Features, int cells, int PolicyLen,
+                           uint64_t* digest) {
+  AGZ_REQUIRE(digest && n >= 0 && Features >= 1 && cells >= 1 && PolicyLen >= 1 && (n == 0 || (planes && policy && value)), AGZ_E_INVALID,
+              "agz_replay_digest_host: bad argument");
+  *digest = replay::digest_rows(reinterpret_cast<const uint32_t*>(planes), reinterpret_cast<const uint32_t*>(policy),
+                                reinterpret_cast<const uint32_t*>(value), (uint64_t)n, (uint64_t)Features * (uint64_t)cells, (uint64_t)PolicyLen);
   return AGZ_OK;
 }
 

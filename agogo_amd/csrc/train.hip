@@ -2300,7 +2300,9 @@ struct agz_trainer {
   int m_glob() const { return g.M * n_ranks; }
   int exchange(int site, const double* send, size_t count) { return shard.gather(site, send, xg, count); }
   bool bn_single_pass(int C) const { return C % 4 == 0 && C <= 1024 && g.M >= 4096; }
-  int step(const float* planes, const float* pi, const float* v);   // forward_backward_dev, collective on a sharded trainer
+  // forward_backward_dev, collective on a sharded trainer; pre != AGZ_OK: what filled the batch failed — nothing runs, and a sharded
+  // step still enters its collectives with `pre` as this rank's status
+  int step(const float* planes, const float* pi, const float* v, int pre = AGZ_OK);
   int eval_pass(const float* planes, const float* pi, const float* v);   // the forward-only pass; collective on a sharded trainer
 };
 
@@ -2733,9 +2735,10 @@ void agz_trainer_slices(const agz_trainer* t, std::vector<std::pair<size_t, size
 
 // one training step's forward / backward; on a sharded trainer a COLLECTIVE step (the communicator enters whatever exchanges a failure
 // skipped, sums the shared tensors' gradients and agrees on the status: comm.hip)
-int agz_trainer::step(const float* planes, const float* pi, const float* v) {
-  if (!sharded) return forward_backward_dev(planes, pi, v);
+int agz_trainer::step(const float* planes, const float* pi, const float* v, int pre) {
+  if (!sharded) return pre != AGZ_OK ? pre : forward_backward_dev(planes, pi, v);
   return shard.step([&]() -> int {
+    if (pre != AGZ_OK) return pre;
     const int r = forward_backward_dev(planes, pi, v);
     if (r != AGZ_OK) {
       // a step that failed part-way may have left work on the side stream: join it, so that the next step starts on a quiet trainer; and
@@ -3436,10 +3439,11 @@ int agz_train(agz_trainer* t, float* Xs, float* policies, float* values, int bat
 }
 
 // one batch of dual.Train's loop (meta.go:33-40) on the trainer's own batch buffers, already filled on its stream: the fused step at
-// dual.Train's learn rate, then the solver on what the backward did not step itself.  Nothing is synchronised.
-static int train_step_on_batch(agz_trainer* t) {
+// dual.Train's learn rate, then the solver on what the backward did not step itself.  Nothing is synchronised.  `filled`: the status of
+// what filled the buffers (agz_trainer::step's `pre`).
+static int train_step_on_batch(agz_trainer* t, int filled = AGZ_OK) {
   t->fuse_lr = DUAL_TRAIN_LR;
-  int rc = t->step(t->d_planes, t->d_pi, t->d_v);
+  int rc = t->step(t->d_planes, t->d_pi, t->d_v, filled);
   t->fused_done = rc == AGZ_OK;
   t->fuse_lr = 0.f;
   if (rc == AGZ_OK) rc = agz_trainer_apply(t, DUAL_TRAIN_LR, 1.0f);
@@ -3501,7 +3505,8 @@ int agz_train_dev(agz_trainer* t, const float* Xs_dev, const float* policies_dev
 // entry; nothing is uploaded and nothing waited for between steps; the cost is read back once at the end.
 int agz_train_replay(agz_trainer* t, agz_replay* rp, int steps, uint64_t seed, int symmetric, float* last_cost) {
   AGZ_REQUIRE(t && rp && steps >= 0, AGZ_E_INVALID, "agz_train_replay: bad argument");
-  AGZ_REQUIRE(!t->sharded, AGZ_E_UNSUPPORTED, "agz_train_replay: a sharded trainer cannot train from a replay window yet");
+  AGZ_REQUIRE(!t->sharded, AGZ_E_UNSUPPORTED,
+              "agz_train_replay: a sharded trainer trains from a replay window through the collective agz_train_replay_sharded");
   const agz::ReplayInfo w = agz::replay_info(rp);
   AGZ_REQUIRE(w.ctx == t->ctx, AGZ_E_INVALID, "agz_train_replay: the trainer and the window belong to different contexts");
   AGZ_REQUIRE(w.F == t->conf.Features && w.H == t->conf.Height && w.W == t->conf.Width && w.A1 == t->conf.ActionSpace, AGZ_E_INVALID,
@@ -3514,8 +3519,77 @@ int agz_train_replay(agz_trainer* t, agz_replay* rp, int steps, uint64_t seed, i
   hipStream_t s = t->ctx->stream;
   const uint64_t n = w.total < w.cap ? w.total : w.cap;
   for (int st = 0; st < steps && rc == AGZ_OK; st++) {
-    rc = agz::replay_sample_launch(rp, t->B, seed, (uint64_t)st, symmetric, n, w.total, t->d_planes, t->d_pi, t->d_v);
+    rc = agz::replay_sample_launch(rp, t->B, 0, t->B, seed, (uint64_t)st, symmetric, n, w.total, t->d_planes, t->d_pi, t->d_v);
     if (rc == AGZ_OK) rc = train_step_on_batch(t);
+  }
+  float c[2] = {0, 0};
+  hipError_t e = hipMemcpyAsync(c, t->cost, 8, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (rc != AGZ_OK) return rc;
+  AGZ_HIP_TRY(e);
+  if (last_cost) *last_cost = steps > 0 ? c[0] + c[1] : 0.f;
+  return AGZ_OK;
+}
+
+// agz_train_replay on a SHARDED trainer (DESIGN.md §2 replay-sharded): collective.  Every rank holds a replica of the window; step s trains
+// on minibatch s of n_ranks * B rows, of which this rank draws rows [rank * B, (rank + 1) * B) itself — replay::draw is a pure function of
+// the global row index, so nothing is exchanged for the draw and the step's collectives are those of agz_train_dev's step.  Entry: the local
+// checks, shard.agree on them, then ONE all-gather of {total, capacity, live, packed, digest} (digest: agz_replay_digest if verify, else
+// 0); any difference from rank 0's tuple is AGZ_E_STATE on every rank and nothing is changed.
+int agz_train_replay_sharded(agz_trainer* t, agz_replay* rp, int steps, uint64_t seed, int symmetric, int verify, float* last_cost) {
+  AGZ_REQUIRE(t && rp && steps >= 0, AGZ_E_INVALID, "agz_train_replay_sharded: bad argument");
+  AGZ_REQUIRE(t->sharded, AGZ_E_STATE,
+              "agz_train_replay_sharded: not a sharded trainer (agz_trainer_create_sharded / _sharded_tied); agz_train_replay trains this one");
+  const agz::ReplayInfo w = agz::replay_info(rp);
+  const uint64_t n = w.total < w.cap ? w.total : w.cap;
+  // the local checks of agz_train_replay, then the window's digest; whatever they give, this rank enters the two exchanges below
+  auto local = [&]() -> int {
+    AGZ_REQUIRE(w.ctx == t->ctx, AGZ_E_INVALID, "agz_train_replay_sharded: the trainer and the window belong to different contexts");
+    AGZ_REQUIRE(w.F == t->conf.Features && w.H == t->conf.Height && w.W == t->conf.Width && w.A1 == t->conf.ActionSpace, AGZ_E_INVALID,
+                "agz_train_replay_sharded: the window's rows are [%d, %d, %d] + %d, the trainer's [%d, %d, %d] + %d", w.F, w.H, w.W, w.A1,
+                t->conf.Features, t->conf.Height, t->conf.Width, t->conf.ActionSpace);
+    const int r = agz::replay_check_symmetric(rp, symmetric, "agz_train_replay_sharded");
+    if (r != AGZ_OK) return r;
+    AGZ_REQUIRE(w.total > 0, AGZ_E_STATE, "agz_train_replay_sharded: the window is empty");
+    AGZ_HIP_TRY(hipSetDevice(t->ctx->device));
+    return AGZ_OK;
+  };
+  uint64_t mine[5] = {w.total, w.cap, n, w.packed ? 1u : 0u, 0};
+  int rc = local();
+  if (rc == AGZ_OK && verify) rc = agz_replay_digest(rp, &mine[4]);
+  uint64_t* d = nullptr;   // [n_ranks][5] gathered tuples, then this rank's
+  const size_t nr = (size_t)t->n_ranks;
+  if (rc == AGZ_OK && hipMalloc(&d, (nr + 1) * sizeof(mine)) != hipSuccess) {
+    (void)hipGetLastError();
+    d = nullptr;
+    agz::set_error("agz_train_replay_sharded: out of device memory for the window check");
+    rc = AGZ_E_NOMEM;
+  }
+  rc = t->shard.agree(rc);
+  if (rc != AGZ_OK) { if (d) hipFree(d); return rc; }
+  std::vector<uint64_t> all(nr * 5);
+  if (hipMemcpy(d + nr * 5, mine, sizeof(mine), hipMemcpyHostToDevice) != hipSuccess) rc = AGZ_E_HIP;
+  const int g = t->shard.allgather_bytes(d + nr * 5, d, sizeof(mine));
+  if (rc == AGZ_OK) rc = g;
+  if (rc == AGZ_OK && hipMemcpy(all.data(), d, all.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) rc = AGZ_E_HIP;
+  hipFree(d);
+  if (rc == AGZ_E_HIP) agz::set_error("agz_train_replay_sharded: the exchange of the window check failed");
+  rc = t->shard.agree(rc);
+  if (rc != AGZ_OK) return rc;
+  // (every rank holds the same gathered tuples, so every rank takes the same branch here)
+  static const char* const FIELD[5] = {"total", "capacity", "live", "the packed flag", "the digest"};
+  for (size_t r = 1; r < nr; r++)
+    for (int f = 0; f < 5; f++)
+      AGZ_REQUIRE(all[r * 5 + f] == all[f], AGZ_E_STATE,
+                  "agz_train_replay_sharded: the windows differ: rank %zu holds %s %llu (0x%llx), rank 0 holds %llu (0x%llx); nothing was trained",
+                  r, FIELD[f], (unsigned long long)all[r * 5 + f], (unsigned long long)all[r * 5 + f], (unsigned long long)all[f],
+                  (unsigned long long)all[f]);
+  hipStream_t s = t->ctx->stream;
+  const int Bg = t->B * t->n_ranks, row0 = t->rank * t->B;
+  for (int st = 0; st < steps && rc == AGZ_OK; st++) {
+    // (a rank whose sampler launch fails still enters the step's collectives: its error travels in the step's status word)
+    const int filled = agz::replay_sample_launch(rp, Bg, row0, t->B, seed, (uint64_t)st, symmetric, n, w.total, t->d_planes, t->d_pi, t->d_v);
+    rc = train_step_on_batch(t, filled);
   }
   float c[2] = {0, 0};
   hipError_t e = hipMemcpyAsync(c, t->cost, 8, hipMemcpyDeviceToHost, s);

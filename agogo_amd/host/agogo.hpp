@@ -130,6 +130,13 @@ inline float TrainReplay(Trainable& d, agz_replay* window, int steps, uint64_t s
   agz::check(agz_train_replay(d.h, window, steps, seed, symmetric ? 1 : 0, &cost), "dual.Train");
   return cost;
 }
+// the same on a sharded Trainable, collective: every rank calls it with its own replica of the window and the same arguments; step s trains
+// on minibatch s of n_ranks * BatchSize rows.  The replicas' counts — with verify their digests too — are compared at entry.
+inline float TrainReplaySharded(Trainable& d, agz_replay* window, int steps, uint64_t seed, bool symmetric, bool verify) {
+  float cost = 0;
+  agz::check(agz_train_replay_sharded(d.h, window, steps, seed, symmetric ? 1 : 0, verify ? 1 : 0, &cost), "dual.Train");
+  return cost;
+}
 }  // namespace dual
 
 namespace mcts {

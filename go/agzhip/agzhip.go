@@ -381,6 +381,28 @@ func (r *Replay) Len() (int64, error) {
 	return int64(live), err
 }
 
+// Digest is the uint64 digest of the window's logical content, computed on the device: equal for replicas that hold the same rows in the
+// same order, packed or not.  Synchronises the context's queue once.
+func (r *Replay) Digest() (uint64, error) {
+	defer r.ctx.enter()()
+	var d C.uint64_t
+	err := lastErr(C.agz_replay_digest(r.h, &d))
+	return uint64(d), err
+}
+
+// SampleSlice is rows [row0, row0+cnt) of minibatch `step` of `rows` rows, on the host: x [cnt*F*H*W], pi [cnt*PolicyLen], v [cnt].
+func (r *Replay) SampleSlice(rows, row0, cnt int, seed, step uint64, symmetric bool, x, pi, v []float32) error {
+	defer r.ctx.enter()()
+	if len(x) == 0 || len(pi) == 0 || len(v) == 0 {
+		return errors.New("agzhip: SampleSlice: empty buffer")
+	}
+	sym := C.int(0)
+	if symmetric {
+		sym = 1
+	}
+	return lastErr(C.agz_replay_sample_slice(r.h, C.int(rows), C.int(row0), C.int(cnt), C.uint64_t(seed), C.uint64_t(step), sym, (*C.float)(unsafe.Pointer(&x[0])), (*C.float)(unsafe.Pointer(&pi[0])), (*C.float)(unsafe.Pointer(&v[0]))))
+}
+
 func (r *Replay) Close() error { defer r.ctx.enter()(); C.agz_replay_destroy(r.h); r.h = nil; return nil }
 
 // ---- tournament use: Agent.Search against an outside opponent (agent.go:76-81, BASELINE configs[4]) ----
@@ -1006,7 +1028,7 @@ func (t *Trainer) TrainDev(ex *Examples, iterations int, seed uint64) error {
 }
 
 // TrainReplay is dual.Train's loop over `steps` minibatches sampled from a Replay window on the device; symmetric: every sampled row under
-// one of the eight board symmetries.  Not available on a sharded trainer.
+// one of the eight board symmetries.  A sharded trainer's route is TrainReplaySharded.
 func (t *Trainer) TrainReplay(w *Replay, steps int, seed uint64, symmetric bool) error {
 	defer t.ctx.enter()()
 	sym := C.int(0)
@@ -1015,6 +1037,22 @@ func (t *Trainer) TrainReplay(w *Replay, steps int, seed uint64, symmetric bool)
 	}
 	var cost C.float
 	return lastErr(C.agz_train_replay(t.h, w.h, C.int(steps), C.uint64_t(seed), sym, &cost))
+}
+
+// TrainReplaySharded is TrainReplay on a sharded trainer.  Collective: every rank calls it with its own replica of the window and the same
+// arguments; step s trains on minibatch s of nRanks * BatchSize rows, this rank on its own rows of it.  The replicas' counts are compared
+// at entry, with verify their digests too: a difference is an error on every rank and nothing is trained.
+func (t *Trainer) TrainReplaySharded(w *Replay, steps int, seed uint64, symmetric, verify bool) error {
+	defer t.ctx.enter()()
+	sym, ver := C.int(0), C.int(0)
+	if symmetric {
+		sym = 1
+	}
+	if verify {
+		ver = 1
+	}
+	var cost C.float
+	return lastErr(C.agz_train_replay_sharded(t.h, w.h, C.int(steps), C.uint64_t(seed), sym, ver, &cost))
 }
 
 // Export is dual.Infer's copy loop (meta.go:141-146): row 0 of every learnable into an inference Net.

@@ -829,6 +829,26 @@ int agz_replay_get(agz_replay* rp, int64_t j0, int64_t cnt, float* planes, float
  * (AGZ_E_INVALID with agz_examples_augment_rotate's messages).  An empty window: AGZ_E_STATE. */
 int agz_replay_sample_dev(agz_replay* rp, int rows, uint64_t seed, uint64_t step, int symmetric, float* X_dev, float* Pi_dev, float* V_dev);
 int agz_replay_sample(agz_replay* rp, int rows, uint64_t seed, uint64_t step, int symmetric, float* X, float* Pi, float* V);
+/* rows [row0, row0 + cnt) of minibatch `step` of `rows` rows: out row r = row (row0 + r) of what agz_replay_sample_dev(rows) gives, bit for
+ * bit; the buffers hold cnt rows.  The same kernel and ONE launch; with row0 = 0 and cnt = rows it is agz_replay_sample_dev.  What rank
+ * rho of a sharded trainer draws of the global minibatch (agz_train_replay_sharded): rows = n_ranks * B, row0 = rho * B, cnt = B.
+ * AGZ_E_INVALID unless rows >= 1, row0 >= 0, cnt >= 1 and row0 + cnt <= rows; the symmetric preconditions and the empty window as above. */
+int agz_replay_sample_slice_dev(agz_replay* rp, int rows, int row0, int cnt, uint64_t seed, uint64_t step, int symmetric,
+                                float* X_dev, float* Pi_dev, float* V_dev);
+int agz_replay_sample_slice(agz_replay* rp, int rows, int row0, int cnt, uint64_t seed, uint64_t step, int symmetric,
+                            float* X, float* Pi, float* V);
+/* The digest of a window's LOGICAL content (agogo_amd/csrc/replay.hpp, one host/device definition; DESIGN.md §2 replay-sharded): with
+ * mix64 the SplitMix64 finaliser, rowlen = F*H*W + PolicyLen + 1 and bits(j, e) the 32-bit pattern of element e (planes, then policy, then
+ * value) of logical row j (0 = the oldest live row; a packed window's decoded palette pattern),
+ *     digest = live + sum over j < live, e < rowlen of mix64(mix64(j * rowlen + e) ^ bits(j, e))          (uint64, wrapping)
+ * An integer sum: the same whatever the launch geometry, for a packed and an unpacked window fed the same rows, and wherever the ring
+ * sits physically.  Patterns, not floats: +0.0 and -0.0 differ.  agz_replay_digest reads the window once on the device and SYNCHRONISES
+ * THE CONTEXT'S QUEUE ONCE; agz_replay_digest_host is the same definition over n rows in host arrays (planes [n][Features * cells],
+ * policy [n][PolicyLen], value [n]) and needs no context: digest_host of agz_replay_get(0, live) is agz_replay_digest.  Replicas of a
+ * window (one per rank) hold the same rows exactly if their digests agree, up to a 2^-64 collision. */
+int agz_replay_digest(agz_replay* rp, uint64_t* digest);
+int agz_replay_digest_host(const float* planes, const float* policy, const float* value, int64_t n, int Features, int cells, int PolicyLen,
+                           uint64_t* digest);
 /* The same draw without a context or a device: j[r] in [0, n) and k[r] for the `rows` rows of minibatch `step` over n live rows (either
  * array may be NULL, not both).  AGZ_E_INVALID unless rows >= 1 and n >= 1. */
 int agz_replay_draw(uint64_t seed, uint64_t step, int rows, int64_t n, int symmetric, int64_t* j, int32_t* k);
@@ -836,9 +856,22 @@ int agz_replay_draw(uint64_t seed, uint64_t step, int rows, int64_t n, int symme
  * trainer's batch buffers and the trainer takes exactly the step agz_train_dev takes per batch (learn rate 0.1, the solver options / Adam
  * that are set).  live is read once at entry; no host synchronisation between steps; the cost of the last step is read back at the end
  * (last_cost may be NULL; 0 when steps == 0).  The trainer and the window must share a context and a shape (AGZ_E_INVALID); an empty
- * window is AGZ_E_STATE; a SHARDED trainer (agz_trainer_create_sharded / _sharded_tied) is AGZ_E_UNSUPPORTED: multi-GPU windows are not
- * built yet. */
+ * window is AGZ_E_STATE; a SHARDED trainer (agz_trainer_create_sharded / _sharded_tied) is AGZ_E_UNSUPPORTED: its route is the
+ * collective agz_train_replay_sharded. */
 int agz_train_replay(agz_trainer* t, agz_replay* rp, int steps, uint64_t seed, int symmetric, float* last_cost);
+/* agz_train_replay on a SHARDED trainer (agz_trainer_create_sharded / _sharded_tied; DESIGN.md §2 replay-sharded, §7).  COLLECTIVE: every
+ * rank calls it with its own handle and its own REPLICA of the window (the same rows in the same logical order, e.g. every rank appending
+ * what agz_examples_allgather gave it), and with the same steps, seed, symmetric and verify.  Declared result: what agz_train_replay
+ * computes on the single-process trainer of the same kind at the GLOBAL BatchSize — step s trains on minibatch s of n_ranks * B rows of
+ * the window, of which this rank draws rows [row0, row0 + B) itself (row0: agz_trainer_shard; agz_replay_sample_slice_dev), with the
+ * differences §7 declares for every sharded step and no other.  No collective is added to a step and nothing is exchanged for the draw.
+ * Entry, before anything is trained: the local checks of agz_train_replay, agreed on by all ranks (a failing rank returns its error, the
+ * others AGZ_E_PEER), then ONE all-gather of {total, capacity, live, packed flag, digest}, digest = agz_replay_digest if verify != 0,
+ * else 0.  If any rank's tuple differs from rank 0's, EVERY rank returns AGZ_E_STATE, the message names the first differing rank and
+ * field, and no parameter changed.  verify = 0 checks the counts only: replicas with equal counts and different rows then train on
+ * different data without an error.  A handle that is not sharded: AGZ_E_STATE (use agz_train_replay).  A rank whose sampler launch fails
+ * in a step still enters that step's collectives; the error ends the run on every rank, as in agz_train_dev. */
+int agz_train_replay_sharded(agz_trainer* t, agz_replay* rp, int steps, uint64_t seed, int symmetric, int verify, float* last_cost);
 
 /* ---- multi-GPU exchange over RCCL / xGMI -------------------------------------------------------------------
  * Self-play games shard across GPUs with NO data-path collective (one agz_ctx + arena set per GPU).  The path has exactly
