@@ -11,7 +11,7 @@ SRCS := $(CS)/ctx.hip $(CS)/net.hip $(CS)/engine.hip $(CS)/train.hip $(CS)/examp
 OBJS := $(OUT)/ctx.o $(OUT)/net.o $(OUT)/engine.o $(OUT)/train.o $(OUT)/examples.o $(OUT)/comm.o $(OUT)/replay.o
 HDRS := $(wildcard $(CS)/*.hpp) include/agz.h
 
-all: $(OUT)/libagz.so oracle tests/cpp/az_learn_ttt tests/cpp/az_learn_replay tests/cpp/az_learn_replay_packed tests/cpp/gtp_main tests/fake_rccl/librccl_fake.so
+all: $(OUT)/libagz.so oracle tests/cpp/az_learn_ttt tests/cpp/az_learn_replay tests/cpp/az_learn_replay_packed tests/cpp/az_learn_resume tests/cpp/gtp_main tests/fake_rccl/librccl_fake.so
 
 # TEST INFRASTRUCTURE: a process-per-rank stand-in for librccl (AGZ_RCCL_LIB) so the N > 1 exchange executes on a one-GPU box
 tests/fake_rccl/librccl_fake.so: tests/fake_rccl/fake_rccl.cpp
@@ -27,6 +27,10 @@ tests/cpp/az_learn_replay: tests/cpp/az_learn_replay.cpp agogo_amd/host/agogo.hp
 
 # the same with the window's planes kept as 2-bit codes (Config::ReplayPacked)
 tests/cpp/az_learn_replay_packed: tests/cpp/az_learn_replay_packed.cpp agogo_amd/host/agogo.hpp include/agz.h $(OUT)/libagz.so
+	g++ -std=c++17 -O1 -Iinclude $< -o $@ -L$(OUT) -lagz -Wl,-rpath,'$$ORIGIN/../../agogo_amd/lib'
+
+# AZ.Learn stopped at an epoch boundary, saved (AZ::SaveRun) and resumed on a new AZ (AZ::LoadRun)
+tests/cpp/az_learn_resume: tests/cpp/az_learn_resume.cpp agogo_amd/host/agogo.hpp include/agz.h $(OUT)/libagz.so
 	g++ -std=c++17 -O1 -Iinclude $< -o $@ -L$(OUT) -lagz -Wl,-rpath,'$$ORIGIN/../../agogo_amd/lib'
 
 # GTP front end over the C ABI (agogo_amd/host/gtp.hpp)

@@ -287,6 +287,9 @@ def lib():
     sig("agz_replay_sample_slice", i32, vp, i32, i32, i32, u64, u64, i32, pf, pf, pf)
     sig("agz_replay_digest", i32, vp, C.POINTER(C.c_uint64))
     sig("agz_replay_digest_host", i32, pf, pf, pf, i64, i32, i32, i32, C.POINTER(C.c_uint64))
+    sig("agz_replay_save", i32, vp, C.c_char_p)
+    sig("agz_replay_load", i32, vp, C.c_char_p)
+    sig("agz_replay_set_ckpt_staging", i32, vp, C.c_size_t)
     sig("agz_train_replay_sharded", i32, vp, vp, i32, u64, i32, i32, pf)
     sig("agz_rotate_boards", i32, vp, pf, i32, i32, i32, pf)
     sig("agz_ctx_prof_set_stride", i32, vp, i32, i32)
@@ -1457,6 +1460,20 @@ class Replay:
         d = C.c_uint64(0)
         _check(lib().agz_replay_digest(self.h, C.byref(d)), "agz_replay_digest")
         return d.value
+
+    def save(self, path):
+        """checkpoint of the window (agz_replay_save): the live rows in logical order, total, form and digest; `path` is replaced only
+        once the file is complete"""
+        _check(lib().agz_replay_save(self.h, os.fsencode(path)), "agz_replay_save")
+
+    def load(self, path):
+        """replace the window's content by a checkpoint of a window of the same row shape (agz_replay_load); capacity and form may
+        differ.  The whole file is validated first: after an AgzError the window is as it was"""
+        _check(lib().agz_replay_load(self.h, os.fsencode(path)), "agz_replay_load")
+
+    def set_ckpt_staging(self, nbytes):
+        """tests: the size of the staging buffers save / load stream through (agz_debug.h)"""
+        _check(lib().agz_replay_set_ckpt_staging(self.h, int(nbytes)), "agz_replay_set_ckpt_staging")
 
 
 def replay_digest_host(planes, policy, value, Features, cells, PolicyLen):

@@ -6,11 +6,15 @@
 // agz_replay_create_packed, the planes as 2-bit codes under a palette (replay_pack.hpp), decoded by the sampler as it draws.
 #include <algorithm>
 #include <cstring>
+#include <string>
 #include <vector>
+
+#include <unistd.h>
 
 #include "replay_win.hpp"   // (hip_runtime.h first: replay.hpp's device half uses __umul64hi)
 #include "replay.hpp"
 #include "replay_pack.hpp"
+#include "replay_ckpt.hpp"
 #include "sym.hpp"
 
 namespace agz {
@@ -214,6 +218,99 @@ __global__ __launch_bounds__(REPLAY_THREADS) void k_replay_digest(const uint32_t
   }
 }
 
+// ---- checkpoints (agz_replay_save / agz_replay_load, DESIGN.md §2 replay-ckpt; the bytes are replay_ckpt.hpp's) ------------------------
+
+constexpr int CKPT_BLOCKS = 4096;   // workgroups of a scan at most: a chunk is walked grid-stride
+
+// One staged chunk of a checkpoint file, validated and digested without a look at the ring: rows [j0, j0 + cnt) of ONE of the file's three
+// arrays, `n_el` words a row as they lie in the file.  acc[0] += the digest terms of the chunk's elements at their file logical index
+// (replay.hpp: an integer sum, so it is taken chunk by chunk and run by run; the host adds `live` and compares with the header's word);
+// acc[1] += the bad elements, acc[2] = min(acc[2], the first bad one's linear index in its array).
+//   words == 0    fp32 elements: element e of a row is element e_off + e of the logical row.  wn > 0 (the planes of an fp32 file on their
+//                 way into a packed window): a pattern outside the window's palette w0 .. w3 is bad, linear index j * n_el + e.
+//   words == 1    packed planes, n_el = F * wpp words a row, walked in the PADDED index t = word * 16 + i of k_replay_pack: cell c = (word
+//                 mod wpp) * 16 + i of plane word / wpp contributes the file palette's (p0 .. p3) pattern at element f * mm + c; a code not
+//                 below pn and a set bit past the plane's last cell are bad, linear index
+//                 j * n_el * 16 + t.
+// The reduction is k_replay_digest's; a lane touches acc[1], acc[2] only if it met a bad element.
+__global__ __launch_bounds__(REPLAY_THREADS) void k_replay_ckpt_scan(const uint32_t* __restrict__ chunk, int words, uint64_t n_el, uint64_t e_off,
+                                                                     uint64_t rowlen, uint64_t j0, uint64_t cnt, int mm, int wpp, uint32_t p0,
+                                                                     uint32_t p1, uint32_t p2, uint32_t p3, int pn, uint32_t w0, uint32_t w1,
+                                                                     uint32_t w2, uint32_t w3, int wn, unsigned long long* __restrict__ acc) {
+  __shared__ unsigned long long part[REPLAY_THREADS / 64];
+  unsigned long long sum = 0, bad = 0, first = PACK_NONE;
+  const uint64_t per_row = words ? n_el * replay_pack::CODES_PER_WORD : n_el;
+  const uint64_t n = cnt * per_row, stride = (uint64_t)gridDim.x * REPLAY_THREADS;
+  for (uint64_t i = (uint64_t)blockIdx.x * REPLAY_THREADS + threadIdx.x; i < n; i += stride) {
+    const uint64_t r = i / per_row, t = i - r * per_row, j = j0 + r;
+    if (words) {
+      const uint64_t word = t >> 4;
+      const int f = (int)(word / (uint64_t)wpp), c = (int)(word - (uint64_t)f * wpp) * replay_pack::CODES_PER_WORD + (int)(t & 15);
+      const uint32_t code = (chunk[r * n_el + word] >> replay_pack::shift_of(c)) & (uint32_t)(replay_pack::MAX_PALETTE - 1);
+      if (c < mm) {
+        if ((int)code >= pn) { bad++; if (j * per_row + t < first) first = j * per_row + t; }
+        sum += replay::digest_term(j, rowlen, e_off + (uint64_t)f * mm + c, replay_pack::decode(p0, p1, p2, p3, code));
+      } else if (code != 0) {
+        bad++;
+        if (j * per_row + t < first) first = j * per_row + t;
+      }
+    } else {
+      const uint32_t bits = chunk[i];
+      if (wn > 0 && replay_pack::code_of(w0, w1, w2, w3, wn, bits) < 0) { bad++; if (j * per_row + t < first) first = j * per_row + t; }
+      sum += replay::digest_term(j, rowlen, e_off + t, bits);
+    }
+  }
+  if (bad) {
+    atomicAdd(&acc[1], bad);
+    atomicMin(&acc[2], first);
+  }
+  // (every lane arrives here: the loop above has no barrier in it)
+  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+  const int wave = (int)threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) part[wave] = sum;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long s = 0;
+    for (int w = 0; w < REPLAY_THREADS / 64; w++) s += part[w];
+    atomicAdd(&acc[0], s);
+  }
+}
+
+// A staged chunk of PACKED planes a scan has accepted ([rows][F * wpp] words under the file's palette p0 .. p3) into the ring slots
+// (slot0 + r) mod cap of a window of the other form or another palette.  planes != NULL: an fp32 window, one lane a cell, the file
+// palette's pattern of its code.  Otherwise a packed window: one lane a word, every code c of a cell replaced by (remap >> 2 c) & 3, the
+// window's code of the same pattern (the host built the table; every file entry is in the window's palette); the bits past a plane's last
+// cell stay zero.  An fp32 chunk on its way into a packed window takes k_replay_pack.
+__global__ __launch_bounds__(REPLAY_THREADS) void k_replay_ckpt_put(const uint32_t* __restrict__ chunk, uint32_t* __restrict__ planes,
+                                                                    uint32_t* __restrict__ packed, int F, int mm, int wpp, int rows,
+                                                                    uint64_t slot0, uint64_t cap, uint32_t p0, uint32_t p1, uint32_t p2,
+                                                                    uint32_t p3, uint32_t remap) {
+  const int row_words = F * wpp, xs = F * mm;
+  for (int r = (int)blockIdx.y; r < rows; r += (int)gridDim.y) {
+    const uint32_t* in = chunk + (size_t)r * row_words;
+    const size_t s = (size_t)((slot0 + (uint64_t)r) % cap);
+    if (planes) {
+      uint32_t* out = planes + s * (size_t)xs;
+      for (int e = (int)blockIdx.x * REPLAY_THREADS + threadIdx.x; e < xs; e += (int)gridDim.x * REPLAY_THREADS) {
+        const int f = e / mm, c = e - f * mm;
+        out[e] = replay_pack::decode(p0, p1, p2, p3, in[f * wpp + (c >> 4)] >> replay_pack::shift_of(c));
+      }
+    } else {
+      uint32_t* out = packed + s * (size_t)row_words;
+      for (int w = (int)blockIdx.x * REPLAY_THREADS + threadIdx.x; w < row_words; w += (int)gridDim.x * REPLAY_THREADS) {
+        const int c0 = (w % wpp) * replay_pack::CODES_PER_WORD, cells = min(replay_pack::CODES_PER_WORD, mm - c0);
+        const uint32_t word = in[w];
+        uint32_t bits = 0;
+        for (int i = 0; i < cells; i++) {
+          const uint32_t code = (word >> (replay_pack::CODE_BITS * i)) & 3u;
+          bits |= ((remap >> (replay_pack::CODE_BITS * code)) & 3u) << (replay_pack::CODE_BITS * i);
+        }
+        out[w] = bits;
+      }
+    }
+  }
+}
+
 }  // namespace agz
 
 using namespace agz;
@@ -224,13 +321,18 @@ struct agz_replay {
   size_t xs = 0;
   float *planes = nullptr, *policy = nullptr, *value = nullptr;   // [cap][xs], [cap][A1], [cap]
   uint64_t cap = 0, total = 0;
+  // rows below this append number were never stored: 0 except after agz_replay_load put a file that does not fill the window (live <
+  // min(total, cap)) into it.  The ring then counts from `base`: row number g lives in slot (g - base) mod cap, live = min(total - base, cap).
+  uint64_t base = 0;
   // a packed window (agz_replay_create_packed): `planes` stays NULL, the planes live in `words` [cap][F * wpp] under `pal`
   bool is_packed = false;
   uint32_t* words = nullptr;
   int wpp = 0;
   replay_pack::Palette pal{};
+  size_t ckpt_staging = 256u << 20;   // bytes of the device buffer and of each of the two page-locked host buffers of a save or load (agz_replay_set_ckpt_staging)
 
-  uint64_t live() const { return replay::live(total, cap); }
+  uint64_t ring_total() const { return total - base; }   // what replay.hpp's ring arithmetic takes as `total`
+  uint64_t live() const { return replay::live(ring_total(), cap); }
   size_t row_words() const { return (size_t)F * wpp; }
   size_t row_bytes() const { return ((is_packed ? row_words() : xs) + (size_t)A1 + 1) * 4; }
 
@@ -309,6 +411,11 @@ struct agz_replay {
   }
   // c rows from (p, q, v) as c single-row appends in order: at most two contiguous row ranges per array; only the last cap rows of a
   // longer append survive
+  // checkpoints (agz_replay_save / agz_replay_load, at the end of this file)
+  replay_ckpt::Header ckpt_header() const;
+  char* ckpt_array(int k) const;
+  int ckpt_write(FILE* f, const replay_ckpt::Layout& l);
+  int ckpt_read(FILE* f, const char* path, const replay_ckpt::Header& h, const replay_ckpt::Layout& l, bool commit);
   int append(const float* p, const float* q, const float* v, uint64_t c, hipMemcpyKind kind, const char* who) {
     if (is_packed) {
       AGZ_REQUIRE(c <= (uint64_t)INT32_MAX, AGZ_E_INVALID, "%s: %llu rows in one append to a packed window (at most %d)", who,
@@ -317,7 +424,7 @@ struct agz_replay {
       if (r != AGZ_OK) return r;
     }
     const uint64_t skip = c > cap ? c - cap : 0, cnt = c - skip;
-    const uint64_t s0 = replay::head(total + skip, cap);
+    const uint64_t s0 = replay::head(ring_total() + skip, cap);
     const uint64_t first = std::min<uint64_t>(cnt, cap - s0);
     hipStream_t s = ctx->stream;
     if (is_packed) {
@@ -336,7 +443,7 @@ struct agz_replay {
   }
 };
 
-ReplayInfo agz::replay_info(const agz_replay* rp) { return ReplayInfo{rp->ctx, rp->F, rp->H, rp->W, rp->A1, rp->total, rp->cap, rp->is_packed}; }
+ReplayInfo agz::replay_info(const agz_replay* rp) { return ReplayInfo{rp->ctx, rp->F, rp->H, rp->W, rp->A1, rp->ring_total(), rp->cap, rp->is_packed}; }
 
 int agz::replay_check_symmetric(const agz_replay* rp, int symmetric, const char* who) {
   if (!symmetric) return AGZ_OK;
@@ -381,7 +488,7 @@ static int sample_slice_dev(const char* who, agz_replay* rp, int rows, int row0,
   if (r != AGZ_OK) return r;
   AGZ_REQUIRE(rp->total > 0, AGZ_E_STATE, "%s: the window is empty", who);
   AGZ_HIP_TRY(hipSetDevice(rp->ctx->device));
-  return replay_sample_launch(rp, rows, row0, cnt, seed, step, symmetric, rp->live(), rp->total, X_dev, Pi_dev, V_dev);
+  return replay_sample_launch(rp, rows, row0, cnt, seed, step, symmetric, rp->live(), rp->ring_total(), X_dev, Pi_dev, V_dev);
 }
 // ... and into host buffers of cnt rows
 static int sample_slice_host(const char* who, agz_replay* rp, int rows, int row0, int cnt, uint64_t seed, uint64_t step, int symmetric,
@@ -398,7 +505,7 @@ static int sample_slice_host(const char* who, agz_replay* rp, int rows, int row0
     return AGZ_E_NOMEM;
   }
   hipStream_t s = rp->ctx->stream;
-  r = replay_sample_launch(rp, rows, row0, cnt, seed, step, symmetric, rp->live(), rp->total, d, d + nx, d + nx + np);
+  r = replay_sample_launch(rp, rows, row0, cnt, seed, step, symmetric, rp->live(), rp->ring_total(), d, d + nx, d + nx + np);
   hipError_t e = hipSuccess;
   if (r == AGZ_OK) e = hipMemcpyAsync(X, d, nx * 4, hipMemcpyDeviceToHost, s);
   if (r == AGZ_OK && e == hipSuccess) e = hipMemcpyAsync(Pi, d + nx, np * 4, hipMemcpyDeviceToHost, s);
@@ -532,6 +639,7 @@ int agz_replay_count(const agz_replay* rp, int64_t* live, uint64_t* total, int64
 int agz_replay_clear(agz_replay* rp) {
   AGZ_REQUIRE(rp, AGZ_E_INVALID, "agz_replay_clear: NULL window");
   rp->total = 0;
+  rp->base = 0;
   return AGZ_OK;
 }
 
@@ -570,7 +678,7 @@ int agz_replay_get(agz_replay* rp, int64_t j0, int64_t cnt, float* planes, float
   if (cnt == 0) return AGZ_OK;
   AGZ_HIP_TRY(hipSetDevice(rp->ctx->device));
   AGZ_HIP_TRY(hipStreamSynchronize(rp->ctx->stream));
-  const uint64_t s0 = replay::slot(rp->total, rp->cap, (uint64_t)j0);
+  const uint64_t s0 = replay::slot(rp->ring_total(), rp->cap, (uint64_t)j0);
   const uint64_t first = std::min<uint64_t>((uint64_t)cnt, rp->cap - s0);
   const uint64_t at[2] = {0, first}, from[2] = {s0, 0}, len[2] = {first, (uint64_t)cnt - first};
   for (int i = 0; i < 2; i++) {
@@ -633,7 +741,7 @@ int agz_replay_digest(agz_replay* rp, uint64_t* digest) {
     const replay_pack::Palette& pal = rp->pal;   // (an unpacked window's is all zero and unused)
     hipLaunchKernelGGL(k_replay_digest, grid, dim3(REPLAY_THREADS), 0, s, reinterpret_cast<const uint32_t*>(rp->planes), rp->words,
                        reinterpret_cast<const uint32_t*>(rp->policy), reinterpret_cast<const uint32_t*>(rp->value), rp->F, rp->H * rp->W,
-                       rp->wpp, rp->A1, n, rp->total, rp->cap, pal.e[0], pal.e[1], pal.e[2], pal.e[3], d);
+                       rp->wpp, rp->A1, n, rp->ring_total(), rp->cap, pal.e[0], pal.e[1], pal.e[2], pal.e[3], d);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpyAsync(&got, d, 8, hipMemcpyDeviceToHost, s);
@@ -662,6 +770,260 @@ int agz_replay_draw(uint64_t seed, uint64_t step, int rows, int64_t n, int symme
     if (j) j[r] = (int64_t)d.j;
     if (k) k[r] = d.k;
   }
+  return AGZ_OK;
+}
+
+}  // extern "C"
+
+// ---- checkpoints (agz_replay_save / agz_replay_load) ----------------------------------------------------------------------------------
+// The bytes are replay_ckpt.hpp's; this side describes the window and streams its three arrays through TWO page-locked host buffers of
+// ckpt_staging bytes each (and, on a load, ONE device staging buffer): the copy of chunk i + 1 between device and host runs while the file
+// system has chunk i.  A chunk is a range of logical rows of one array; a logical range is at most two contiguous slot ranges
+// (replay::slot), so a save needs no kernel.  A load reads the file twice: k_replay_ckpt_scan sees every chunk in the staging buffer
+// first and nothing of the ring is touched until the whole file has passed; only then is it streamed again, into the ring.
+namespace {
+
+struct CkptStaging {
+  hipStream_t s = nullptr;
+  void* dev = nullptr;
+  void* host[2] = {nullptr, nullptr};
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  unsigned long long* acc = nullptr;   // the scan's sum, bad count, first bad index
+  int init(hipStream_t stream, size_t bytes, bool device) {
+    s = stream;
+    for (int i = 0; i < 2; i++) { AGZ_HIP_TRY(hipHostMalloc(&host[i], bytes, hipHostMallocDefault)); AGZ_HIP_TRY(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming)); }
+    if (device) { AGZ_HIP_TRY(hipMalloc(&dev, bytes)); AGZ_HIP_TRY(hipMalloc(&acc, 3 * sizeof(unsigned long long))); }
+    return AGZ_OK;
+  }
+  ~CkptStaging() {   // released (after the queue has drained) when the call returns, whatever happened
+    if (s) hipStreamSynchronize(s);
+    if (dev) hipFree(dev);
+    if (acc) hipFree(acc);
+    for (int i = 0; i < 2; i++) { if (host[i]) hipHostFree(host[i]); if (ev[i]) hipEventDestroy(ev[i]); }
+  }
+};
+
+struct CkptChunk { int k; uint64_t j0, cnt; };   // rows [j0, j0 + cnt) of array k, in the file's logical order
+
+constexpr uint64_t CKPT_MAX_ROWS = 1u << 30;   // of one chunk: the kernels count a chunk's rows in an int
+
+// rows [from, to) of the three arrays in file order, each cut into chunks of as many whole rows as `staging` bytes hold (at least one);
+// *bytes = the largest chunk
+std::vector<CkptChunk> ckpt_chunks(const replay_ckpt::Layout& l, uint64_t from, uint64_t to, size_t staging, size_t* bytes) {
+  std::vector<CkptChunk> out;
+  *bytes = 64;
+  for (int k = 0; k < replay_ckpt::ARRAYS; k++) {
+    const uint64_t rows = std::min(std::max<uint64_t>(1, staging / l.row_bytes[k]), CKPT_MAX_ROWS);
+    for (uint64_t j = from; j < to; j += rows) {
+      out.push_back({k, j, std::min(rows, to - j)});
+      *bytes = std::max<size_t>(*bytes, (size_t)(out.back().cnt * l.row_bytes[k]));
+    }
+  }
+  return out;
+}
+
+}  // namespace
+
+replay_ckpt::Header agz_replay::ckpt_header() const {
+  replay_ckpt::Header h{};
+  h.F = (uint32_t)F; h.H = (uint32_t)H; h.W = (uint32_t)W; h.A1 = (uint32_t)A1;
+  h.form = is_packed ? 1u : 0u;
+  h.n_palette = is_packed ? (uint32_t)pal.n : 0u;
+  for (int i = 0; i < pal.n && is_packed; i++) h.palette[i] = pal.e[i];
+  h.total = total; h.live = live();
+  // the capacity word is informational beyond the file's own rule live == min(total, capacity).  A window that a larger-capacity load left
+  // not yet full (base != 0: live < min(total, cap)) writes its live count there, the capacity of the smallest window that holds these
+  // rows of this total: the file is then sound by that rule and loads anywhere, as any other
+  h.capacity = base ? h.live : cap;
+  return h;
+}
+
+char* agz_replay::ckpt_array(int k) const {
+  return k == replay_ckpt::PLANES ? (is_packed ? (char*)words : (char*)planes) : k == replay_ckpt::POLICY ? (char*)policy : (char*)value;
+}
+
+// the three arrays and the end mark behind a written head.  AGZ_E_INVALID: the file system refused a write.
+int agz_replay::ckpt_write(FILE* f, const replay_ckpt::Layout& l) {
+  hipStream_t s = ctx->stream;
+  size_t bytes = 0;
+  const std::vector<CkptChunk> ch = ckpt_chunks(l, 0, live(), ckpt_staging, &bytes);
+  CkptStaging st;
+  int r = st.init(s, bytes, false);
+  if (r != AGZ_OK) return r;
+  auto issue = [&](size_t i) -> int {   // chunk i -> host[i & 1], asynchronously: the one or two slot ranges of its rows
+    const CkptChunk& c = ch[i];
+    const uint64_t rb = l.row_bytes[c.k], s0 = replay::slot(ring_total(), cap, c.j0), first = std::min(c.cnt, cap - s0);
+    char* to = (char*)st.host[i & 1];
+    AGZ_HIP_TRY(hipMemcpyAsync(to, ckpt_array(c.k) + s0 * rb, first * rb, hipMemcpyDeviceToHost, s));
+    if (c.cnt > first) AGZ_HIP_TRY(hipMemcpyAsync(to + first * rb, ckpt_array(c.k), (c.cnt - first) * rb, hipMemcpyDeviceToHost, s));
+    AGZ_HIP_TRY(hipEventRecord(st.ev[i & 1], s));
+    return AGZ_OK;
+  };
+  if (!ch.empty() && (r = issue(0)) != AGZ_OK) return r;
+  for (size_t i = 0; i < ch.size(); i++) {
+    if (i + 1 < ch.size() && (r = issue(i + 1)) != AGZ_OK) return r;   // the next chunk's copy runs under this chunk's write
+    AGZ_HIP_TRY(hipEventSynchronize(st.ev[i & 1]));
+    AGZ_REQUIRE(replay_ckpt::write_rows(f, l, ch[i].k, ch[i].j0, ch[i].cnt, st.host[i & 1]), AGZ_E_INVALID, "agz_replay_save: write failed");
+  }
+  AGZ_REQUIRE(replay_ckpt::write_end(f, l), AGZ_E_INVALID, "agz_replay_save: write failed");
+  return AGZ_OK;
+}
+
+// One pass over a file whose head read_head() has accepted.  commit == false: every chunk goes through the device staging buffer and
+// k_replay_ckpt_scan; the codes, the unused bits, the palette membership and the digest are checked and NOTHING of the window changes.
+// commit == true (after such a pass): the newest min(live, cap) rows go into the slots replay.hpp gives them, in the window's form, and
+// total := the file's.  A device error in the committing pass leaves the window's content undefined.
+int agz_replay::ckpt_read(FILE* f, const char* path, const replay_ckpt::Header& h, const replay_ckpt::Layout& l, bool commit) {
+  hipStream_t s = ctx->stream;
+  const int mm = H * W;
+  const replay_pack::Palette fpal = h.form ? replay_pack::make_palette(h.palette, (int)h.n_palette) : replay_pack::Palette{};
+  const int fwpp = replay_pack::wpp(mm);
+  // the planes need a kernel unless the file holds them as the window does
+  bool same_planes = (h.form != 0) == is_packed;
+  uint32_t remap = 0;
+  if (h.form && is_packed) {
+    for (int c = 0; c < fpal.n; c++) {
+      const int code = replay_pack::code_of(pal, fpal.e[c]);
+      AGZ_REQUIRE(code >= 0, AGZ_E_INVALID, "agz_replay_load: entry %d of the palette of %s, the bit pattern 0x%08X, is not in the window's palette", c, path, fpal.e[c]);
+      remap |= (uint32_t)code << (replay_pack::CODE_BITS * c);
+      same_planes = same_planes && code == c;
+    }
+  }
+  const uint64_t keep = std::min<uint64_t>(h.live, cap), skip = commit ? h.live - keep : 0;
+  // a file that fills this window (keep == min(total, cap)) lies as its appends laid it, row number g in slot g mod cap; one that does not
+  // starts the ring anew at its oldest row
+  const uint64_t new_base = keep == replay::live(h.total, cap) ? 0 : h.total - keep;
+  size_t bytes = 0;
+  const std::vector<CkptChunk> ch = ckpt_chunks(l, skip, h.live, ckpt_staging, &bytes);
+  CkptStaging st;
+  int r = st.init(s, bytes, true);
+  if (r != AGZ_OK) return r;
+  if (!commit) {
+    AGZ_HIP_TRY(hipMemsetAsync(st.acc, 0, 16, s));
+    AGZ_HIP_TRY(hipMemsetAsync(st.acc + 2, 0xFF, 8, s));   // PACK_NONE
+  }
+  for (size_t i = 0; i < ch.size(); i++) {   // the file read of chunk i runs under the copy and the kernel of chunk i - 1
+    const CkptChunk& c = ch[i];
+    const uint64_t rb = l.row_bytes[c.k];
+    if (i >= 2) AGZ_HIP_TRY(hipEventSynchronize(st.ev[i & 1]));   // host[i & 1] has left for the device
+    char* from = (char*)st.host[i & 1];
+    AGZ_REQUIRE(replay_ckpt::read_rows(f, l, c.k, c.j0, c.cnt, from), AGZ_E_INVALID, "agz_replay_load: reading %s failed", path);
+    const bool planes_k = c.k == replay_ckpt::PLANES;
+    const uint64_t slot0 = (h.total - h.live + c.j0 - new_base) % cap;   // (commit) the slot the append of this row wrote, or would have
+    if (commit && (!planes_k || same_planes)) {               // a plain copy into the one or two slot ranges
+      const uint64_t first = std::min(c.cnt, cap - slot0);
+      AGZ_HIP_TRY(hipMemcpyAsync(ckpt_array(c.k) + slot0 * rb, from, first * rb, hipMemcpyHostToDevice, s));
+      if (c.cnt > first) AGZ_HIP_TRY(hipMemcpyAsync(ckpt_array(c.k), from + first * rb, (c.cnt - first) * rb, hipMemcpyHostToDevice, s));
+      AGZ_HIP_TRY(hipEventRecord(st.ev[i & 1], s));
+      continue;
+    }
+    AGZ_HIP_TRY(hipMemcpyAsync(st.dev, from, c.cnt * rb, hipMemcpyHostToDevice, s));
+    AGZ_HIP_TRY(hipEventRecord(st.ev[i & 1], s));
+    const uint32_t* chunk = static_cast<const uint32_t*>(st.dev);
+    if (!commit) {
+      const bool words_k = planes_k && h.form;
+      const uint64_t n_el = rb / 4, e_off = planes_k ? 0 : c.k == replay_ckpt::POLICY ? h.xs() : h.xs() + h.A1;
+      const uint64_t n = c.cnt * n_el * (words_k ? replay_pack::CODES_PER_WORD : 1);
+      const unsigned grid = (unsigned)std::min<uint64_t>((n + REPLAY_THREADS - 1) / REPLAY_THREADS, CKPT_BLOCKS);
+      const int wn = planes_k && !h.form && is_packed ? pal.n : 0;   // fp32 planes on their way into a packed window
+      hipLaunchKernelGGL(k_replay_ckpt_scan, dim3(grid), dim3(REPLAY_THREADS), 0, s, chunk, words_k ? 1 : 0, n_el, e_off, h.rowlen(), c.j0, c.cnt, mm,
+                         fwpp, fpal.e[0], fpal.e[1], fpal.e[2], fpal.e[3], fpal.n, pal.e[0], pal.e[1], pal.e[2], pal.e[3], wn, st.acc);
+    } else if (is_packed && !h.form) {   // fp32 rows the scan found inside the palette: the append's own pack kernel
+      const unsigned gx = (unsigned)std::min<size_t>((row_words() * replay_pack::CODES_PER_WORD + REPLAY_THREADS - 1) / REPLAY_THREADS, 1024);
+      hipLaunchKernelGGL(k_replay_pack, dim3(gx, (unsigned)std::min<uint64_t>(c.cnt, 65535)), dim3(REPLAY_THREADS), 0, s, chunk, words, F, mm, wpp, (int)c.cnt,
+                         slot0, cap, pal.e[0], pal.e[1], pal.e[2], pal.e[3], pal.n);
+    } else {                             // packed rows into an fp32 window, or into a packed window of another palette
+      const size_t per_row = is_packed ? row_words() : xs;
+      const unsigned gx = (unsigned)std::min<size_t>((per_row + REPLAY_THREADS - 1) / REPLAY_THREADS, 1024);
+      hipLaunchKernelGGL(k_replay_ckpt_put, dim3(gx, (unsigned)std::min<uint64_t>(c.cnt, 65535)), dim3(REPLAY_THREADS), 0, s, chunk,
+                         reinterpret_cast<uint32_t*>(planes), words, F, mm, fwpp, (int)c.cnt, slot0, cap, fpal.e[0], fpal.e[1], fpal.e[2], fpal.e[3], remap);
+    }
+    AGZ_HIP_TRY(hipGetLastError());
+  }
+  if (commit) {
+    AGZ_HIP_TRY(hipStreamSynchronize(s));
+    total = h.total;
+    base = new_base;
+    return AGZ_OK;
+  }
+  unsigned long long got[3] = {0, 0, PACK_NONE};
+  AGZ_HIP_TRY(hipMemcpyAsync(got, st.acc, sizeof(got), hipMemcpyDeviceToHost, s));
+  AGZ_HIP_TRY(hipStreamSynchronize(s));
+  if (got[1]) {   // the first bad element: its value is read where it lies, in the file
+    const uint64_t at = got[2];
+    uint32_t word = 0;
+    if (h.form) {
+      const uint64_t per_row = h.row_words() * replay_pack::CODES_PER_WORD, row = at / per_row, t = at % per_row, w = t >> 4;
+      const int f_ = (int)(w / fwpp), cell = (int)(w % fwpp) * replay_pack::CODES_PER_WORD + (int)(t & 15);
+      const bool ok = replay_ckpt::seek_to(f, l.off[replay_ckpt::PLANES] + (row * h.row_words() + w) * 4) && fread(&word, 4, 1, f) == 1;
+      const unsigned code = (word >> replay_pack::shift_of(cell)) & 3u;
+      AGZ_REQUIRE(ok, AGZ_E_INVALID, "agz_replay_load: reading %s failed", path);
+      AGZ_REQUIRE(cell < mm, AGZ_E_INVALID,
+                  "agz_replay_load: %s: row %llu, plane %d: the word 0x%08X has a bit set past the plane's last cell (%llu bad cells in all); nothing was loaded",
+                  path, (unsigned long long)row, f_, word, got[1]);
+      agz::set_error("agz_replay_load: %s: row %llu, element %llu holds the code %u, the file's palette has %d entries (%llu bad cells in all); nothing was loaded",
+                     path, (unsigned long long)row, (unsigned long long)((uint64_t)f_ * mm + cell), code, fpal.n, got[1]);
+      return AGZ_E_INVALID;
+    }
+    const bool ok = replay_ckpt::seek_to(f, l.off[replay_ckpt::PLANES] + at * 4) && fread(&word, 4, 1, f) == 1;
+    AGZ_REQUIRE(ok, AGZ_E_INVALID, "agz_replay_load: reading %s failed", path);
+    agz::set_error("agz_replay_load: %s: row %llu, element %llu (linear element %llu) holds the bit pattern 0x%08X, which is not in the window's palette "
+                   "(%llu bad cells in all); nothing was loaded",
+                   path, (unsigned long long)(at / h.xs()), (unsigned long long)(at % h.xs()), (unsigned long long)at, word, got[1]);
+    return AGZ_E_INVALID;
+  }
+  const uint64_t digest = h.live + (uint64_t)got[0];
+  AGZ_REQUIRE(digest == h.digest, AGZ_E_INVALID, "agz_replay_load: %s: the rows' digest is %016llx, the header's %016llx; nothing was loaded", path,
+              (unsigned long long)digest, (unsigned long long)h.digest);
+  return AGZ_OK;
+}
+
+extern "C" {
+
+int agz_replay_save(agz_replay* rp, const char* path) {
+  AGZ_REQUIRE(rp && path, AGZ_E_INVALID, "agz_replay_save: NULL argument");
+  replay_ckpt::Header h = rp->ckpt_header();
+  int r = agz_replay_digest(rp, &h.digest);   // (joins the context's queue: every append enqueued so far is in the window)
+  if (r != AGZ_OK) return r;
+  const replay_ckpt::Layout l = replay_ckpt::layout(h);
+  const std::string tmp = std::string(path) + ".tmp";
+  FILE* f = fopen(tmp.c_str(), "wb");
+  AGZ_REQUIRE(f, AGZ_E_INVALID, "agz_replay_save: cannot open %s", tmp.c_str());
+  if (!replay_ckpt::write_head(f, h)) { agz::set_error("agz_replay_save: write to %s failed", tmp.c_str()); r = AGZ_E_INVALID; }
+  if (r == AGZ_OK) r = rp->ckpt_write(f, l);
+  const bool flushed = fflush(f) == 0 && fsync(fileno(f)) == 0;
+  const bool closed = fclose(f) == 0;
+  if (r == AGZ_OK && !(flushed && closed)) { agz::set_error("agz_replay_save: write to %s failed", tmp.c_str()); r = AGZ_E_INVALID; }
+  if (r == AGZ_OK && rename(tmp.c_str(), path) != 0) { agz::set_error("agz_replay_save: cannot rename %s to %s", tmp.c_str(), path); r = AGZ_E_INVALID; }
+  if (r != AGZ_OK) remove(tmp.c_str());
+  return r;
+}
+
+int agz_replay_load(agz_replay* rp, const char* path) {
+  AGZ_REQUIRE(rp && path, AGZ_E_INVALID, "agz_replay_load: NULL argument");
+  AGZ_HIP_TRY(hipSetDevice(rp->ctx->device));
+  AGZ_HIP_TRY(hipStreamSynchronize(rp->ctx->stream));
+  FILE* f = fopen(path, "rb");
+  AGZ_REQUIRE(f, AGZ_E_INVALID, "agz_replay_load: cannot open %s", path);
+  replay_ckpt::Header h{};
+  replay_ckpt::Layout l;
+  std::string why;
+  const replay_ckpt::Status st = replay_ckpt::read_head(f, rp->ckpt_header(), &h, &l, &why);
+  int r = AGZ_OK;
+  if (st != replay_ckpt::OK) {
+    agz::set_error("agz_replay_load: %s %s: %s", path, st == replay_ckpt::MISMATCH ? "holds rows of another shape" : st == replay_ckpt::NOT_WINDOW ? "is not a replay window checkpoint" : "is truncated or inconsistent", why.c_str());
+    r = AGZ_E_INVALID;
+  }
+  if (r == AGZ_OK) r = rp->ckpt_read(f, path, h, l, false);   // the whole file, validated in the staging buffer ...
+  if (r == AGZ_OK) r = rp->ckpt_read(f, path, h, l, true);    // ... and only then into the ring
+  fclose(f);
+  return r;
+}
+
+int agz_replay_set_ckpt_staging(agz_replay* rp, size_t bytes) {
+  AGZ_REQUIRE(rp, AGZ_E_INVALID, "agz_replay_set_ckpt_staging: NULL window");
+  AGZ_REQUIRE(bytes >= 4 && bytes <= ((size_t)4 << 30), AGZ_E_INVALID, "agz_replay_set_ckpt_staging: %zu bytes (4 bytes .. 4 GiB)", bytes);
+  rp->ckpt_staging = bytes;
   return AGZ_OK;
 }
 

@@ -9,7 +9,8 @@ namespace agz {
 struct ReplayInfo {
   agz_ctx* ctx;
   int F, H, W, A1;
-  uint64_t total, cap;
+  uint64_t ring_total, cap;   // ring_total: the rows the ring has taken, what replay.hpp's arithmetic calls `total` (agz_replay_count's
+                              // total, less the rows a loaded checkpoint did not hold: agz_replay_load into a larger window)
   bool packed;
 };
 ReplayInfo replay_info(const agz_replay* rp);

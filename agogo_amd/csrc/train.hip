@@ -3514,12 +3514,12 @@ int agz_train_replay(agz_trainer* t, agz_replay* rp, int steps, uint64_t seed, i
               t->conf.Features, t->conf.Height, t->conf.Width, t->conf.ActionSpace);
   int rc = agz::replay_check_symmetric(rp, symmetric, "agz_train_replay");
   if (rc != AGZ_OK) return rc;
-  AGZ_REQUIRE(w.total > 0, AGZ_E_STATE, "agz_train_replay: the window is empty");
+  AGZ_REQUIRE(w.ring_total > 0, AGZ_E_STATE, "agz_train_replay: the window is empty");
   AGZ_HIP_TRY(hipSetDevice(t->ctx->device));
   hipStream_t s = t->ctx->stream;
-  const uint64_t n = w.total < w.cap ? w.total : w.cap;
+  const uint64_t n = w.ring_total < w.cap ? w.ring_total : w.cap;
   for (int st = 0; st < steps && rc == AGZ_OK; st++) {
-    rc = agz::replay_sample_launch(rp, t->B, 0, t->B, seed, (uint64_t)st, symmetric, n, w.total, t->d_planes, t->d_pi, t->d_v);
+    rc = agz::replay_sample_launch(rp, t->B, 0, t->B, seed, (uint64_t)st, symmetric, n, w.ring_total, t->d_planes, t->d_pi, t->d_v);
     if (rc == AGZ_OK) rc = train_step_on_batch(t);
   }
   float c[2] = {0, 0};
@@ -3541,7 +3541,7 @@ int agz_train_replay_sharded(agz_trainer* t, agz_replay* rp, int steps, uint64_t
   AGZ_REQUIRE(t->sharded, AGZ_E_STATE,
               "agz_train_replay_sharded: not a sharded trainer (agz_trainer_create_sharded / _sharded_tied); agz_train_replay trains this one");
   const agz::ReplayInfo w = agz::replay_info(rp);
-  const uint64_t n = w.total < w.cap ? w.total : w.cap;
+  const uint64_t n = w.ring_total < w.cap ? w.ring_total : w.cap;
   // the local checks of agz_train_replay, then the window's digest; whatever they give, this rank enters the two exchanges below
   auto local = [&]() -> int {
     AGZ_REQUIRE(w.ctx == t->ctx, AGZ_E_INVALID, "agz_train_replay_sharded: the trainer and the window belong to different contexts");
@@ -3550,11 +3550,11 @@ int agz_train_replay_sharded(agz_trainer* t, agz_replay* rp, int steps, uint64_t
                 t->conf.Features, t->conf.Height, t->conf.Width, t->conf.ActionSpace);
     const int r = agz::replay_check_symmetric(rp, symmetric, "agz_train_replay_sharded");
     if (r != AGZ_OK) return r;
-    AGZ_REQUIRE(w.total > 0, AGZ_E_STATE, "agz_train_replay_sharded: the window is empty");
+    AGZ_REQUIRE(w.ring_total > 0, AGZ_E_STATE, "agz_train_replay_sharded: the window is empty");
     AGZ_HIP_TRY(hipSetDevice(t->ctx->device));
     return AGZ_OK;
   };
-  uint64_t mine[5] = {w.total, w.cap, n, w.packed ? 1u : 0u, 0};
+  uint64_t mine[5] = {w.ring_total, w.cap, n, w.packed ? 1u : 0u, 0};
   int rc = local();
   if (rc == AGZ_OK && verify) rc = agz_replay_digest(rp, &mine[4]);
   uint64_t* d = nullptr;   // [n_ranks][5] gathered tuples, then this rank's
@@ -3588,7 +3588,7 @@ int agz_train_replay_sharded(agz_trainer* t, agz_replay* rp, int steps, uint64_t
   const int Bg = t->B * t->n_ranks, row0 = t->rank * t->B;
   for (int st = 0; st < steps && rc == AGZ_OK; st++) {
     // (a rank whose sampler launch fails still enters the step's collectives: its error travels in the step's status word)
-    const int filled = agz::replay_sample_launch(rp, Bg, row0, t->B, seed, (uint64_t)st, symmetric, n, w.total, t->d_planes, t->d_pi, t->d_v);
+    const int filled = agz::replay_sample_launch(rp, Bg, row0, t->B, seed, (uint64_t)st, symmetric, n, w.ring_total, t->d_planes, t->d_pi, t->d_v);
     rc = train_step_on_batch(t, filled);
   }
   float c[2] = {0, 0};

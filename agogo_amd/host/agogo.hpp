@@ -5,11 +5,15 @@
 // Errors: the reference returns `error` or panics; here agz::Error is thrown with agz_last_error().
 #pragma once
 #include <cstdint>
+#include <cstdio>
+#include <cstring>
 #include <map>
 #include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
+
+#include <unistd.h>
 
 #include "../../include/agz.h"
 
@@ -259,6 +263,11 @@ struct Replay {
   Replay& operator=(const Replay&) = delete;
   size_t size() const { int64_t n = 0; agz::check(agz_replay_count(h, &n, nullptr, nullptr), "len(window)"); return (size_t)n; }   // live rows
   void Append(Examples& ex) { agz::check(agz_replay_append_examples(h, ex.h), "append(window, ex...)"); }
+  // Checkpoint of the window and the continuation from one (agz_replay_save / agz_replay_load): the live rows in logical order, total,
+  // form and digest.  A file loads into a window of the same row shape, whatever its capacity and form; a bad file changes nothing.
+  void Save(const std::string& path) { agz::check(agz_replay_save(h, path.c_str()), "Replay.Save"); }
+  void Load(const std::string& path) { agz::check(agz_replay_load(h, path.c_str()), "Replay.Load"); }
+  uint64_t Digest() const { uint64_t d = 0; agz::check(agz_replay_digest(h, &d), "window digest"); return d; }
 };
 // agogo.Config (datatypes.go:14-25)
 struct Config {
@@ -327,6 +336,7 @@ struct AZ {
   std::vector<EpochStats> log;
   Statistics stats;
   int a_id = 1, b_id = 2, next_id = 3;         // network identities (the reference's %p of Agent.NN)
+  int epochs_done = 0;                         // the epoch the next Learn of a continued run starts at (SaveRun / LoadRun)
 
   AZ(agz::Ctx& c, GameSpec g, const Config& cf, uint64_t seed_ = 1337) : ctx(c), game(g), conf(cf), seed(seed_) {  // agogo.go:41-72
     if (!cf.NNConf.IsValid()) throw agz::Error("NNConf is not valid. Unable to proceed");
@@ -347,9 +357,10 @@ struct AZ {
   void applySolver(dual::Trainable& t) const {   // (the default options leave the trainer untouched: no call)
     if (conf.Solver.momentum != 0.f || conf.Solver.l2reg != 0.f || conf.Solver.clip != 0.f) t.SetSolver(conf.Solver.momentum, conf.Solver.l2reg, conf.Solver.clip);
   }
-  // AZ.Learn (agogo.go:100-172)
-  void Learn(int iters, int episodes, int nniters, int arenaGames) {
-    for (int epoch = 0; epoch < iters; epoch++) {
+  // AZ.Learn (agogo.go:100-172).  Build extension: epochs first_epoch .. first_epoch + iters - 1, each with the seeds epoch number `epoch`
+  // has in an uninterrupted run, so Learn(2, ...), SaveRun, LoadRun on a new AZ and Learn(1, ..., 2) is Learn(3, ...).
+  void Learn(int iters, int episodes, int nniters, int arenaGames, int first_epoch = 0) {
+    for (int epoch = first_epoch; epoch < first_epoch + iters; epoch++) {
       EpochStats st{}; st.epoch = epoch;
       A->SwitchToInference(*infA); B->SwitchToInference(*infB);           // setupSelfPlay, agogo.go:75-90
       agz::check(agz_net_set_compute_mode(infA->h, conf.ComputeMode), "compute mode");
@@ -411,6 +422,204 @@ struct AZ {
       applySolver(*B);
       useDummy = useDummy && false;                                        // the dummy is only used in epoch 0 (agogo.go:83-87)
       log.push_back(st);
+      epochs_done = epoch + 1;
+    }
+  }
+
+  // ---- a run saved at an epoch boundary (build extension) ----------------------------------------------------------------------------
+  // SaveRun(prefix) writes prefix + ".A" (A->Save: the trainer checkpoint of the network A holds), prefix + ".window" (window->Save, only
+  // if there is a window) and, LAST, prefix + ".run", which is flushed, fsynced and renamed into place from a temporary file and names
+  // the two files it belongs to: the length and an FNV-1a hash of the ".A" file's bytes, and the total and digest words of the ".window"
+  // file.  The three files are not replaced together: a crash between two of them leaves a newer ".A" or ".window" beside the older
+  // ".run", and LoadRun refuses that set, naming the file that does not match; the run is then lost back to the previous complete
+  // SaveRun only if its files were kept under another prefix (alternate two prefixes to keep one complete set at all times).  B needs no
+  // file: at every epoch boundary it is a fresh random network whose seed follows from `seed` and the epoch.  The ".run" file,
+  // little-endian and unpadded:
+  //
+  //     "AGZRUN01"
+  //     conf      uint32 n (= 45), float64 [n]: game kind, m, n, k, komi; NNConf K, SharedLayers, FC, L2, BatchSize, Width, Height, Features,
+  //               ActionSpace, FwdOnly; MCTSConf PUCT, M, N, RandomCount, Budget, RandomMinVisits, RandomTemperature, DumbPass,
+  //               ResignPercentage, PassPreference; UpdateThreshold, MaxExamples, Encoder, AugmentRotate, AugmentDihedral, LeafSymmetry,
+  //               RootNoiseEps, RootNoiseAlpha, ComputeMode, Solver momentum, l2reg, clip; ReplayWindow, ReplaySteps, ReplaySymmetric,
+  //               ReplayPacked; SelfPlayInferencer[2], EvalInferencer[2]   (every value is exact as a float64; compared bit by bit)
+  //     state     uint64 seed, uint32 epochs_done, uint32 useDummy, int32 a_id, b_id, next_id, uint32 has_window
+  //     files     uint64 bytes of the ".A" file, uint64 FNV-1a (64 bit) of them, uint64 total and uint64 digest of the ".window" file (its
+  //               header words at byte offsets 48 and 72, csrc/replay_ckpt.hpp; 0, 0 without a window)
+  //     stats     uint32 nets, then per network in Creation order: int32 id, uint32 n, float32 Wins[n], Losses[n], Draws[n]
+  //     log       uint32 n, then per epoch: int32 epoch, uint64 examples, int32 batches, float32 cost, int64 a_wins, b_wins, draws,
+  //               uint32 killedA, int32 a_id, uint64 window, int32 steps
+  //     end       "AGZRUNZZ", uint64 the file's total length
+  //
+  // LoadRun(prefix), on a newly constructed AZ of the same game and Config: the ".run" file is read and checked WHOLE first — a malformed
+  // one, one of another configuration (the message names the field), or one whose ".A" / ".window" files are not the ones it was written
+  // beside throws before anything is loaded.  Then the ".A" file is loaded into a NEW trainer and the window file into the window
+  // (agz_replay_load: a bad file changes nothing); only when both have succeeded does the new trainer become A, with the solver options
+  // applied again (l2reg and clip are not in a trainer file), are the fields above restored and is B rebuilt exactly as the end of epoch
+  // epochs_done - 1 builds it.  A failure anywhere leaves the AZ as it was.
+  static void fileHash(const std::string& path, uint64_t* bytes, uint64_t* fnv) {
+    FILE* f = fopen(path.c_str(), "rb");
+    if (!f) throw agz::Error("cannot open " + path);
+    std::vector<unsigned char> buf(1 << 20);
+    uint64_t d = 0xcbf29ce484222325ull, n = 0;
+    for (size_t got; (got = fread(buf.data(), 1, buf.size(), f)) > 0; n += got)
+      for (size_t i = 0; i < got; i++) d = (d ^ buf[i]) * 0x100000001b3ull;
+    fclose(f);
+    *bytes = n; *fnv = d;
+  }
+  static void windowWords(const std::string& path, uint64_t* total, uint64_t* digest) {
+    FILE* f = fopen(path.c_str(), "rb");
+    if (!f) throw agz::Error("cannot open " + path);
+    const bool ok = fseek(f, 48, SEEK_SET) == 0 && fread(total, 8, 1, f) == 1 && fseek(f, 72, SEEK_SET) == 0 && fread(digest, 8, 1, f) == 1;
+    fclose(f);
+    if (!ok) throw agz::Error(path + " is shorter than a window checkpoint's header");
+  }
+  std::vector<std::pair<const char*, double>> runConf() const {
+    const dual::Config& n = conf.NNConf;
+    const mcts::Config& m = conf.MCTSConf;
+    return {{"game.kind", game.kind}, {"game.m", game.m}, {"game.n", game.n}, {"game.k", game.k}, {"game.komi", game.komi},
+            {"NNConf.K", n.K}, {"NNConf.SharedLayers", n.SharedLayers}, {"NNConf.FC", n.FC}, {"NNConf.L2", n.L2}, {"NNConf.BatchSize", n.BatchSize},
+            {"NNConf.Width", n.Width}, {"NNConf.Height", n.Height}, {"NNConf.Features", n.Features}, {"NNConf.ActionSpace", n.ActionSpace},
+            {"NNConf.FwdOnly", n.FwdOnly}, {"MCTSConf.PUCT", m.PUCT}, {"MCTSConf.M", m.M}, {"MCTSConf.N", m.N}, {"MCTSConf.RandomCount", m.RandomCount},
+            {"MCTSConf.Budget", m.Budget}, {"MCTSConf.RandomMinVisits", m.RandomMinVisits}, {"MCTSConf.RandomTemperature", m.RandomTemperature},
+            {"MCTSConf.DumbPass", m.DumbPass}, {"MCTSConf.ResignPercentage", m.ResignPercentage}, {"MCTSConf.PassPreference", m.PassPreference},
+            {"UpdateThreshold", conf.UpdateThreshold}, {"MaxExamples", conf.MaxExamples}, {"Encoder", conf.Encoder},
+            {"AugmentRotate", conf.AugmentRotate}, {"AugmentDihedral", conf.AugmentDihedral}, {"LeafSymmetry", conf.LeafSymmetry},
+            {"RootNoiseEps", conf.RootNoiseEps}, {"RootNoiseAlpha", conf.RootNoiseAlpha}, {"ComputeMode", conf.ComputeMode},
+            {"Solver.momentum", conf.Solver.momentum}, {"Solver.l2reg", conf.Solver.l2reg}, {"Solver.clip", conf.Solver.clip},
+            {"ReplayWindow", (double)conf.ReplayWindow}, {"ReplaySteps", conf.ReplaySteps}, {"ReplaySymmetric", conf.ReplaySymmetric},
+            {"ReplayPacked", conf.ReplayPacked}, {"SelfPlayInferencer[0]", conf.SelfPlayInferencer[0]},
+            {"SelfPlayInferencer[1]", conf.SelfPlayInferencer[1]}, {"EvalInferencer[0]", conf.EvalInferencer[0]},
+            {"EvalInferencer[1]", conf.EvalInferencer[1]}};
+  }
+  void SaveRun(const std::string& prefix) {
+    A->Save(prefix + ".A");
+    if (window) window->Save(prefix + ".window");
+    std::string b = "AGZRUN01";
+    auto put = [&b](const auto& v) { b.append(reinterpret_cast<const char*>(&v), sizeof(v)); };
+    const auto cw = runConf();
+    put((uint32_t)cw.size());
+    for (const auto& w : cw) put(w.second);
+    put((uint64_t)seed); put((uint32_t)epochs_done); put((uint32_t)(useDummy ? 1 : 0));
+    put((int32_t)a_id); put((int32_t)b_id); put((int32_t)next_id); put((uint32_t)(window ? 1 : 0));
+    uint64_t files[4] = {0, 0, 0, 0};
+    fileHash(prefix + ".A", &files[0], &files[1]);
+    if (window) windowWords(prefix + ".window", &files[2], &files[3]);
+    for (uint64_t w : files) put(w);
+    put((uint32_t)stats.Creation.size());
+    for (int id : stats.Creation) {
+      const std::vector<float>&w = stats.Wins.at(id), &l = stats.Losses.at(id), &d = stats.Draws.at(id);
+      put((int32_t)id); put((uint32_t)w.size());
+      for (const std::vector<float>* v : {&w, &l, &d}) b.append(reinterpret_cast<const char*>(v->data()), v->size() * 4);
+    }
+    put((uint32_t)log.size());
+    for (const EpochStats& e : log) {
+      put((int32_t)e.epoch); put((uint64_t)e.examples); put((int32_t)e.batches); put((float)e.cost); put((int64_t)e.a_wins); put((int64_t)e.b_wins);
+      put((int64_t)e.draws); put((uint32_t)(e.killedA ? 1 : 0)); put((int32_t)e.a_id); put((uint64_t)e.window); put((int32_t)e.steps);
+    }
+    b += "AGZRUNZZ";
+    put((uint64_t)(b.size() + 8));
+    const std::string path = prefix + ".run", tmp = path + ".tmp";
+    FILE* f = fopen(tmp.c_str(), "wb");
+    if (!f) throw agz::Error("AZ.SaveRun: cannot open " + tmp);
+    const bool written = fwrite(b.data(), 1, b.size(), f) == b.size() && fflush(f) == 0 && fsync(fileno(f)) == 0;
+    const bool closed = fclose(f) == 0;
+    if (!(written && closed && rename(tmp.c_str(), path.c_str()) == 0)) {
+      remove(tmp.c_str());
+      throw agz::Error("AZ.SaveRun: cannot write " + path);
+    }
+  }
+  void LoadRun(const std::string& prefix) {
+    const std::string path = prefix + ".run";
+    std::string b;
+    {
+      FILE* f = fopen(path.c_str(), "rb");
+      if (!f) throw agz::Error("AZ.LoadRun: cannot open " + path);
+      char buf[4096];
+      for (size_t n; (n = fread(buf, 1, sizeof(buf), f)) > 0;) b.append(buf, n);
+      fclose(f);
+    }
+    size_t at = 0;
+    auto bad = [&path](const std::string& why) { return agz::Error("AZ.LoadRun: " + path + " is malformed: " + why); };
+    auto get = [&](auto& v) {
+      if (b.size() - at < sizeof(v)) throw bad("truncated");
+      memcpy(&v, b.data() + at, sizeof(v));
+      at += sizeof(v);
+    };
+    if (b.size() < 24 || b.compare(0, 8, "AGZRUN01") != 0) throw bad("not a run file (magic)");
+    uint64_t length = 0;
+    memcpy(&length, b.data() + b.size() - 8, 8);
+    if (b.compare(b.size() - 16, 8, "AGZRUNZZ") != 0 || length != b.size()) throw bad("bad end marker (truncated or overlong)");
+    at = 8;
+    const auto cw = runConf();
+    uint32_t n = 0;
+    get(n);
+    if (n != cw.size()) throw bad("it holds " + std::to_string(n) + " configuration words, this build writes " + std::to_string(cw.size()));
+    for (const auto& w : cw) {
+      double v = 0;
+      get(v);
+      if (memcmp(&v, &w.second, 8) != 0)
+        throw agz::Error("AZ.LoadRun: " + path + " belongs to another configuration: " + w.first + " is " + std::to_string(v) + " in the file, " +
+                         std::to_string(w.second) + " here");
+    }
+    uint64_t seed_ = 0;
+    uint32_t done = 0, dummy = 0, has_window = 0, nets = 0, entries = 0;
+    int32_t ia = 0, ib = 0, inext = 0;
+    get(seed_); get(done); get(dummy); get(ia); get(ib); get(inext); get(has_window);
+    if (dummy > 1 || has_window > 1 || done > 0x7fffffffu) throw bad("a flag or the epoch count is out of range");
+    if ((has_window != 0) != (window != nullptr)) throw bad("it was written with" + std::string(has_window ? "" : "out") + " a replay window");
+    uint64_t files[4] = {0, 0, 0, 0};
+    for (uint64_t& w : files) get(w);
+    Statistics st;
+    get(nets);
+    for (uint32_t i = 0; i < nets; i++) {
+      int32_t id = 0;
+      uint32_t cnt = 0;
+      get(id); get(cnt);
+      if ((b.size() - at) / 12 < cnt || st.Wins.count(id)) throw bad("statistics");
+      st.Creation.push_back(id);
+      for (std::vector<float>* v : {&st.Wins[id], &st.Losses[id], &st.Draws[id]}) {
+        v->resize(cnt);
+        if (cnt) memcpy(v->data(), b.data() + at, (size_t)cnt * 4);
+        at += (size_t)cnt * 4;
+      }
+    }
+    std::vector<EpochStats> lg;
+    get(entries);
+    for (uint32_t i = 0; i < entries; i++) {
+      EpochStats e{};
+      int32_t epoch = 0, batches = 0, id = 0, steps = 0;
+      uint64_t examples = 0, win = 0;
+      int64_t aw = 0, bw = 0, dr = 0;
+      uint32_t killed = 0;
+      get(epoch); get(examples); get(batches); get(e.cost); get(aw); get(bw); get(dr); get(killed); get(id); get(win); get(steps);
+      if (killed > 1) throw bad("log");
+      e.epoch = epoch; e.examples = (size_t)examples; e.batches = batches; e.a_wins = (long)aw; e.b_wins = (long)bw; e.draws = (long)dr;
+      e.killedA = killed != 0; e.a_id = id; e.window = (size_t)win; e.steps = steps;
+      lg.push_back(e);
+    }
+    if (at + 16 != b.size()) throw bad("bytes between the log and the end marker");
+    // the ".A" and ".window" files are the ones this ".run" was written beside
+    uint64_t have[4] = {0, 0, 0, 0};
+    fileHash(prefix + ".A", &have[0], &have[1]);
+    if (have[0] != files[0] || have[1] != files[1])
+      throw agz::Error("AZ.LoadRun: " + prefix + ".A is not the trainer file " + path + " was written beside (another length or hash: a SaveRun that did not finish?)");
+    if (window) {
+      windowWords(prefix + ".window", &have[2], &have[3]);
+      if (have[2] != files[2] || have[3] != files[3])
+        throw agz::Error("AZ.LoadRun: " + prefix + ".window is not the window file " + path + " was written beside (another total or digest: a SaveRun that did not finish?)");
+    }
+    // the set is sound and of this configuration: from here on things are loaded, A into a new trainer so that a failure changes nothing
+    std::unique_ptr<dual::Trainable> loaded(new dual::Trainable(ctx, conf.NNConf));
+    loaded->Load(prefix + ".A");
+    applySolver(*loaded);
+    if (window) window->Load(prefix + ".window");
+    A = std::move(loaded);
+    seed = seed_; epochs_done = (int)done; useDummy = dummy != 0; a_id = ia; b_id = ib; next_id = inext;
+    stats = st; log = lg;
+    if (epochs_done > 0) {
+      B.reset(new dual::Trainable(ctx, conf.NNConf));
+      B->Init(seed * 3 + 100 + (uint64_t)(epochs_done - 1));
+      applySolver(*B);
     }
   }
 };

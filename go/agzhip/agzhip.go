@@ -390,6 +390,24 @@ func (r *Replay) Digest() (uint64, error) {
 	return uint64(d), err
 }
 
+// Save writes a checkpoint of the window — its live rows in logical order, total, form and digest (agz_replay_save).  The file replaces
+// `path` only once it is complete; the window is not changed.
+func (r *Replay) Save(path string) error {
+	defer r.ctx.enter()()
+	p := C.CString(path)
+	defer C.free(unsafe.Pointer(p))
+	return lastErr(C.agz_replay_save(r.h, p))
+}
+
+// Load replaces the window's content by a checkpoint of a window of the same row shape (agz_replay_load); capacity and form may differ.
+// The whole file is validated before anything changes: after an error the window is as it was.
+func (r *Replay) Load(path string) error {
+	defer r.ctx.enter()()
+	p := C.CString(path)
+	defer C.free(unsafe.Pointer(p))
+	return lastErr(C.agz_replay_load(r.h, p))
+}
+
 // SampleSlice is rows [row0, row0+cnt) of minibatch `step` of `rows` rows, on the host: x [cnt*F*H*W], pi [cnt*PolicyLen], v [cnt].
 func (r *Replay) SampleSlice(rows, row0, cnt int, seed, step uint64, symmetric bool, x, pi, v []float32) error {
 	defer r.ctx.enter()()

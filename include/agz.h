@@ -872,6 +872,40 @@ int agz_train_replay(agz_trainer* t, agz_replay* rp, int steps, uint64_t seed, i
  * different data without an error.  A handle that is not sharded: AGZ_E_STATE (use agz_train_replay).  A rank whose sampler launch fails
  * in a step still enters that step's collectives; the error ends the run on every rank, as in agz_train_dev. */
 int agz_train_replay_sharded(agz_trainer* t, agz_replay* rp, int steps, uint64_t seed, int symmetric, int verify, float* last_cost);
+/* Checkpoint of a window (DESIGN.md §2 replay-ckpt): the live rows in LOGICAL order, oldest first, with total, the saving capacity, the
+ * form (fp32 planes or 2-bit codes with their palette) and agz_replay_digest of the window, so that a run interrupted between two epochs
+ * continues EXACTLY as the uninterrupted one — the same slots, samples, digests and trained parameters, bit for bit (the format is
+ * specified in agogo_amd/csrc/replay_ckpt.hpp, the one place that reads, writes and validates the header and the lengths).
+ * save: joins the context's queue (every append enqueued so far is in the file), writes `path` + ".tmp", flushes and fsyncs it and renames
+ * it over `path`: a crash during a save never destroys the previous checkpoint; on failure the temporary file is removed.  The window is
+ * never changed by a save.  An empty window is a valid file, and so is a window that a load into a larger capacity left not yet full: its
+ * file carries its live count in the (informational) capacity word, so that the file's own rule live == min(total, capacity) holds.  A packed window writes its words as they are (8.8 times fewer bytes at 19x19).
+ * load: replaces the window's content.  total := the file's total, live := min(the file's live, capacity), and the live rows are the NEWEST
+ * live rows of the file, each in the slot replay.hpp's arithmetic gives the append that wrote it: into a window of the saving capacity every
+ * row sits where it sat and later appends go where they would have gone; into a smaller window only the newest rows survive, as after one
+ * long append; into a larger one the window is simply not yet full.  Features, Height, Width and PolicyLen must match (AGZ_E_INVALID,
+ * agz_last_error() names the field).  The form need NOT match, the chunks are converted on the device as they arrive: an fp32 file into a
+ * packed window looks every cell up in the window's palette, a packed file into an fp32 window decodes with the file's palette, a packed
+ * file into a packed window of another palette order remaps the codes through the patterns (every palette entry of the file must be in
+ * the window's palette, else AGZ_E_INVALID).
+ * A BAD FILE CHANGES NOTHING.  A window does not fit in host memory twice, so the file is read twice: the first pass streams every chunk
+ * into a device staging buffer, where one kernel adds up the digest and checks what a later kernel would trust, and the ring is not
+ * touched; only when the whole file has passed does the second pass stream it into the ring.  AGZ_E_INVALID with total, live and every
+ * stored bit as they were: a missing file, bad magic or end mark, a truncated or overlong file, live != min(total, capacity), live >
+ * total, bad form or palette words, another shape, a code of a packed file that is not below its n_palette, a set bit past the last cell
+ * of a plane's last word, a cell of an fp32 file that is not in a packed window's palette (the message names the first such row,
+ * element and pattern), and rows whose digest is not the header's.  After a device error in the second pass (AGZ_E_HIP) the content is
+ * undefined.  I/O failures are AGZ_E_INVALID, as for agz_trainer_save and agz_arena_save.  The host holds two page-locked staging
+ * buffers (256 MB each at most), never the window.
+ * Sharded use is not a call of its own: every rank loads the same file into its replica, the digests agree and
+ * agz_train_replay_sharded(verify = 1) accepts them.
+ * NOT in the file: the window's capacity as a requirement (any capacity loads), the sampler's seed and step (the caller's arguments).
+ * Not covered: the agz_examples store, the arena's example buffer (agz_arena_save holds it), compression beyond the packed form,
+ * asynchronous or incremental saves, a save while agz_train_replay runs on another thread.
+ * Tests: tests/test_replay_ckpt_cpu.py (the format and every header refusal, without a GPU), tests/test_replay_ckpt_gpu.py (round trips,
+ * continuations, conversions, refusals), tests/test_replay_ckpt_learn_gpu.py (AZ::Learn resumed at an epoch boundary). */
+int agz_replay_save(agz_replay* rp, const char* path);
+int agz_replay_load(agz_replay* rp, const char* path);
 
 /* ---- multi-GPU exchange over RCCL / xGMI -------------------------------------------------------------------
  * Self-play games shard across GPUs with NO data-path collective (one agz_ctx + arena set per GPU).  The path has exactly

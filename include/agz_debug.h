@@ -136,6 +136,11 @@ int agz_arena_pool_capacity(agz_arena* arena, int* nodes_per_pool, int* grows);
  * at tiny shapes.  The file does not depend on it. */
 int agz_arena_set_ckpt_staging(agz_arena* arena, size_t bytes);
 
+/* Tests: the same for agz_replay_save / agz_replay_load (default 256 MB; 4 bytes .. 4 GiB).  A chunk holds as many whole rows of the array
+ * being moved as fit, at least one: the bytes of three rows of planes cut chunks inside every array and across the ring's wrap at toy
+ * sizes.  The file does not depend on it. */
+int agz_replay_set_ckpt_staging(agz_replay* rp, size_t bytes);
+
 /* Failure injection (tests): the data-parallel step of this communicator fails on THIS rank right before it would enter the collective of
  * slice k (0 = the heads, 1 .. = layer L .. 0; k < 0: off).  One shot: cleared by the step it hits.  What the test checks is the rule of
  * agz_trainer_forward_backward_allreduce: the failing rank still enters every collective, every rank's call fails (AGZ_E_PEER on the
