@@ -23,6 +23,13 @@ PATH_FWD_F32, PATH_FWD_BF16X3, PATH_FWD_H2W, PATH_FWD_H2DMA, PATH_FWD_H2DMA3 = 1
 PATH_WGRAD_F32, PATH_WGRAD_X3, PATH_WGRAD_H2, PATH_WGRAD_H2T3 = 1, 2, 3, 4
 PATH_DGRAD_RAW, PATH_DGRAD_X3, PATH_DGRAD_WINO_H2 = 1, 2, 3
 PATH_BN2_SCALAR, PATH_BN2_V = 1, 2
+# agz_debug.h, agz_net_last_paths: the kernels a net's last whole-batch forward launched (0 = none)
+NPATH_IN_LAT, NPATH_IN_X3, NPATH_IN_F32_411, NPATH_IN_F32_221, NPATH_IN_F32_222 = 1, 2, 3, 4, 5
+NPATH_BLK_F32_411, NPATH_BLK_F32_221, NPATH_BLK_F32_222 = 1, 2, 3
+NPATH_BLK_F32_411_SPLITK, NPATH_BLK_F32_221_SPLITK, NPATH_BLK_F32_222_SPLITK = 4, 5, 6
+NPATH_BLK_X3, NPATH_BLK_H2W, NPATH_BLK_H2, NPATH_BLK_WINO = 7, 8, 9, 10
+NPATH_BLK_WINO_H2_3K, NPATH_BLK_WINO_H2_3K_WIDE, NPATH_BLK_WINO_H2_CHAINED, NPATH_BLK_LAT_H2 = 11, 12, 13, 14
+NPATH_HEADS_ONE, NPATH_HEADS_SPREAD, NPATH_HEADS_SPREAD_NB4 = 1, 2, 3
 PROF_CONV, PROF_HEADS, PROF_SELECT, PROF_EXPAND, PROF_MOVE, PROF_CONV_INIT = 0, 1, 2, 3, 4, 5
 PROF_WINO_IN, PROF_WINO_GEMM, PROF_WINO_OUT = 6, 7, 8
 DONT_PREFER_PASS, PREFER_PASS, DONT_RESIGN = 0, 1, 2
@@ -298,6 +305,8 @@ def lib():
     sig("agz_net_set_wino_h2_form", i32, vp, i32)
     sig("agz_net_set_wino_h2_gemm", i32, vp, i32)
     sig("agz_net_wino_h2_last_rows", i32, vp, C.POINTER(C.c_int), C.POINTER(C.c_int))
+    sig("agz_net_last_paths", i32, vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int))
+    sig("agz_net_tower_out", i32, vp, i32, pf)
     sig("agz_net_min_same_batch", i32, vp, i32, i32, C.POINTER(C.c_int))
     sig("agz_arena_set_prep_compact", i32, vp, i32)
     sig("agz_arena_set_split", i32, vp, i32)
@@ -519,6 +528,19 @@ class Net:
         r, c = C.c_int(0), C.c_int(0)
         _check(lib().agz_net_wino_h2_last_rows(self.h, C.byref(r), C.byref(c)), "agz_net_wino_h2_last_rows")
         return r.value, c.value
+
+    def last_paths(self):
+        """agz_debug.h: (input_conv, block, heads) NPATH_* of the kernels the last whole-batch forward launched"""
+        i, b, h = C.c_int(0), C.c_int(0), C.c_int(0)
+        _check(lib().agz_net_last_paths(self.h, C.byref(i), C.byref(b), C.byref(h)), "agz_net_last_paths")
+        return i.value, b.value, h.value
+
+    def tower_out(self, B):
+        """agz_debug.h: the tensor the heads of the last forward of B boards read, [B, K, H, W] float32"""
+        c = self.conf
+        t = np.zeros((int(B), c.K, c.Height, c.Width), dtype=np.float32)
+        _check(lib().agz_net_tower_out(self.h, int(B), _pf(t)), "agz_net_tower_out")
+        return t
 
     def min_same_batch(self, n, G):
         """agz_debug.h: the smallest batch >= n whose per-board outputs equal those of a G-board batch bit for bit"""

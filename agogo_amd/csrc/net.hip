@@ -1312,6 +1312,7 @@ int agz_net::forward_half(int B, int half, hipStream_t st, float* policy_dev, fl
   const int nb = B / 2, b0 = half * nb;
   const FwdPlan plan = fwd_plan(B);
   const H2Tower t = wino_h2_tower(B);
+  last_tower = nullptr; last_tower_B = 0;   // (agz_net_tower_out reads whole-batch forwards only)
   // input convolution (bf16x3 products) with the tower's per-board input ranges out of its epilogue
   ConvArgs a{};
   a.M = nb * HW; a.HW = HW; a.W = W; a.Wp = Wp; a.HpWp = Hp * Wp;
@@ -1385,6 +1386,7 @@ int agz_net::forward_packed(int B, float* policy_dev, float* value_dev) {
     li.B = B; li.H = H; li.W = W; li.Hp = Hp; li.Wp = Wp; li.Cout_p = Kp; li.groups_per_board = in_groups;
     ProfScope ps(ctx, AGZ_PROF_CONV_INIT);
     hipLaunchKernelGGL(agz::lat_input_kernel, dim3(Kp / 64, B * in_groups), dim3(256), 0, ctx->stream, li);
+    path_input = AGZ_NPATH_IN_LAT;
     rc = AGZ_OK;
   }
   else if (split_ok && compute_mode != AGZ_COMPUTE_F32_MFMA && d_w3_init && Kp % 128 == 0 &&
@@ -1401,12 +1403,14 @@ int agz_net::forward_packed(int B, float* policy_dev, float* value_dev) {
     }
     hipLaunchKernelGGL((conv3x3_x3_kernel<false>), dim3(a.n_mtiles * a.n_ntiles), dim3(256), 0, ctx->stream, a, d_w3_init);
     a.amax_out = nullptr;
+    path_input = AGZ_NPATH_IN_X3;
     rc = AGZ_OK;
   }
-  else if (cfg != 0) rc = launch_conv<4, 1, 1, false>(ctx, a, wsp, &ws_cap);
-  else if (half_init) rc = launch_conv<2, 2, 1, false>(ctx, a, wsp, &ws_cap);
-  else rc = launch_conv<2, 2, 2, false>(ctx, a, wsp, &ws_cap);
+  else if (cfg != 0) { rc = launch_conv<4, 1, 1, false>(ctx, a, wsp, &ws_cap); path_input = AGZ_NPATH_IN_F32_411; }
+  else if (half_init) { rc = launch_conv<2, 2, 1, false>(ctx, a, wsp, &ws_cap); path_input = AGZ_NPATH_IN_F32_221; }
+  else { rc = launch_conv<2, 2, 2, false>(ctx, a, wsp, &ws_cap); path_input = AGZ_NPATH_IN_F32_222; }
   if (rc != AGZ_OK) return rc;
+  path_block = 0;
   // K2: SharedLayers x fused dual-branch block
   float* cur = d_actA;
   float* nxt = d_actB;
@@ -1441,6 +1445,7 @@ int agz_net::forward_packed(int B, float* policy_dev, float* value_dev) {
       const bool last = l + 1 == conf.SharedLayers;
       for (int b0 = 0; b0 < B; b0 += chunk, ci++)
         wino_h2c_block(l, B, b0, ci, tw, (ci % ns) ? ctx->stream2 : (hipStream_t)ctx->stream, cur, nxt);
+      path_block = AGZ_NPATH_BLK_WINO_H2_CHAINED;
       if (last) std::swap(cur, nxt);
     }
     for (int l = 0; !chained && l < conf.SharedLayers; l++) {
@@ -1459,6 +1464,7 @@ int agz_net::forward_packed(int B, float* policy_dev, float* value_dev) {
         hh.wave_max = d_wave_max + (size_t)b0 * wm_board;
         hh.fuse_prev = l > 0;   // block 0's input range comes from board_amax_kernel above
         wino_h2_launch(ctx, hh, wide, q ? ctx->stream2 : ctx->stream);
+        path_block = wide ? AGZ_NPATH_BLK_WINO_H2_3K_WIDE : AGZ_NPATH_BLK_WINO_H2_3K;
       }
       std::swap(cur, nxt);
     }
@@ -1481,8 +1487,10 @@ int agz_net::forward_packed(int B, float* policy_dev, float* value_dev) {
       if ((2 * Kp) % 256 == 0) {   // wide tile: 128 x 256
         a.n_ntiles = (2 * Kp) / 256;
         hipLaunchKernelGGL(conv3x3_h2w_kernel, dim3(a.n_mtiles * a.n_ntiles), dim3(256), 0, ctx->stream, a, d_w2_dual[l]);
+        path_block = AGZ_NPATH_BLK_H2W;
       } else {
         hipLaunchKernelGGL(conv3x3_h2_kernel, dim3(a.n_mtiles * a.n_ntiles), dim3(256), 0, ctx->stream, a, d_w2_dual[l]);
+        path_block = AGZ_NPATH_BLK_H2;
       }
       rc = AGZ_OK;
     }
@@ -1510,6 +1518,7 @@ int agz_net::forward_packed(int B, float* policy_dev, float* value_dev) {
         wa.V = d_wV; wa.Mb = d_wM; wa.U3 = d_u3_dual[l]; wa.ep = d_ep_dual[l];
         wa.B = std::min(chunk, B - b0); wa.H = H; wa.W = W; wa.Hp = Hp; wa.Wp = Wp; wa.C = Kp; wa.Cout_p = Kp; wa.Ntot = 2 * Kp;
         wino_launch(ctx, wa, WINO_IN | WINO_GEMM | WINO_OUT);
+        path_block = AGZ_NPATH_BLK_WINO;
       }
       rc = AGZ_OK;
     }
@@ -1518,6 +1527,7 @@ int agz_net::forward_packed(int B, float* policy_dev, float* value_dev) {
       a.splits = 1; a.per = 0; a.ws = nullptr; a.raw = 0;
       ProfScope ps(ctx, AGZ_PROF_CONV);
       hipLaunchKernelGGL((conv3x3_x3_kernel<true>), dim3(a.n_mtiles * a.n_ntiles), dim3(256), 0, ctx->stream, a, d_w3_dual[l]);
+      path_block = AGZ_NPATH_BLK_X3;
       rc = AGZ_OK;
     }
     // (fp16x2 products: only in the modes whose contract is split operands — AGZ_COMPUTE_F32_MFMA keeps exact fp32 products at
@@ -1541,11 +1551,13 @@ int agz_net::forward_packed(int B, float* policy_dev, float* value_dev) {
       la.wmax_out = more ? d_lat_wmax[l & 1] : nullptr;
       ProfScope ps(ctx, AGZ_PROF_CONV);
       agz::conv_lat_h2_launch(ctx, la);
+      path_block = AGZ_NPATH_BLK_LAT_H2;
       rc = AGZ_OK;
     }
-    else if (cfg != 0) rc = launch_conv<4, 1, 1, true>(ctx, a, wsp, &ws_cap);
-    else if (half_dual) rc = launch_conv<2, 2, 1, true>(ctx, a, wsp, &ws_cap);
-    else rc = launch_conv<2, 2, 2, true>(ctx, a, wsp, &ws_cap);
+    // (launch_conv leaves the split count it ran with in a.splits: > 1 = split-K + splitk_epilogue_kernel)
+    else if (cfg != 0) { rc = launch_conv<4, 1, 1, true>(ctx, a, wsp, &ws_cap); path_block = a.splits > 1 ? AGZ_NPATH_BLK_F32_411_SPLITK : AGZ_NPATH_BLK_F32_411; }
+    else if (half_dual) { rc = launch_conv<2, 2, 1, true>(ctx, a, wsp, &ws_cap); path_block = a.splits > 1 ? AGZ_NPATH_BLK_F32_221_SPLITK : AGZ_NPATH_BLK_F32_221; }
+    else { rc = launch_conv<2, 2, 2, true>(ctx, a, wsp, &ws_cap); path_block = a.splits > 1 ? AGZ_NPATH_BLK_F32_222_SPLITK : AGZ_NPATH_BLK_F32_222; }
     if (rc != AGZ_OK) return rc;
     std::swap(cur, nxt);
   }
@@ -1554,6 +1566,7 @@ int agz_net::forward_packed(int B, float* policy_dev, float* value_dev) {
   h.x = cur; h.conv = d_head_conv; h.bn = d_head_bn; h.Wp = d_Wp; h.bp = d_bp; h.W1 = d_W1; h.b1 = d_b1; h.W2 = d_W2;
   h.b2 = d_b2; h.policy = policy_dev; h.value = value_dev;
   h.H = H; h.W = W; h.HW = HW; h.Wp_ = Wp; h.HpWp = Hp * Wp; h.Kp = Kp; h.A = conf.ActionSpace; h.FC = conf.FC;
+  last_tower = cur; last_tower_B = B;   // agz_net_tower_out (agz_debug.h): the tensor the heads below read
   size_t smem = (size_t)(3 * HW + 8 + conf.FC) * sizeof(float);
   {
     ProfScope ps(ctx, AGZ_PROF_HEADS);
@@ -1569,8 +1582,10 @@ int agz_net::forward_packed(int B, float* policy_dev, float* value_dev) {
         hs_cap = need;
       }
       heads_spread_range(h, plan.heads_nb, B, 0, B, ctx->stream);
+      path_heads = plan.heads_nb ? AGZ_NPATH_HEADS_SPREAD_NB4 : AGZ_NPATH_HEADS_SPREAD;
     } else {
       hipLaunchKernelGGL(heads_kernel, dim3(B), dim3(256), smem, ctx->stream, h);
+      path_heads = AGZ_NPATH_HEADS_ONE;
     }
   }
   AGZ_HIP_TRY(hipGetLastError());
@@ -1959,6 +1974,29 @@ int agz_net_min_same_batch(agz_net* n, int k, int G, int* batch) {
 int agz_net_wino_h2_last_rows(agz_net* n, int* live_r, int* live_c) {
   AGZ_REQUIRE(n && live_r && live_c, AGZ_E_INVALID, "agz_net_wino_h2_last_rows: null argument");
   *live_r = n->wino_live_r; *live_c = n->wino_live_c;
+  return AGZ_OK;
+}
+
+int agz_net_tower_out(agz_net* n, int B, float* host) {
+  AGZ_REQUIRE(n && host, AGZ_E_INVALID, "agz_net_tower_out: null argument");
+  AGZ_REQUIRE(n->last_tower && n->last_tower_B > 0, AGZ_E_STATE, "agz_net_tower_out: no whole-batch forward to read (none yet, or the last one was a split step)");
+  AGZ_REQUIRE(B == n->last_tower_B, AGZ_E_INVALID, "agz_net_tower_out: batch %d, the last forward ran %d boards", B, n->last_tower_B);
+  AGZ_HIP_TRY(hipSetDevice(n->ctx->device));
+  AGZ_HIP_TRY(hipStreamSynchronize(n->ctx->stream));
+  const int H = n->H, W = n->W, Hp = n->Hp, Wp = n->Wp, Kp = n->Kp, K = n->conf.K;
+  std::vector<float> pad((size_t)B * Hp * Wp * Kp);
+  AGZ_HIP_TRY(hipMemcpy(pad.data(), n->last_tower, pad.size() * sizeof(float), hipMemcpyDeviceToHost));
+  for (int b = 0; b < B; b++)
+    for (int k = 0; k < K; k++)
+      for (int y = 0; y < H; y++)
+        for (int x = 0; x < W; x++)
+          host[(((size_t)b * K + k) * H + y) * W + x] = pad[(((size_t)b * Hp + y + 1) * Wp + x + 1) * Kp + k];
+  return AGZ_OK;
+}
+
+int agz_net_last_paths(agz_net* n, int* input_conv, int* block, int* heads) {
+  AGZ_REQUIRE(n && input_conv && block && heads, AGZ_E_INVALID, "agz_net_last_paths: null argument");
+  *input_conv = n->path_input; *block = n->path_block; *heads = n->path_heads;
   return AGZ_OK;
 }
 

@@ -132,6 +132,11 @@ struct agz_net {
   size_t ws_cap = 0;
   float* d_hs = nullptr;      // latency-regime head scratch: [B][3][HW] features + [B][A+FC] columns
   size_t hs_cap = 0;
+  // agz_debug.h test hooks, written by forward_packed on the host: the tensor the heads of the last whole-batch forward read (nullptr: none,
+  // or the last forward was forward_half) and the AGZ_NPATH_* of the kernels it launched.  Nothing reads them but the two hooks.
+  const float* last_tower = nullptr;
+  int last_tower_B = 0;
+  int path_input = 0, path_block = 0, path_heads = 0;
   int tower_queues = 0;       // agz_net_set_tower_queues: 0 = auto (two from 256 boards), 1, 2
   bool latency_mode = true;   // allow the small-batch regime (split-K tower + spread heads), agz_net_set_latency_mode
 

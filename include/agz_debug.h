@@ -117,6 +117,38 @@ int agz_trainer_set_dma_forward(agz_trainer* t, int on);
 #define AGZ_PATH_BN2_V 2        /* k_bn_bwd2_v: vector form, writes dz's range itself */
 int agz_trainer_last_paths(agz_trainer* t, int layer, int* fwd, int* wgrad, int* dgrad, int* bn_bwd2);
 
+/* Tests: which kernels the last whole-batch forward of a net (agz_net_infer / agz_net_infer_dev, the arena's joined step) launched for the
+ * input convolution, the dual blocks and the heads.  Every value is written on the host at the very branch of agz_net::forward_packed that
+ * launches the kernel; read-only, no effect on any launch.  0 = nothing launched yet (block: also a net without blocks). */
+#define AGZ_NPATH_IN_LAT 1                /* lat_input_kernel: latency regime, one launch with the first block's range words */
+#define AGZ_NPATH_IN_X3 2                 /* conv3x3_x3_kernel<false>: bf16x3 products (the split modes, K % 128 == 0) */
+#define AGZ_NPATH_IN_F32_411 3            /* launch_conv<4,1,1>: K % 64 != 0 (split-K inside it in the latency regime, as for the two below) */
+#define AGZ_NPATH_IN_F32_221 4            /* launch_conv<2,2,1>: 64-row half tiles */
+#define AGZ_NPATH_IN_F32_222 5            /* launch_conv<2,2,2> */
+#define AGZ_NPATH_BLK_F32_411 1           /* launch_conv<4,1,1,true> */
+#define AGZ_NPATH_BLK_F32_221 2           /* launch_conv<2,2,1,true> */
+#define AGZ_NPATH_BLK_F32_222 3           /* launch_conv<2,2,2,true> */
+#define AGZ_NPATH_BLK_F32_411_SPLITK 4    /* the same three with split-K and splitk_epilogue_kernel (latency regime, fp32) */
+#define AGZ_NPATH_BLK_F32_221_SPLITK 5
+#define AGZ_NPATH_BLK_F32_222_SPLITK 6
+#define AGZ_NPATH_BLK_X3 7                /* conv3x3_x3_kernel<true> */
+#define AGZ_NPATH_BLK_H2W 8               /* conv3x3_h2w_kernel (128 x 256 tile) */
+#define AGZ_NPATH_BLK_H2 9                /* conv3x3_h2_kernel */
+#define AGZ_NPATH_BLK_WINO 10             /* wino_launch: F(4x4,3x3), bf16x3 */
+#define AGZ_NPATH_BLK_WINO_H2_3K 11       /* three-kernel Winograd fp16x2 block, 128 x 128 GEMM tile */
+#define AGZ_NPATH_BLK_WINO_H2_3K_WIDE 12  /* ... 128 x 256 GEMM tile */
+#define AGZ_NPATH_BLK_WINO_H2_CHAINED 13  /* chained Winograd fp16x2 block (conv_wino_h2c.hpp) */
+#define AGZ_NPATH_BLK_LAT_H2 14           /* conv_lat_h2_launch: latency regime, one launch per block */
+#define AGZ_NPATH_HEADS_ONE 1             /* heads_kernel: one workgroup per board */
+#define AGZ_NPATH_HEADS_SPREAD 2          /* heads_feat / heads_fc / heads_out */
+#define AGZ_NPATH_HEADS_SPREAD_NB4 3      /* ... with heads_fc_nb_kernel<4> (from 32 boards) */
+int agz_net_last_paths(agz_net* net, int* input_conv, int* block, int* heads);
+
+/* Tests: the tensor the heads of the last agz_net_infer / agz_net_infer_dev of B boards read — the tower's output — unpacked on the host
+ * from the padded NHWC device layout [B][Hp][Wp][Kp] to host[B][K][H][W].  Synchronises and copies; launches nothing.  AGZ_E_STATE before
+ * the first forward and after a split step (forward_half), which clears the record. */
+int agz_net_tower_out(agz_net* net, int B, float* host);
+
 /* The smallest batch >= n that runs the kernels of a batch of G boards on this net in its current compute mode (agz_net::min_same_batch, what
  * prepareRoot's packed forward uses): per board the outputs of such a batch are those of the G-board batch bit for bit.  The parity tests
  * evaluate single leaves for the oracle with it instead of G copies of the board. */

@@ -7,48 +7,10 @@ built only from the topology in dualnet/dual.go:50-103 and ermahagerdmonards.go:
 """
 import numpy as np
 import pytest
-import torch
-import torch.nn.functional as Fn
 
 import oracle_lib as O
+from f64_tower import torch_forward   # tests/f64_tower.py: the float64 restatement, shared with test_tower_f64_gpu.py
 from f64_train import f64_train_of
-
-
-def torch_forward(net, x, bn_mode, stats=None, eps=1e-5):
-    c = net.conf
-    K, L, FC, W, H, F, A = c["K"], c["SharedLayers"], c["FC"], c["Width"], c["Height"], c["Features"], c["ActionSpace"]
-    P = [torch.from_numpy(net.get_param(i).astype(np.float64)) for i in range(net.num_params())]
-    it = iter(range(len(P)))
-    bi = [0]
-
-    def conv_bn_relu(t, cin, cout, k):
-        w = P[next(it)].reshape(cout, cin, k, k)
-        g = P[next(it)].reshape(1, cout, H, W)
-        b = P[next(it)].reshape(1, cout, H, W)
-        y = Fn.conv2d(t, w, padding=k // 2)
-        if bn_mode == 0:
-            y = y / np.sqrt(0.0 + eps)
-        elif bn_mode == 1:
-            mean, var = stats[bi[0]]
-            y = (y - torch.from_numpy(mean.astype(np.float64)).reshape(1, -1, 1, 1)) / torch.sqrt(
-                torch.from_numpy(var.astype(np.float64)).reshape(1, -1, 1, 1) + eps)
-        bi[0] += 1
-        return torch.relu(y * g + b)
-
-    t = torch.from_numpy(x.astype(np.float64))
-    t = conv_bn_relu(t, F, K, 3)
-    for _ in range(L):
-        a = conv_bn_relu(t, K, K, 3)
-        b = conv_bn_relu(t, K, K, 3)
-        t = torch.relu(a + b)
-    p = conv_bn_relu(t, K, 2, 1).reshape(-1, 2 * H * W)
-    Wp, bp = P[next(it)].reshape(2 * H * W, A), P[next(it)]
-    pol = torch.softmax(p @ Wp + bp, dim=1)
-    v = conv_bn_relu(t, K, 1, 1).reshape(-1, H * W)
-    W1, b1 = P[next(it)].reshape(H * W, FC), P[next(it)]
-    W2, b2 = P[next(it)].reshape(FC, 1), P[next(it)]
-    val = torch.tanh(torch.relu(v @ W1 + b1) @ W2 + b2).reshape(-1)
-    return pol.numpy(), val.numpy()
 
 
 def tame(net, seed, bn_mode):
