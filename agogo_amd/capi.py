@@ -313,6 +313,7 @@ def lib():
     sig("agz_arena_split_steps", i32, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int))
     sig("agz_trainer_set_dma_forward", i32, vp, i32)
     sig("agz_trainer_last_paths", i32, vp, i32, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int))
+    sig("agz_trainer_last_planes", i32, vp, i32, C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32))
     sig("agz_arena_last_prep_batch", i32, vp, C.POINTER(C.c_int), C.POINTER(C.c_int))
     sig("agz_arena_debug_counter", i32, vp, i32, C.POINTER(C.c_int64))
     sig("agz_arena_pool_capacity", i32, vp, C.POINTER(C.c_int), C.POINTER(C.c_int))
@@ -785,6 +786,13 @@ class Trainer:
         f, w, d, b = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
         _check(lib().agz_trainer_last_paths(self.h, int(layer), C.byref(f), C.byref(w), C.byref(d), C.byref(b)), "agz_trainer_last_paths")
         return f.value, w.value, d.value, b.value
+
+    def last_planes(self, layer):
+        """agz_debug.h test hook: (fused, est_bits, range_bits) of tower layer `layer`'s input planes in the last step — written by the
+        previous layer's BatchNorm pass and read by the forward; last step's range word (the estimate); this step's range word"""
+        f, e, r = C.c_int(0), C.c_uint32(0), C.c_uint32(0)
+        _check(lib().agz_trainer_last_planes(self.h, int(layer), C.byref(f), C.byref(e), C.byref(r)), "agz_trainer_last_planes")
+        return bool(f.value), e.value, r.value
 
     def grads_dev(self):
         ptr, n = C.c_void_p(), C.c_size_t(0)

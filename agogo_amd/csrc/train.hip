@@ -250,6 +250,7 @@ __device__ __forceinline__ void board_amax_commit(unsigned m0, unsigned m1, int 
 // here as well, scaled by the power of two of `est_bits` — the exact range of the same tensor one step earlier.  The exact range of THIS
 // step comes out of this very pass; k_split_h2p_cond then keeps the planes if both ranges have the same exponent (the usual case: the
 // scale is what the exact range prescribes, the results do not depend on the history) and re-splits the tensor otherwise.
+// tests/test_train_history_gpu.py guards that promise: steps on a trainer with history against a fresh one (agz_trainer_last_planes).
 __device__ __forceinline__ float wg_h2_scale(unsigned amax_bits);
 typedef _Float16 bn_f16x4_t __attribute__((ext_vector_type(4)));
 template <bool TIED>
@@ -3396,6 +3397,20 @@ int agz_trainer_last_paths(agz_trainer* t, int layer, int* fwd, int* wgrad, int*
   AGZ_REQUIRE(layer >= 0 && layer <= t->L, AGZ_E_INVALID, "agz_trainer_last_paths: layer %d of 0..%d", layer, t->L);
   const TLayer& ly = t->layers[layer];
   *fwd = ly.path_fwd; *wgrad = ly.path_wgrad; *dgrad = ly.path_dgrad; *bn_bwd2 = ly.path_bn2;
+  return AGZ_OK;
+}
+
+int agz_trainer_last_planes(agz_trainer* t, int layer, int* fused, uint32_t* est_bits, uint32_t* range_bits) {
+  AGZ_REQUIRE(t && fused && est_bits && range_bits, AGZ_E_INVALID, "agz_trainer_last_planes: NULL argument");
+  AGZ_REQUIRE(layer >= 0 && layer <= t->L, AGZ_E_INVALID, "agz_trainer_last_planes: layer %d of 0..%d", layer, t->L);
+  AGZ_HIP_TRY(hipSetDevice(t->ctx->device));
+  AGZ_HIP_TRY(hipStreamSynchronize(t->ctx->stream));   // (the step's last kernels; the side stream was joined into it by the step)
+  if (t->wg_stream) AGZ_HIP_TRY(hipStreamSynchronize(t->wg_stream));
+  unsigned w[2] = {0u, 0u};
+  AGZ_HIP_TRY(hipMemcpy(&w[0], t->amax_prev + 2 * layer + 1, sizeof(unsigned), hipMemcpyDeviceToHost));
+  AGZ_HIP_TRY(hipMemcpy(&w[1], t->amax_words + 2 * layer + 1, sizeof(unsigned), hipMemcpyDeviceToHost));
+  *fused = t->planes_fused[layer] && t->layers[layer].x_planes ? 1 : 0;
+  *est_bits = w[0]; *range_bits = w[1];
   return AGZ_OK;
 }
 

@@ -117,6 +117,17 @@ int agz_trainer_set_dma_forward(agz_trainer* t, int on);
 #define AGZ_PATH_BN2_V 2        /* k_bn_bwd2_v: vector form, writes dz's range itself */
 int agz_trainer_last_paths(agz_trainer* t, int layer, int* fwd, int* wgrad, int* dgrad, int* bn_bwd2);
 
+/* Tests: how tower layer `layer` (0 .. SharedLayers) came by the fp16 hi / lo planes of its input in the trainer's last step
+ * (agz_trainer_forward_backward / _batch / _eval).  In AGZ_COMPUTE_WINO_H2 mode the vector BatchNorm pass of layer l - 1 writes them under
+ * LAST step's range word of the tensor, and k_split_h2p_cond keeps them when that word and this step's exact one prescribe the same power
+ * of two, else splits the tensor again (train.hip).  fused: 1 when the planes were written by the previous layer's BatchNorm pass and the
+ * layer's forward convolution read planes (the host's planes_fused[layer] && x_planes as they stood after the step), else 0.  est_bits:
+ * the estimate, amax_prev[2 layer + 1] — the bits of last step's max|x|.  range_bits: amax_words[2 layer + 1], this step's.  The planes
+ * were kept iff fused && est_bits != 0 && both words give the same scale exponent (tests/test_train_history_gpu.py restates the rule).
+ * Both words are zero for layers that never had them.  Synchronises and copies two words; launches nothing and has no effect on any
+ * launch.  Lets a test see whether a layer kept or re-split its planes, which identical results cannot show. */
+int agz_trainer_last_planes(agz_trainer* t, int layer, int* fused, uint32_t* est_bits, uint32_t* range_bits);
+
 /* Tests: which kernels the last whole-batch forward of a net (agz_net_infer / agz_net_infer_dev, the arena's joined step) launched for the
  * input convolution, the dual blocks and the heads.  Every value is written on the host at the very branch of agz_net::forward_packed that
  * launches the kernel; read-only, no effect on any launch.  0 = nothing launched yet (block: also a net without blocks). */
