@@ -18,6 +18,7 @@ INF_NET, INF_DUMMY, INF_SCRIPT, INF_HASH, INF_UNIFORM, INF_CALLBACK = 0, 1, 2, 3
 BN_DEGENERATE_EPS, BN_RUNNING, BN_IDENTITY = 0, 1, 2
 COMPUTE_F32_MFMA, COMPUTE_BF16X3, COMPUTE_FP16X2, COMPUTE_WINO, COMPUTE_AUTO, COMPUTE_WINO_H2 = 0, 1, 2, 3, 4, 5
 COMPUTE_FORCE = 0x100
+LOSS_REFERENCE, LOSS_ALPHAZERO = 0, 1   # agz_trainer_set_loss
 # agz_debug.h, agz_trainer_last_paths: the kernel a trainer layer's last step took (0 = none launched)
 PATH_FWD_F32, PATH_FWD_BF16X3, PATH_FWD_H2W, PATH_FWD_H2DMA, PATH_FWD_H2DMA3 = 1, 2, 3, 4, 5
 PATH_WGRAD_F32, PATH_WGRAD_X3, PATH_WGRAD_H2, PATH_WGRAD_H2T3 = 1, 2, 3, 4
@@ -220,6 +221,9 @@ def lib():
     sig("agz_trainer_reset_bn_stats", i32, vp)
     sig("agz_trainer_eval", i32, vp, pf, pf, pf, pf)
     sig("agz_trainer_eval_dev", i32, vp, vp, vp, vp, pf)
+    sig("agz_trainer_set_loss", i32, vp, i32)
+    sig("agz_trainer_get_loss", i32, vp, C.POINTER(C.c_int))
+    sig("agz_trainer_get_costs", i32, vp, pf, pf)
     sig("agz_trainer_set_compute_mode", i32, vp, i32)
     sig("agz_train", i32, vp, pf, pf, pf, i32, i32, u64, pf)
     sig("agz_trainer_export", i32, vp, vp)
@@ -765,6 +769,22 @@ class Trainer:
         c = C.c_float(0)
         _check(lib().agz_trainer_eval(self.h, _pf(x), _pf(p), _pf(vv), C.byref(c)), "agz_trainer_eval")
         return c.value
+
+    def set_loss(self, kind):
+        """the loss kind (agz_trainer_set_loss): LOSS_REFERENCE (default, the reference's cost on raw logits and pre-tanh value) or
+        LOSS_ALPHAZERO (softmax cross-entropy and an MSE on tanh); not stored in checkpoints"""
+        _check(lib().agz_trainer_set_loss(self.h, int(kind)), "agz_trainer_set_loss")
+
+    def get_loss(self):
+        k = C.c_int(0)
+        _check(lib().agz_trainer_get_loss(self.h, C.byref(k)), "agz_trainer_get_loss")
+        return k.value
+
+    def costs(self):
+        """(policy, value): the two terms of the last forward's cost (training or eval)"""
+        p, v = C.c_float(0), C.c_float(0)
+        _check(lib().agz_trainer_get_costs(self.h, C.byref(p), C.byref(v)), "agz_trainer_get_costs")
+        return p.value, v.value
 
     def eval_dev(self, planes_ptr, pi_ptr, v_ptr, want_cost=True):
         c = C.c_float(0)

@@ -1398,6 +1398,9 @@ struct HeadT {
   float *logits, *hpre, *o;
   float *dWp, *dbp, *dW1, *db1, *dW2, *db2, *dyh;  // dyh [B][3][HW]
   float* cost;  // [2]: pcost, vcost sums
+  // AGZ_LOSS_ALPHAZERO only (k_az_loss writes them, the <AZ = true> backward kernels read them; NULL otherwise)
+  float *az_dz, *az_do;  // [B][A] d cost / d logits, [B] d cost / d o
+  double* az_row;        // [B][2] the row's policy and value cost terms
 };
 // TIED: the biases are [A], [FC], [1], shared by every row
 template <bool TIED>
@@ -1442,6 +1445,9 @@ __global__ void k_cost(HeadT h) {  // single block
   if (threadIdx.x == 0) h.cost[1] = (float)(red[0] / h.Bn);
 }
 // backward of the FC parts.  One thread per gradient element (sums over the batch inside).
+// AZ (here and in the second form below): the per-(b, j) factor of the policy head and the per-b factor of the value head are read from
+// k_az_loss's az_dz / az_do instead of being computed inline; <false> is the reference loss, the code as it always was.
+template <bool AZ>
 __global__ void k_fc_bwd(HeadT h) {
   int idx = blockIdx.x * blockDim.x + threadIdx.x;
   const float sc = 1.0f / ((float)h.Bn * (float)h.A);
@@ -1450,18 +1456,18 @@ __global__ void k_fc_bwd(HeadT h) {
   if (idx < n_wp) {  // dWp[i][j] = sum_b yp[b][i] * dl[b][j]
     int i = idx / h.A, j = idx - i * h.A;
     float s = 0.f;
-    for (int b = 0; b < h.B; b++) s += h.yh[(size_t)b * 3 * h.HW + i] * ((1.f - 2.f * h.Pi[(size_t)b * h.A + j]) * sc);
+    for (int b = 0; b < h.B; b++) s += h.yh[(size_t)b * 3 * h.HW + i] * (AZ ? h.az_dz[(size_t)b * h.A + j] : (1.f - 2.f * h.Pi[(size_t)b * h.A + j]) * sc);
     h.dWp[idx] = s;
     return;
   }
   idx -= n_wp;
-  if (idx < n_bp) { h.dbp[idx] = (1.f - 2.f * h.Pi[idx]) * sc; return; }
+  if (idx < n_bp) { h.dbp[idx] = AZ ? h.az_dz[idx] : (1.f - 2.f * h.Pi[idx]) * sc; return; }
   idx -= n_bp;
   if (idx < n_w1) {  // dW1[i][j] = sum_b yv[b][i] * dh[b][j]
     int i = idx / h.FC, j = idx - i * h.FC;
     float s = 0.f;
     for (int b = 0; b < h.B; b++) {
-      float dob = 2.f * (h.o[b] - h.V[b]) / (float)h.Bn;
+      float dob = AZ ? h.az_do[b] : 2.f * (h.o[b] - h.V[b]) / (float)h.Bn;
       float dh = h.hpre[(size_t)b * h.FC + j] > 0.f ? dob * h.W2[j] : 0.f;
       s += h.yh[((size_t)b * 3 + 2) * h.HW + i] * dh;
     }
@@ -1471,28 +1477,28 @@ __global__ void k_fc_bwd(HeadT h) {
   idx -= n_w1;
   if (idx < n_b1) {
     int b = idx / h.FC, j = idx - b * h.FC;
-    float dob = 2.f * (h.o[b] - h.V[b]) / (float)h.Bn;
+    float dob = AZ ? h.az_do[b] : 2.f * (h.o[b] - h.V[b]) / (float)h.Bn;
     h.db1[idx] = h.hpre[idx] > 0.f ? dob * h.W2[j] : 0.f;
     return;
   }
   idx -= n_b1;
   if (idx < n_w2) {
     float s = 0.f;
-    for (int b = 0; b < h.B; b++) { float hv = h.hpre[(size_t)b * h.FC + idx]; s += (2.f * (h.o[b] - h.V[b]) / (float)h.Bn) * (hv > 0.f ? hv : 0.f); }
+    for (int b = 0; b < h.B; b++) { float hv = h.hpre[(size_t)b * h.FC + idx]; s += (AZ ? h.az_do[b] : 2.f * (h.o[b] - h.V[b]) / (float)h.Bn) * (hv > 0.f ? hv : 0.f); }
     h.dW2[idx] = s;
     return;
   }
   idx -= n_w2;
-  if (idx < n_b2) { h.db2[idx] = 2.f * (h.o[idx] - h.V[idx]) / (float)h.Bn; return; }
+  if (idx < n_b2) { h.db2[idx] = AZ ? h.az_do[idx] : 2.f * (h.o[idx] - h.V[idx]) / (float)h.Bn; return; }
   idx -= n_b2;
   if (idx < n_dy) {  // d(yh)[b][j][p]
     int b = idx / (3 * h.HW), q = idx - b * 3 * h.HW;
     float s = 0.f;
     if (q < 2 * h.HW) {
-      for (int j = 0; j < h.A; j++) s += ((1.f - 2.f * h.Pi[(size_t)b * h.A + j]) * sc) * h.Wp[(size_t)q * h.A + j];
+      for (int j = 0; j < h.A; j++) s += (AZ ? h.az_dz[(size_t)b * h.A + j] : (1.f - 2.f * h.Pi[(size_t)b * h.A + j]) * sc) * h.Wp[(size_t)q * h.A + j];
     } else {
       int i = q - 2 * h.HW;
-      float dob = 2.f * (h.o[b] - h.V[b]) / (float)h.Bn;
+      float dob = AZ ? h.az_do[b] : 2.f * (h.o[b] - h.V[b]) / (float)h.Bn;
       for (int j = 0; j < h.FC; j++) if (h.hpre[(size_t)b * h.FC + j] > 0.f) s += dob * h.W2[j] * h.W1[(size_t)i * h.FC + j];
     }
     h.dyh[idx] = s;
@@ -1650,11 +1656,71 @@ __global__ __launch_bounds__(256) void k_cost_part(HeadT h, double* __restrict__
   __syncthreads();
   if (threadIdx.x < 2) atomicAdd(&hacc[6 + threadIdx.x], red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3]);
 }
+// AZ: hacc[6] holds k_az_cost_sum's sum of the rows' cross-entropies, a mean over the rows alone
+template <bool AZ>
 __global__ void k_cost_fin(HeadT h, const double* __restrict__ hacc) {
-  if (threadIdx.x == 0) { h.cost[0] = (float)(hacc[6] / ((double)h.Bn * h.A)); h.cost[1] = (float)(hacc[7] / h.Bn); }
+  if (threadIdx.x == 0) { h.cost[0] = (float)(hacc[6] / (AZ ? (double)h.Bn : (double)h.Bn * h.A)); h.cost[1] = (float)(hacc[7] / h.Bn); }
+}
+// ---- the AlphaZero loss (agz_trainer_set_loss(AGZ_LOSS_ALPHAZERO); the definition: agz.h): softmax cross-entropy of the logits against Pi
+// and an MSE of tanh(o) against V.  One wave per batch row, after k_value_out*: A <= 512, so a lane holds at most eight logits (column
+// lane + 64 k) and the row is read once.  The row maximum is taken off before the exponentials.  Writes dz [B][A], do [B] for the
+// <AZ = true> backward kernels and the row's two cost terms; the policy term is summed as sum_j Pi_j (lse - z_j) = S lse - sum_j Pi_j z_j,
+// whose terms are all >= 0 where Pi >= 0.
+__global__ __launch_bounds__(64) void k_az_loss(HeadT h) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const float* __restrict__ zp = h.logits + (size_t)b * h.A;
+  const float* __restrict__ pp = h.Pi + (size_t)b * h.A;
+  float z[8], pi[8];
+  float m = -INFINITY, S = 0.f;
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    const int j = lane + 64 * k;
+    const bool in = j < h.A;
+    z[k] = in ? zp[j] : -INFINITY; pi[k] = in ? pp[j] : 0.f;
+    m = fmaxf(m, z[k]); S += pi[k];
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { m = fmaxf(m, __shfl_xor(m, o, 64)); S += __shfl_xor(S, o, 64); }
+  float e[8], se = 0.f;
+#pragma unroll
+  for (int k = 0; k < 8; k++) { e[k] = expf(z[k] - m); se += e[k]; }   // (columns past A: exp(-inf) = 0)
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) se += __shfl_xor(se, o, 64);
+  const float lse = m + logf(se), inv = 1.0f / se, bn = (float)h.Bn;
+  float pc = 0.f;
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    const int j = lane + 64 * k;
+    if (j < h.A) {
+      h.az_dz[(size_t)b * h.A + j] = (S * (e[k] * inv) - pi[k]) / bn;
+      pc += pi[k] * (lse - z[k]);
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) pc += __shfl_xor(pc, o, 64);
+  if (lane == 0) {
+    const float t = tanhf(h.o[b]), d = t - h.V[b];
+    h.az_do[b] = 2.f * d * (1.f - t * t) / bn;
+    h.az_row[2 * b] = (double)pc;
+    h.az_row[2 * b + 1] = (double)d * d;
+  }
+}
+// the rows' cost terms summed in double in ONE fixed order (a lane's rows b = lane, lane + 64, ..., then the wave tree): no atomics, so the
+// cost reproduces to the bit.  hacc != NULL (second form of the heads): the sums -> hacc[6], hacc[7], where the sharded exchange and
+// k_cost_fin<true> expect them; hacc == NULL (first form): cost[0..1] directly.
+__global__ __launch_bounds__(64) void k_az_cost_sum(HeadT h, double* __restrict__ hacc) {
+  double sp = 0, sv = 0;
+  for (int b = threadIdx.x; b < h.B; b += 64) { sp += h.az_row[2 * b]; sv += h.az_row[2 * b + 1]; }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { sp += __shfl_xor(sp, o, 64); sv += __shfl_xor(sv, o, 64); }
+  if (threadIdx.x == 0) {
+    if (hacc) { hacc[6] = sp; hacc[7] = sv; }
+    else { h.cost[0] = (float)(sp / h.Bn); h.cost[1] = (float)(sv / h.Bn); }
+  }
 }
 // dW[i][j] = sum_b y[b][i] * d[b][j], eight rows i per block: grid (ceil(N / 256), ceil(K / 8), 2); z = 0: dWp (d = the xent gradient),
 // z = 1: dW1 (d = the value head's hidden-layer gradient).  The b loop is the old kernel's.
+template <bool AZ>
 __global__ __launch_bounds__(256) void k_fc_bwd_w(HeadT h) {
   extern __shared__ float ys[];                      // [B][8]
   const bool pol = blockIdx.z == 0;
@@ -1671,8 +1737,8 @@ __global__ __launch_bounds__(256) void k_fc_bwd_w(HeadT h) {
   float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   for (int b = 0; b < h.B; b++) {
     float d;
-    if (pol) d = (1.f - 2.f * h.Pi[(size_t)b * h.A + j]) * sc;
-    else { const float dob = 2.f * (h.o[b] - h.V[b]) / (float)h.Bn; d = h.hpre[(size_t)b * h.FC + j] > 0.f ? dob * h.W2[j] : 0.f; }
+    if (pol) d = AZ ? h.az_dz[(size_t)b * h.A + j] : (1.f - 2.f * h.Pi[(size_t)b * h.A + j]) * sc;
+    else { const float dob = AZ ? h.az_do[b] : 2.f * (h.o[b] - h.V[b]) / (float)h.Bn; d = h.hpre[(size_t)b * h.FC + j] > 0.f ? dob * h.W2[j] : 0.f; }
 #pragma unroll
     for (int t = 0; t < 8; t++) acc[t] += ys[b * 8 + t] * d;
   }
@@ -1681,30 +1747,32 @@ __global__ __launch_bounds__(256) void k_fc_bwd_w(HeadT h) {
   for (int t = 0; t < 8; t++) if (i0 + t < K) dW[(size_t)(i0 + t) * N + j] = acc[t];
 }
 // the elementwise / small parts of the FC backward: dbp, db1, dW2, db2
+template <bool AZ>
 __global__ void k_fc_bwd_small(HeadT h) {
   int idx = blockIdx.x * blockDim.x + threadIdx.x;
   const float sc = 1.0f / ((float)h.Bn * (float)h.A);
   const int n_bp = h.B * h.A, n_b1 = h.B * h.FC, n_w2 = h.FC, n_b2 = h.B;
-  if (idx < n_bp) { h.dbp[idx] = (1.f - 2.f * h.Pi[idx]) * sc; return; }
+  if (idx < n_bp) { h.dbp[idx] = AZ ? h.az_dz[idx] : (1.f - 2.f * h.Pi[idx]) * sc; return; }
   idx -= n_bp;
   if (idx < n_b1) {
     const int b = idx / h.FC, j = idx - b * h.FC;
-    const float dob = 2.f * (h.o[b] - h.V[b]) / (float)h.Bn;
+    const float dob = AZ ? h.az_do[b] : 2.f * (h.o[b] - h.V[b]) / (float)h.Bn;
     h.db1[idx] = h.hpre[idx] > 0.f ? dob * h.W2[j] : 0.f;
     return;
   }
   idx -= n_b1;
   if (idx < n_w2) {
     float s = 0.f;
-    for (int b = 0; b < h.B; b++) { const float hv = h.hpre[(size_t)b * h.FC + idx]; s += (2.f * (h.o[b] - h.V[b]) / (float)h.Bn) * (hv > 0.f ? hv : 0.f); }
+    for (int b = 0; b < h.B; b++) { const float hv = h.hpre[(size_t)b * h.FC + idx]; s += (AZ ? h.az_do[b] : 2.f * (h.o[b] - h.V[b]) / (float)h.Bn) * (hv > 0.f ? hv : 0.f); }
     h.dW2[idx] = s;
     return;
   }
   idx -= n_w2;
-  if (idx < n_b2) h.db2[idx] = 2.f * (h.o[idx] - h.V[idx]) / (float)h.Bn;
+  if (idx < n_b2) h.db2[idx] = AZ ? h.az_do[idx] : 2.f * (h.o[idx] - h.V[idx]) / (float)h.Bn;
 }
 // d(yh)[b][q] for eight batch rows per block: grid (ceil(Q / 256), ceil(B / 8), 2); z = 0: q < 2 HW (sum over the A logits), z = 1: the value
 // channel (sum over the FC hidden units).  The j loop is the old kernel's; the per-(b, j) factor comes from an LDS tile.
+template <bool AZ>
 __global__ __launch_bounds__(256) void k_fc_bwd_y(HeadT h) {
   extern __shared__ float ds[];                      // [8][J]
   const bool pol = blockIdx.z == 0;
@@ -1716,8 +1784,8 @@ __global__ __launch_bounds__(256) void k_fc_bwd_y(HeadT h) {
     const int t = e / J, j = e - t * J, b = b0 + t;
     float d = 0.f;
     if (b < h.B) {
-      if (pol) d = (1.f - 2.f * h.Pi[(size_t)b * h.A + j]) * sc;
-      else { const float dob = 2.f * (h.o[b] - h.V[b]) / (float)h.Bn; d = h.hpre[(size_t)b * h.FC + j] > 0.f ? dob * h.W2[j] : 0.f; }
+      if (pol) d = AZ ? h.az_dz[(size_t)b * h.A + j] : (1.f - 2.f * h.Pi[(size_t)b * h.A + j]) * sc;
+      else { const float dob = AZ ? h.az_do[b] : 2.f * (h.o[b] - h.V[b]) / (float)h.Bn; d = h.hpre[(size_t)b * h.FC + j] > 0.f ? dob * h.W2[j] : 0.f; }
     }
     ds[e] = d;
   }
@@ -2192,6 +2260,12 @@ struct agz_trainer {
   std::function<int(size_t off, size_t n, hipStream_t ready)> on_slice;
   unsigned* amax_prev = nullptr;   // [(L + 2) * 2] last step's amax_words: the range estimates k_bn_apply_v writes the next layer's planes under
   double* head_acc = nullptr;   // [16] partial sums of the head kernels' second form (statistics, cost, BatchNorm backward)
+  // the loss kind (agz_trainer_set_loss; the caller's configuration like lr, in no checkpoint).  az_dz [B][A], az_do [B], az_row [B][2]
+  // are allocated when the kind is first set to AGZ_LOSS_ALPHAZERO: a trainer that never asks allocates nothing
+  int loss_kind = AGZ_LOSS_REFERENCE;
+  float *az_dz = nullptr, *az_do = nullptr;
+  double* az_row = nullptr;
+  bool cost_valid = false;  // a forward (training or eval) has written cost[0..1] (agz_trainer_get_costs)
   bool fast_heads = true;   // agz_trainer_set_dma_forward(t, on | 2 * heads): the second form of the head kernels (A/B hook)
   bool dma_fwd = true;      // AGZ_COMPUTE_WINO_H2 forward convolutions through k_conv_h2dma (agz_trainer_set_dma_forward, agz_debug.h: A/B hook)
   bool hoist_w = true;      // ... every layer's weight images at the start of the step on the side stream (bit 3 of the same hook: per layer, in line)
@@ -2480,6 +2554,8 @@ int agz_trainer::forward_backward_dev(const float* planes, const float* pi, cons
   h.B = B; h.Bn = B * n_ranks; h.HW = g.HW; h.A = A; h.FC = FC; h.yh = yh; h.Wp = P + o_Wp; h.bp = P + o_bp; h.W1 = P + o_W1; h.b1 = P + o_b1;
   h.W2 = P + o_W2; h.b2 = P + o_b2; h.Pi = pi; h.V = v; h.logits = logits; h.hpre = hpre; h.o = o;
   h.dWp = G + o_Wp; h.dbp = G + o_bp; h.dW1 = G + o_W1; h.db1 = G + o_b1; h.dW2 = G + o_W2; h.db2 = G + o_b2; h.dyh = dyh; h.cost = cost;
+  const bool az = loss_kind == AGZ_LOSS_ALPHAZERO;
+  if (az) { h.az_dz = az_dz; h.az_do = az_do; h.az_row = az_row; }
   // tied: the head kernels write their per-row gradients of the batch-shaped tensors into tied_rows; k_rows_sum adds the rows into G
   float *dhg = G + o_hg, *dhb = G + o_hb;
   if (tied) {
@@ -2506,13 +2582,17 @@ int agz_trainer::forward_backward_dev(const float* planes, const float* pi, cons
     hipLaunchKernelGGL(tied ? k_head_apply<true> : k_head_apply<false>, dim3(nblk((size_t)g.M * 3)), dim3(256), 0, s, g, zh, P + o_hg, P + o_hb, hmean, hinv, yh);
     hipLaunchKernelGGL(tied ? k_fc_fwd2<true> : k_fc_fwd2<false>, dim3(nblk(std::max(A, FC)), nblk(B, 8), 2), dim3(256), (size_t)8 * 2 * g.HW * sizeof(float), s, h);
     hipLaunchKernelGGL(tied ? k_value_out2<true> : k_value_out2<false>, dim3(B), dim3(64), 0, s, h);
+    if (az) {
+      hipLaunchKernelGGL(k_az_loss, dim3(B), dim3(64), 0, s, h);
+      hipLaunchKernelGGL(k_az_cost_sum, dim3(1), dim3(64), 0, s, h, head_acc);
+    } else
     hipLaunchKernelGGL(k_cost_part, dim3(std::min(nblk((size_t)B * A), 64)), dim3(256), 0, s, h, head_acc);
     if (sharded) {
       int r = exchange(L + 1, head_acc, 16);
       if (r != AGZ_OK) return r;
       hipLaunchKernelGGL(k_sum_ranks, dim3(1), dim3(64), 0, s, xg, n_ranks, 16, head_acc, 6, 2);
     }
-    hipLaunchKernelGGL(k_cost_fin, dim3(1), dim3(64), 0, s, h, head_acc);
+    hipLaunchKernelGGL(az ? k_cost_fin<true> : k_cost_fin<false>, dim3(1), dim3(64), 0, s, h, head_acc);
   } else {
   hipLaunchKernelGGL(k_head_conv, dim3(nblk((size_t)g.M * 3)), dim3(256), 0, s, g, cur, P + o_hc, zh, Kp);
   if (eval) hipLaunchKernelGGL(k_bn_from_running, dim3(1), dim3(64), 0, s, hbt, conf.bn_eps, hmean, hinv);
@@ -2520,15 +2600,20 @@ int agz_trainer::forward_backward_dev(const float* planes, const float* pi, cons
   hipLaunchKernelGGL(tied ? k_head_apply<true> : k_head_apply<false>, dim3(nblk((size_t)g.M * 3)), dim3(256), 0, s, g, zh, P + o_hg, P + o_hb, hmean, hinv, yh);
   hipLaunchKernelGGL(tied ? k_fc_fwd<true> : k_fc_fwd<false>, dim3(nblk((size_t)B * A + (size_t)B * FC)), dim3(256), 0, s, h);
   hipLaunchKernelGGL(tied ? k_value_out<true> : k_value_out<false>, dim3(nblk(B)), dim3(256), 0, s, h);
+  if (az) {
+    hipLaunchKernelGGL(k_az_loss, dim3(B), dim3(64), 0, s, h);
+    hipLaunchKernelGGL(k_az_cost_sum, dim3(1), dim3(64), 0, s, h, (double*)nullptr);
+  } else
   hipLaunchKernelGGL(k_cost, dim3(1), dim3(256), 0, s, h);
   }
+  cost_valid = true;
   if (eval) { AGZ_HIP_TRY(hipGetLastError()); return AGZ_OK; }   // (forward only: no gradient, no state touched)
   // ---- heads backward
   size_t n_fc = (size_t)2 * g.HW * A + (size_t)B * A + (size_t)g.HW * FC + (size_t)B * FC + FC + B + (size_t)B * 3 * g.HW;
   if (fh) {
-    hipLaunchKernelGGL(k_fc_bwd_w, dim3(nblk(std::max(A, FC)), nblk(2 * g.HW, 8), 2), dim3(256), (size_t)B * 8 * sizeof(float), s, h);
-    hipLaunchKernelGGL(k_fc_bwd_small, dim3(nblk((size_t)B * A + (size_t)B * FC + FC + B)), dim3(256), 0, s, h);
-    hipLaunchKernelGGL(k_fc_bwd_y, dim3(nblk(2 * g.HW), nblk(B, 8), 2), dim3(256), (size_t)8 * fcJ * sizeof(float), s, h);
+    hipLaunchKernelGGL(az ? k_fc_bwd_w<true> : k_fc_bwd_w<false>, dim3(nblk(std::max(A, FC)), nblk(2 * g.HW, 8), 2), dim3(256), (size_t)B * 8 * sizeof(float), s, h);
+    hipLaunchKernelGGL(az ? k_fc_bwd_small<true> : k_fc_bwd_small<false>, dim3(nblk((size_t)B * A + (size_t)B * FC + FC + B)), dim3(256), 0, s, h);
+    hipLaunchKernelGGL(az ? k_fc_bwd_y<true> : k_fc_bwd_y<false>, dim3(nblk(2 * g.HW), nblk(B, 8), 2), dim3(256), (size_t)8 * fcJ * sizeof(float), s, h);
     hipLaunchKernelGGL(tied ? k_head_bn_bwd_a<true> : k_head_bn_bwd_a<false>, dim3(std::min(nblk(g.M), ctx->num_cus)), dim3(256), 0, s, g, zh, yh, dyh, P + o_hg, hmean, hinv, dhg, dhb, dzh, head_acc);
     if (tied_sharded()) {
       // the five tied head tensors' partials over this rank's rows ride the same gather, behind the 16 words; summed in rank order into G
@@ -2548,7 +2633,7 @@ int agz_trainer::forward_backward_dev(const float* planes, const float* pi, cons
     hipLaunchKernelGGL(k_head_bn_bwd_b, dim3(nblk((size_t)g.M * 3)), dim3(256), 0, s, g, zh, hmean, hinv, dzh, head_acc, (float)m_glob());
     hipLaunchKernelGGL(k_head_conv_bwd_w2, dim3(nblk(g.M, RPB)), dim3(256), 0, s, g, cur, dzh, G + o_hc, Kp, RPB);
   } else {
-  hipLaunchKernelGGL(k_fc_bwd, dim3(nblk(n_fc)), dim3(256), 0, s, h);
+  hipLaunchKernelGGL(az ? k_fc_bwd<true> : k_fc_bwd<false>, dim3(nblk(n_fc)), dim3(256), 0, s, h);
   hipLaunchKernelGGL(tied ? k_head_bn_bwd<true> : k_head_bn_bwd<false>, dim3(3), dim3(256), 0, s, g, zh, yh, dyh, P + o_hg, hmean, hinv, dhg, dhb, dzh);
   hipLaunchKernelGGL(k_head_conv_bwd_w, dim3(nblk(g.M, RPB)), dim3(256), 0, s, g, cur, dzh, G + o_hc, Kp, RPB);
   }
@@ -3389,6 +3474,40 @@ int agz_trainer_set_dma_forward(agz_trainer* t, int on) {
   t->hoist_w = (on & 8) == 0;         // bit 3: weight images per layer in line, not at the start of the step on the side stream (A/B)
   t->wg_pad_lds = (on & 256) ? 0 : 16384;   // bit 8: k_wgrad_h2t3 at two workgroups per CU as in round 5 (default: one, 73.7 KB static + 16 KB dynamic LDS)
   t->wg_low_prio = (on & 512) != 0;     // bit 9: the side stream at the lowest priority (before the first step)
+  return AGZ_OK;
+}
+
+// The loss kind (agz.h).  Local on a sharded handle: every rank sets the same.
+int agz_trainer_set_loss(agz_trainer* t, int kind) {
+  AGZ_REQUIRE(t, AGZ_E_INVALID, "agz_trainer_set_loss: NULL trainer");
+  AGZ_REQUIRE(kind == AGZ_LOSS_REFERENCE || kind == AGZ_LOSS_ALPHAZERO, AGZ_E_INVALID, "agz_trainer_set_loss: unknown loss kind %d", kind);
+  if (kind == AGZ_LOSS_ALPHAZERO && !t->az_row) {
+    AGZ_REQUIRE(t->A <= 512, AGZ_E_UNSUPPORTED, "agz_trainer_set_loss: the loss kernel holds a row of at most 512 logits (ActionSpace %d)", t->A);
+    AGZ_HIP_TRY(hipSetDevice(t->ctx->device));
+    int r = AGZ_OK;
+    if (!t->az_dz) r = t->alloc(&t->az_dz, (size_t)t->B * t->A);
+    if (r == AGZ_OK && !t->az_do) r = t->alloc(&t->az_do, (size_t)t->B);
+    if (r == AGZ_OK) r = t->alloc(&t->az_row, (size_t)t->B * 2);
+    if (r != AGZ_OK) return r;
+    AGZ_HIP_TRY(hipStreamSynchronize(t->ctx->stream));
+  }
+  t->loss_kind = kind;
+  return AGZ_OK;
+}
+int agz_trainer_get_loss(const agz_trainer* t, int* kind) {
+  AGZ_REQUIRE(t && kind, AGZ_E_INVALID, "agz_trainer_get_loss: NULL argument");
+  *kind = t->loss_kind;
+  return AGZ_OK;
+}
+int agz_trainer_get_costs(agz_trainer* t, float* policy, float* value) {
+  AGZ_REQUIRE(t, AGZ_E_INVALID, "agz_trainer_get_costs: NULL trainer");
+  AGZ_REQUIRE(t->cost_valid, AGZ_E_STATE, "agz_trainer_get_costs: no forward pass has run yet");
+  AGZ_HIP_TRY(hipSetDevice(t->ctx->device));
+  float c[2] = {0, 0};
+  AGZ_HIP_TRY(hipMemcpyAsync(c, t->cost, 8, hipMemcpyDeviceToHost, t->ctx->stream));
+  AGZ_HIP_TRY(hipStreamSynchronize(t->ctx->stream));
+  if (policy) *policy = c[0];
+  if (value) *value = c[1];
   return AGZ_OK;
 }
 

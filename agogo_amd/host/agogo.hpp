@@ -98,6 +98,10 @@ struct Trainable {
   }
   agz_solver_conf Solver() const { agz_solver_conf sc{}; agz::check(agz_trainer_get_solver(h, &sc), "solver options"); return sc; }
   void ResetSolver() { agz::check(agz_trainer_reset_solver(h), "solver reset"); }   // velocity := 0
+  // the loss kind (agz_trainer_set_loss): AGZ_LOSS_REFERENCE (default, dual.go:113-121) or AGZ_LOSS_ALPHAZERO (softmax cross-entropy and
+  // an MSE on tanh: what the exported network plays).  Configuration like the solver's: no checkpoint stores it.
+  void SetLoss(int kind) { agz::check(agz_trainer_set_loss(h, kind), "loss kind"); }
+  int Loss() const { int k = 0; agz::check(agz_trainer_get_loss(h, &k), "loss kind"); return k; }
   // running BatchNorm statistics (the reference asks gorgonia for momentum 0.997, ermahagerdmonards.go:54): from here on every training
   // forward feeds the estimates that SwitchToInference, Eval and Save use.  Off by default.
   void TrackBatchNorm(float momentum = 0.997f) { agz::check(agz_trainer_set_bn_tracking(h, 1, momentum), "BatchNorm tracking"); }
@@ -292,6 +296,10 @@ struct Config {
   // build extension: the options of the solver dual.Train builds (agz_trainer_set_solver); all 0 (default) = the reference's vanilla solver.
   // Applied to A, B and every newB.
   agz_solver_conf Solver = {0.f, 0.f, 0.f, 0};
+  // build extension: the loss dual.Train optimises (agz_trainer_set_loss): AGZ_LOSS_REFERENCE (default) = the reference's, AGZ_LOSS_ALPHAZERO
+  // = softmax cross-entropy and an MSE on tanh.  Applied with the solver options to A, B and every newB.  Like the kind in a trainer file,
+  // it is not in a SaveRun file (AGZRUN01 unchanged): a resumed run trains under the Loss of the Config its AZ was constructed with.
+  int Loss = AGZ_LOSS_REFERENCE;
   // build extension: train from a replay window instead of one epoch's examples.  ReplayWindow = rows the window keeps across epochs; 0
   // (default) = off, AZ.Learn exactly as the reference has it.  ReplaySteps = minibatches per epoch; 0 = (live rows / BatchSize) * nniters.
   // ReplaySymmetric = every sampled row under one of the eight board symmetries, chosen per draw; the materialising augmenters
@@ -356,6 +364,7 @@ struct AZ {
   }
   void applySolver(dual::Trainable& t) const {   // (the default options leave the trainer untouched: no call)
     if (conf.Solver.momentum != 0.f || conf.Solver.l2reg != 0.f || conf.Solver.clip != 0.f) t.SetSolver(conf.Solver.momentum, conf.Solver.l2reg, conf.Solver.clip);
+    if (conf.Loss != AGZ_LOSS_REFERENCE) t.SetLoss(conf.Loss);
   }
   // AZ.Learn (agogo.go:100-172).  Build extension: epochs first_epoch .. first_epoch + iters - 1, each with the seeds epoch number `epoch`
   // has in an uninterrupted run, so Learn(2, ...), SaveRun, LoadRun on a new AZ and Learn(1, ..., 2) is Learn(3, ...).

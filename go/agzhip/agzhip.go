@@ -1229,6 +1229,35 @@ func (t *Trainer) EvalDev(planes, pi, v unsafe.Pointer) (float32, error) {
 	return float32(cost), err
 }
 
+// The loss kinds of SetLoss (agz.h, DESIGN §2 `az-loss`).
+const (
+	LossReference = 0 // the reference's cost on the raw logits and the pre-tanh value (dualnet/dual.go:113-121); the default
+	LossAlphaZero = 1 // softmax cross-entropy against Pi, MSE of tanh(o) against V: what the exported net plays
+)
+
+// SetLoss chooses the loss every forward of this trainer computes (agz_trainer_set_loss).  It is configuration, like the learn rate:
+// no checkpoint stores it.  On a sharded trainer every rank sets the same kind.
+func (t *Trainer) SetLoss(kind int) error {
+	defer t.ctx.enter()()
+	return lastErr(C.agz_trainer_set_loss(t.h, C.int(kind)))
+}
+
+// Loss returns the kind SetLoss chose (LossReference on a new trainer).
+func (t *Trainer) Loss() (int, error) {
+	defer t.ctx.enter()()
+	var k C.int
+	err := lastErr(C.agz_trainer_get_loss(t.h, &k))
+	return int(k), err
+}
+
+// Costs returns the policy and the value term of the last forward's cost (training or Eval); their sum is the cost that call returned.
+func (t *Trainer) Costs() (float32, float32, error) {
+	defer t.ctx.enter()()
+	var p, v C.float
+	err := lastErr(C.agz_trainer_get_costs(t.h, &p, &v))
+	return float32(p), float32(v), err
+}
+
 func (t *Trainer) Export(n *Net) error { defer t.ctx.enter()(); return lastErr(C.agz_trainer_export(t.h, n.h)) }
 
 func (t *Trainer) Close() error { defer t.ctx.enter()(); C.agz_trainer_destroy(t.h); t.h = nil; return nil }

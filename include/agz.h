@@ -367,6 +367,36 @@ int agz_trainer_reset_bn_stats(agz_trainer* t);
  * Tests: tests/test_bn_tracking_gpu.py (eval equals the forward it was made from, eval against float64), test_bn_tracking_sharded_gpu.py. */
 int agz_trainer_eval(agz_trainer* t, const float* planes, const float* pi, const float* v, float* cost);
 int agz_trainer_eval_dev(agz_trainer* t, const float* planes_dev, const float* pi_dev, const float* v_dev, float* cost);
+/* The loss kind (DESIGN §2 `az-loss`).  AGZ_LOSS_REFERENCE, the default, is the reference's cost as restated by agz_trainer_forward_backward:
+ * -mean(Pi z + (1 - Pi)(1 - z)) on the raw logits z and an MSE on the pre-tanh value output o (dualnet/dual.go:113-121).  The exported
+ * net plays softmax(z) and tanh(o); AGZ_LOSS_ALPHAZERO trains exactly those.  With Bn the batch the loss is normalised by (BatchSize, or
+ * the global batch of a sharded trainer), z [Bn][A] the logits, o [Bn] the value output, Pi / V the targets:
+ *     per row b:  m_b = max_j z_bj    s_b = sum_j exp(z_bj - m_b)    lse_b = m_b + log s_b    p_bj = exp(z_bj - m_b) / s_b
+ *                 S_b = sum_j Pi_bj   t_b = tanh(o_b)
+ *     pcost = (1/Bn) sum_b ( S_b lse_b - sum_j Pi_bj z_bj )     ( = -sum Pi log softmax(z): a mean over the rows, NOT over rows x A )
+ *     vcost = (1/Bn) sum_b (t_b - V_b)^2                          cost = pcost + vcost
+ *     dz_bj = (S_b p_bj - Pi_bj) / Bn                             do_b = 2 (t_b - V_b)(1 - t_b^2) / Bn
+ * The rows of Pi need not sum to 1: the factor S_b is part of the definition.  So is the subtraction of the row maximum before the
+ * exponentials: logits of +-100 give finite costs and gradients.  The row reductions run in fp32 over one wave (ActionSpace <= 512:
+ * AGZ_E_UNSUPPORTED above), the two cost sums in double in a fixed order: where every other reduction of a step runs in one workgroup, the
+ * step reproduces to the bit, as the reference loss does there.
+ * The kind is the caller's configuration, as the learn rate and agz_solver_conf are: NOT stored by agz_trainer_save (every AGZTRN0x format
+ * is unchanged), and it covers every entry that runs a forward — agz_trainer_forward_backward(_dev), agz_trainer_batch, agz_train(_dev),
+ * agz_train_replay(_sharded), the _allreduce forms, and agz_trainer_eval(_dev), which then returns a held-out cross-entropy — on plain,
+ * tied, sharded and sharded-tied handles.  Sharded: a local call, every rank sets the same; the cost words travel in the exchange that
+ * always carried them, no collective is added.  With the kind never set, or set back to AGZ_LOSS_REFERENCE, every path launches exactly
+ * the kernels it launched before; the two small device buffers of the AlphaZero kind (dz [B][A], do [B]; 370 KB at B = 256, A = 362) are
+ * allocated when it is first asked for.
+ * set_loss: AGZ_E_INVALID for any other kind, the setting then stays as it was.
+ * get_costs: the two terms of the last forward (training or eval) under either kind, *policy + *value being the cost that forward
+ * returned; either pointer may be NULL; AGZ_E_STATE before the first forward.
+ * Tests: tests/test_az_loss_cpu.py (ABI, the float64 module against the closed forms), tests/test_az_loss_gpu.py (off is untouched,
+ * float64 parity at every shape, both head forms, stability, tied, reproducible, descent, eval, validation), test_az_loss_sharded_gpu.py. */
+#define AGZ_LOSS_REFERENCE 0
+#define AGZ_LOSS_ALPHAZERO 1
+int agz_trainer_set_loss(agz_trainer* t, int kind);
+int agz_trainer_get_loss(const agz_trainer* t, int* kind);
+int agz_trainer_get_costs(agz_trainer* t, float* policy, float* value);
 
 /* ---- batched self-play arenas: game.State + mcts.MCTS + agogo.Arena on device ---------------- */
 #define AGZ_GAME_MNK 0  /* game/mnk  (m,n,k) */
