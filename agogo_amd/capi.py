@@ -36,6 +36,7 @@ PROF_WINO_IN, PROF_WINO_GEMM, PROF_WINO_OUT = 6, 7, 8
 DONT_PREFER_PASS, PREFER_PASS, DONT_RESIGN = 0, 1, 2
 POOL_STRICT, POOL_STOP_SEARCH, POOL_GROW = 0, 1, 2
 SYM_OFF, SYM_RANDOM, SYM_FIXED = 0, 1, 8   # set_leaf_symmetry: SYM_FIXED + k applies S_k at every leaf
+TARGET_REFERENCE, TARGET_VISITS = 0, 1     # Arena.set_policy_target
 
 
 class AgzError(RuntimeError):
@@ -74,6 +75,11 @@ class MctsConf(C.Structure):
 class NoiseConf(C.Structure):
     """agz_noise_conf (include/agz.h): root noise P = (1 - eps) p + eps eta, eta ~ Dir(alpha); 16 bytes"""
     _fields_ = [("eps", C.c_float), ("alpha", C.c_float), ("on", C.c_int32), ("reserved", C.c_int32)]
+
+
+class TargetConf(C.Structure):
+    """agz_target_conf (include/agz.h): what an arena records as an example's policy row; 16 bytes"""
+    _fields_ = [("kind", C.c_int32), ("temperature", C.c_float), ("reserved", C.c_int32 * 2)]
 
 
 class ArenaStats(C.Structure):
@@ -250,6 +256,10 @@ def lib():
     sig("agz_mcts_set_root_noise", i32, vp, pnc)
     sig("agz_mcts_root_noise", i32, vp, pu64, pi, pf, i32, C.POINTER(C.c_int))
     sig("agz_root_noise_of", i32, u64, i32, C.c_float, pf)
+    ptc = C.POINTER(TargetConf)
+    sig("agz_arena_set_policy_target", i32, vp, ptc)
+    sig("agz_arena_get_policy_target", i32, vp, ptc)
+    sig("agz_visit_target_of", i32, pi, C.POINTER(C.c_uint32), i32, i32, C.c_float, pf)
     sig("agz_arena_begin_move", i32, vp)
     sig("agz_arena_simulate", i32, vp, i32)
     sig("agz_arena_end_move", i32, vp, i32)
@@ -948,6 +958,17 @@ class Arena:
         k = min(cap, n.value)
         return key.value, mv[:k].copy(), eta[:k].copy(), n.value
 
+    def set_policy_target(self, kind, temperature=1.0):
+        """TARGET_REFERENCE (default: the reference's Policies row) or TARGET_VISITS: the policy row of a recorded example is the root's
+        visit distribution pi(a) ~ N(a)^(1/temperature), on every searched ply (include/agz.h)"""
+        conf = TargetConf(int(kind), temperature, (C.c_int32 * 2)(0, 0))
+        _check(lib().agz_arena_set_policy_target(self.h, C.byref(conf)), "agz_arena_set_policy_target")
+
+    def get_policy_target(self):
+        conf = TargetConf()
+        _check(lib().agz_arena_get_policy_target(self.h, C.byref(conf)), "agz_arena_get_policy_target")
+        return {"kind": conf.kind, "temperature": conf.temperature}
+
     def begin_move(self):
         _check(lib().agz_arena_begin_move(self.h), "agz_arena_begin_move")
 
@@ -1641,3 +1662,15 @@ def root_noise_of(key, n, alpha):
     eta = np.zeros(max(int(n), 1), np.float32)
     _check(lib().agz_root_noise_of(int(key) & (2 ** 64 - 1), int(n), float(alpha), _pf(eta)), "agz_root_noise_of")
     return eta[:int(n)]
+
+
+def visit_target_of(moves, visits, action_space, temperature=1.0):
+    """the policy row (action_space + 1 floats, Pass last) of root children (moves[i], visits[i]) under TARGET_VISITS (target.hpp;
+    host only): what the device records for a root whose read-back is (moves, visits)"""
+    mv = np.ascontiguousarray(moves, dtype=np.int32).reshape(-1)
+    vis = np.ascontiguousarray(visits, dtype=np.uint32).reshape(-1)
+    assert mv.size == vis.size
+    row = np.zeros(max(int(action_space), 0) + 1, np.float32)
+    _check(lib().agz_visit_target_of(_pi(mv), vis.ctypes.data_as(C.POINTER(C.c_uint32)), mv.size, int(action_space), temperature, _pf(row)),
+           "agz_visit_target_of")
+    return row

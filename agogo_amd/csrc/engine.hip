@@ -1033,8 +1033,12 @@ __global__ __launch_bounds__(64) void k_expand(Dev d, GameCfg c, MctsCfg mc, Inf
 // example, the mover's tree is left alone and re-roots over the extra plies at its next search).
 // search_only != 0: MCTS.Search's own tail only (search.go:151-163) — bestMove, t.prev = current.Clone(), cachedPolicies++ —
 // the move goes to d.best_out[g] and the game is NOT advanced (the caller of Search applies it to its own game.State).
+// tkind / ttau: agz_arena_set_policy_target (BUILD EXTENSION, DESIGN.md §2 visit-target; target.hpp holds the definition).
+// AGZ_TARGET_REFERENCE records the Policies row below.  AGZ_TARGET_VISITS records the root's visit distribution instead,
+// pi(a) ~ N(a)^(1/ttau), on every searched ply whose root has a visited child — a ply that chose Pass or Resign included.
+// Only the row and the number of rows differ: the move, the sort, the RNG draws, the trees and cachedPolicies are the same.
 __global__ __launch_bounds__(64) void k_end_move(Dev d, GameCfg c, MctsCfg mc, int record, int restart, const int32_t* forced,
-                                                 int search_only) {
+                                                 int search_only, int tkind, float ttau) {
   __shared__ Sh s;
   __shared__ uint32_t cv[CELLS_PAD];   // child visits
   __shared__ int16_t ckn[CELLS_PAD];   // child kids_n
@@ -1169,22 +1173,56 @@ __global__ __launch_bounds__(64) void k_end_move(Dev d, GameCfg c, MctsCfg mc, i
   __syncthreads();
   if (record) {  // arena.go:105-123
     // Policies (tree.go:128-142): counts of (hash, a) for a in [0, A], normalised; NaN when the move was Pass/Resign
+    const bool by_visits = tkind == AGZ_TARGET_VISITS;   // (a forced move has n == 0 and record == 0)
     float tot = 0.f;
-    for (int q = 0; q < pcn; q++) {
-      int mv = d.pc_move[(size_t)t * d.moves_stride + q];
-      if (d.pc_hash[(size_t)t * d.moves_stride + q] == hash && mv >= 0 && mv <= c.A) tot += 1.f;
+    uint32_t nmax = 0;
+    if (by_visits) {   // Nmax over the root's children, still in LDS in their pre-sort order (the row does not depend on the order)
+      for (int i = lane; i < n; i += WAVE) nmax = cv[i] > nmax ? cv[i] : nmax;
+      for (int o = 32; o > 0; o >>= 1) { uint32_t v = __shfl_xor(nmax, o, 64); nmax = v > nmax ? v : nmax; }
+    } else {
+      for (int q = 0; q < pcn; q++) {
+        int mv = d.pc_move[(size_t)t * d.moves_stride + q];
+        if (d.pc_hash[(size_t)t * d.moves_stride + q] == hash && mv >= 0 && mv <= c.A) tot += 1.f;
+      }
     }
-    if (tot > 0.f) {  // validPolicies (arena.go:241-251): sum 0 -> NaN -> dropped
+    if (by_visits ? nmax > 0 : tot > 0.f) {  // validPolicies (arena.go:241-251): sum 0 -> NaN -> dropped; visits: no visited child, no target
       int e = -1;
       if (lane == 0) e = atomicAdd(d.ex_count, 1);
       e = __shfl(e, 0, 64);
       if (e < d.ex_cap) {
         float* P = d.ex_policy + (size_t)e * (c.A + 1);
-        for (int a = lane; a <= c.A; a += WAVE) {
-          float cnt = 0.f;
-          for (int q = 0; q < pcn; q++)
-            if (d.pc_hash[(size_t)t * d.moves_stride + q] == hash && d.pc_move[(size_t)t * d.moves_stride + q] == a) cnt += 1.f;
-          P[a] = __fdiv_rn(cnt, tot);
+        if (by_visits) {
+          // target.hpp: integer weights, lane keeps those of children lane, lane + 64, ...; their sum is exact, so any reduction order gives S
+          constexpr int PER_LANE = CELLS_PAD / WAVE;
+          const double tau = (double)ttau;
+          uint64_t w[PER_LANE], S = 0;
+#pragma unroll
+          for (int k = 0; k < PER_LANE; k++) {
+            const int i = lane + k * WAVE;
+            w[k] = i < n ? target::weight(cv[i], nmax, tau) : 0;
+            S += w[k];
+          }
+          for (int o = 32; o > 0; o >>= 1) {
+            const uint32_t lo = __shfl_xor((uint32_t)S, o, 64), hi = __shfl_xor((uint32_t)(S >> 32), o, 64);
+            S += ((uint64_t)hi << 32) | lo;
+          }
+          for (int a = lane; a <= c.A; a += WAVE) P[a] = 0.f;
+          __syncthreads();   // (e and nmax are the same in every lane: the whole workgroup is here)
+#pragma unroll
+          for (int k = 0; k < PER_LANE; k++) {
+            const int i = lane + k * WAVE;
+            if (i < n) {
+              const int a = target::index_of(s.fmove[i], c.A);
+              if (a >= 0 && a <= c.A) P[a] = target::entry(w[k], S);
+            }
+          }
+        } else {
+          for (int a = lane; a <= c.A; a += WAVE) {
+            float cnt = 0.f;
+            for (int q = 0; q < pcn; q++)
+              if (d.pc_hash[(size_t)t * d.moves_stride + q] == hash && d.pc_move[(size_t)t * d.moves_stride + q] == a) cnt += 1.f;
+            P[a] = __fdiv_rn(cnt, tot);
+          }
         }
         encode_nchw(c, s, st, d.ex_planes + (size_t)e * c.F * c.cells, lane);
         if (lane == 0) {
@@ -1399,6 +1437,7 @@ struct agz_arena {
   int nA_slots = 0, nB_slots = 0;
   bool in_move = false;
   agz_noise_conf noise{0.25f, 0.3f, 0, 0};   // agz_arena_set_root_noise; the caller's configuration, not in a checkpoint
+  agz_target_conf target{AGZ_TARGET_REFERENCE, 1.0f, {0, 0}};   // agz_arena_set_policy_target; likewise
   bool restart = false;  // continuous self-play: finished games restart immediately
   int moves_done = 0;
   // AGZ_INF_CALLBACK (mcts.Inferencer as a host function, mcts/mcts.go:15-18): the callee, its policy width, page-locked staging
@@ -2110,6 +2149,45 @@ int agz_root_noise_of(uint64_t key, int n, float alpha, float* eta) {
   return AGZ_OK;
 }
 
+// Policy-target kind (BUILD EXTENSION, DESIGN.md §2 visit-target): what k_end_move writes into an example's policy row.  The setting
+// lives in the arena and rides on k_end_move's arguments: no buffer, no launch, no read-back.  Not part of an arena checkpoint.
+static bool target_tau_ok(float t) { return t > 0.f && t <= 3.402823466e38f; }   // finite and positive (NaN fails every comparison)
+int agz_arena_set_policy_target(agz_arena* a, const agz_target_conf* conf) {
+  AGZ_REQUIRE(a, AGZ_E_INVALID, "arena is NULL");
+  AGZ_REQUIRE(conf && (conf->kind == AGZ_TARGET_REFERENCE || conf->kind == AGZ_TARGET_VISITS) && target_tau_ok(conf->temperature) &&
+                  conf->reserved[0] == 0 && conf->reserved[1] == 0,
+              AGZ_E_INVALID, "agz_arena_set_policy_target: kind in {0,1}, temperature finite and > 0, reserved == 0 (kind %d, temperature %g)",
+              conf ? conf->kind : -1, conf ? (double)conf->temperature : 0.0);
+  AGZ_REQUIRE(!a->in_move, AGZ_E_STATE, "agz_arena_set_policy_target: a search is in progress");
+  a->target = *conf;
+  return AGZ_OK;
+}
+int agz_arena_get_policy_target(agz_arena* a, agz_target_conf* out) {
+  AGZ_REQUIRE(a && out, AGZ_E_INVALID, "agz_arena_get_policy_target: NULL argument");
+  *out = a->target;
+  return AGZ_OK;
+}
+// The same definition without a context or a device.
+int agz_visit_target_of(const int32_t* moves, const uint32_t* visits, int n, int action_space, float temperature, float* row) {
+  AGZ_REQUIRE(moves && visits && row, AGZ_E_INVALID, "agz_visit_target_of: NULL argument");
+  AGZ_REQUIRE(n >= 1 && n <= target::MAX_N && action_space >= 1 && action_space <= target::MAX_N && target_tau_ok(temperature), AGZ_E_INVALID,
+              "agz_visit_target_of: 1 <= n, action_space <= %d, temperature finite and > 0 (n %d, action_space %d, temperature %g)", target::MAX_N, n,
+              action_space, (double)temperature);
+  std::vector<uint8_t> seen((size_t)action_space + 1, 0);
+  uint32_t nmax = 0;
+  for (int i = 0; i < n; i++) {
+    const int mv = moves[i];
+    AGZ_REQUIRE(mv == AGZ_PASS || (mv >= 0 && mv < action_space), AGZ_E_INVALID, "agz_visit_target_of: moves[%d] = %d is neither in [0, %d) nor AGZ_PASS", i, mv, action_space);
+    uint8_t& mark = seen[(size_t)target::index_of(mv, action_space)];
+    AGZ_REQUIRE(!mark, AGZ_E_INVALID, "agz_visit_target_of: move %d appears twice", mv);
+    mark = 1;
+    nmax = std::max(nmax, visits[i]);
+  }
+  AGZ_REQUIRE(nmax > 0, AGZ_E_INVALID, "agz_visit_target_of: every visit count is 0, there is no target");
+  target::row_of(moves, visits, n, action_space, (double)temperature, row);
+  return AGZ_OK;
+}
+
 int agz_arena_reset(agz_arena* a, const uint8_t* a_is_black) {
   AGZ_REQUIRE(a, AGZ_E_INVALID, "arena is NULL");
   AGZ_HIP_TRY(hipSetDevice(a->ctx->device));
@@ -2228,7 +2306,8 @@ int agz_arena_end_move(agz_arena* a, int record) {
   AGZ_HIP_TRY(hipSetDevice(a->ctx->device));
   {
     ProfScope ps(a->ctx, AGZ_PROF_MOVE);
-    hipLaunchKernelGGL(k_end_move, dim3(a->G), dim3(64), 0, a->ctx->stream, a->d, a->gc, a->mc, record, a->restart ? 1 : 0, (const int32_t*)nullptr, 0);
+    hipLaunchKernelGGL(k_end_move, dim3(a->G), dim3(64), 0, a->ctx->stream, a->d, a->gc, a->mc, record, a->restart ? 1 : 0, (const int32_t*)nullptr, 0,
+                       a->target.kind, a->target.temperature);
   }
   AGZ_HIP_TRY(hipGetLastError());
   a->in_move = false;
@@ -2246,7 +2325,7 @@ int agz_arena_apply_moves(agz_arena* a, const int32_t* moves) {
   AGZ_HIP_TRY(hipMemcpyAsync(&before, a->d.counters + CNT_ILLEGAL, 8, hipMemcpyDeviceToHost, s));
   AGZ_HIP_TRY(hipMemcpyAsync(a->d_forced, moves, (size_t)a->G * sizeof(int32_t), hipMemcpyHostToDevice, s));
   AGZ_HIP_TRY(hipStreamSynchronize(s));   // `moves` is the caller's buffer
-  hipLaunchKernelGGL(k_end_move, dim3(a->G), dim3(64), 0, s, a->d, a->gc, a->mc, 0, 0, (const int32_t*)a->d_forced, 0);
+  hipLaunchKernelGGL(k_end_move, dim3(a->G), dim3(64), 0, s, a->d, a->gc, a->mc, 0, 0, (const int32_t*)a->d_forced, 0, a->target.kind, a->target.temperature);
   AGZ_HIP_TRY(hipGetLastError());
   AGZ_HIP_TRY(hipMemcpyAsync(&after, a->d.counters + CNT_ILLEGAL, 8, hipMemcpyDeviceToHost, s));
   AGZ_HIP_TRY(hipStreamSynchronize(s));
@@ -2520,7 +2599,7 @@ int agz_arena_random_moves(agz_arena* a, const int32_t* n_moves, uint64_t seed) 
   AGZ_HIP_TRY(hipStreamSynchronize(s));   // `n_moves` is the caller's buffer
   for (int i = 0; i < most; i++) {
     hipLaunchKernelGGL(k_random_pick, dim3(a->G), dim3(64), 0, s, a->d, a->gc, a->d_remaining, (unsigned long long)seed, a->d_forced);
-    hipLaunchKernelGGL(k_end_move, dim3(a->G), dim3(64), 0, s, a->d, a->gc, a->mc, 0, 0, (const int32_t*)a->d_forced, 0);
+    hipLaunchKernelGGL(k_end_move, dim3(a->G), dim3(64), 0, s, a->d, a->gc, a->mc, 0, 0, (const int32_t*)a->d_forced, 0, a->target.kind, a->target.temperature);
   }
   AGZ_HIP_TRY(hipGetLastError());
   AGZ_HIP_TRY(hipStreamSynchronize(s));
@@ -3052,7 +3131,7 @@ int agz_mcts_search(agz_mcts* m, int player, int32_t* best) {
   }
   {
     ProfScope ps(a->ctx, AGZ_PROF_MOVE);
-    hipLaunchKernelGGL(k_end_move, dim3(1), dim3(64), 0, s, a->d, a->gc, a->mc, 0, 0, (const int32_t*)nullptr, 1);
+    hipLaunchKernelGGL(k_end_move, dim3(1), dim3(64), 0, s, a->d, a->gc, a->mc, 0, 0, (const int32_t*)nullptr, 1, AGZ_TARGET_REFERENCE, 1.0f);
   }
   a->in_move = false;
   AGZ_HIP_TRY(hipGetLastError());

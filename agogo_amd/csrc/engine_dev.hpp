@@ -17,6 +17,7 @@
 #include "../../include/agz.h"
 #include "noise.hpp"
 #include "sym.hpp"
+#include "target.hpp"
 
 namespace agz {
 

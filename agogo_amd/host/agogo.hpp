@@ -205,6 +205,12 @@ struct Arena {
     const agz_noise_conf conf = {eps, alpha, on ? 1 : 0, 0};
     agz::check(agz_arena_set_root_noise(h, &conf), "SetRootNoise");
   }
+  // build extension: the policy row of a recorded example (agz_arena_set_policy_target): AGZ_TARGET_REFERENCE (default) or AGZ_TARGET_VISITS,
+  // the root's visit distribution N(a)^(1/temperature) on every searched ply.  Not in a checkpoint: set it again after Load.
+  void SetPolicyTarget(int kind, float temperature = 1.f) {
+    const agz_target_conf conf = {kind, temperature, {0, 0}};
+    agz::check(agz_arena_set_policy_target(h, &conf), "SetPolicyTarget");
+  }
   void Opponent(const std::vector<int32_t>& moves) { agz::check(agz_arena_apply_moves(h, moves.data()), "opponent move"); }
   // Checkpoint of the running arena between two moves, and the continuation from one (agz_arena_save / agz_arena_load): games, trees, RNG
   // states, counters, examples.  The agents, the lanes and the pool policy are not in the file: set them again as they were.
@@ -300,6 +306,11 @@ struct Config {
   // = softmax cross-entropy and an MSE on tanh.  Applied with the solver options to A, B and every newB.  Like the kind in a trainer file,
   // it is not in a SaveRun file (AGZRUN01 unchanged): a resumed run trains under the Loss of the Config its AZ was constructed with.
   int Loss = AGZ_LOSS_REFERENCE;
+  // build extension: the policy row the SELF-PLAY arena records (Arena::SetPolicyTarget): AGZ_TARGET_REFERENCE (default) = the reference's
+  // Policies, AGZ_TARGET_VISITS = the root's visit distribution N(a)^(1/TargetTemperature), the target AGZ_LOSS_ALPHAZERO is meant for.  The
+  // evaluation arena records nothing.  Like Loss, neither field is in a SaveRun file (AGZRUN01 unchanged)
+  int PolicyTarget = AGZ_TARGET_REFERENCE;
+  float TargetTemperature = 1.f;
   // build extension: train from a replay window instead of one epoch's examples.  ReplayWindow = rows the window keeps across epochs; 0
   // (default) = off, AZ.Learn exactly as the reference has it.  ReplaySteps = minibatches per epoch; 0 = (live rows / BatchSize) * nniters.
   // ReplaySymmetric = every sampled row under one of the eight board symmetries, chosen per draw; the materialising augmenters
@@ -383,6 +394,7 @@ struct AZ {
         else sp.SetAgentKinds(conf.SelfPlayInferencer[0], infA.get(), conf.SelfPlayInferencer[1], infB.get());
         if (conf.LeafSymmetry != AGZ_SYM_OFF) sp.SetLeafSymmetry(conf.LeafSymmetry, seed + 1000 * epoch + 1);
         if (conf.RootNoiseEps > 0.f) sp.SetRootNoise(conf.RootNoiseEps, conf.RootNoiseAlpha);
+        if (conf.PolicyTarget != AGZ_TARGET_REFERENCE) sp.SetPolicyTarget(conf.PolicyTarget, conf.TargetTemperature);
         sp.PlayOnDevice(true);                                            // episodes x SelfPlay(), agogo.go:110-114
         ex.Append(sp);                                                     // device to device, episode after episode
       }

@@ -541,6 +541,45 @@ func RootNoiseOf(key uint64, n int, alpha float32) ([]float32, error) {
 	return eta[:n], nil
 }
 
+// Policy-target kinds of SetPolicyTarget.
+const (
+	TargetReference = int(C.AGZ_TARGET_REFERENCE)
+	TargetVisits    = int(C.AGZ_TARGET_VISITS)
+)
+
+// SetPolicyTarget chooses what this arena records as the policy row of an example (agz_arena_set_policy_target): TargetReference, the
+// reference's Policies (the default), or TargetVisits, the root's visit distribution N(a)^(1/temperature) on every searched ply, a ply
+// that chose Pass or Resign included.  Between moves.  The setting is not part of a checkpoint: set it again after Load.
+func (a *BatchedArena) SetPolicyTarget(kind int, temperature float32) error {
+	defer a.ctx.enter()()
+	conf := C.agz_target_conf{kind: C.int32_t(kind), temperature: C.float(temperature)}
+	return lastErr(C.agz_arena_set_policy_target(a.h, &conf))
+}
+
+// PolicyTarget returns the arena's policy-target setting (agz_arena_get_policy_target).
+func (a *BatchedArena) PolicyTarget() (kind int, temperature float32, err error) {
+	defer a.ctx.enter()()
+	var conf C.agz_target_conf
+	if err = lastErr(C.agz_arena_get_policy_target(a.h, &conf)); err != nil {
+		return 0, 0, err
+	}
+	return int(conf.kind), float32(conf.temperature), nil
+}
+
+// VisitTargetOf is the same definition on the host: the policy row (actionSpace+1 entries, Pass last) of root children
+// (moves[i], visits[i]) (agz_visit_target_of).
+func VisitTargetOf(moves []int32, visits []uint32, actionSpace int, temperature float32) ([]float32, error) {
+	if len(moves) != len(visits) || len(moves) == 0 || actionSpace < 1 {
+		return nil, errors.New("agzhip: VisitTargetOf needs as many moves as visits, at least one, and an action space of at least 1")
+	}
+	row := make([]float32, actionSpace+1)
+	if err := lastErr(C.agz_visit_target_of((*C.int32_t)(unsafe.Pointer(&moves[0])), (*C.uint32_t)(unsafe.Pointer(&visits[0])), C.int(len(moves)),
+		C.int(actionSpace), C.float(temperature), (*C.float)(unsafe.Pointer(&row[0])))); err != nil {
+		return nil, err
+	}
+	return row, nil
+}
+
 // Save writes a checkpoint of the running arena — games, both trees of every game, RNG states, counters, recorded examples — between two
 // moves (agz_arena_save).  The file replaces `path` only once it is complete.
 func (a *BatchedArena) Save(path string) error {

@@ -582,6 +582,36 @@ int agz_arena_root_noise(agz_arena* arena, int g, int agent, uint64_t* key, int3
 /* The same definition without a context or a device: eta[0..n) of the draw `key`.  AGZ_E_INVALID unless 1 <= n <= 4096,
  * 0 < alpha <= 1 and eta != NULL. */
 int agz_root_noise_of(uint64_t key, int n, float alpha, float* eta);
+/* BUILD EXTENSION (DESIGN.md §2 visit-target): what an arena records as the POLICY ROW of an example.  Opt-in, default
+ * AGZ_TARGET_REFERENCE; with it (or never called) everything is as without this call, bit for bit: the same launches, no allocation,
+ * no read-back.
+ *   AGZ_TARGET_REFERENCE  the reference's Policies (tree.go:128-142): normalised counts of the moves chosen at this board hash — in
+ *                         practice a one-hot row of the move played; no row on a ply that chose Pass or Resign.
+ *   AGZ_TARGET_VISITS     the root's visit distribution pi(a) ~ N(a)^(1/temperature), what AlphaZero trains on; one row on EVERY
+ *                         searched ply whose root has a visited child, a ply that chose Pass or Resign included.
+ * The kind changes the rows and how many are recorded, nothing else: the chosen move, the sort, the RNG draws, the trees, the games
+ * and agz_mcts_policies (the cachedPolicies list) are the same.  Rows are ordinary example rows (agz_arena_get_examples, checkpoints,
+ * the augmenters, the replay window and AGZ_LOSS_ALPHAZERO take any row).
+ * The definition (one copy, csrc/target.hpp; IEEE double + - * /, integer and bit operations, ln_b / exp_b of the root noise above).
+ * Children (move_i, N_i) of the root, N_i the uint32 visit count; A = the action space; tau = the double obtained from `temperature`:
+ *   Nmax      max N_i; Nmax == 0: no target (no row; agz_visit_target_of returns AGZ_E_INVALID)
+ *   w_i       64-bit integers.  tau == 1: N_i.  Otherwise 2^40 if N_i == Nmax, 0 if N_i == 0, else
+ *             (uint64)(exp_b(ln_b((double)N_i / (double)Nmax) / tau) * 2^40), truncated
+ *   S         the sum of the w_i, exact (below 2^53 for up to 4096 children): independent of the order of the children
+ *   row[idx]  (float)((double)w_i / (double)S), idx = move_i for a board move, A for AGZ_PASS; every other of the A + 1 entries +0.0f
+ * The setting is not stored in an arena checkpoint (AGZARN01 unchanged): re-apply it after agz_arena_load and the continuation is bit
+ * for bit.  The single-tree agz_mcts_* handle records nothing and keeps AGZ_TARGET_REFERENCE.
+ * AGZ_E_INVALID, with the setting unchanged, unless kind is 0 or 1, temperature is finite and > 0 and the reserved words are 0;
+ * AGZ_E_STATE inside a move. */
+#define AGZ_TARGET_REFERENCE 0
+#define AGZ_TARGET_VISITS 1
+typedef struct agz_target_conf { int32_t kind; float temperature; int32_t reserved[2]; } agz_target_conf;  /* 16 bytes; defaults 0, 1.0f */
+int agz_arena_set_policy_target(agz_arena* arena, const agz_target_conf* conf);
+int agz_arena_get_policy_target(agz_arena* arena, agz_target_conf* out);
+/* The same definition without a context or a device: row[0 .. action_space] of n children.  AGZ_E_INVALID, with row untouched, for a
+ * NULL pointer, n or action_space outside [1, 4096], a move that is neither in [0, action_space) nor AGZ_PASS, a move given twice, a
+ * temperature that is not finite and > 0, and visits that are all 0. */
+int agz_visit_target_of(const int32_t* moves, const uint32_t* visits, int n, int action_space, float temperature, float* row);
 int agz_arena_begin_move(agz_arena* arena);
 int agz_arena_simulate(agz_arena* arena, int k);
 int agz_arena_end_move(agz_arena* arena, int record);
