@@ -1,4 +1,5 @@
-// The self-play arena's checkpoint file (agz_arena_save / agz_arena_load): its byte layout and its validation, and nothing else.  Host-only:
+// The self-play arena's checkpoint file (agz_arena_save / agz_arena_load): its byte layout, its validation, and the steps its two large
+// sections are streamed in (node_chunks, example_chunks), and nothing else.  Host-only:
 // include/agz.h and the standard library, so tests/cpp/arena_ckpt_check.cpp checks this very code under g++ (tests/test_arena_ckpt_cpu.py).
 // engine.hip describes an arena as a Shape, hands the small state over as whole arrays (Small) and the two large sections — the trees' nodes
 // and the example rows — as ranges of their per-field runs; it knows nothing of the bytes.
@@ -133,6 +134,47 @@ inline Layout layout(const Shape& h, const Small& s) {
   l.end_off = o;
   l.total = o + 16;
   return l;
+}
+
+// ---- the steps the two large sections are streamed in (engine.hip, through ckpt_stream.hpp's pump) ------------------------------------
+// one step: nodes [a, b) of the file's order (trees t0 .. t0 + nt - 1), or bytes [a, b) of example run `field`
+struct Chunk { int field; uint64_t a, b; int t0, nt; };   // field < 0: nodes
+// a chunk of cnt nodes takes 20 * cnt + 4 bytes of staging: six runs, every run on a 4-byte boundary
+inline uint64_t chunk_nodes(uint64_t staging_bytes) { return (staging_bytes - 4) / 20; }
+// the staging a save or load takes: what the caller allows, no more than the larger section needs, no less than 64 bytes
+inline uint64_t staging_bytes(const Shape& h, const Layout& l, uint64_t allowed) {
+  uint64_t es[EX_FIELDS], ex_most = 0;
+  ex_sizes(h, es);
+  for (uint64_t e : es) ex_most = std::max(ex_most, l.examples * e);
+  return std::max<uint64_t>(std::min<uint64_t>(allowed, std::max<uint64_t>(l.nodes * 20 + 4, ex_most)), 64);
+}
+// the node section: whole trees while they fit the staging buffer; a tree that does not fit alone is cut by node range
+inline std::vector<Chunk> node_chunks(const Layout& l, uint64_t staging) {
+  std::vector<Chunk> out;
+  const std::vector<uint64_t>& f = l.tree_first;
+  const uint64_t capn = chunk_nodes(staging);
+  const int T = (int)f.size() - 1;
+  for (uint64_t n0 = 0; n0 < l.nodes;) {
+    const int t0 = (int)(std::upper_bound(f.begin(), f.end(), n0) - f.begin()) - 1;   // the tree that holds node n0 (empty trees before it skipped)
+    uint64_t n1 = std::min(n0 + capn, l.nodes);
+    int t1 = (int)(std::upper_bound(f.begin(), f.end(), n1) - f.begin()) - 1;          // largest t with first[t] <= n1
+    if (t1 > t0 + 65535) t1 = t0 + 65535;                                                // (a launch's grid holds so many trees)
+    if (f[t1] > n0) n1 = f[t1];                                                          // end on a tree boundary when one lies inside
+    const int last = (int)(std::lower_bound(f.begin(), f.end(), n1) - f.begin()) - 1;    // the tree that holds node n1 - 1
+    out.push_back({-1, n0, n1, t0, std::min(last, T - 1) - t0 + 1});
+    n0 = n1;
+  }
+  return out;
+}
+// the example section: run by run, in steps of the staging buffer rounded down to 16 bytes
+inline std::vector<Chunk> example_chunks(const Shape& h, const Layout& l, uint64_t staging) {
+  std::vector<Chunk> out;
+  uint64_t es[EX_FIELDS];
+  ex_sizes(h, es);
+  const uint64_t step = staging & ~(uint64_t)15;
+  for (int k = 0; k < EX_FIELDS; k++)
+    for (uint64_t a = 0; a < l.examples * es[k]; a += step) out.push_back({k, a, std::min(a + step, l.examples * es[k]), 0, 0});
+  return out;
 }
 
 // ---- validation of the small state (no file needed).  Returns "" or what is wrong. ----------------------------------------------------

@@ -25,9 +25,9 @@
 #include <string>
 #include <vector>
 
-#include <unistd.h>
-
 #include "arena_ckpt.hpp"
+#include "atomic_file.hpp"
+#include "ckpt_stream.hpp"
 #include "engine_dev.hpp"
 #include "net.hpp"
 
@@ -2657,12 +2657,12 @@ int agz_arena_set_state(agz_arena* a, int g, const agz_state* st) {
 }  // extern "C"
 
 // ---- arena checkpoints (agz_arena_save / agz_arena_load) ------------------------------------------------------------------------------
-// The bytes are arena_ckpt.hpp's; this side describes the arena, moves the small state as whole arrays, and streams the two large
-// sections through ONE device staging buffer and TWO page-locked host buffers of ckpt_staging bytes each: the copy of chunk i + 1 between
-// device and host runs while the file system has chunk i.  The trees' nodes lie [T][2][cap]; what is live at a move boundary is the prefix
-// [0, n_nodes[t]) of pool cur_pool[t], so k_ckpt_pack gathers those prefixes into per-field runs (the file's node order: tree by tree)
-// and k_ckpt_unpack scatters them back at the loading arena's own stride.  A chunk is a range of whole trees; a tree larger than the
-// staging buffer is cut by node range.  Example rows are contiguous already and take the same double buffer without a kernel.
+// The bytes are arena_ckpt.hpp's, and so are the chunks (node_chunks, example_chunks); this side describes the arena, moves the small state
+// as whole arrays, and streams the two large sections through ckpt_stream.hpp's pump (stream_out, stream_in) with buffers of ckpt_staging
+// bytes.  The trees' nodes lie [T][2][cap]; what is live at a move boundary is the prefix [0, n_nodes[t]) of pool cur_pool[t], so
+// k_ckpt_pack gathers those prefixes into per-field runs (the file's node order: tree by tree) and k_ckpt_unpack scatters them back at the
+// loading arena's own stride.  A chunk is a range of whole trees; a tree larger than the staging buffer is cut by node range.  Example
+// rows are contiguous already and take the same pump without a kernel.  The file itself is atomic_file.hpp's: whole, or the previous one.
 // Nothing here is on the step path: no existing kernel and no existing field of Dev changes.
 namespace agz {
 
@@ -2673,7 +2673,6 @@ __host__ __device__ inline CkptRuns ckpt_runs(void* staging, size_t cnt) {
   const size_t even = (cnt + 1) & ~(size_t)1;
   return {(float*)p, (uint32_t*)(p + 4 * cnt), (float*)(p + 8 * cnt), (int32_t*)(p + 12 * cnt), (int16_t*)(p + 16 * cnt), (int16_t*)(p + 16 * cnt + 2 * even)};
 }
-inline size_t ckpt_chunk_nodes(size_t staging_bytes) { return (staging_bytes - 4) / 20; }
 
 // n 16-bit words, src -> dst, by threads tid, tid + nth, ...  A tree's run may start at an odd element on either side; the body is written as
 // aligned 32-bit words of the DESTINATION (one full-width store per lane instead of a half-width one), the odd element at either end alone.
@@ -2719,59 +2718,13 @@ __global__ __launch_bounds__(256) void k_ckpt_unpack(Dev d, const long long* __r
   ckpt_move<false>(d, first, t0, n0, n1, staging);
 }
 
-// the staging of one save or load; released (after the queue has drained) when the call returns, whatever happened
-struct CkptStaging {
-  hipStream_t s = nullptr;
-  void* dev = nullptr;
-  void* host[2] = {nullptr, nullptr};
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  long long* first = nullptr;   // device copy of the node prefix sums
-  size_t bytes = 0;
-  int init(hipStream_t stream, size_t want, const std::vector<uint64_t>& tree_first) {
-    s = stream; bytes = want;
-    AGZ_HIP_TRY(hipMalloc(&dev, bytes));
-    for (int i = 0; i < 2; i++) { AGZ_HIP_TRY(hipHostMalloc(&host[i], bytes, hipHostMallocDefault)); AGZ_HIP_TRY(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming)); }
-    AGZ_HIP_TRY(hipMalloc(&first, tree_first.size() * 8));
-    AGZ_HIP_TRY(hipMemcpyAsync(first, tree_first.data(), tree_first.size() * 8, hipMemcpyHostToDevice, s));
-    AGZ_HIP_TRY(hipStreamSynchronize(s));
-    return AGZ_OK;
-  }
-  ~CkptStaging() {
-    if (s) hipStreamSynchronize(s);
-    if (dev) hipFree(dev);
-    if (first) hipFree(first);
-    for (int i = 0; i < 2; i++) { if (host[i]) hipHostFree(host[i]); if (ev[i]) hipEventDestroy(ev[i]); }
-  }
-};
-
-// one step of a section: nodes [a, b) of the file's order (trees t0 .. t0 + nt - 1), or bytes [a, b) of example run `field`
-struct CkptChunk { int field; uint64_t a, b; int t0, nt; };   // field < 0: nodes
-
-// whole trees while they fit the staging buffer; a tree that does not fit alone is cut by node range
-static std::vector<CkptChunk> ckpt_chunks(const arena_ckpt::Shape& h, const arena_ckpt::Layout& l, size_t staging, bool nodes) {
-  std::vector<CkptChunk> out;
-  if (nodes) {
-    const std::vector<uint64_t>& f = l.tree_first;
-    const uint64_t capn = ckpt_chunk_nodes(staging);
-    const int T = (int)f.size() - 1;
-    for (uint64_t n0 = 0; n0 < l.nodes;) {
-      const int t0 = (int)(std::upper_bound(f.begin(), f.end(), n0) - f.begin()) - 1;   // the tree that holds node n0 (empty trees before it skipped)
-      uint64_t n1 = std::min(n0 + capn, l.nodes);
-      int t1 = (int)(std::upper_bound(f.begin(), f.end(), n1) - f.begin()) - 1;          // largest t with first[t] <= n1
-      if (t1 > t0 + 65535) t1 = t0 + 65535;                                                // (a launch's grid holds so many trees)
-      if (f[t1] > n0) n1 = f[t1];                                                          // end on a tree boundary when one lies inside
-      const int last = (int)(std::lower_bound(f.begin(), f.end(), n1) - f.begin()) - 1;    // the tree that holds node n1 - 1
-      out.push_back({-1, n0, n1, t0, std::min(last, T - 1) - t0 + 1});
-      n0 = n1;
-    }
-  } else {
-    uint64_t es[arena_ckpt::EX_FIELDS];
-    arena_ckpt::ex_sizes(h, es);
-    const uint64_t step = staging & ~(uint64_t)15;
-    for (int k = 0; k < arena_ckpt::EX_FIELDS; k++)
-      for (uint64_t a = 0; a < l.examples * es[k]; a += step) out.push_back({k, a, std::min(a + step, l.examples * es[k]), 0, 0});
-  }
-  return out;
+// k_ckpt_pack or k_ckpt_unpack on the nodes of chunk c
+template <class K>
+int ckpt_launch(K kernel, hipStream_t s, const Dev& d, const void* first, const arena_ckpt::Chunk& c, void* staging) {
+  const size_t cnt = (size_t)(c.b - c.a);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)std::min<size_t>(64, (cnt + 255) / 256), (unsigned)c.nt), dim3(256), 0, s, d, (const long long*)first, c.t0, (long long)c.a, (long long)c.b, staging);
+  AGZ_HIP_TRY(hipGetLastError());
+  return AGZ_OK;
 }
 
 }  // namespace agz
@@ -2798,46 +2751,32 @@ int agz_arena::ckpt_small(Sm& sm, Fn xfer) {
 // everything behind the head: nodes, counters, examples, end marker.  AGZ_E_INVALID: the file system refused a write.
 int agz_arena::ckpt_write(FILE* f, const arena_ckpt::Shape& h, const arena_ckpt::Small& sm, const arena_ckpt::Layout& l) {
   hipStream_t s = ctx->stream;
-  uint64_t es[arena_ckpt::EX_FIELDS], ex_most = 0;
-  arena_ckpt::ex_sizes(h, es);
-  for (uint64_t e : es) ex_most = std::max(ex_most, l.examples * e);
-  const size_t staging = (size_t)std::max<uint64_t>(std::min<uint64_t>(ckpt_staging, std::max<uint64_t>(l.nodes * 20 + 4, ex_most)), 64);
+  const size_t staging = (size_t)arena_ckpt::staging_bytes(h, l, ckpt_staging);
   CkptStaging st;
-  int r = st.init(s, staging, l.tree_first);
-  if (r != AGZ_OK) return r;
-  const char* ex_base[arena_ckpt::EX_FIELDS] = {(const char*)d.ex_planes, (const char*)d.ex_policy, (const char*)d.ex_value, (const char*)d.ex_game, (const char*)d.ex_prev, (const char*)d.ex_labelled};
-  for (int section = 0; section < 2; section++) {
-    const std::vector<CkptChunk> ch = ckpt_chunks(h, l, staging, section == 0);
-    auto issue = [&](size_t i) -> int {   // chunk i -> host[i & 1], asynchronously
-      const CkptChunk& c = ch[i];
-      if (c.field < 0) {
-        const size_t cnt = (size_t)(c.b - c.a);
-        hipLaunchKernelGGL(k_ckpt_pack, dim3((unsigned)std::min<size_t>(64, (cnt + 255) / 256), (unsigned)c.nt), dim3(256), 0, s, d, (const long long*)st.first, c.t0, (long long)c.a, (long long)c.b, st.dev);
-        AGZ_HIP_TRY(hipGetLastError());
-        AGZ_HIP_TRY(hipMemcpyAsync(st.host[i & 1], st.dev, 20 * cnt + 4, hipMemcpyDeviceToHost, s));
-      } else {
-        AGZ_HIP_TRY(hipMemcpyAsync(st.host[i & 1], ex_base[c.field] + c.a, (size_t)(c.b - c.a), hipMemcpyDeviceToHost, s));
-      }
-      AGZ_HIP_TRY(hipEventRecord(st.ev[i & 1], s));
+  CkptScratch first;   // device copy of the node prefix sums
+  int r;
+  if ((r = st.init(s, staging, true)) != AGZ_OK || (r = first.init(s, l.tree_first.size() * 8, l.tree_first.data())) != AGZ_OK) return r;
+  const std::vector<arena_ckpt::Chunk> nodes = arena_ckpt::node_chunks(l, staging), rows = arena_ckpt::example_chunks(h, l, staging);
+  r = stream_out(st, nodes.size(),
+    [&](size_t i, void* host) -> int {
+      const int launched = ckpt_launch(k_ckpt_pack, s, d, first.p, nodes[i], st.dev);
+      if (launched != AGZ_OK) return launched;
+      AGZ_HIP_TRY(hipMemcpyAsync(host, st.dev, 20 * (size_t)(nodes[i].b - nodes[i].a) + 4, hipMemcpyDeviceToHost, s));
       return AGZ_OK;
-    };
-    if (!ch.empty() && (r = issue(0)) != AGZ_OK) return r;
-    for (size_t i = 0; i < ch.size(); i++) {
-      if (i + 1 < ch.size() && (r = issue(i + 1)) != AGZ_OK) return r;   // the next chunk's copy runs under this chunk's write
-      AGZ_HIP_TRY(hipEventSynchronize(st.ev[i & 1]));
-      const CkptChunk& c = ch[i];
-      bool ok;
-      if (c.field < 0) {
-        const CkptRuns q = ckpt_runs(st.host[i & 1], (size_t)(c.b - c.a));
-        const void* runs[arena_ckpt::NODE_FIELDS] = {q.prior, q.visits, q.bsum, q.kids_off, q.kids_n, q.nmove};
-        ok = arena_ckpt::write_nodes(f, l, c.a, c.b - c.a, runs);
-      } else {
-        ok = arena_ckpt::write_examples(f, l, c.field, c.a, c.b - c.a, st.host[i & 1]);
-      }
-      AGZ_REQUIRE(ok, AGZ_E_INVALID, "agz_arena_save: write failed");
-    }
-    if (section == 0) AGZ_REQUIRE(arena_ckpt::write_counters(f, l, sm), AGZ_E_INVALID, "agz_arena_save: write failed");
-  }
+    },
+    [&](size_t i, void* host) -> int {
+      const CkptRuns q = ckpt_runs(host, (size_t)(nodes[i].b - nodes[i].a));
+      const void* runs[arena_ckpt::NODE_FIELDS] = {q.prior, q.visits, q.bsum, q.kids_off, q.kids_n, q.nmove};
+      AGZ_REQUIRE(arena_ckpt::write_nodes(f, l, nodes[i].a, nodes[i].b - nodes[i].a, runs), AGZ_E_INVALID, "agz_arena_save: write failed");
+      return AGZ_OK;
+    });
+  if (r != AGZ_OK) return r;
+  AGZ_REQUIRE(arena_ckpt::write_counters(f, l, sm), AGZ_E_INVALID, "agz_arena_save: write failed");
+  const char* ex_base[arena_ckpt::EX_FIELDS] = {(const char*)d.ex_planes, (const char*)d.ex_policy, (const char*)d.ex_value, (const char*)d.ex_game, (const char*)d.ex_prev, (const char*)d.ex_labelled};
+  r = stream_out(st, rows.size(),
+    [&](size_t i, void* host) -> int { AGZ_HIP_TRY(hipMemcpyAsync(host, ex_base[rows[i].field] + rows[i].a, (size_t)(rows[i].b - rows[i].a), hipMemcpyDeviceToHost, s)); return AGZ_OK; },
+    [&](size_t i, void* host) -> int { AGZ_REQUIRE(arena_ckpt::write_examples(f, l, rows[i].field, rows[i].a, rows[i].b - rows[i].a, host), AGZ_E_INVALID, "agz_arena_save: write failed"); return AGZ_OK; });
+  if (r != AGZ_OK) return r;
   AGZ_REQUIRE(arena_ckpt::write_end(f, l), AGZ_E_INVALID, "agz_arena_save: write failed");
   return AGZ_OK;
 }
@@ -2860,34 +2799,30 @@ int agz_arena::ckpt_apply(FILE* f, const arena_ckpt::Scan& sc) {
   // virtual-loss flags are not in the file: every round clears what it set, so they are all clear at a move boundary
   AGZ_HIP_TRY(hipMemsetAsync(d.vl, 0, (size_t)d.T * 2 * (size_t)d.cap, s));
   AGZ_HIP_TRY(hipStreamSynchronize(s));
-  uint64_t es[arena_ckpt::EX_FIELDS], ex_most = 0;
-  arena_ckpt::ex_sizes(h, es);
-  for (uint64_t e : es) ex_most = std::max(ex_most, l.examples * e);
-  const size_t staging = (size_t)std::max<uint64_t>(std::min<uint64_t>(ckpt_staging, std::max<uint64_t>(l.nodes * 20 + 4, ex_most)), 64);
+  const size_t staging = (size_t)arena_ckpt::staging_bytes(h, l, ckpt_staging);
   CkptStaging st;
-  if ((r = st.init(s, staging, l.tree_first)) != AGZ_OK) return r;
+  CkptScratch first;   // device copy of the node prefix sums
+  if ((r = st.init(s, staging, true)) != AGZ_OK || (r = first.init(s, l.tree_first.size() * 8, l.tree_first.data())) != AGZ_OK) return r;
+  const std::vector<arena_ckpt::Chunk> nodes = arena_ckpt::node_chunks(l, staging), rows = arena_ckpt::example_chunks(h, l, staging);
+  r = stream_in(st, nodes.size(),
+    [&](size_t i, void* host) -> int {
+      const size_t cnt = (size_t)(nodes[i].b - nodes[i].a);
+      const CkptRuns q = ckpt_runs(host, cnt);
+      void* runs[arena_ckpt::NODE_FIELDS] = {q.prior, q.visits, q.bsum, q.kids_off, q.kids_n, q.nmove};
+      AGZ_REQUIRE(arena_ckpt::read_nodes(f, l, nodes[i].a, cnt, runs), AGZ_E_INVALID, "agz_arena_load: reading the nodes failed");
+      return AGZ_OK;
+    },
+    [&](size_t i, void* host) -> int { AGZ_HIP_TRY(hipMemcpyAsync(st.dev, host, 20 * (size_t)(nodes[i].b - nodes[i].a) + 4, hipMemcpyHostToDevice, s)); return AGZ_OK; },
+    [&](size_t i) -> int { return ckpt_launch(k_ckpt_unpack, s, d, first.p, nodes[i], st.dev); });
+  if (r != AGZ_OK) return r;
+  AGZ_HIP_TRY(hipStreamSynchronize(s));
   char* ex_base[arena_ckpt::EX_FIELDS] = {(char*)d.ex_planes, (char*)d.ex_policy, (char*)d.ex_value, (char*)d.ex_game, (char*)d.ex_prev, (char*)d.ex_labelled};
-  for (int section = 0; section < 2; section++) {
-    const std::vector<CkptChunk> ch = ckpt_chunks(h, l, staging, section == 0);
-    for (size_t i = 0; i < ch.size(); i++) {   // the file read of chunk i runs under the copy and scatter of chunk i - 1
-      const CkptChunk& c = ch[i];
-      if (i >= 2) AGZ_HIP_TRY(hipEventSynchronize(st.ev[i & 1]));   // host[i & 1] has left for the device
-      if (c.field < 0) {
-        const size_t cnt = (size_t)(c.b - c.a);
-        const CkptRuns q = ckpt_runs(st.host[i & 1], cnt);
-        void* runs[arena_ckpt::NODE_FIELDS] = {q.prior, q.visits, q.bsum, q.kids_off, q.kids_n, q.nmove};
-        AGZ_REQUIRE(arena_ckpt::read_nodes(f, l, c.a, cnt, runs), AGZ_E_INVALID, "agz_arena_load: reading the nodes failed");
-        AGZ_HIP_TRY(hipMemcpyAsync(st.dev, st.host[i & 1], 20 * cnt + 4, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_ckpt_unpack, dim3((unsigned)std::min<size_t>(64, (cnt + 255) / 256), (unsigned)c.nt), dim3(256), 0, s, d, (const long long*)st.first, c.t0, (long long)c.a, (long long)c.b, st.dev);
-        AGZ_HIP_TRY(hipGetLastError());
-      } else {
-        AGZ_REQUIRE(arena_ckpt::read_examples(f, l, c.field, c.a, c.b - c.a, st.host[i & 1]), AGZ_E_INVALID, "agz_arena_load: reading the examples failed");
-        AGZ_HIP_TRY(hipMemcpyAsync(ex_base[c.field] + c.a, st.host[i & 1], (size_t)(c.b - c.a), hipMemcpyHostToDevice, s));
-      }
-      AGZ_HIP_TRY(hipEventRecord(st.ev[i & 1], s));
-    }
-    AGZ_HIP_TRY(hipStreamSynchronize(s));
-  }
+  r = stream_in(st, rows.size(),
+    [&](size_t i, void* host) -> int { AGZ_REQUIRE(arena_ckpt::read_examples(f, l, rows[i].field, rows[i].a, rows[i].b - rows[i].a, host), AGZ_E_INVALID, "agz_arena_load: reading the examples failed"); return AGZ_OK; },
+    [&](size_t i, void* host) -> int { AGZ_HIP_TRY(hipMemcpyAsync(ex_base[rows[i].field] + rows[i].a, host, (size_t)(rows[i].b - rows[i].a), hipMemcpyHostToDevice, s)); return AGZ_OK; },
+    [](size_t) -> int { return AGZ_OK; });
+  if (r != AGZ_OK) return r;
+  AGZ_HIP_TRY(hipStreamSynchronize(s));
   seed = sc.host.seed; seed0 = sc.host.seed0; prep_expand_seen = sc.host.prep_expand_seen; moves_done = sc.host.moves_done; restart = sc.host.restart != 0;
   for (int g = 0; g < G; g++) a_is_black[g] = (uint8_t)sm.a_is_black[g];
   in_move = false; sims_this_move = 0; room_sims = 0;
@@ -2924,18 +2859,14 @@ int agz_arena_save(agz_arena* a, const char* path) {
   const std::string why = arena_ckpt::check_small(h, sm);
   AGZ_REQUIRE(why.empty(), AGZ_E_STATE, "agz_arena_save: the arena is in a state a checkpoint cannot hold (%s)", why.c_str());
   const arena_ckpt::Layout l = arena_ckpt::layout(h, sm);
-  const std::string tmp = std::string(path) + ".tmp";
-  FILE* f = fopen(tmp.c_str(), "wb");
-  AGZ_REQUIRE(f, AGZ_E_INVALID, "agz_arena_save: cannot open %s", tmp.c_str());
-  r = AGZ_OK;
-  if (!arena_ckpt::write_head(f, h, host, sm, l)) { agz::set_error("agz_arena_save: write to %s failed", tmp.c_str()); r = AGZ_E_INVALID; }
-  if (r == AGZ_OK) r = a->ckpt_write(f, h, sm, l);
-  const bool flushed = fflush(f) == 0 && fsync(fileno(f)) == 0;
-  const bool closed = fclose(f) == 0;
-  if (r == AGZ_OK && !(flushed && closed)) { agz::set_error("agz_arena_save: write to %s failed", tmp.c_str()); r = AGZ_E_INVALID; }
-  if (r == AGZ_OK && rename(tmp.c_str(), path) != 0) { agz::set_error("agz_arena_save: cannot rename %s to %s", tmp.c_str(), path); r = AGZ_E_INVALID; }
-  if (r != AGZ_OK) remove(tmp.c_str());
-  return r;
+  AtomicFile out(path);
+  AGZ_REQUIRE(out.f, AGZ_E_INVALID, "agz_arena_save: cannot open %s", out.tmp.c_str());
+  AGZ_REQUIRE(arena_ckpt::write_head(out.f, h, host, sm, l), AGZ_E_INVALID, "agz_arena_save: write to %s failed", out.tmp.c_str());
+  if ((r = a->ckpt_write(out.f, h, sm, l)) != AGZ_OK) return r;
+  const AtomicFile::End end = out.commit();
+  AGZ_REQUIRE(end != AtomicFile::WRITE_FAILED, AGZ_E_INVALID, "agz_arena_save: write to %s failed", out.tmp.c_str());
+  AGZ_REQUIRE(end != AtomicFile::RENAME_FAILED, AGZ_E_INVALID, "agz_arena_save: cannot rename %s to %s", out.tmp.c_str(), path);
+  return AGZ_OK;
 }
 
 int agz_arena_load(agz_arena* a, const char* path) {

@@ -9,12 +9,12 @@
 #include <string>
 #include <vector>
 
-#include <unistd.h>
-
 #include "replay_win.hpp"   // (hip_runtime.h first: replay.hpp's device half uses __umul64hi)
 #include "replay.hpp"
 #include "replay_pack.hpp"
 #include "replay_ckpt.hpp"
+#include "atomic_file.hpp"
+#include "ckpt_stream.hpp"
 #include "sym.hpp"
 
 namespace agz {
@@ -776,54 +776,11 @@ int agz_replay_draw(uint64_t seed, uint64_t step, int rows, int64_t n, int symme
 }  // extern "C"
 
 // ---- checkpoints (agz_replay_save / agz_replay_load) ----------------------------------------------------------------------------------
-// The bytes are replay_ckpt.hpp's; this side describes the window and streams its three arrays through TWO page-locked host buffers of
-// ckpt_staging bytes each (and, on a load, ONE device staging buffer): the copy of chunk i + 1 between device and host runs while the file
-// system has chunk i.  A chunk is a range of logical rows of one array; a logical range is at most two contiguous slot ranges
-// (replay::slot), so a save needs no kernel.  A load reads the file twice: k_replay_ckpt_scan sees every chunk in the staging buffer
-// first and nothing of the ring is touched until the whole file has passed; only then is it streamed again, into the ring.
-namespace {
-
-struct CkptStaging {
-  hipStream_t s = nullptr;
-  void* dev = nullptr;
-  void* host[2] = {nullptr, nullptr};
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  unsigned long long* acc = nullptr;   // the scan's sum, bad count, first bad index
-  int init(hipStream_t stream, size_t bytes, bool device) {
-    s = stream;
-    for (int i = 0; i < 2; i++) { AGZ_HIP_TRY(hipHostMalloc(&host[i], bytes, hipHostMallocDefault)); AGZ_HIP_TRY(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming)); }
-    if (device) { AGZ_HIP_TRY(hipMalloc(&dev, bytes)); AGZ_HIP_TRY(hipMalloc(&acc, 3 * sizeof(unsigned long long))); }
-    return AGZ_OK;
-  }
-  ~CkptStaging() {   // released (after the queue has drained) when the call returns, whatever happened
-    if (s) hipStreamSynchronize(s);
-    if (dev) hipFree(dev);
-    if (acc) hipFree(acc);
-    for (int i = 0; i < 2; i++) { if (host[i]) hipHostFree(host[i]); if (ev[i]) hipEventDestroy(ev[i]); }
-  }
-};
-
-struct CkptChunk { int k; uint64_t j0, cnt; };   // rows [j0, j0 + cnt) of array k, in the file's logical order
-
-constexpr uint64_t CKPT_MAX_ROWS = 1u << 30;   // of one chunk: the kernels count a chunk's rows in an int
-
-// rows [from, to) of the three arrays in file order, each cut into chunks of as many whole rows as `staging` bytes hold (at least one);
-// *bytes = the largest chunk
-std::vector<CkptChunk> ckpt_chunks(const replay_ckpt::Layout& l, uint64_t from, uint64_t to, size_t staging, size_t* bytes) {
-  std::vector<CkptChunk> out;
-  *bytes = 64;
-  for (int k = 0; k < replay_ckpt::ARRAYS; k++) {
-    const uint64_t rows = std::min(std::max<uint64_t>(1, staging / l.row_bytes[k]), CKPT_MAX_ROWS);
-    for (uint64_t j = from; j < to; j += rows) {
-      out.push_back({k, j, std::min(rows, to - j)});
-      *bytes = std::max<size_t>(*bytes, (size_t)(out.back().cnt * l.row_bytes[k]));
-    }
-  }
-  return out;
-}
-
-}  // namespace
-
+// The bytes are replay_ckpt.hpp's, and so are the chunks (row_chunks); this side describes the window and streams its three arrays
+// through ckpt_stream.hpp's pump (stream_out, stream_in) with buffers of ckpt_staging bytes.  A chunk is a range of logical rows of one
+// array; a logical range is at most two contiguous slot ranges (replay::slot), so a save needs no kernel and no device buffer.  A load
+// reads the file twice: k_replay_ckpt_scan sees every chunk in the staging buffer first and nothing of the ring is touched until the whole
+// file has passed; only then is it streamed again, into the ring.  The file itself is atomic_file.hpp's: whole, or the previous one.
 replay_ckpt::Header agz_replay::ckpt_header() const {
   replay_ckpt::Header h{};
   h.F = (uint32_t)F; h.H = (uint32_t)H; h.W = (uint32_t)W; h.A1 = (uint32_t)A1;
@@ -845,26 +802,22 @@ char* agz_replay::ckpt_array(int k) const {
 // the three arrays and the end mark behind a written head.  AGZ_E_INVALID: the file system refused a write.
 int agz_replay::ckpt_write(FILE* f, const replay_ckpt::Layout& l) {
   hipStream_t s = ctx->stream;
-  size_t bytes = 0;
-  const std::vector<CkptChunk> ch = ckpt_chunks(l, 0, live(), ckpt_staging, &bytes);
+  std::vector<replay_ckpt::Chunk> ch;
+  const size_t bytes = (size_t)replay_ckpt::row_chunks(l, 0, live(), ckpt_staging, [&](const replay_ckpt::Chunk& c) { ch.push_back(c); });
   CkptStaging st;
   int r = st.init(s, bytes, false);
   if (r != AGZ_OK) return r;
-  auto issue = [&](size_t i) -> int {   // chunk i -> host[i & 1], asynchronously: the one or two slot ranges of its rows
-    const CkptChunk& c = ch[i];
-    const uint64_t rb = l.row_bytes[c.k], s0 = replay::slot(ring_total(), cap, c.j0), first = std::min(c.cnt, cap - s0);
-    char* to = (char*)st.host[i & 1];
-    AGZ_HIP_TRY(hipMemcpyAsync(to, ckpt_array(c.k) + s0 * rb, first * rb, hipMemcpyDeviceToHost, s));
-    if (c.cnt > first) AGZ_HIP_TRY(hipMemcpyAsync(to + first * rb, ckpt_array(c.k), (c.cnt - first) * rb, hipMemcpyDeviceToHost, s));
-    AGZ_HIP_TRY(hipEventRecord(st.ev[i & 1], s));
-    return AGZ_OK;
-  };
-  if (!ch.empty() && (r = issue(0)) != AGZ_OK) return r;
-  for (size_t i = 0; i < ch.size(); i++) {
-    if (i + 1 < ch.size() && (r = issue(i + 1)) != AGZ_OK) return r;   // the next chunk's copy runs under this chunk's write
-    AGZ_HIP_TRY(hipEventSynchronize(st.ev[i & 1]));
-    AGZ_REQUIRE(replay_ckpt::write_rows(f, l, ch[i].k, ch[i].j0, ch[i].cnt, st.host[i & 1]), AGZ_E_INVALID, "agz_replay_save: write failed");
-  }
+  r = stream_out(st, ch.size(),
+    [&](size_t i, void* host) -> int {   // the one or two slot ranges of the chunk's rows
+      const replay_ckpt::Chunk& c = ch[i];
+      const uint64_t rb = l.row_bytes[c.k], s0 = replay::slot(ring_total(), cap, c.j0), first = std::min(c.cnt, cap - s0);
+      char* to = (char*)host;
+      AGZ_HIP_TRY(hipMemcpyAsync(to, ckpt_array(c.k) + s0 * rb, first * rb, hipMemcpyDeviceToHost, s));
+      if (c.cnt > first) AGZ_HIP_TRY(hipMemcpyAsync(to + first * rb, ckpt_array(c.k), (c.cnt - first) * rb, hipMemcpyDeviceToHost, s));
+      return AGZ_OK;
+    },
+    [&](size_t i, void* host) -> int { AGZ_REQUIRE(replay_ckpt::write_rows(f, l, ch[i].k, ch[i].j0, ch[i].cnt, host), AGZ_E_INVALID, "agz_replay_save: write failed"); return AGZ_OK; });
+  if (r != AGZ_OK) return r;
   AGZ_REQUIRE(replay_ckpt::write_end(f, l), AGZ_E_INVALID, "agz_replay_save: write failed");
   return AGZ_OK;
 }
@@ -893,53 +846,63 @@ int agz_replay::ckpt_read(FILE* f, const char* path, const replay_ckpt::Header& 
   // a file that fills this window (keep == min(total, cap)) lies as its appends laid it, row number g in slot g mod cap; one that does not
   // starts the ring anew at its oldest row
   const uint64_t new_base = keep == replay::live(h.total, cap) ? 0 : h.total - keep;
-  size_t bytes = 0;
-  const std::vector<CkptChunk> ch = ckpt_chunks(l, skip, h.live, ckpt_staging, &bytes);
+  std::vector<replay_ckpt::Chunk> ch;
+  const size_t bytes = (size_t)replay_ckpt::row_chunks(l, skip, h.live, ckpt_staging, [&](const replay_ckpt::Chunk& c) { ch.push_back(c); });
   CkptStaging st;
-  int r = st.init(s, bytes, true);
-  if (r != AGZ_OK) return r;
+  CkptScratch acc_mem;   // the scan's sum, bad count, first bad index
+  int r;
+  if ((r = st.init(s, bytes, true)) != AGZ_OK || (r = acc_mem.init(s, 3 * sizeof(unsigned long long))) != AGZ_OK) return r;
+  unsigned long long* acc = static_cast<unsigned long long*>(acc_mem.p);
   if (!commit) {
-    AGZ_HIP_TRY(hipMemsetAsync(st.acc, 0, 16, s));
-    AGZ_HIP_TRY(hipMemsetAsync(st.acc + 2, 0xFF, 8, s));   // PACK_NONE
+    AGZ_HIP_TRY(hipMemsetAsync(acc, 0, 16, s));
+    AGZ_HIP_TRY(hipMemsetAsync(acc + 2, 0xFF, 8, s));   // PACK_NONE
   }
-  for (size_t i = 0; i < ch.size(); i++) {   // the file read of chunk i runs under the copy and the kernel of chunk i - 1
-    const CkptChunk& c = ch[i];
-    const uint64_t rb = l.row_bytes[c.k];
-    if (i >= 2) AGZ_HIP_TRY(hipEventSynchronize(st.ev[i & 1]));   // host[i & 1] has left for the device
-    char* from = (char*)st.host[i & 1];
-    AGZ_REQUIRE(replay_ckpt::read_rows(f, l, c.k, c.j0, c.cnt, from), AGZ_E_INVALID, "agz_replay_load: reading %s failed", path);
-    const bool planes_k = c.k == replay_ckpt::PLANES;
-    const uint64_t slot0 = (h.total - h.live + c.j0 - new_base) % cap;   // (commit) the slot the append of this row wrote, or would have
-    if (commit && (!planes_k || same_planes)) {               // a plain copy into the one or two slot ranges
-      const uint64_t first = std::min(c.cnt, cap - slot0);
-      AGZ_HIP_TRY(hipMemcpyAsync(ckpt_array(c.k) + slot0 * rb, from, first * rb, hipMemcpyHostToDevice, s));
-      if (c.cnt > first) AGZ_HIP_TRY(hipMemcpyAsync(ckpt_array(c.k), from + first * rb, (c.cnt - first) * rb, hipMemcpyHostToDevice, s));
-      AGZ_HIP_TRY(hipEventRecord(st.ev[i & 1], s));
-      continue;
-    }
-    AGZ_HIP_TRY(hipMemcpyAsync(st.dev, from, c.cnt * rb, hipMemcpyHostToDevice, s));
-    AGZ_HIP_TRY(hipEventRecord(st.ev[i & 1], s));
-    const uint32_t* chunk = static_cast<const uint32_t*>(st.dev);
-    if (!commit) {
-      const bool words_k = planes_k && h.form;
-      const uint64_t n_el = rb / 4, e_off = planes_k ? 0 : c.k == replay_ckpt::POLICY ? h.xs() : h.xs() + h.A1;
-      const uint64_t n = c.cnt * n_el * (words_k ? replay_pack::CODES_PER_WORD : 1);
-      const unsigned grid = (unsigned)std::min<uint64_t>((n + REPLAY_THREADS - 1) / REPLAY_THREADS, CKPT_BLOCKS);
-      const int wn = planes_k && !h.form && is_packed ? pal.n : 0;   // fp32 planes on their way into a packed window
-      hipLaunchKernelGGL(k_replay_ckpt_scan, dim3(grid), dim3(REPLAY_THREADS), 0, s, chunk, words_k ? 1 : 0, n_el, e_off, h.rowlen(), c.j0, c.cnt, mm,
-                         fwpp, fpal.e[0], fpal.e[1], fpal.e[2], fpal.e[3], fpal.n, pal.e[0], pal.e[1], pal.e[2], pal.e[3], wn, st.acc);
-    } else if (is_packed && !h.form) {   // fp32 rows the scan found inside the palette: the append's own pack kernel
-      const unsigned gx = (unsigned)std::min<size_t>((row_words() * replay_pack::CODES_PER_WORD + REPLAY_THREADS - 1) / REPLAY_THREADS, 1024);
-      hipLaunchKernelGGL(k_replay_pack, dim3(gx, (unsigned)std::min<uint64_t>(c.cnt, 65535)), dim3(REPLAY_THREADS), 0, s, chunk, words, F, mm, wpp, (int)c.cnt,
-                         slot0, cap, pal.e[0], pal.e[1], pal.e[2], pal.e[3], pal.n);
-    } else {                             // packed rows into an fp32 window, or into a packed window of another palette
-      const size_t per_row = is_packed ? row_words() : xs;
-      const unsigned gx = (unsigned)std::min<size_t>((per_row + REPLAY_THREADS - 1) / REPLAY_THREADS, 1024);
-      hipLaunchKernelGGL(k_replay_ckpt_put, dim3(gx, (unsigned)std::min<uint64_t>(c.cnt, 65535)), dim3(REPLAY_THREADS), 0, s, chunk,
-                         reinterpret_cast<uint32_t*>(planes), words, F, mm, fwpp, (int)c.cnt, slot0, cap, fpal.e[0], fpal.e[1], fpal.e[2], fpal.e[3], remap);
-    }
-    AGZ_HIP_TRY(hipGetLastError());
-  }
+  // (commit) the slot the append of the chunk's first row wrote, or would have; a plain copy unless the planes need a kernel
+  auto slot_of = [&](const replay_ckpt::Chunk& c) { return (h.total - h.live + c.j0 - new_base) % cap; };
+  auto plain = [&](const replay_ckpt::Chunk& c) { return commit && (c.k != replay_ckpt::PLANES || same_planes); };
+  r = stream_in(st, ch.size(),
+    [&](size_t i, void* host) -> int { AGZ_REQUIRE(replay_ckpt::read_rows(f, l, ch[i].k, ch[i].j0, ch[i].cnt, host), AGZ_E_INVALID, "agz_replay_load: reading %s failed", path); return AGZ_OK; },
+    [&](size_t i, void* host) -> int {
+      const replay_ckpt::Chunk& c = ch[i];
+      const uint64_t rb = l.row_bytes[c.k];
+      const char* from = (const char*)host;
+      if (plain(c)) {   // into the one or two slot ranges
+        const uint64_t slot0 = slot_of(c), first = std::min(c.cnt, cap - slot0);
+        AGZ_HIP_TRY(hipMemcpyAsync(ckpt_array(c.k) + slot0 * rb, from, first * rb, hipMemcpyHostToDevice, s));
+        if (c.cnt > first) AGZ_HIP_TRY(hipMemcpyAsync(ckpt_array(c.k), from + first * rb, (c.cnt - first) * rb, hipMemcpyHostToDevice, s));
+      } else {
+        AGZ_HIP_TRY(hipMemcpyAsync(st.dev, from, c.cnt * rb, hipMemcpyHostToDevice, s));
+      }
+      return AGZ_OK;
+    },
+    [&](size_t i) -> int {
+      const replay_ckpt::Chunk& c = ch[i];
+      if (plain(c)) return AGZ_OK;
+      const bool planes_k = c.k == replay_ckpt::PLANES;
+      const uint64_t rb = l.row_bytes[c.k], slot0 = slot_of(c);
+      const uint32_t* chunk = static_cast<const uint32_t*>(st.dev);
+      if (!commit) {
+        const bool words_k = planes_k && h.form;
+        const uint64_t n_el = rb / 4, e_off = planes_k ? 0 : c.k == replay_ckpt::POLICY ? h.xs() : h.xs() + h.A1;
+        const uint64_t n = c.cnt * n_el * (words_k ? replay_pack::CODES_PER_WORD : 1);
+        const unsigned grid = (unsigned)std::min<uint64_t>((n + REPLAY_THREADS - 1) / REPLAY_THREADS, CKPT_BLOCKS);
+        const int wn = planes_k && !h.form && is_packed ? pal.n : 0;   // fp32 planes on their way into a packed window
+        hipLaunchKernelGGL(k_replay_ckpt_scan, dim3(grid), dim3(REPLAY_THREADS), 0, s, chunk, words_k ? 1 : 0, n_el, e_off, h.rowlen(), c.j0, c.cnt, mm,
+                           fwpp, fpal.e[0], fpal.e[1], fpal.e[2], fpal.e[3], fpal.n, pal.e[0], pal.e[1], pal.e[2], pal.e[3], wn, acc);
+      } else if (is_packed && !h.form) {   // fp32 rows the scan found inside the palette: the append's own pack kernel
+        const unsigned gx = (unsigned)std::min<size_t>((row_words() * replay_pack::CODES_PER_WORD + REPLAY_THREADS - 1) / REPLAY_THREADS, 1024);
+        hipLaunchKernelGGL(k_replay_pack, dim3(gx, (unsigned)std::min<uint64_t>(c.cnt, 65535)), dim3(REPLAY_THREADS), 0, s, chunk, words, F, mm, wpp, (int)c.cnt,
+                           slot0, cap, pal.e[0], pal.e[1], pal.e[2], pal.e[3], pal.n);
+      } else {                             // packed rows into an fp32 window, or into a packed window of another palette
+        const size_t per_row = is_packed ? row_words() : xs;
+        const unsigned gx = (unsigned)std::min<size_t>((per_row + REPLAY_THREADS - 1) / REPLAY_THREADS, 1024);
+        hipLaunchKernelGGL(k_replay_ckpt_put, dim3(gx, (unsigned)std::min<uint64_t>(c.cnt, 65535)), dim3(REPLAY_THREADS), 0, s, chunk,
+                           reinterpret_cast<uint32_t*>(planes), words, F, mm, fwpp, (int)c.cnt, slot0, cap, fpal.e[0], fpal.e[1], fpal.e[2], fpal.e[3], remap);
+      }
+      AGZ_HIP_TRY(hipGetLastError());
+      return AGZ_OK;
+    });
+  if (r != AGZ_OK) return r;
   if (commit) {
     AGZ_HIP_TRY(hipStreamSynchronize(s));
     total = h.total;
@@ -947,7 +910,7 @@ int agz_replay::ckpt_read(FILE* f, const char* path, const replay_ckpt::Header& 
     return AGZ_OK;
   }
   unsigned long long got[3] = {0, 0, PACK_NONE};
-  AGZ_HIP_TRY(hipMemcpyAsync(got, st.acc, sizeof(got), hipMemcpyDeviceToHost, s));
+  AGZ_HIP_TRY(hipMemcpyAsync(got, acc, sizeof(got), hipMemcpyDeviceToHost, s));
   AGZ_HIP_TRY(hipStreamSynchronize(s));
   if (got[1]) {   // the first bad element: its value is read where it lies, in the file
     const uint64_t at = got[2];
@@ -986,17 +949,14 @@ int agz_replay_save(agz_replay* rp, const char* path) {
   int r = agz_replay_digest(rp, &h.digest);   // (joins the context's queue: every append enqueued so far is in the window)
   if (r != AGZ_OK) return r;
   const replay_ckpt::Layout l = replay_ckpt::layout(h);
-  const std::string tmp = std::string(path) + ".tmp";
-  FILE* f = fopen(tmp.c_str(), "wb");
-  AGZ_REQUIRE(f, AGZ_E_INVALID, "agz_replay_save: cannot open %s", tmp.c_str());
-  if (!replay_ckpt::write_head(f, h)) { agz::set_error("agz_replay_save: write to %s failed", tmp.c_str()); r = AGZ_E_INVALID; }
-  if (r == AGZ_OK) r = rp->ckpt_write(f, l);
-  const bool flushed = fflush(f) == 0 && fsync(fileno(f)) == 0;
-  const bool closed = fclose(f) == 0;
-  if (r == AGZ_OK && !(flushed && closed)) { agz::set_error("agz_replay_save: write to %s failed", tmp.c_str()); r = AGZ_E_INVALID; }
-  if (r == AGZ_OK && rename(tmp.c_str(), path) != 0) { agz::set_error("agz_replay_save: cannot rename %s to %s", tmp.c_str(), path); r = AGZ_E_INVALID; }
-  if (r != AGZ_OK) remove(tmp.c_str());
-  return r;
+  AtomicFile out(path);
+  AGZ_REQUIRE(out.f, AGZ_E_INVALID, "agz_replay_save: cannot open %s", out.tmp.c_str());
+  AGZ_REQUIRE(replay_ckpt::write_head(out.f, h), AGZ_E_INVALID, "agz_replay_save: write to %s failed", out.tmp.c_str());
+  if ((r = rp->ckpt_write(out.f, l)) != AGZ_OK) return r;
+  const AtomicFile::End end = out.commit();
+  AGZ_REQUIRE(end != AtomicFile::WRITE_FAILED, AGZ_E_INVALID, "agz_replay_save: write to %s failed", out.tmp.c_str());
+  AGZ_REQUIRE(end != AtomicFile::RENAME_FAILED, AGZ_E_INVALID, "agz_replay_save: cannot rename %s to %s", out.tmp.c_str(), path);
+  return AGZ_OK;
 }
 
 int agz_replay_load(agz_replay* rp, const char* path) {

@@ -1,7 +1,7 @@
-// The replay window's checkpoint file (agz_replay_save / agz_replay_load): its byte layout and the validation of its header and lengths,
-// and nothing else.  Host-only: include/agz.h, replay.hpp, replay_pack.hpp and the standard library, so tests/cpp/replay_ckpt_check.cpp
-// checks this very code under g++ (tests/test_replay_ckpt_cpu.py).  replay.hip describes a window as a Header and hands the three arrays
-// over as ranges of rows; it knows nothing of the bytes.
+// The replay window's checkpoint file (agz_replay_save / agz_replay_load): its byte layout, the validation of its header and lengths,
+// and the chunks its rows are streamed in (row_chunks), and nothing else.  Host-only: include/agz.h, replay.hpp, replay_pack.hpp and the
+// standard library, so tests/cpp/replay_ckpt_check.cpp checks this very code under g++ (tests/test_replay_ckpt_cpu.py).  replay.hip
+// describes a window as a Header and hands the three arrays over as ranges of rows; it knows nothing of the bytes.
 //
 // All words are little-endian, nothing is padded, every count is 64 bits wide.  F, H, W = the planes' shape, A1 = PolicyLen, mm = H * W,
 // wpp = (mm + 15) / 16 (replay_pack.hpp).  A file is
@@ -66,6 +66,29 @@ inline Layout layout(const Header& h) {
   l.end_off = o;
   l.total = o + END_BYTES;
   return l;
+}
+
+// ---- the steps the arrays are streamed in (replay.hip, through ckpt_stream.hpp's pump) -------------------------------------------------
+constexpr uint64_t CKPT_MAX_ROWS = 1u << 30;   // of one chunk: the kernels count a chunk's rows in an int
+
+struct Chunk { int k; uint64_t j0, cnt; };     // rows [j0, j0 + cnt) of array k, in the file's logical order
+
+// rows [from, to) of the three arrays in file order, each cut into chunks of as many whole rows as `staging` bytes hold (at least one):
+// emit(Chunk) for each.  Returns the bytes of the largest chunk, and at least 64.
+template <class Fn>
+inline uint64_t row_chunks(const Layout& l, uint64_t from, uint64_t to, uint64_t staging, Fn emit) {
+  uint64_t bytes = 64;
+  for (int k = 0; k < ARRAYS; k++) {
+    uint64_t rows = staging / l.row_bytes[k];
+    if (rows < 1) rows = 1;
+    if (rows > CKPT_MAX_ROWS) rows = CKPT_MAX_ROWS;
+    for (uint64_t j = from; j < to; j += rows) {
+      const uint64_t cnt = rows < to - j ? rows : to - j;
+      emit(Chunk{k, j, cnt});
+      if (cnt * l.row_bytes[k] > bytes) bytes = cnt * l.row_bytes[k];
+    }
+  }
+  return bytes;
 }
 
 // ---- writer -----------------------------------------------------------------------------------------------------------------------------

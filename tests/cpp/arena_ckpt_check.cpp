@@ -3,7 +3,9 @@
 // chained across games 0 and 2 — is written into DIR/toy.bin through the codec in chunks of 4 nodes (so trees are cut) and 5 bytes of
 // examples (tests/test_arena_ckpt_cpu.py compares the file with bytes it builds itself from the documented format).  Then: scan returns
 // what was written, the nodes and examples read back equal, EVERY truncation and a trailing byte are refused, and every single-field
-// corruption scan() must catch is refused with the field named.  Prints "ARENA CKPT OK".
+// corruption scan() must catch is refused with the field named.  Last, the planners engine.hip streams the two large sections by
+// (node_chunks, example_chunks, staging_bytes) are held to their contract on tree counts that cut trees, skip empty ones and fill a
+// launch's grid.  Prints "ARENA CKPT OK".
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -118,6 +120,74 @@ static Status scan_path(const std::string& path, const Shape& want, Scan* sc, st
 }
 
 template <class V> static bool same(const V& a, const V& b) { return a.size() == b.size() && (a.empty() || memcmp(a.data(), b.data(), a.size() * sizeof(a[0])) == 0); }
+
+// node_chunks on trees of `counts` nodes: the chunks tile [0, nodes) in order; each is non-empty and fits the staging; t0 is the tree of
+// its first node and [t0, t0 + nt) holds every tree it touches, inside the arena and inside one launch's grid.  Returns the largest nt.
+static int check_node_plan(const char* name, const std::vector<uint64_t>& counts, uint64_t staging) {
+  Layout l;
+  l.tree_first.assign(1, 0);
+  for (uint64_t c : counts) l.tree_first.push_back(l.tree_first.back() + c);
+  l.nodes = l.tree_first.back();
+  const std::vector<uint64_t>& f = l.tree_first;
+  const int T = (int)counts.size();
+  const std::vector<Chunk> ch = node_chunks(l, staging);
+  CHECK(l.nodes > 0 || ch.empty(), "%s, %llu bytes: %zu chunks of no nodes", name, (unsigned long long)staging, ch.size());
+  uint64_t at = 0;
+  int t = 0, most = 0;   // t: the tree that holds node `at` (walked, not searched)
+  for (const Chunk& c : ch) {
+    CHECK(c.field == -1 && c.a == at && c.b > c.a && c.b <= l.nodes, "%s, %llu bytes: chunk [%llu, %llu) at %llu of %llu", name, (unsigned long long)staging,
+          (unsigned long long)c.a, (unsigned long long)c.b, (unsigned long long)at, (unsigned long long)l.nodes);
+    CHECK(c.b - c.a <= (staging - 4) / 20, "%s, %llu bytes: a chunk of %llu nodes", name, (unsigned long long)staging, (unsigned long long)(c.b - c.a));
+    if (c.a != at || c.b <= c.a || c.b > l.nodes) return most;
+    while (f[t + 1] <= c.a) t++;
+    int last = t;   // the tree that holds node b - 1
+    while (f[last + 1] <= c.b - 1) last++;
+    CHECK(c.t0 == t, "%s, %llu bytes: node %llu lies in tree %d, the chunk starts at tree %d", name, (unsigned long long)staging, (unsigned long long)c.a, t, c.t0);
+    CHECK(c.nt >= 1 && c.nt <= 65535 && c.t0 + c.nt <= T && last < c.t0 + c.nt, "%s, %llu bytes: chunk [%llu, %llu) ends in tree %d, its launch covers [%d, %d + %d) of %d trees", name,
+          (unsigned long long)staging, (unsigned long long)c.a, (unsigned long long)c.b, last, c.t0, c.t0, c.nt, T);
+    most = std::max(most, c.nt);
+    at = c.b;
+  }
+  CHECK(at == l.nodes, "%s, %llu bytes: the chunks end at node %llu of %llu", name, (unsigned long long)staging, (unsigned long long)at, (unsigned long long)l.nodes);
+  return most;
+}
+
+// example_chunks: run by run the chunks tile [0, examples * size); every chunk but a run's last is the staging rounded down to 16 bytes
+static void check_example_plan(const Shape& h, const Layout& l, uint64_t staging) {
+  uint64_t es[EX_FIELDS];
+  ex_sizes(h, es);
+  const std::vector<Chunk> ch = example_chunks(h, l, staging);
+  size_t i = 0;
+  for (int k = 0; k < EX_FIELDS; k++) {
+    uint64_t at = 0;
+    for (; i < ch.size() && ch[i].field == k; i++) {
+      CHECK(ch[i].a == at && ch[i].b > at && ch[i].b <= l.examples * es[k], "%llu bytes, run %d: chunk [%llu, %llu) at %llu", (unsigned long long)staging, k,
+            (unsigned long long)ch[i].a, (unsigned long long)ch[i].b, (unsigned long long)at);
+      const bool last = i + 1 == ch.size() || ch[i + 1].field != k;
+      CHECK(last || ch[i].b - ch[i].a == (staging & ~15ull), "%llu bytes, run %d: an inner chunk of %llu bytes", (unsigned long long)staging, k, (unsigned long long)(ch[i].b - ch[i].a));
+      CHECK(ch[i].b - ch[i].a <= staging, "%llu bytes, run %d: a chunk of %llu bytes", (unsigned long long)staging, k, (unsigned long long)(ch[i].b - ch[i].a));
+      if (ch[i].b <= at) return;
+      at = ch[i].b;
+    }
+    CHECK(at == l.examples * es[k], "%llu bytes, run %d: the chunks end at byte %llu of %llu", (unsigned long long)staging, k, (unsigned long long)at, (unsigned long long)(l.examples * es[k]));
+  }
+  CHECK(i == ch.size(), "%llu bytes: %zu chunks out of run order", (unsigned long long)staging, ch.size() - i);
+}
+
+static void check_planners(const Toy& y, const Layout& l) {
+  const std::vector<std::vector<uint64_t>> small = {{1, 0, 5, 9, 2, 4}, {0, 0, 3, 0, 7, 0, 0}, {0, 0, 0}};
+  for (const std::vector<uint64_t>& counts : small)
+    for (uint64_t staging : {64, 84, 104, 184, 424, 2004}) check_node_plan("small trees", counts, staging);
+  std::vector<uint64_t> many(70000, 1);   // more trees than one launch's grid holds, two of them empty
+  many[5] = many[69999] = 0;
+  check_node_plan("70000 trees", many, 64);
+  const int most = check_node_plan("70000 trees", many, 2000004);
+  CHECK(most == 65535, "70000 trees in one staging buffer: the largest launch covers %d trees, a grid holds 65535", most);
+  check_example_plan(y.h, l, 64);
+  check_example_plan(y.h, l, E * 4 * F * CELLS + 1);   // one byte more than the planes
+  check_example_plan(y.h, l, E * 4 * (A + 1) + 1);     // ... than the policies
+  CHECK(staging_bytes(y.h, l, 256u << 20) == 20 * 21 + 4 && staging_bytes(y.h, l, 200) == 200 && staging_bytes(y.h, l, 10) == 64, "staging_bytes");
+}
 
 int main(int argc, char** argv) {
   if (argc < 2) { printf("usage: arena_ckpt_check DIR\n"); return 2; }
@@ -268,6 +338,7 @@ int main(int argc, char** argv) {
     std::string why;
     CHECK(scan_path(good, want, &sc, &why) == OK, "lanes: %s", why.c_str());
   }
+  check_planners(y, l);
   remove(bad.c_str());
   printf("%d corruptions refused\n", cases);
   if (fails) { printf("%d check(s) failed\n", fails); return 1; }

@@ -4,7 +4,8 @@
 // live 7, capacity 7 — is written into DIR/toy_fp32.bin and DIR/toy_packed.bin through the codec in chunks of 3 rows
 // (tests/test_replay_ckpt_cpu.py compares both files with bytes it builds itself from the documented format).  Then, for both forms:
 // read_head returns what was written, the rows read back in chunks of 3 are equal, EVERY truncation and a trailing byte are refused, and
-// every single-word corruption of the header that read_head() must catch is refused with its reason named.  Prints the digest of the rows
+// every single-word corruption of the header that read_head() must catch is refused with its reason named.  Last, row_chunks, the planner
+// replay.hip streams the arrays by, is held to its contract at a staging below one row, of three plane rows and of 1 MB.  Prints the digest of the rows
 // ("digest N") and "REPLAY CKPT OK".
 #include <algorithm>
 #include <cstdio>
@@ -86,6 +87,33 @@ static Status head_of(const std::string& path, const Header& want, Header* h, La
   return st;
 }
 
+// row_chunks over rows [from, to): array by array the chunks tile the range, each holds max(1, staging / row_bytes) rows (an array's last
+// chunk what is left), and the result is the largest chunk's bytes, or 64 where none is as large
+static void check_row_plan(const Layout& l, uint64_t from, uint64_t to, uint64_t staging) {
+  int k_at = 0, n = 0;
+  uint64_t at = from, most = 0;
+  const uint64_t bytes = row_chunks(l, from, to, staging, [&](const Chunk& c) {
+    const int k = c.k;
+    const uint64_t j0 = c.j0, cnt = c.cnt;
+    if (cnt == 0 || ++n > 3 * (int)(to - from)) {   // (a planner that does not advance would never return)
+      printf("FAIL row_chunks(%llu, %llu, %llu bytes): chunk %d holds %llu rows\n", (unsigned long long)from, (unsigned long long)to, (unsigned long long)staging, n, (unsigned long long)cnt);
+      exit(1);
+    }
+    if (k != k_at) {
+      CHECK(k == k_at + 1 && at == to, "%llu bytes: array %d ends at row %llu of %llu", (unsigned long long)staging, k_at, (unsigned long long)at, (unsigned long long)to);
+      k_at = k; at = from;
+    }
+    const uint64_t rows = std::max<uint64_t>(1, staging / l.row_bytes[k]);
+    CHECK(j0 == at && cnt == std::min(rows, to - at), "%llu bytes, array %d: chunk [%llu, +%llu) at row %llu, %llu rows a chunk", (unsigned long long)staging, k,
+          (unsigned long long)j0, (unsigned long long)cnt, (unsigned long long)at, (unsigned long long)rows);
+    at = j0 + cnt;
+    most = std::max(most, cnt * l.row_bytes[k]);
+  });
+  if (from == to) CHECK(n == 0, "%llu bytes: %d chunks of no rows", (unsigned long long)staging, n);
+  else CHECK(k_at == ARRAYS - 1 && at == to, "%llu bytes: the chunks end in array %d at row %llu of %llu", (unsigned long long)staging, k_at, (unsigned long long)at, (unsigned long long)to);
+  CHECK(bytes == std::max<uint64_t>(64, most) && bytes >= 64, "%llu bytes: the largest chunk is %llu bytes, reported %llu", (unsigned long long)staging, (unsigned long long)most, (unsigned long long)bytes);
+}
+
 int main(int argc, char** argv) {
   if (argc < 2) { printf("usage: replay_ckpt_check DIR\n"); return 2; }
   const std::string dir = argv[1], bad = dir + "/bad.bin";
@@ -99,6 +127,11 @@ int main(int argc, char** argv) {
     const std::vector<unsigned char> bytes = slurp(good);
     CHECK(bytes.size() == l.total && l.total == 80 + LIVE * (l.row_bytes[PLANES] + 104 + 4) + 16, "file %zu bytes, layout %llu", bytes.size(), (unsigned long long)l.total);
     if (!packed) printf("digest %llu\n", (unsigned long long)y.h.digest);
+    for (uint64_t staging : {(uint64_t)4, 3 * l.row_bytes[PLANES], (uint64_t)1 << 20}) {   // below one row of any array; three plane rows; everything at once
+      check_row_plan(l, 0, LIVE, staging);
+      check_row_plan(l, 2, LIVE, staging);   // (a load into a smaller window skips the oldest rows)
+      check_row_plan(l, 5, 5, staging);
+    }
 
     {  // ---- round trip, read back in chunks of 3 rows
       Header h;

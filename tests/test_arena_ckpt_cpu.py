@@ -4,7 +4,8 @@ agogo_amd/csrc/arena_ckpt.hpp is the only place that knows the bytes of an agz_a
 includes nothing from HIP, so tests/cpp/arena_ckpt_check.cpp runs it under g++ on a toy arena (3 games of a 2x3 board, 6 trees with 1, 0,
 5, 9, 2, 4 live nodes, two of them in pool 1, a 2-deep ring, 4 example rows chained across two games), written and read in chunks that cut
 trees: the round trip, EVERY truncation, a trailing byte, and one corruption per rule scan() enforces.  The bytes themselves are rebuilt
-here with `struct` from the format comment of the header, so the comment and the code cannot drift."""
+here with `struct` from the format comment of the header, so the comment and the code cannot drift.  The same program holds the header's
+chunk planners (node_chunks, example_chunks), by which engine.hip streams the nodes and the examples, to their contract."""
 import os
 import shutil
 import struct
@@ -94,13 +95,15 @@ def test_the_same_under_the_address_and_undefined_behaviour_sanitizers(tmp_path)
 
 
 def test_a_mutated_header_fails_the_check(tmp_path):
-    """the check is not vacuous: two runs swapped, a rule of scan() dropped or weakened, a file that may run on — each is caught by the
-    program or by the byte comparison"""
+    """the check is not vacuous: two runs swapped, a rule of scan() dropped or weakened, a file that may run on, a planner that breaks its
+    contract — each is caught by the program or by the byte comparison"""
     hdr = open(os.path.join(ROOT, HEADER)).read()
     muts = [("constexpr uint64_t NODE_SIZE[NODE_FIELDS] = {4, 4, 4, 4, 2, 2};", "constexpr uint64_t NODE_SIZE[NODE_FIELDS] = {4, 4, 4, 2, 4, 2};"),
             ("if (off <= i || off >= n)", "if (off < 0 || off >= n)"), ("if (ep[i] < -1 || ep[i] >= e)", "if (ep[i] < -1 || ep[i] >= (int64_t)E)"),
             ("if ((uint64_t)len != l.total)", "if ((uint64_t)len < l.total)"), ("f(s.ex_last, 1); f(s.best_out, 1);", "f(s.best_out, 1); f(s.ex_last, 1);"),
-            ("if (claimed[(size_t)j]) return", "if (false) return")]
+            ("if (claimed[(size_t)j]) return", "if (false) return"),
+            # the planners: a chunk no longer ends on a tree boundary (its launch outgrows the grid), a run's last chunk runs past its end
+            ("    if (f[t1] > n0) n1 = f[t1];", "    ;"), ("out.push_back({k, a, std::min(a + step, l.examples * es[k]), 0, 0});", "out.push_back({k, a, a + step, 0, 0});")]
     os.makedirs(tmp_path / "agogo_amd" / "csrc")
     os.makedirs(tmp_path / "tests" / "cpp")
     shutil.copy(os.path.join(ROOT, CHECK), tmp_path / CHECK)

@@ -167,6 +167,31 @@ def test_wq9_ring_wrapped_both_pools_trees_across_chunks(ctx, tmp_path):
     l_.close()
 
 
+@pytest.mark.parametrize("games", [2, 3])
+def test_the_smallest_staging_c4(ctx, tmp_path, games):
+    """64 bytes of staging, the floor: three nodes a chunk and 64-byte steps through the examples, so every tree is cut, chunks begin and
+    end at odd nodes of a tree (the 16-bit runs at odd elements), and a tree's last chunk is shorter than the others"""
+    conf = dict(C4, n_games=games, Budget=8)
+    path = str(tmp_path / "floor.ckpt")
+    u, s = make(ctx, conf, 11), make(ctx, conf, 11, staging=64)
+    for _ in range(3):
+        move(u)
+        move(s)
+    n_nodes = [s.tree_nodes(g, agent) for g in range(games) for agent in (0, 1)]
+    assert min(n_nodes) > 3 and sum(n_nodes) < 2000 and any(n % 3 for n in n_nodes), n_nodes
+    s.save(path)
+    assert_equal(s, u, "after the save")
+    s.close()
+    l_ = make(ctx, conf, 977, staging=64)
+    l_.load(path)
+    assert_equal(l_, u, "after the load")
+    move(u)
+    move(l_)
+    assert_equal(l_, u, "a move after the load")
+    l_.close()
+    u.close()
+
+
 def test_lane_rounds_komi5(ctx, tmp_path):
     """set_parallel(4): rounds of four lanes with virtual loss; the flags are not in the file (all clear at a move boundary)"""
     _, l_ = continuation(ctx, tmp_path, KOMI5, 4, lanes=4)

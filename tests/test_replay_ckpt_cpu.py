@@ -6,7 +6,8 @@ board: 25 cells, two words a plane with fourteen unused bits in the second; Poli
 written and read in chunks of 3 rows: the round trip, EVERY truncation, a trailing byte, and one corruption per rule read_head()
 enforces.  The bytes themselves are rebuilt here with `struct` from the format comment of the header (file_bytes, which
 tests/test_replay_ckpt_gpu.py uses too), so the comment and the code cannot drift; the digest in the header is replay.hpp's, restated here
-with Python integers and compared with agz_replay_digest_host."""
+with Python integers and compared with agz_replay_digest_host.  The same program holds the header's chunk planner (row_chunks), by which
+replay.hip streams the arrays, to its contract."""
 import ctypes as C
 import os
 import re
@@ -126,14 +127,15 @@ def test_the_header_digest_is_the_library_digest_of_the_same_rows():
 
 
 def test_a_mutated_header_fails_the_check(tmp_path):
-    """the check is not vacuous: two runs swapped, a rule of read_head() dropped or weakened, a file that may run on — each is caught by
-    the program or by the byte comparison"""
+    """the check is not vacuous: two runs swapped, a rule of read_head() dropped or weakened, a file that may run on, a planner that breaks
+    its contract — each is caught by the program or by the byte comparison"""
     hdr = open(os.path.join(ROOT, HEADER)).read()
     muts = [("const uint64_t counts[4] = {h.total, h.live, h.capacity, h.digest};", "const uint64_t counts[4] = {h.live, h.total, h.capacity, h.digest};"),
             ("if ((uint64_t)len != l.total)", "if ((uint64_t)len < l.total)"), ("if (h.live > h.total)", "if (false)"),
             ("h.live != replay::live(h.total, h.capacity)", "h.live > replay::live(h.total, h.capacity)"),
             ("l.row_bytes[POLICY] = 4ull * h.A1;", "l.row_bytes[POLICY] = 4ull * h.A1 + 4;"), ("if (h.form > 1)", "if (h.form > 2)"),
-            ("      if (h.palette[i]) return fail", "      if (false) return fail"), ("|| total != l.total) return fail", ") return fail")]
+            ("      if (h.palette[i]) return fail", "      if (false) return fail"), ("|| total != l.total) return fail", ") return fail"),
+            ("if (rows < 1) rows = 1;", "if (rows < 1) rows = 0;")]     # the planner: staging below one row no longer gives one row a chunk
     os.makedirs(tmp_path / "agogo_amd" / "csrc")
     os.makedirs(tmp_path / "tests" / "cpp")
     shutil.copy(os.path.join(ROOT, CHECK), tmp_path / CHECK)

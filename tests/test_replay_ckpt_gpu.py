@@ -128,6 +128,25 @@ def test_a_loaded_window_continues_as_the_one_never_saved(ctx, tmp_path, shape, 
 
 
 @pytest.mark.parametrize("form", FORMS)
+def test_the_smallest_staging_one_row_a_chunk(ctx, tmp_path, form):
+    """4 bytes of staging, the floor, on the smallest shape: every chunk of every array is one row, through the wrap of the ring"""
+    sh, pal, packed = SHAPES["3x3"], "twoplane", form == "packed"
+    src, fd = source(ctx, sh, packed, pal)                                # capacity 7 fed 10 rows: the oldest live row lies in slot 3
+    src.set_ckpt_staging(4)
+    path = str(tmp_path / "floor.rpw")
+    before = state(src)
+    src.save(path)
+    assert state(src) == before
+    assert open(path, "rb").read() == file_bytes(sh, *fd.live(), FED, CAP, palette=PALETTES[pal] if packed else None)
+    dst = window(ctx, sh, CAP, packed, pal)
+    dst.set_ckpt_staging(4)
+    dst.load(path)
+    assert state(dst) == before and dst.digest() == header(path)["digest"]
+    for h in (fd, src, dst):
+        h.close()
+
+
+@pytest.mark.parametrize("form", FORMS)
 @pytest.mark.parametrize("shape", ["5x5", "4x4", "3x5"])
 def test_other_capacities(ctx, tmp_path, shape, form):
     sh, pal, packed = SHAPES[shape], "wq", form == "packed"
