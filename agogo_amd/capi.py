@@ -24,6 +24,10 @@ PATH_FWD_F32, PATH_FWD_BF16X3, PATH_FWD_H2W, PATH_FWD_H2DMA, PATH_FWD_H2DMA3 = 1
 PATH_WGRAD_F32, PATH_WGRAD_X3, PATH_WGRAD_H2, PATH_WGRAD_H2T3 = 1, 2, 3, 4
 PATH_DGRAD_RAW, PATH_DGRAD_X3, PATH_DGRAD_WINO_H2 = 1, 2, 3
 PATH_BN2_SCALAR, PATH_BN2_V = 1, 2
+# agz_debug.h, agz_trainer_last_rows: the words of a tower layer's row plan, and of the heads' (layer SharedLayers + 1)
+ROWS_WGRAD_CHUNKS, ROWS_SINGLE_PASS, ROWS_APPLY_RPB, ROWS_BWD2_RPB = 0, 1, 2, 3
+ROWS_APPLY_BOARD_WORDS, ROWS_BWD2_BOARD_WORDS, ROWS_SPLIT_BLOCKS, ROWS_SPLIT_NEED = 4, 5, 6, 7
+ROWS_HEAD_SECOND_FORM, ROWS_HEAD_CONV2_GRID, ROWS_HEAD_STATS_GRID, ROWS_HEAD_COST_GRID = 0, 1, 2, 3
 # agz_debug.h, agz_net_last_paths: the kernels a net's last whole-batch forward launched (0 = none)
 NPATH_IN_LAT, NPATH_IN_X3, NPATH_IN_F32_411, NPATH_IN_F32_221, NPATH_IN_F32_222 = 1, 2, 3, 4, 5
 NPATH_BLK_F32_411, NPATH_BLK_F32_221, NPATH_BLK_F32_222 = 1, 2, 3
@@ -327,6 +331,7 @@ def lib():
     sig("agz_arena_split_steps", i32, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int))
     sig("agz_trainer_set_dma_forward", i32, vp, i32)
     sig("agz_trainer_last_paths", i32, vp, i32, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int))
+    sig("agz_trainer_last_rows", i32, vp, i32, C.POINTER(C.c_int32))
     sig("agz_trainer_last_planes", i32, vp, i32, C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32))
     sig("agz_arena_last_prep_batch", i32, vp, C.POINTER(C.c_int), C.POINTER(C.c_int))
     sig("agz_arena_debug_counter", i32, vp, i32, C.POINTER(C.c_int64))
@@ -816,6 +821,13 @@ class Trainer:
         f, w, d, b = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
         _check(lib().agz_trainer_last_paths(self.h, int(layer), C.byref(f), C.byref(w), C.byref(d), C.byref(b)), "agz_trainer_last_paths")
         return f.value, w.value, d.value, b.value
+
+    def last_rows(self, layer):
+        """agz_debug.h test hook: the eight ROWS_* words of tower layer `layer`'s row plan in the last step (layer SharedLayers + 1: the
+        heads, ROWS_HEAD_*), as a tuple"""
+        out = (C.c_int32 * 8)()
+        _check(lib().agz_trainer_last_rows(self.h, int(layer), out), "agz_trainer_last_rows")
+        return tuple(out)
 
     def last_planes(self, layer):
         """agz_debug.h test hook: (fused, est_bits, range_bits) of tower layer `layer`'s input planes in the last step — written by the

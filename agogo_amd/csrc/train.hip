@@ -2179,6 +2179,9 @@ struct TLayer {
   bool fw_ready = false, bw_ready = false;         // ... built for THIS step
   // agz_trainer_last_paths (agz_debug.h): the kernels the last step launched for this layer, written at the launching branches (AGZ_PATH_*)
   int path_fwd = 0, path_wgrad = 0, path_dgrad = 0, path_bn2 = 0;
+  // agz_trainer_last_rows (agz_debug.h): the row plan of the last step's batch-sized loops for this layer (AGZ_ROWS_*), copied from the
+  // very values the launchers pass to the kernels
+  int rows[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 struct TParamRef { std::string name; int kind; std::vector<int> shape; int layer; int sub; };  // sub: 0 filter(a) 1 gamma 2 beta, for dual +10 = branch b
 
@@ -2265,6 +2268,7 @@ struct agz_trainer {
   int loss_kind = AGZ_LOSS_REFERENCE;
   float *az_dz = nullptr, *az_do = nullptr;
   double* az_row = nullptr;
+  int head_rows[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // agz_trainer_last_rows(layer = L + 1): AGZ_ROWS_HEAD_*
   bool cost_valid = false;  // a forward (training or eval) has written cost[0..1] (agz_trainer_get_costs)
   bool fast_heads = true;   // agz_trainer_set_dma_forward(t, on | 2 * heads): the second form of the head kernels (A/B hook)
   bool dma_fwd = true;      // AGZ_COMPUTE_WINO_H2 forward convolutions through k_conv_h2dma (agz_trainer_set_dma_forward, agz_debug.h: A/B hook)
@@ -2504,6 +2508,7 @@ int agz_trainer::forward_backward_dev(const float* planes, const float* pi, cons
     if (r != AGZ_OK) return r;
     int C = ly.Cout_p;
     const BnTrack bt = bn_track(l);
+    ly.rows[AGZ_ROWS_SINGLE_PASS] = !eval && bn_single_pass(C);
     // (sharded: this rank's partial sums are gathered from every rank and k_bn_fin_ranks sums them in rank order over the global rows)
     if (eval) {   // the tracked estimates in place of this batch's statistics
       hipLaunchKernelGGL(k_bn_from_running, dim3(nblk(C)), dim3(256), 0, s, bt, conf.bn_eps, ly.mean, ly.inv);
@@ -2542,8 +2547,10 @@ int agz_trainer::forward_backward_dev(const float* planes, const float* pi, cons
                          nph, nph ? nph + (size_t)B * g.Hp * g.Wp * Kp : nullptr, (const unsigned*)(amax_prev + 2 * (l + 1) + 1));
       x_amax_ready[l + 1] = 1;
       xb_ready[l + 1] = per_board;
+      ly.rows[AGZ_ROWS_APPLY_RPB] = rpb; ly.rows[AGZ_ROWS_APPLY_BOARD_WORDS] = per_board;
     } else {
       if (l < L) planes_fused[l + 1] = 0;
+      ly.rows[AGZ_ROWS_APPLY_RPB] = 0; ly.rows[AGZ_ROWS_APPLY_BOARD_WORDS] = 0;
       hipLaunchKernelGGL(tied ? k_bn_apply<true> : k_bn_apply<false>, dim3(nblk((size_t)g.M * Kp)), dim3(256), 0, s, g, ly.z, P + ly.o_gamma, P + ly.o_beta, ly.mean,
                          ly.inv, ly.out, Kp, ly.nbr);
     }
@@ -2568,10 +2575,13 @@ int agz_trainer::forward_backward_dev(const float* planes, const float* pi, cons
   const BnTrack hbt = bn_track(L + 1);
   if (fh) {
     AGZ_HIP_TRY(hipMemsetAsync(head_acc, 0, 16 * sizeof(double), s));
-    hipLaunchKernelGGL(k_head_conv2, dim3(std::min(nblk(g.M, 4), ctx->num_cus * 16)), dim3(256), 0, s, g, cur, P + o_hc, zh, Kp);
+    const int g_conv2 = std::min(nblk(g.M, 4), ctx->num_cus * 16), g_stats = std::min(nblk(g.M), ctx->num_cus), g_cost = std::min(nblk((size_t)B * A), 64);
+    head_rows[AGZ_ROWS_HEAD_SECOND_FORM] = 1; head_rows[AGZ_ROWS_HEAD_CONV2_GRID] = g_conv2;
+    head_rows[AGZ_ROWS_HEAD_STATS_GRID] = eval ? 0 : g_stats; head_rows[AGZ_ROWS_HEAD_COST_GRID] = az ? 0 : g_cost;
+    hipLaunchKernelGGL(k_head_conv2, dim3(g_conv2), dim3(256), 0, s, g, cur, P + o_hc, zh, Kp);
     if (eval) hipLaunchKernelGGL(k_bn_from_running, dim3(1), dim3(64), 0, s, hbt, conf.bn_eps, hmean, hinv);
     else {
-    hipLaunchKernelGGL(k_head_stats_part, dim3(std::min(nblk(g.M), ctx->num_cus)), dim3(256), 0, s, g, zh, head_acc);
+    hipLaunchKernelGGL(k_head_stats_part, dim3(g_stats), dim3(256), 0, s, g, zh, head_acc);
     if (sharded) {   // (head_acc [16] is gathered whole; each exchange sums the ranks' part it concerns into this rank's head_acc)
       int r = exchange(L + 1, head_acc, 16);
       if (r != AGZ_OK) return r;
@@ -2586,7 +2596,7 @@ int agz_trainer::forward_backward_dev(const float* planes, const float* pi, cons
       hipLaunchKernelGGL(k_az_loss, dim3(B), dim3(64), 0, s, h);
       hipLaunchKernelGGL(k_az_cost_sum, dim3(1), dim3(64), 0, s, h, head_acc);
     } else
-    hipLaunchKernelGGL(k_cost_part, dim3(std::min(nblk((size_t)B * A), 64)), dim3(256), 0, s, h, head_acc);
+    hipLaunchKernelGGL(k_cost_part, dim3(g_cost), dim3(256), 0, s, h, head_acc);
     if (sharded) {
       int r = exchange(L + 1, head_acc, 16);
       if (r != AGZ_OK) return r;
@@ -2594,6 +2604,7 @@ int agz_trainer::forward_backward_dev(const float* planes, const float* pi, cons
     }
     hipLaunchKernelGGL(az ? k_cost_fin<true> : k_cost_fin<false>, dim3(1), dim3(64), 0, s, h, head_acc);
   } else {
+  std::fill(head_rows, head_rows + 8, 0);
   hipLaunchKernelGGL(k_head_conv, dim3(nblk((size_t)g.M * 3)), dim3(256), 0, s, g, cur, P + o_hc, zh, Kp);
   if (eval) hipLaunchKernelGGL(k_bn_from_running, dim3(1), dim3(64), 0, s, hbt, conf.bn_eps, hmean, hinv);
   else hipLaunchKernelGGL(trk ? k_head_stats<true> : k_head_stats<false>, dim3(3), dim3(256), 0, s, g, zh, conf.bn_eps, hmean, hinv, hbt);
@@ -2722,7 +2733,9 @@ int agz_trainer::forward_backward_dev(const float* planes, const float* pi, cons
                          dzb_ready ? board_words + (size_t)(L + 2 + l) * B : nullptr, (float)m_glob());
       dz_amax_ready = true;
       ly.path_bn2 = AGZ_PATH_BN2_V;
+      ly.rows[AGZ_ROWS_BWD2_RPB] = rpb; ly.rows[AGZ_ROWS_BWD2_BOARD_WORDS] = dzb_ready;
     } else {
+      ly.rows[AGZ_ROWS_BWD2_RPB] = 0; ly.rows[AGZ_ROWS_BWD2_BOARD_WORDS] = 0;
       hipLaunchKernelGGL(k_bn_bwd2, dim3(nblk((size_t)g.M * C)), dim3(256), 0, s, g, ly.z, ly.mean, ly.inv, dz, s1, s2, C, (float)m_glob());
       ly.path_bn2 = AGZ_PATH_BN2_SCALAR;
     }
@@ -2737,12 +2750,14 @@ int agz_trainer::forward_backward_dev(const float* planes, const float* pi, cons
     const unsigned wg_grid = (unsigned)(wa.n_tiles * wa.c_tiles * 9 * round_up(chunks, 8));   // k_wgrad_x3 / _h2: XCD-aware order
     const bool chip_full = x3_force || (size_t)wa.n_tiles * wa.c_tiles * 9 * chunks >= (size_t)ctx->num_cus;
     const bool off31 = (size_t)B * g.Hp * g.Wp * (size_t)std::max(C, ly.Cin_p) * 4 < ((size_t)1 << 31);   // byte offsets of the buffer loads
+    ly.rows[AGZ_ROWS_WGRAD_CHUNKS] = chunks; ly.rows[AGZ_ROWS_SPLIT_BLOCKS] = 0; ly.rows[AGZ_ROWS_SPLIT_NEED] = 0;
     if (wino && chip_full && off31 && C % 4 == 0 && ly.Cin_p % 4 == 0) {
       // fp16x2 products: range + split pass over dz and x (once per layer, not once per tap workgroup), then the GEMM
       const size_t n_dz = (size_t)B * g.Hp * g.Wp * C, n_x = (size_t)B * g.Hp * g.Wp * ly.Cin_p;
       if (dz_h2_cap < n_dz) { if (dz_h2) hipFree(dz_h2); dz_h2 = nullptr; dz_h2_cap = 0; AGZ_HIP_TRY(hipMalloc(&dz_h2, n_dz * 4)); dz_h2_cap = n_dz; }
       if (x_h2_cap < n_x) { if (x_h2) hipFree(x_h2); x_h2 = nullptr; x_h2_cap = 0; AGZ_HIP_TRY(hipMalloc(&x_h2, n_x * 4)); x_h2_cap = n_x; }
       const unsigned gs = (unsigned)std::min<size_t>(nblk(n_dz / 4), (size_t)ctx->num_cus * 8);
+      ly.rows[AGZ_ROWS_SPLIT_BLOCKS] = (int)gs; ly.rows[AGZ_ROWS_SPLIT_NEED] = nblk(n_dz / 4);
       if (!dz_amax_ready) hipLaunchKernelGGL(k_absmax, dim3(gs), dim3(256), 0, sw, dz, n_dz / 4, wg_amax);
       if (!x_amax_ready[l]) hipLaunchKernelGGL(k_absmax, dim3(gs), dim3(256), 0, sw, xin, n_x / 4, wg_amax + 1);
       if (g.W >= 16 && C % 8 == 0 && ly.Cin_p % 8 == 0) {
@@ -2762,6 +2777,7 @@ int agz_trainer::forward_backward_dev(const float* planes, const float* pi, cons
         w3.n_chunks = std::min(B, 8 * std::max(1, 2 * slots / per_chunk3));
         hipLaunchKernelGGL(k_wgrad_h2t3, dim3((unsigned)(per_chunk3 * round_up(w3.n_chunks, 8))), dim3(256), (size_t)wg_pad_lds, sw, w3);
         ly.path_wgrad = AGZ_PATH_WGRAD_H2T3;
+        ly.rows[AGZ_ROWS_WGRAD_CHUNKS] = w3.n_chunks;
       } else {
         hipLaunchKernelGGL(k_split_h2, dim3(gs), dim3(256), 0, sw, dz, dz_h2, n_dz / 4, wg_amax);
         if (sw != s) { AGZ_HIP_TRY(hipEventRecord(ev_split, sw)); split_recorded = true; }
@@ -3516,6 +3532,14 @@ int agz_trainer_last_paths(agz_trainer* t, int layer, int* fwd, int* wgrad, int*
   AGZ_REQUIRE(layer >= 0 && layer <= t->L, AGZ_E_INVALID, "agz_trainer_last_paths: layer %d of 0..%d", layer, t->L);
   const TLayer& ly = t->layers[layer];
   *fwd = ly.path_fwd; *wgrad = ly.path_wgrad; *dgrad = ly.path_dgrad; *bn_bwd2 = ly.path_bn2;
+  return AGZ_OK;
+}
+
+int agz_trainer_last_rows(agz_trainer* t, int layer, int32_t out[8]) {
+  AGZ_REQUIRE(t && out, AGZ_E_INVALID, "agz_trainer_last_rows: NULL argument");
+  AGZ_REQUIRE(layer >= 0 && layer <= t->L + 1, AGZ_E_INVALID, "agz_trainer_last_rows: layer %d of 0..%d", layer, t->L + 1);
+  const int* src = layer <= t->L ? t->layers[layer].rows : t->head_rows;
+  for (int i = 0; i < 8; i++) out[i] = src[i];
   return AGZ_OK;
 }
 

@@ -117,6 +117,38 @@ int agz_trainer_set_dma_forward(agz_trainer* t, int on);
 #define AGZ_PATH_BN2_V 2        /* k_bn_bwd2_v: vector form, writes dz's range itself */
 int agz_trainer_last_paths(agz_trainer* t, int layer, int* fwd, int* wgrad, int* dgrad, int* bn_bwd2);
 
+/* Tests: the row plan of the trainer's last step (agz_trainer_forward_backward / _batch) — how the kernels whose loops are sized by the
+ * batch (M = B * H * W rows, B boards) were dealt their rows.  Every value is a copy of the very number the launcher passed to the kernel or
+ * used as its grid; nothing is computed for the report and it has no effect on any launch.  A test restates the rules and compares, so that
+ * a changed constant (rows per workgroup, a grid cap, the single-pass threshold) cannot silently move a shape back to a loop of one round.
+ * layer 0 .. SharedLayers, out[AGZ_ROWS_*]:
+ *   WGRAD_CHUNKS       chunks of the weight gradient's reduction: row chunks of 2048 rows for k_wgrad / k_wgrad_x3 / k_wgrad_h2
+ *                      (ceil(M / 2048)), chunks of whole boards for k_wgrad_h2t3
+ *   SINGLE_PASS        1: the BatchNorm statistics came from k_bn_stats + k_bn_fin2 (M >= 4096), 0: from the two k_bn_sum passes
+ *   APPLY_RPB          rows per workgroup of k_bn_apply_v; 0 when the scalar k_bn_apply ran
+ *   BWD2_RPB           rows per workgroup of k_bn_bwd2_v; 0 when the scalar k_bn_bwd2 ran
+ *   APPLY_BOARD_WORDS  1: k_bn_apply_v also wrote per-board range words (its rows per workgroup <= H * W)
+ *   BWD2_BOARD_WORDS   the same for k_bn_bwd2_v
+ *   SPLIT_BLOCKS       workgroups the fp16x2 weight gradient's range / split passes over dz were launched with (k_absmax, k_split_h2,
+ *                      k_split_h2p); 0 when the layer's weight gradient took no split pass
+ *   SPLIT_NEED         workgroups those passes would take at one vector of four per thread: SPLIT_BLOCKS < SPLIT_NEED means they strided
+ * layer SharedLayers + 1 reports the heads, out[AGZ_ROWS_HEAD_*]: SECOND_FORM 1 when the second form of the head kernels ran, then the grids
+ * of k_head_conv2, k_head_stats_part (k_head_bn_bwd_a runs on the same grid) and k_cost_part (0 under AGZ_LOSS_ALPHAZERO); all 0 after a
+ * step in the first form.  Unused words are 0.  After an eval the backward fields still hold the last training step's. */
+#define AGZ_ROWS_WGRAD_CHUNKS 0
+#define AGZ_ROWS_SINGLE_PASS 1
+#define AGZ_ROWS_APPLY_RPB 2
+#define AGZ_ROWS_BWD2_RPB 3
+#define AGZ_ROWS_APPLY_BOARD_WORDS 4
+#define AGZ_ROWS_BWD2_BOARD_WORDS 5
+#define AGZ_ROWS_SPLIT_BLOCKS 6
+#define AGZ_ROWS_SPLIT_NEED 7
+#define AGZ_ROWS_HEAD_SECOND_FORM 0
+#define AGZ_ROWS_HEAD_CONV2_GRID 1
+#define AGZ_ROWS_HEAD_STATS_GRID 2
+#define AGZ_ROWS_HEAD_COST_GRID 3
+int agz_trainer_last_rows(agz_trainer* t, int layer, int32_t out[8]);
+
 /* Tests: how tower layer `layer` (0 .. SharedLayers) came by the fp16 hi / lo planes of its input in the trainer's last step
  * (agz_trainer_forward_backward / _batch / _eval).  In AGZ_COMPUTE_WINO_H2 mode the vector BatchNorm pass of layer l - 1 writes them under
  * LAST step's range word of the tensor, and k_split_h2p_cond keeps them when that word and this step's exact one prescribe the same power

@@ -233,7 +233,10 @@ FB_CASES = [
     (40, 2, 24, 5, 4, 3, 21, 7),
 ]
 # 4332 rows per rank: the single-pass k_bn_stats path.  f32 only: at this shape (3x Glorot filters, 24 boards) AGZ_COMPUTE_WINO_H2 misses the
-# 2e-5 bar on the PLAIN trainer as well (5.7e-3 of a beta gradient's maximum at the global batch: its fp16x2 forward flips ReLU units)
+# 2e-5 bar on the PLAIN trainer as well (5.7e-3 of a beta gradient's maximum at the global batch: its fp16x2 forward flips ReLU units).
+# The single-GPU answer to that is tests/test_train_rows_gpu.py: at thousands of rows some unit lies within fp32 rounding of zero on every
+# draw, and the fp32 oracle flips units of its own; there the draws are conditioned (f64_train.condition) and float64 is the only judge, and
+# AGZ_COMPUTE_WINO_H2 holds the bar from 2 048 to 65 910 rows.
 BIG = (64, 2, 32, 19, 19, 18, 362, 12)
 
 
