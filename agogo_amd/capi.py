@@ -41,6 +41,7 @@ DONT_PREFER_PASS, PREFER_PASS, DONT_RESIGN = 0, 1, 2
 POOL_STRICT, POOL_STOP_SEARCH, POOL_GROW = 0, 1, 2
 SYM_OFF, SYM_RANDOM, SYM_FIXED = 0, 1, 8   # set_leaf_symmetry: SYM_FIXED + k applies S_k at every leaf
 TARGET_REFERENCE, TARGET_VISITS = 0, 1     # Arena.set_policy_target
+CAP_FULL, CAP_FAST = 0, 1                  # Arena.playout_cap / playout_cap_of
 
 
 class AgzError(RuntimeError):
@@ -84,6 +85,11 @@ class NoiseConf(C.Structure):
 class TargetConf(C.Structure):
     """agz_target_conf (include/agz.h): what an arena records as an example's policy row; 16 bytes"""
     _fields_ = [("kind", C.c_int32), ("temperature", C.c_float), ("reserved", C.c_int32 * 2)]
+
+
+class PlayoutCapConf(C.Structure):
+    """agz_playout_cap_conf (include/agz.h): every ply a FULL search with probability p_full, else fast_budget simulations; 24 bytes"""
+    _fields_ = [("p_full", C.c_float), ("fast_budget", C.c_int32), ("on", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_uint64)]
 
 
 class ArenaStats(C.Structure):
@@ -260,6 +266,12 @@ def lib():
     sig("agz_mcts_set_root_noise", i32, vp, pnc)
     sig("agz_mcts_root_noise", i32, vp, pu64, pi, pf, i32, C.POINTER(C.c_int))
     sig("agz_root_noise_of", i32, u64, i32, C.c_float, pf)
+    ppc, pi32, pi64 = C.POINTER(PlayoutCapConf), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+    sig("agz_arena_set_playout_cap", i32, vp, ppc)
+    sig("agz_arena_get_playout_cap", i32, vp, ppc)
+    sig("agz_arena_playout_cap", i32, vp, i32, pu64, pi32, pi32, pi32)
+    sig("agz_arena_playout_cap_counts", i32, vp, pi64, pi64)
+    sig("agz_playout_cap_of", i32, u64, u64, C.c_int32, C.c_float, pi32)
     ptc = C.POINTER(TargetConf)
     sig("agz_arena_set_policy_target", i32, vp, ptc)
     sig("agz_arena_get_policy_target", i32, vp, ptc)
@@ -334,6 +346,8 @@ def lib():
     sig("agz_trainer_last_rows", i32, vp, i32, C.POINTER(C.c_int32))
     sig("agz_trainer_last_planes", i32, vp, i32, C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32))
     sig("agz_arena_last_prep_batch", i32, vp, C.POINTER(C.c_int), C.POINTER(C.c_int))
+    sig("agz_arena_set_cap_compact", i32, vp, i32)
+    sig("agz_arena_last_cap_batch", i32, vp, C.POINTER(C.c_int), C.POINTER(C.c_int))
     sig("agz_arena_debug_counter", i32, vp, i32, C.POINTER(C.c_int64))
     sig("agz_arena_pool_capacity", i32, vp, C.POINTER(C.c_int), C.POINTER(C.c_int))
     sig("agz_wino_h2_chained", i32, i32, i32, i32)
@@ -980,6 +994,39 @@ class Arena:
         conf = TargetConf()
         _check(lib().agz_arena_get_policy_target(self.h, C.byref(conf)), "agz_arena_get_policy_target")
         return {"kind": conf.kind, "temperature": conf.temperature}
+
+    def set_playout_cap(self, p_full=0.25, fast_budget=0, on=True, seed=0, reserved=0):
+        """playout cap randomization: every ply of every game is a FULL search (Budget simulations, root noise, a recorded row) with
+        probability p_full, else a FAST one (fast_budget simulations, no noise, no row) (include/agz.h); default off"""
+        conf = PlayoutCapConf(p_full, int(fast_budget), int(on), int(reserved), int(seed) & (2 ** 64 - 1))
+        _check(lib().agz_arena_set_playout_cap(self.h, C.byref(conf)), "agz_arena_set_playout_cap")
+
+    def get_playout_cap(self):
+        conf = PlayoutCapConf()
+        _check(lib().agz_arena_get_playout_cap(self.h, C.byref(conf)), "agz_arena_get_playout_cap")
+        return {"p_full": conf.p_full, "fast_budget": conf.fast_budget, "on": bool(conf.on), "seed": conf.seed}
+
+    def playout_cap(self, g):
+        """the decision of game g's current / last searched ply: (key, ply, kind, budget); kind = -1 before the first one"""
+        key, ply, kind, budget = C.c_uint64(0), C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        _check(lib().agz_arena_playout_cap(self.h, int(g), C.byref(key), C.byref(ply), C.byref(kind), C.byref(budget)), "agz_arena_playout_cap")
+        return key.value, ply.value, kind.value, budget.value
+
+    def playout_cap_counts(self):
+        """(plies searched as FULL, as FAST) since the last reset / load"""
+        full, fast = C.c_int64(0), C.c_int64(0)
+        _check(lib().agz_arena_playout_cap_counts(self.h, C.byref(full), C.byref(fast)), "agz_arena_playout_cap_counts")
+        return full.value, fast.value
+
+    def set_cap_compact(self, on=True):
+        """agz_debug.h: a playout-cap tail step on the packed batch of the still-searching games (default) or on the whole arena batch"""
+        _check(lib().agz_arena_set_cap_compact(self.h, int(on)), "agz_arena_set_cap_compact")
+
+    def last_cap_batch(self):
+        """agz_debug.h: (network batch, still-searching games) of the last simulation step if it was a playout-cap tail step, else (0, 0)"""
+        b, g = C.c_int(0), C.c_int(0)
+        _check(lib().agz_arena_last_cap_batch(self.h, C.byref(b), C.byref(g)), "agz_arena_last_cap_batch")
+        return b.value, g.value
 
     def begin_move(self):
         _check(lib().agz_arena_begin_move(self.h), "agz_arena_begin_move")
@@ -1674,6 +1721,13 @@ def root_noise_of(key, n, alpha):
     eta = np.zeros(max(int(n), 1), np.float32)
     _check(lib().agz_root_noise_of(int(key) & (2 ** 64 - 1), int(n), float(alpha), _pf(eta)), "agz_root_noise_of")
     return eta[:int(n)]
+
+
+def playout_cap_of(seed, key, ply, p_full):
+    """CAP_FULL / CAP_FAST of ply `ply` of the game slot with key `key` under the playout cap (cap.hpp; host only)"""
+    kind = C.c_int32(0)
+    _check(lib().agz_playout_cap_of(int(seed) & (2 ** 64 - 1), int(key) & (2 ** 64 - 1), int(ply), p_full, C.byref(kind)), "agz_playout_cap_of")
+    return kind.value
 
 
 def visit_target_of(moves, visits, action_space, temperature=1.0):

@@ -470,6 +470,7 @@ __global__ __launch_bounds__(64) void k_root_noise(Dev d, GameCfg c, float eps, 
   __shared__ unsigned long long skey;
   const int g = blockIdx.x, lane = threadIdx.x;
   if (d.ended[g]) return;
+  if (d.cap_kind && d.cap_kind[g] == cap::FAST) return;   // playout cap: a fast search gets no noise — no key, no mark, the record untouched
   const int t = agent_of(d, g) * d.G + g;
   const size_t base = pool_base(d, t, d.cur_pool[t]);
   const int off = d.kids_off[base];
@@ -499,6 +500,51 @@ __global__ __launch_bounds__(64) void k_root_noise(Dev d, GameCfg c, float eps, 
   if (lane == 0) { d.noise_key[t] = key; d.noise_n[t] = n; d.noised[t] = 1; }
 }
 
+// Playout cap (BUILD EXTENSION, DESIGN.md §2 playout-cap; cap.hpp holds the definition): the kind and the budget of the ply every
+// unfinished game is about to search.  Only launched while the setting is on, after k_begin_move and before prepareRoot; ONE wavefront
+// walks the games in order, 64 at a time, so the compact slot of a FULL game (the number of earlier unfinished FULL games: the batch
+// slot of a compacted tail step) and the counts need no atomics.  counts: [0] FULL plies, [1] FAST plies since the last reset / load,
+// [2] this move's number of FULL games (read back with prepareRoot's counter).  A finished game keeps the record of its last search.
+struct CapBufs {
+  int32_t* kind;       // [G] -1 until the game's first decision
+  int32_t* budget;     // [G]
+  int32_t* slot;       // [G]
+  int32_t* ply;        // [G] the observer's record: the ply
+  uint64_t* key;       // [G] and the key the decision was made from
+  unsigned long long* counts;   // [3]
+};
+__global__ __launch_bounds__(64) void k_cap_decide(Dev d, CapBufs b, unsigned long long seed, uint32_t thr, int fast_budget, int budget) {
+  const int lane = threadIdx.x;
+  int n_full = 0, n_fast = 0;
+  for (int g0 = 0; g0 < d.G; g0 += WAVE) {
+    const int g = g0 + lane;
+    const bool live = g < d.G && !d.ended[g];
+    int kind = cap::FAST;
+    if (live) {
+      const uint64_t key = d.rng_game[g];
+      const int32_t ply = d.ply[g];
+      kind = cap::kind_of(seed, key, ply, thr);
+      b.kind[g] = kind; b.budget[g] = kind == cap::FULL ? budget : fast_budget; b.ply[g] = ply; b.key[g] = key;
+    }
+    const unsigned long long m_full = __ballot(live && kind == cap::FULL), m_live = __ballot(live);
+    if (live) b.slot[g] = kind == cap::FULL ? n_full + __popcll(m_full & ((1ull << lane) - 1ull)) : 0;
+    n_full += __popcll(m_full);
+    n_fast += __popcll(m_live & ~m_full);
+  }
+  if (lane == 0) { b.counts[0] += (unsigned long long)n_full; b.counts[1] += (unsigned long long)n_fast; b.counts[2] = (unsigned long long)n_full; }
+}
+
+// The lanes game g runs in a round of nl whose first simulation has index d.cap_i0: all nl unless this is a tail step of a capped move
+// (d.cap_budget != nullptr), then clamp(budget - i0, 0, nl).  The lanes it does not run are marked LEAF_NONE (every later kernel of the
+// step passes such a lane by, and it is not counted as a simulation).
+__device__ __forceinline__ int cap_lanes(const Dev& d, int g, size_t q0, int nl, int lane) {
+  if (!d.cap_budget) return nl;
+  const int left = d.cap_budget[g] - d.cap_i0;
+  const int run = left < 0 ? 0 : (left < nl ? left : nl);
+  if (lane >= run && lane < nl) d.leaf_kind[q0 + lane] = LEAF_NONE;
+  return run;
+}
+
 // pipeline() descent: mcts/search.go:209-257 up to (and excluding) the network call.
 // prep != 0 runs prepareRoot (search.go:392-408) instead: the root itself is the leaf if it is expandable.
 // g0: first game of this launch (the split step runs the two halves of an arena as launches of their own)
@@ -507,6 +553,8 @@ __global__ __launch_bounds__(64) void k_select(Dev d, GameCfg c, MctsCfg mc, flo
   int g = g0 + blockIdx.x, lane = threadIdx.x;
   const size_t q0 = (size_t)g * d.V;
   if (d.ended[g]) { if (lane < nl) d.leaf_kind[q0 + lane] = LEAF_NONE; return; }
+  nl = cap_lanes(d, g, q0, nl, lane);
+  if (nl == 0) return;
   int agent = agent_of(d, g);
   int t = agent * d.G + g;
   if (d.stalled[t]) { if (lane < nl) { d.leaf_kind[q0 + lane] = LEAF_NULL; d.path_len[q0 + lane] = 0; } return; }
@@ -598,6 +646,8 @@ __global__ __launch_bounds__(64) void k_select_paths(Dev d, GameCfg c, MctsCfg m
   const int g = blockIdx.x, lane = threadIdx.x;
   const size_t q0 = (size_t)g * d.V;
   if (d.ended[g]) { if (lane < nl) d.leaf_kind[q0 + lane] = LEAF_NONE; return; }
+  nl = cap_lanes(d, g, q0, nl, lane);
+  if (nl == 0) return;
   const int agent = agent_of(d, g);
   const int t = agent * d.G + g;
   if (d.stalled[t]) { if (lane < nl) { d.leaf_kind[q0 + lane] = LEAF_NULL; d.path_len[q0 + lane] = 0; } return; }
@@ -778,6 +828,7 @@ __global__ __launch_bounds__(64) void k_expand_prep(Dev d, GameCfg c, MctsCfg mc
 __global__ __launch_bounds__(64) void k_expand_commit(Dev d, GameCfg c, MctsCfg mc, int prep, int nl) {
   const int g = blockIdx.x, lane = threadIdx.x;
   if (d.ended[g]) return;
+  if (d.cap_budget && d.cap_budget[g] <= d.cap_i0) return;   // playout cap, tail step: this game's search is over (every lane is LEAF_NONE)
   const int agent = agent_of(d, g);
   const int t = agent * d.G + g;
   const size_t q0 = (size_t)g * d.V;
@@ -851,6 +902,7 @@ __global__ __launch_bounds__(64) void k_expand(Dev d, GameCfg c, MctsCfg mc, Inf
   __shared__ Sh s;
   int g = g0 + blockIdx.x, lane = threadIdx.x;
   if (d.ended[g]) return;
+  if (d.cap_budget && d.cap_budget[g] <= d.cap_i0) return;   // playout cap, tail step: this game's search is over (every lane is LEAF_NONE)
   int agent = agent_of(d, g);
   int t = agent * d.G + g;
   const size_t q0 = (size_t)g * d.V;
@@ -1037,6 +1089,7 @@ __global__ __launch_bounds__(64) void k_expand(Dev d, GameCfg c, MctsCfg mc, Inf
 // AGZ_TARGET_REFERENCE records the Policies row below.  AGZ_TARGET_VISITS records the root's visit distribution instead,
 // pi(a) ~ N(a)^(1/ttau), on every searched ply whose root has a visited child — a ply that chose Pass or Resign included.
 // Only the row and the number of rows differ: the move, the sort, the RNG draws, the trees and cachedPolicies are the same.
+// d.cap_kind (agz_arena_set_playout_cap, handed in only while that setting is on): a game whose ply was a FAST search records no row.
 __global__ __launch_bounds__(64) void k_end_move(Dev d, GameCfg c, MctsCfg mc, int record, int restart, const int32_t* forced,
                                                  int search_only, int tkind, float ttau) {
   __shared__ Sh s;
@@ -1056,6 +1109,7 @@ __global__ __launch_bounds__(64) void k_end_move(Dev d, GameCfg c, MctsCfg mc, i
   int best = AGZ_PASS;
   float bestScore = 0.f;
   const bool is_forced = forced != nullptr;
+  if (d.cap_kind && d.cap_kind[g] == cap::FAST) record = 0;   // playout cap: a fast search records no row, under either target kind
   if (is_forced) {
     n = 0; record = 0;
     best = forced[g];
@@ -1438,6 +1492,15 @@ struct agz_arena {
   bool in_move = false;
   agz_noise_conf noise{0.25f, 0.3f, 0, 0};   // agz_arena_set_root_noise; the caller's configuration, not in a checkpoint
   agz_target_conf target{AGZ_TARGET_REFERENCE, 1.0f, {0, 0}};   // agz_arena_set_policy_target; likewise
+  // agz_arena_set_playout_cap (cap.hpp); the caller's configuration, not in a checkpoint.  The buffers are allocated when the setting is
+  // first turned on and reach the kernels through Dev copies (cap_dev), never through `d`
+  agz_playout_cap_conf cap{0.25f, 0, 0, 0, 0};
+  CapBufs cap_b{};
+  bool cap_compact = true;                        // agz_arena_set_cap_compact (agz_debug.h)
+  int cap_n_full = 0;                             // unfinished FULL games of the current move (read back by prepareRoot's step)
+  int last_cap_batch = 0, last_cap_games = 0;     // network batch / still-searching games of the last step if it was a tail step, else 0
+  Dev cap_dev() const { Dev x = d; if (cap.on) x.cap_kind = cap_b.kind; return x; }   // what k_root_noise and k_end_move get
+  int cap_clear();                                // counts = 0, every kind = -1 (reset / load)
   bool restart = false;  // continuous self-play: finished games restart immediately
   int moves_done = 0;
   // AGZ_INF_CALLBACK (mcts.Inferencer as a host function, mcts/mcts.go:15-18): the callee, its policy width, page-locked staging
@@ -1483,7 +1546,7 @@ struct agz_arena {
   int cb_setup();                    // (re)allocate the callback staging for G * V leaves
   int cb_run(int nl);                // leaves of callback agents -> host function -> d_policy / d_value
   int update_slots();
-  int nn_step(int prep, int nl = 1);   // nl lanes per tree in this round (<= d.V)
+  int nn_step(int prep, int nl = 1, int cap_i0 = -1);   // nl lanes per tree in this round (<= d.V); cap_i0 >= 0: a playout-cap TAIL step whose first lane is simulation cap_i0 of the move
   // Split step (agz_arena_set_split, agz_debug.h): games [0, G/2) and [G/2, G) as two pipelines on the context's two queues
   int split_mode = 1;                  // 0: joined step; 1: split, free-running after the first step's skew; 2: split, skew held by two events per step
   bool last_step_split = false;
@@ -1759,12 +1822,27 @@ int agz_arena::nn_step_split() {
   return AGZ_OK;
 }
 
-int agz_arena::nn_step(int prep, int nl) {
-  if (prep == 0 && nl == 1 && split_eligible()) {
+int agz_arena::nn_step(int prep, int nl, int cap_i0) {
+  const bool tail = cap_i0 >= 0;
+  last_cap_batch = 0; last_cap_games = 0;
+  if (prep == 0 && nl == 1 && !tail && split_eligible()) {
     last_step_split = true; split_steps++;
     return nn_step_split();
   }
   if (!prep) { last_step_split = false; joined_steps++; }
+  // Playout cap, tail step (simulation index past fast_budget): the joined step with the budgets handed to its kernels — a game runs the
+  // lanes its budget leaves, the others are LEAF_NONE.  One lane, one shared network and a smaller batch with the whole batch's kernels
+  // (agz_net::min_same_batch): the still-searching games take batch slots of their own, cap_b.slot, the trick prep_slot uses below
+  Dev ds = d;                      // what the step's kernels get
+  int tail_batch = 0;              // > 0: the compacted tail batch
+  if (tail) {
+    ds.cap_budget = cap_b.budget; ds.cap_i0 = cap_i0;
+    last_cap_games = cap_n_full; last_cap_batch = G * nl;
+    if (cap_compact && nl == 1 && d.V == 1 && !d.cb_mask && inf_kind[0] == AGZ_INF_NET && inf_kind[1] == AGZ_INF_NET && net[0] == net[1] && cap_n_full >= 1 && cap_n_full < G) {
+      const int nb = net[0]->min_same_batch(cap_n_full, G);
+      if (nb < G) { tail_batch = nb; last_cap_batch = nb; ds.slot_of_game = cap_b.slot; }
+    }
+  }
   // select -> network -> expand, all asynchronous on the ctx stream
   float* act0 = nullptr; float* act1 = nullptr;
   const size_t slot_elems = (size_t)(gc.m + 2) * (gc.n + 2) * 32;
@@ -1775,10 +1853,10 @@ int agz_arena::nn_step(int prep, int nl) {
   {
     ProfScope ps(ctx, AGZ_PROF_SELECT);
     if (split_lanes) {
-      hipLaunchKernelGGL(k_select_paths, dim3(G), dim3(64), 0, ctx->stream, d, gc, mc, prep, nl);
-      hipLaunchKernelGGL(k_leaf, dim3(G * nl), dim3(64), 0, ctx->stream, d, gc, mc, act0, act1, prep, nl);
+      hipLaunchKernelGGL(k_select_paths, dim3(G), dim3(64), 0, ctx->stream, ds, gc, mc, prep, nl);
+      hipLaunchKernelGGL(k_leaf, dim3(G * nl), dim3(64), 0, ctx->stream, ds, gc, mc, act0, act1, prep, nl);
     } else {
-      hipLaunchKernelGGL(k_select, dim3(G), dim3(64), 0, ctx->stream, d, gc, mc, act0, act1, prep, nl, 0);
+      hipLaunchKernelGGL(k_select, dim3(G), dim3(64), 0, ctx->stream, ds, gc, mc, act0, act1, prep, nl, 0);
     }
   }
   // prepareRoot evaluates the network only for a root without children (search.go:392-408).  With tree reuse that is the rare
@@ -1786,9 +1864,11 @@ int agz_arena::nn_step(int prep, int nl) {
   bool need_forward = true;
   int prep_batch = 0;              // > 0: prepareRoot's network batch, packed to the front (k_prep_compact)
   if (prep) {
-    unsigned long long cnt = 0;
+    unsigned long long cnt = 0, n_full = 0;
     AGZ_HIP_TRY(hipMemcpyAsync(&cnt, d.counters + CNT_PREP_EXPAND, 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (cap.on) AGZ_HIP_TRY(hipMemcpyAsync(&n_full, cap_b.counts + 2, 8, hipMemcpyDeviceToHost, ctx->stream));   // playout cap: this move's FULL games, on the same synchronisation
     AGZ_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    cap_n_full = (int)n_full;
     need_forward = cnt != prep_expand_seen;
     const unsigned long long n_need = cnt - prep_expand_seen;
     prep_expand_seen = cnt;
@@ -1804,7 +1884,7 @@ int agz_arena::nn_step(int prep, int nl) {
       }
     }
   }
-  Dev dx = d;                      // what k_expand reads its network rows through
+  Dev dx = ds;                     // what k_expand reads its network rows through
   if (prep_batch > 0) dx.slot_of_game = d.prep_slot;
   InfDesc inf{};
   for (int a = 0; a < 2; a++) {
@@ -1826,7 +1906,7 @@ int agz_arena::nn_step(int prep, int nl) {
     agz_net* n = inf_kind[0] == AGZ_INF_NET ? net[0] : (inf_kind[1] == AGZ_INF_NET ? net[1] : nullptr);
     if (n) {
       int a = inf_kind[0] == AGZ_INF_NET ? 0 : 1;
-      int r = n->forward_packed(prep_batch > 0 ? prep_batch : G * nl, d_policy[a], d_value[a]);   // lane-major slots: one dense batch
+      int r = n->forward_packed(prep_batch > 0 ? prep_batch : (tail_batch > 0 ? tail_batch : G * nl), d_policy[a], d_value[a]);   // lane-major slots: one dense batch
       if (r != AGZ_OK) return r;
       if (inf_kind[0] == AGZ_INF_NET && inf_kind[1] == AGZ_INF_NET) { inf.policy[1] = d_policy[0]; inf.value[1] = d_value[0]; }
     }
@@ -2188,10 +2268,102 @@ int agz_visit_target_of(const int32_t* moves, const uint32_t* visits, int n, int
   return AGZ_OK;
 }
 
+// Playout cap (BUILD EXTENSION, DESIGN.md §2 playout-cap; cap.hpp holds the definition): the setting lives in the arena; the per-game
+// buffers and the counts are allocated when it is first turned on.  It is not part of an arena checkpoint: the caller re-applies it after
+// agz_arena_load.
+static bool cap_p_ok(float p) { return p >= 0.f && p <= 1.f; }   // (NaN fails every comparison)
+int agz_arena_set_playout_cap(agz_arena* a, const agz_playout_cap_conf* conf) {
+  AGZ_REQUIRE(a, AGZ_E_INVALID, "arena is NULL");
+  AGZ_REQUIRE(conf && (conf->on == 0 || conf->on == 1) && cap_p_ok(conf->p_full) && conf->reserved == 0, AGZ_E_INVALID,
+              "agz_arena_set_playout_cap: on in {0,1}, 0 <= p_full <= 1, reserved == 0 (on %d, p_full %g, reserved %d)", conf ? conf->on : -1,
+              conf ? (double)conf->p_full : 0.0, conf ? conf->reserved : -1);
+  AGZ_REQUIRE(!(conf->on && a->mc.Budget <= 0), AGZ_E_UNSUPPORTED, "agz_arena_set_playout_cap: the arena has no simulation budget to cap (mcts.Budget %d)", a->mc.Budget);
+  AGZ_REQUIRE(!conf->on || (conf->fast_budget >= 1 && conf->fast_budget <= a->mc.Budget), AGZ_E_INVALID,
+              "agz_arena_set_playout_cap: 1 <= fast_budget <= mcts.Budget (fast_budget %d, Budget %d)", conf->fast_budget, a->mc.Budget);
+  AGZ_REQUIRE(!a->in_move, AGZ_E_STATE, "agz_arena_set_playout_cap: a search is in progress");
+  if (conf->on && !a->cap_b.kind) {
+    AGZ_HIP_TRY(hipSetDevice(a->ctx->device));
+    CapBufs b{};
+    const size_t G = (size_t)a->G;
+    int r;
+    if ((r = a->alloc(&b.budget, G)) != AGZ_OK || (r = a->alloc(&b.slot, G)) != AGZ_OK || (r = a->alloc(&b.ply, G)) != AGZ_OK ||
+        (r = a->alloc(&b.key, G)) != AGZ_OK || (r = a->alloc(&b.counts, 3)) != AGZ_OK || (r = a->alloc(&b.kind, G)) != AGZ_OK)
+      return r;
+    a->cap_b = b;
+    if ((r = a->cap_clear()) != AGZ_OK) return r;
+  }
+  a->cap = *conf;
+  return AGZ_OK;
+}
+int agz_arena::cap_clear() {
+  if (!cap_b.kind) return AGZ_OK;
+  AGZ_HIP_TRY(hipMemsetAsync(cap_b.kind, 0xFF, (size_t)G * sizeof(int32_t), ctx->stream));
+  AGZ_HIP_TRY(hipMemsetAsync(cap_b.budget, 0, (size_t)G * sizeof(int32_t), ctx->stream));
+  AGZ_HIP_TRY(hipMemsetAsync(cap_b.ply, 0, (size_t)G * sizeof(int32_t), ctx->stream));
+  AGZ_HIP_TRY(hipMemsetAsync(cap_b.key, 0, (size_t)G * sizeof(uint64_t), ctx->stream));
+  AGZ_HIP_TRY(hipMemsetAsync(cap_b.counts, 0, 3 * sizeof(unsigned long long), ctx->stream));
+  return AGZ_OK;
+}
+int agz_arena_get_playout_cap(agz_arena* a, agz_playout_cap_conf* out) {
+  AGZ_REQUIRE(a && out, AGZ_E_INVALID, "agz_arena_get_playout_cap: NULL argument");
+  *out = a->cap;
+  return AGZ_OK;
+}
+int agz_arena_playout_cap(agz_arena* a, int g, uint64_t* key, int32_t* ply, int32_t* kind, int32_t* budget) {
+  AGZ_REQUIRE(a, AGZ_E_INVALID, "arena is NULL");
+  AGZ_REQUIRE(g >= 0 && g < a->G, AGZ_E_INVALID, "agz_arena_playout_cap: game %d (of %d)", g, a->G);
+  uint64_t k = 0;
+  int32_t v[3] = {0, -1, 0};   // ply, kind, budget
+  if (a->cap_b.kind) {         // (the setting was never on: no decision, nothing to read back)
+    AGZ_HIP_TRY(hipSetDevice(a->ctx->device));
+    hipStream_t s = a->ctx->stream;
+    AGZ_HIP_TRY(hipMemcpyAsync(&k, a->cap_b.key + g, 8, hipMemcpyDeviceToHost, s));
+    AGZ_HIP_TRY(hipMemcpyAsync(&v[0], a->cap_b.ply + g, 4, hipMemcpyDeviceToHost, s));
+    AGZ_HIP_TRY(hipMemcpyAsync(&v[1], a->cap_b.kind + g, 4, hipMemcpyDeviceToHost, s));
+    AGZ_HIP_TRY(hipMemcpyAsync(&v[2], a->cap_b.budget + g, 4, hipMemcpyDeviceToHost, s));
+    AGZ_HIP_TRY(hipStreamSynchronize(s));
+  }
+  if (key) *key = k;
+  if (ply) *ply = v[0];
+  if (kind) *kind = v[1];
+  if (budget) *budget = v[2];
+  return AGZ_OK;
+}
+int agz_arena_playout_cap_counts(agz_arena* a, int64_t* full_plies, int64_t* fast_plies) {
+  AGZ_REQUIRE(a, AGZ_E_INVALID, "arena is NULL");
+  unsigned long long c[2] = {0, 0};
+  if (a->cap_b.counts) {
+    AGZ_HIP_TRY(hipSetDevice(a->ctx->device));
+    AGZ_HIP_TRY(hipMemcpyAsync(c, a->cap_b.counts, sizeof(c), hipMemcpyDeviceToHost, a->ctx->stream));
+    AGZ_HIP_TRY(hipStreamSynchronize(a->ctx->stream));
+  }
+  if (full_plies) *full_plies = (int64_t)c[0];
+  if (fast_plies) *fast_plies = (int64_t)c[1];
+  return AGZ_OK;
+}
+// The same definition without a context or a device.
+int agz_playout_cap_of(uint64_t seed, uint64_t key, int32_t ply, float p_full, int32_t* kind) {
+  AGZ_REQUIRE(kind && ply >= 0 && cap_p_ok(p_full), AGZ_E_INVALID, "agz_playout_cap_of: ply >= 0, 0 <= p_full <= 1, kind != NULL (ply %d, p_full %g)", ply,
+              (double)p_full);
+  *kind = cap::kind_of(seed, key, ply, cap::threshold(p_full));
+  return AGZ_OK;
+}
+int agz_arena_set_cap_compact(agz_arena* a, int on) {
+  AGZ_REQUIRE(a, AGZ_E_INVALID, "arena is NULL");
+  a->cap_compact = on != 0;
+  return AGZ_OK;
+}
+int agz_arena_last_cap_batch(agz_arena* a, int* boards, int* games) {
+  AGZ_REQUIRE(a && boards && games, AGZ_E_INVALID, "agz_arena_last_cap_batch: NULL argument");
+  *boards = a->last_cap_batch; *games = a->last_cap_games;
+  return AGZ_OK;
+}
+
 int agz_arena_reset(agz_arena* a, const uint8_t* a_is_black) {
   AGZ_REQUIRE(a, AGZ_E_INVALID, "arena is NULL");
   AGZ_HIP_TRY(hipSetDevice(a->ctx->device));
   hipStream_t s = a->ctx->stream;
+  { int r = a->cap_clear(); if (r != AGZ_OK) return r; }
   uint8_t* dab = nullptr;
   if (a_is_black) {
     AGZ_HIP_TRY(hipMalloc(&dab, a->G));
@@ -2219,7 +2391,11 @@ int agz_arena_begin_move(agz_arena* a) {
   {
     ProfScope ps(a->ctx, AGZ_PROF_MOVE);
     hipLaunchKernelGGL(k_begin_move, dim3(a->G), dim3(64), 0, a->ctx->stream, a->d, a->gc, a->mc);
+    if (a->cap.on)   // playout cap: this ply's kind and budget per game, one small launch, only while the setting is on
+      hipLaunchKernelGGL(k_cap_decide, dim3(1), dim3(64), 0, a->ctx->stream, a->d, a->cap_b, (unsigned long long)a->cap.seed, cap::threshold(a->cap.p_full),
+                         a->cap.fast_budget, a->mc.Budget);
   }
+  a->cap_n_full = 0;
   a->in_move = true;
   a->sims_this_move = 0; a->room_sims = 0;
   if (a->pool_grow) {   // room for this move's search before its first expansion (prepareRoot's): AGZ_POOL_GROW
@@ -2231,7 +2407,7 @@ int agz_arena_begin_move(agz_arena* a) {
   int r = a->nn_step(1);  // prepareRoot
   if (r == AGZ_OK && a->noise.on) {   // root noise on the priors prepareRoot left (or tree reuse kept): one launch, only while the setting is on
     ProfScope ps(a->ctx, AGZ_PROF_MOVE);
-    hipLaunchKernelGGL(k_root_noise, dim3(a->G), dim3(64), 0, a->ctx->stream, a->d, a->gc, a->noise.eps, a->noise.alpha);
+    hipLaunchKernelGGL(k_root_noise, dim3(a->G), dim3(64), 0, a->ctx->stream, a->cap_dev(), a->gc, a->noise.eps, a->noise.alpha);
     AGZ_HIP_TRY(hipGetLastError());
   }
   return r;
@@ -2289,11 +2465,20 @@ int agz_arena_simulate(agz_arena* a, int k) {
     if (r != AGZ_OK) return r;
     a->room_sims = a->sims_this_move + k;
   }
+  const long long first = a->sims_this_move;   // the move's simulation index of this call's first simulation
   a->sims_this_move += k;
   // k simulations per tree, in rounds of up to V lanes (agz_arena_set_parallel; V = 1: one at a time)
   for (int done = 0; done < k;) {
     int nl = std::min(a->d.V, k - done);
-    int r = a->nn_step(0, nl);
+    // playout cap: while every lane of the round lies within fast_budget all games search and the step is what it is without the setting
+    // (the split step included).  A round that reaches past it is a tail step: the FAST games run the lanes fast_budget leaves them (a
+    // lane round may straddle it), then none.  It is the ordinary step again while every game is FULL and within Budget, and no step at
+    // all once the round starts at or past fast_budget and the move has no FULL game
+    const long long i0 = first + done;
+    const bool all_full = a->cap_n_full == a->G && i0 + nl <= a->mc.Budget;
+    const bool tail = a->cap.on && i0 + nl > a->cap.fast_budget && !all_full;
+    if (tail && a->cap_n_full == 0 && i0 >= a->cap.fast_budget) { a->last_cap_batch = 0; a->last_cap_games = 0; done += nl; continue; }
+    int r = a->nn_step(0, nl, tail ? (int)std::min<long long>(i0, INT_MAX) : -1);
     if (r != AGZ_OK) return r;
     done += nl;
   }
@@ -2306,7 +2491,7 @@ int agz_arena_end_move(agz_arena* a, int record) {
   AGZ_HIP_TRY(hipSetDevice(a->ctx->device));
   {
     ProfScope ps(a->ctx, AGZ_PROF_MOVE);
-    hipLaunchKernelGGL(k_end_move, dim3(a->G), dim3(64), 0, a->ctx->stream, a->d, a->gc, a->mc, record, a->restart ? 1 : 0, (const int32_t*)nullptr, 0,
+    hipLaunchKernelGGL(k_end_move, dim3(a->G), dim3(64), 0, a->ctx->stream, a->cap_dev(), a->gc, a->mc, record, a->restart ? 1 : 0, (const int32_t*)nullptr, 0,
                        a->target.kind, a->target.temperature);
   }
   AGZ_HIP_TRY(hipGetLastError());
@@ -2895,6 +3080,7 @@ int agz_arena_load(agz_arena* a, const char* path) {
   }
   if (r == AGZ_OK) r = a->ckpt_apply(f, sc);
   fclose(f);
+  if (r == AGZ_OK) r = a->cap_clear();   // playout cap: the counts and the observer's record start anew (neither is in the file)
   return r;
 }
 

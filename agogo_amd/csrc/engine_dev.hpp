@@ -15,6 +15,7 @@
 #include <cstdint>
 
 #include "../../include/agz.h"
+#include "cap.hpp"
 #include "noise.hpp"
 #include "sym.hpp"
 #include "target.hpp"
@@ -143,6 +144,11 @@ struct Dev {
   int32_t* noise_move;    // [T][noise_stride] their moves in the block order of that moment
   float* noise_eta;       // [T][noise_stride] and their eta
   int noise_stride;       // A + 1
+  // ---- playout cap (agz_arena_set_playout_cap, cap.hpp).  The arena's own Dev keeps all three nullptr: the buffers live in the arena and
+  // are handed out in the Dev COPY of the launches that need them, so every other launch is what it is without the setting
+  const int32_t* cap_kind;    // [G] AGZ_CAP_FULL / AGZ_CAP_FAST of the ply being searched (k_cap_decide): k_root_noise and k_end_move while the setting is on
+  const int32_t* cap_budget;  // [G] simulations of this move's search: the step kernels of a TAIL step only (simulation index past fast_budget)
+  int cap_i0;                 // the simulation index of the round's first lane: game g runs clamp(cap_budget[g] - cap_i0, 0, nl) lanes
 };
 
 enum { CNT_SIMS = 0, CNT_NONNULL = 1, CNT_EVALS = 2, CNT_MOVES = 3, CNT_GAMES = 4, CNT_EXAMPLES = 5, CNT_FULL = 6, CNT_A_WINS = 7, CNT_B_WINS = 8,

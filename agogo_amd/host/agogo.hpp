@@ -211,6 +211,13 @@ struct Arena {
     const agz_target_conf conf = {kind, temperature, {0, 0}};
     agz::check(agz_arena_set_policy_target(h, &conf), "SetPolicyTarget");
   }
+  // build extension: playout cap randomization (agz_arena_set_playout_cap): every ply of every game is a full search (Budget simulations,
+  // root noise, a recorded row) with probability p_full, else a fast one (fast_budget simulations, no noise, no row); default off.  Not in a
+  // checkpoint: set it again after Load.
+  void SetPlayoutCap(float p_full, int fast_budget, uint64_t seed = 0, bool on = true) {
+    const agz_playout_cap_conf conf = {p_full, fast_budget, on ? 1 : 0, 0, seed};
+    agz::check(agz_arena_set_playout_cap(h, &conf), "SetPlayoutCap");
+  }
   void Opponent(const std::vector<int32_t>& moves) { agz::check(agz_arena_apply_moves(h, moves.data()), "opponent move"); }
   // Checkpoint of the running arena between two moves, and the continuation from one (agz_arena_save / agz_arena_load): games, trees, RNG
   // states, counters, examples.  The agents, the lanes and the pool policy are not in the file: set them again as they were.
@@ -311,6 +318,12 @@ struct Config {
   // evaluation arena records nothing.  Like Loss, neither field is in a SaveRun file (AGZRUN01 unchanged)
   int PolicyTarget = AGZ_TARGET_REFERENCE;
   float TargetTemperature = 1.f;
+  // build extension: playout cap randomization of the SELF-PLAY arena (Arena::SetPlayoutCap): PlayoutCapFastBudget = 0 (default) means off,
+  // otherwise a ply is a full search of MCTSConf.Budget simulations with probability PlayoutCapFull and a fast one of PlayoutCapFastBudget
+  // simulations — without root noise and without a recorded row — otherwise.  The evaluation arena always searches in full.  Like Loss and
+  // PolicyTarget, neither field is in a SaveRun file (AGZRUN01 unchanged): a resumed run plays under the Config its AZ was constructed with
+  int PlayoutCapFastBudget = 0;
+  float PlayoutCapFull = 0.25f;
   // build extension: train from a replay window instead of one epoch's examples.  ReplayWindow = rows the window keeps across epochs; 0
   // (default) = off, AZ.Learn exactly as the reference has it.  ReplaySteps = minibatches per epoch; 0 = (live rows / BatchSize) * nniters.
   // ReplaySymmetric = every sampled row under one of the eight board symmetries, chosen per draw; the materialising augmenters
@@ -395,6 +408,7 @@ struct AZ {
         if (conf.LeafSymmetry != AGZ_SYM_OFF) sp.SetLeafSymmetry(conf.LeafSymmetry, seed + 1000 * epoch + 1);
         if (conf.RootNoiseEps > 0.f) sp.SetRootNoise(conf.RootNoiseEps, conf.RootNoiseAlpha);
         if (conf.PolicyTarget != AGZ_TARGET_REFERENCE) sp.SetPolicyTarget(conf.PolicyTarget, conf.TargetTemperature);
+        if (conf.PlayoutCapFastBudget > 0) sp.SetPlayoutCap(conf.PlayoutCapFull, conf.PlayoutCapFastBudget, seed + 1000 * epoch + 2);
         sp.PlayOnDevice(true);                                            // episodes x SelfPlay(), agogo.go:110-114
         ex.Append(sp);                                                     // device to device, episode after episode
       }

@@ -580,6 +580,19 @@ func VisitTargetOf(moves []int32, visits []uint32, actionSpace int, temperature 
 	return row, nil
 }
 
+// SetPlayoutCap turns playout cap randomization on or off (agz_arena_set_playout_cap): while on, every ply of every game is a full
+// search — the configured Budget, root noise, a recorded row — with probability pFull and otherwise a fast search of fastBudget
+// simulations without root noise and without a row (0 <= pFull <= 1, 1 <= fastBudget <= Budget).  The decision is a function of seed,
+// the game slot's key and the ply.  Off by default; between moves.  The setting is not part of a checkpoint: set it again after Load.
+func (a *BatchedArena) SetPlayoutCap(pFull float32, fastBudget int, seed uint64, on bool) error {
+	defer a.ctx.enter()()
+	conf := C.agz_playout_cap_conf{p_full: C.float(pFull), fast_budget: C.int32_t(fastBudget), seed: C.uint64_t(seed)}
+	if on {
+		conf.on = 1
+	}
+	return lastErr(C.agz_arena_set_playout_cap(a.h, &conf))
+}
+
 // Save writes a checkpoint of the running arena — games, both trees of every game, RNG states, counters, recorded examples — between two
 // moves (agz_arena_save).  The file replaces `path` only once it is complete.
 func (a *BatchedArena) Save(path string) error {

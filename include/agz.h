@@ -612,6 +612,53 @@ int agz_arena_get_policy_target(agz_arena* arena, agz_target_conf* out);
  * NULL pointer, n or action_space outside [1, 4096], a move that is neither in [0, action_space) nor AGZ_PASS, a move given twice, a
  * temperature that is not finite and > 0, and visits that are all 0. */
 int agz_visit_target_of(const int32_t* moves, const uint32_t* visits, int n, int action_space, float temperature, float* row);
+/* BUILD EXTENSION (no mcts.Config field; DESIGN.md §2 playout-cap): playout cap randomization, KataGo's remedy for self-play that pays
+ * the whole Budget on every ply whether or not its row is worth training on.  Opt-in, default off; off (or never called) is everything
+ * as without this call, bit for bit and launch for launch: no allocation, no read-back, no load in the step's kernels.  While on, every
+ * ply of every game is, with probability p_full, a FULL search — mcts.Budget simulations, root noise (if that setting is on), a recorded
+ * row (if the move records) — and otherwise a FAST search: fast_budget simulations, no root noise (no key is drawn), no row under either
+ * policy-target kind.  Everything else of a ply is the same for both kinds: the move choice, randomizeChildren, cachedPolicies, Apply,
+ * Ended, labelling and restart.
+ * The definition (one copy, csrc/cap.hpp; integer and bit operations only):
+ *   mix64     the SplitMix64 finaliser: z = (z^(z>>30))*0xBF58476D1CE4E5B9; z = (z^(z>>27))*0x94D049BB133111EB; z ^= z>>31
+ *   z         mix64(seed ^ mix64(key + 0x9E3779B97F4A7C15 * (uint64)(ply + 1)))
+ *   thr       (uint32)(p_full * 16777216.0f)       the product is exact; p_full = 1 gives 2^24 (always FULL), p_full = 0 gives 0 (always FAST)
+ *   kind      AGZ_CAP_FULL if (uint32)(z >> 40) < thr, else AGZ_CAP_FAST
+ *   budget    FULL: mcts.Budget      FAST: fast_budget
+ * key is the game slot's own key (seeded at reset, advanced when the slot restarts in agz_arena_selfplay, stored in arena checkpoints)
+ * and ply the number of moves of the game, both as they stand at agz_arena_begin_move; one small launch there makes the decisions.  No
+ * RNG stream is consumed: the decision is a pure function of checkpointed state and the setting, so plies advanced from outside
+ * (agz_arena_apply_moves, agz_arena_random_moves, agz_arena_set_state) need nothing — the next decision follows from the ply.
+ * agz_arena_simulate(k) advances a per-move simulation index i; game g takes part in simulation i iff i < budget[g].  In a round of nl
+ * lanes (agz_arena_set_parallel) that starts at index i0 game g runs clamp(budget[g] - i0, 0, nl) lanes; sims_total counts the
+ * simulations actually run.  agz_arena_play and agz_arena_selfplay keep calling agz_arena_simulate(Budget), AGZ_POOL_GROW keeps sizing
+ * for Budget.  While a round ends within fast_budget every game is active and the step is the one of an arena without the setting, the
+ * split step included; so it is while every game of the arena is an unfinished FULL one.  Otherwise a round that reaches past
+ * fast_budget is a tail step (a lane round may straddle fast_budget: the FAST games run the lanes it leaves them), and from
+ * fast_budget on only the FULL games search: with none of them the remaining steps of the move are not enqueued at all; with one lane,
+ * both agents on one shared net and a smaller batch that runs the whole batch's kernels (agz_net_min_same_batch) the FULL games are
+ * packed to the front of the network batch, each board's result being the bit pattern the whole-arena batch gives; every other
+ * configuration (lanes, two nets, callbacks, synthetic inferencers, no such smaller batch) runs those steps on the whole batch — the
+ * same results and no time saved; where the arena would otherwise take the split step, slightly slower (a tail step is always the
+ * joined step).  A game's search therefore never depends on what the other games drew.
+ * Nothing is added to an arena checkpoint (AGZARN01 unchanged): re-apply the setting after agz_arena_load and the continuation is bit
+ * for bit; until then searches are full searches.  The single-tree agz_mcts_* handle is not covered and keeps full searches.
+ * AGZ_E_INVALID, with the setting unchanged, unless on is 0 or 1, 0 <= p_full <= 1 (finite), reserved == 0 and, when on is 1,
+ * 1 <= fast_budget <= mcts.Budget; AGZ_E_UNSUPPORTED when on is 1 and mcts.Budget <= 0; AGZ_E_STATE inside a move. */
+#define AGZ_CAP_FULL 0
+#define AGZ_CAP_FAST 1
+typedef struct agz_playout_cap_conf { float p_full; int32_t fast_budget; int32_t on; int32_t reserved; uint64_t seed; } agz_playout_cap_conf; /* 24 bytes; defaults 0.25, 0, 0, 0, 0 */
+int agz_arena_set_playout_cap(agz_arena* arena, const agz_playout_cap_conf* conf);
+int agz_arena_get_playout_cap(agz_arena* arena, agz_playout_cap_conf* out);
+/* The decision of game g's current / last searched ply: the key and the ply it was made from, its kind and its budget (any pointer may
+ * be NULL).  kind = -1 (key, ply, budget 0) before the game's first agz_arena_begin_move under the setting, after a reset and a load. */
+int agz_arena_playout_cap(agz_arena* arena, int g, uint64_t* key, int32_t* ply, int32_t* kind, int32_t* budget);
+/* Plies searched under each kind since the last reset / load (a small device buffer of its own: NOT in agz_arena_stats, NOT in a
+ * checkpoint); either pointer may be NULL. */
+int agz_arena_playout_cap_counts(agz_arena* arena, int64_t* full_plies, int64_t* fast_plies);
+/* The same definition without a context or a device: the kind of ply `ply` of the slot with key `key`.  AGZ_E_INVALID unless ply >= 0,
+ * 0 <= p_full <= 1 and kind != NULL. */
+int agz_playout_cap_of(uint64_t seed, uint64_t key, int32_t ply, float p_full, int32_t* kind);
 int agz_arena_begin_move(agz_arena* arena);
 int agz_arena_simulate(agz_arena* arena, int k);
 int agz_arena_end_move(agz_arena* arena, int record);

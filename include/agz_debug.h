@@ -72,6 +72,14 @@ int agz_net_wino_h2_last_rows(agz_net* net, int* live_r, int* live_c);
 int agz_arena_set_prep_compact(agz_arena* arena, int on);
 int agz_arena_last_prep_batch(agz_arena* arena, int* boards, int* roots);
 
+/* Playout cap (agz_arena_set_playout_cap): past fast_budget only the FULL games of a move still search.  With one lane, one shared net and a
+ * smaller batch that takes the whole batch's kernels, such a tail step packs them to the front of the network batch (per board the results
+ * are bit-identical); on = 0 keeps the whole-arena batch (A/B and parity hook), default on.  agz_arena_last_cap_batch: the network batch
+ * (boards) and the number of still-searching games of the last simulation step if it was a tail step; both 0 when it was not (a step within
+ * fast_budget, prepareRoot, or a move without FULL games, whose tail is not enqueued). */
+int agz_arena_set_cap_compact(agz_arena* arena, int on);
+int agz_arena_last_cap_batch(agz_arena* arena, int* boards, int* games);
+
 /* The split step.  Where one shared AGZ_INF_NET net runs the chained AGZ_COMPUTE_WINO_H2 tower of the arena's batch as two half-batch chains
  * on two queues (agz_net_set_tower_queues != 1, from 256 games by default), no lane rounds, no callback inferencer and no kernel-class
  * timer other than AGZ_PROF_MOVE running, agz_arena_simulate enqueues games [0, G/2) and [G/2, G) as two pipelines — select, network half,
