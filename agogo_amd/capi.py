@@ -92,6 +92,11 @@ class PlayoutCapConf(C.Structure):
     _fields_ = [("p_full", C.c_float), ("fast_budget", C.c_int32), ("on", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_uint64)]
 
 
+class ForcedConf(C.Structure):
+    """agz_forced_conf (include/agz.h): forced playouts at the root with coefficient k, and the pruned policy target; 16 bytes"""
+    _fields_ = [("k", C.c_float), ("on", C.c_int32), ("prune", C.c_int32), ("reserved", C.c_int32)]
+
+
 class ArenaStats(C.Structure):
     _fields_ = [("sims_total", C.c_int64), ("sims_nonnull", C.c_int64), ("nn_evals", C.c_int64),
                 ("moves_played", C.c_int64), ("games_finished", C.c_int64), ("examples", C.c_int64),
@@ -272,6 +277,11 @@ def lib():
     sig("agz_arena_playout_cap", i32, vp, i32, pu64, pi32, pi32, pi32)
     sig("agz_arena_playout_cap_counts", i32, vp, pi64, pi64)
     sig("agz_playout_cap_of", i32, u64, u64, C.c_int32, C.c_float, pi32)
+    pfc, pu8, pu32 = C.POINTER(ForcedConf), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
+    sig("agz_arena_set_forced_playouts", i32, vp, pfc)
+    sig("agz_arena_get_forced_playouts", i32, vp, pfc)
+    sig("agz_root_select_of", i32, pu32, pf, pf, pu8, i32, i32, C.c_float, C.c_float, C.POINTER(C.c_int), C.POINTER(C.c_int))
+    sig("agz_pruned_target_of", i32, pi, pu32, pf, pf, i32, i32, i32, C.c_float, C.c_float, C.c_float, pu32, pf)
     ptc = C.POINTER(TargetConf)
     sig("agz_arena_set_policy_target", i32, vp, ptc)
     sig("agz_arena_get_policy_target", i32, vp, ptc)
@@ -1006,6 +1016,17 @@ class Arena:
         _check(lib().agz_arena_get_playout_cap(self.h, C.byref(conf)), "agz_arena_get_playout_cap")
         return {"p_full": conf.p_full, "fast_budget": conf.fast_budget, "on": bool(conf.on), "seed": conf.seed}
 
+    def set_forced_playouts(self, k=2.0, on=True, prune=True, reserved=0):
+        """forced playouts at the root (a child with n playouts and prior P is selected while n^2 < k P T, T the playouts below the
+        root) and, with prune and TARGET_VISITS, the pruned policy target (include/agz.h); default off"""
+        conf = ForcedConf(k, int(on), int(prune), int(reserved))
+        _check(lib().agz_arena_set_forced_playouts(self.h, C.byref(conf)), "agz_arena_set_forced_playouts")
+
+    def get_forced_playouts(self):
+        conf = ForcedConf()
+        _check(lib().agz_arena_get_forced_playouts(self.h, C.byref(conf)), "agz_arena_get_forced_playouts")
+        return {"k": conf.k, "on": bool(conf.on), "prune": bool(conf.prune)}
+
     def playout_cap(self, g):
         """the decision of game g's current / last searched ply: (key, ply, kind, budget); kind = -1 before the first one"""
         key, ply, kind, budget = C.c_uint64(0), C.c_int32(0), C.c_int32(0), C.c_int32(0)
@@ -1728,6 +1749,38 @@ def playout_cap_of(seed, key, ply, p_full):
     kind = C.c_int32(0)
     _check(lib().agz_playout_cap_of(int(seed) & (2 ** 64 - 1), int(key) & (2 ** 64 - 1), int(ply), p_full, C.byref(kind)), "agz_playout_cap_of")
     return kind.value
+
+
+def root_select_of(visits, black_scores, priors, player, puct, k, marks=None):
+    """(block index, forced) of Node.Select at a root with the forced-playout rule (forced.hpp; host only): the child the device
+    descends to from a root whose read-back is (visits, black_scores, priors); marks = the children's virtual-loss marks in a lane
+    round, None in the sequential search; k = 0 is plain Node.Select"""
+    vis = np.ascontiguousarray(visits, dtype=np.uint32).reshape(-1)
+    bs = np.ascontiguousarray(black_scores, dtype=np.float32).reshape(-1)
+    pr = np.ascontiguousarray(priors, dtype=np.float32).reshape(-1)
+    assert vis.size == bs.size == pr.size
+    mk = None if marks is None else np.ascontiguousarray(marks, dtype=np.uint8).reshape(-1)
+    assert mk is None or mk.size == vis.size
+    idx, forced = C.c_int(0), C.c_int(0)
+    _check(lib().agz_root_select_of(vis.ctypes.data_as(C.POINTER(C.c_uint32)), _pf(bs), _pf(pr),
+                                    None if mk is None else mk.ctypes.data_as(C.POINTER(C.c_uint8)), vis.size, int(player), puct, k,
+                                    C.byref(idx), C.byref(forced)), "agz_root_select_of")
+    return idx.value, bool(forced.value)
+
+
+def pruned_target_of(moves, visits, black_scores, priors, action_space, player, puct, k, temperature=1.0):
+    """(row, pruned playouts) of a root under forced playouts with pruning (forced.hpp; host only): the policy row (action_space + 1
+    floats, Pass last) the device records for a root whose read-back is (moves, visits, black_scores, priors), and n'_i per child"""
+    mv = np.ascontiguousarray(moves, dtype=np.int32).reshape(-1)
+    vis = np.ascontiguousarray(visits, dtype=np.uint32).reshape(-1)
+    bs = np.ascontiguousarray(black_scores, dtype=np.float32).reshape(-1)
+    pr = np.ascontiguousarray(priors, dtype=np.float32).reshape(-1)
+    assert mv.size == vis.size == bs.size == pr.size
+    row = np.zeros(max(int(action_space), 0) + 1, np.float32)
+    npl = np.zeros(max(mv.size, 1), np.uint32)
+    _check(lib().agz_pruned_target_of(_pi(mv), vis.ctypes.data_as(C.POINTER(C.c_uint32)), _pf(bs), _pf(pr), mv.size, int(action_space), int(player),
+                                      puct, k, temperature, npl.ctypes.data_as(C.POINTER(C.c_uint32)), _pf(row)), "agz_pruned_target_of")
+    return row, npl[:mv.size]
 
 
 def visit_target_of(moves, visits, action_space, temperature=1.0):

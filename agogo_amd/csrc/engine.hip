@@ -29,6 +29,7 @@
 #include "atomic_file.hpp"
 #include "ckpt_stream.hpp"
 #include "engine_dev.hpp"
+#include "forced.hpp"
 #include "net.hpp"
 
 namespace agz {
@@ -60,7 +61,10 @@ __device__ __forceinline__ float sqrt_cr(float x) {
 }
 
 // Node.Select: mcts/node.go:170-237.  64 lanes over the contiguous child block; strict '>' keeps the first maximum.
-__device__ int select_child(const Dev& d, size_t base, int off, int n, int player, float PUCT, int lane, bool use_vl, int* move_out = nullptr) {
+// root / fkb: forced playouts (agz_arena_set_forced_playouts, forced.hpp), fkb the bits of the coefficient k >= 0.  fkb == 0 — every
+// launch while the setting is off — leaves ONE wave-uniform branch not taken (a scalar compare of a kernel argument and of the descent's
+// loop counter); everything the rule adds is inside it.  Otherwise, at the root of the descent, a forced child's usa is +INFINITY.
+__device__ int select_child(const Dev& d, size_t base, int off, int n, int player, float PUCT, int lane, bool use_vl, bool root, uint32_t fkb, int* move_out = nullptr) {
   // The whole child block goes to registers in ONE batch of loads (n <= CELLS_PAD: six children per lane): visits, sums, priors,
   // virtual-loss marks and the children's moves — the parent-visit sum and the argmax then run without touching memory again, and the
   // caller gets the chosen child's move with it (the descent was four dependent memory round trips per level; now two).
@@ -83,6 +87,19 @@ __device__ int select_child(const Dev& d, size_t base, int off, int n, int playe
   float numerator = sqrt_cr((float)pv);   // math32.Sqrt (node.go:209): correctly rounded — NOT __fsqrt_rn / sqrtf, see sqrt_cr above
   float best = -INFINITY;
   int idx = -1, mv = 0;
+  if (root && fkb != 0u) {
+    // +INFINITY beats every finite usa and ties go to the lowest block index: each lane starts the argmax from its own lowest forced
+    // child, the scan below (strict '>') leaves it, and the reduction keeps the lowest index among the lanes
+    uint32_t kb = fkb;
+    asm volatile("" : "+s"(kb));                 // keeps the conversion (and its two registers) inside this branch instead of hoisted above the descent
+    const double kd = (double)__uint_as_float(kb);
+    const uint32_t T = pv - (uint32_t)n;         // playouts below the root: every child was created with visits = 1
+#pragma unroll
+    for (int k = PER - 1; k >= 0; k--) {
+      const int i = lane + k * WAVE;
+      if (i < n && forced::is_forced(cv[k], cl[k] ? 1u : 0u, forced::rhs(kd, cp[k], T))) { best = INFINITY; idx = i; mv = cm[k]; }
+    }
+  }
 #pragma unroll
   for (int k = 0; k < PER; k++) {
     const int i = lane + k * WAVE;
@@ -548,7 +565,9 @@ __device__ __forceinline__ int cap_lanes(const Dev& d, int g, size_t q0, int nl,
 // pipeline() descent: mcts/search.go:209-257 up to (and excluding) the network call.
 // prep != 0 runs prepareRoot (search.go:392-408) instead: the root itself is the leaf if it is expandable.
 // g0: first game of this launch (the split step runs the two halves of an arena as launches of their own)
-__global__ __launch_bounds__(64) void k_select(Dev d, GameCfg c, MctsCfg mc, float* act_in0, float* act_in1, int prep, int nl, int g0) {
+// fk: forced playouts at the root, 0 while the setting is off; a game whose ply is a FAST search of the playout cap (d.cap_kind, handed in
+// only while both settings are on) searches without them
+__global__ __launch_bounds__(64) void k_select(Dev d, GameCfg c, MctsCfg mc, float* act_in0, float* act_in1, int prep, int nl, int g0, float fk) {
   __shared__ Sh s;
   int g = g0 + blockIdx.x, lane = threadIdx.x;
   const size_t q0 = (size_t)g * d.V;
@@ -560,6 +579,8 @@ __global__ __launch_bounds__(64) void k_select(Dev d, GameCfg c, MctsCfg mc, flo
   if (d.stalled[t]) { if (lane < nl) { d.leaf_kind[q0 + lane] = LEAF_NULL; d.path_len[q0 + lane] = 0; } return; }
   const bool use_ring = c.encoder == AGZ_ENC_WQ;
   const bool use_vl = d.V > 1;   // lanes of one round see each other's stored virtual loss (oracle: MCTS::parallelRound)
+  uint32_t fkb = __float_as_uint(fk);   // k >= 0: nonzero bits are k > 0, tested with scalar integer compares
+  if (fkb != 0u && d.cap_kind && d.cap_kind[g] == cap::FAST) fkb = 0u;
   size_t base = pool_base(d, t, d.cur_pool[t]);
   for (int l = 0; l < nl; l++) {
     const size_t q = q0 + l;
@@ -594,7 +615,7 @@ __global__ __launch_bounds__(64) void k_select(Dev d, GameCfg c, MctsCfg mc, flo
       int n = d.kids_n[base + node];
       kids_seen += n;
       int mv;
-      int ci = select_child(d, base, off, n, st.to_move, mc.PUCT, lane, use_vl, &mv);
+      int ci = select_child(d, base, off, n, st.to_move, mc.PUCT, lane, use_vl, depth == 1, fkb, &mv);   // the root of the descent (node == 0), as the uniform loop counter
       if (ci < 0) { kind = LEAF_NULL; break; }
       int child = off + ci;
       apply_move(c, d, s, st, mv, use_ring, lane);  // children were created from legal moves of this very state
@@ -642,7 +663,7 @@ __global__ __launch_bounds__(64) void k_select(Dev d, GameCfg c, MctsCfg mc, flo
 // the depth from its length.  Replaying the path on the board, the leaf's legal set, its input planes, and the expansion
 // list (renormalise + stable sort) depend on that lane's path / network row alone: one workgroup per (game, lane).
 // Results are bit-identical to the fused kernels (tests/test_parallel_lanes_gpu.py runs both against the oracle).
-__global__ __launch_bounds__(64) void k_select_paths(Dev d, GameCfg c, MctsCfg mc, int prep, int nl) {
+__global__ __launch_bounds__(64) void k_select_paths(Dev d, GameCfg c, MctsCfg mc, int prep, int nl, float fk) {
   const int g = blockIdx.x, lane = threadIdx.x;
   const size_t q0 = (size_t)g * d.V;
   if (d.ended[g]) { if (lane < nl) d.leaf_kind[q0 + lane] = LEAF_NONE; return; }
@@ -651,6 +672,8 @@ __global__ __launch_bounds__(64) void k_select_paths(Dev d, GameCfg c, MctsCfg m
   const int agent = agent_of(d, g);
   const int t = agent * d.G + g;
   if (d.stalled[t]) { if (lane < nl) { d.leaf_kind[q0 + lane] = LEAF_NULL; d.path_len[q0 + lane] = 0; } return; }
+  uint32_t fkb = __float_as_uint(fk);   // forced playouts (k >= 0: nonzero bits are k > 0): not in a FAST search of the playout cap
+  if (fkb != 0u && d.cap_kind && d.cap_kind[g] == cap::FAST) fkb = 0u;
   const size_t base = pool_base(d, t, d.cur_pool[t]);
   const int to_move0 = d.to_move[g], ply0 = d.ply[g], passes0 = d.passes[g];
   for (int l = 0; l < nl; l++) {
@@ -669,7 +692,7 @@ __global__ __launch_bounds__(64) void k_select_paths(Dev d, GameCfg c, MctsCfg m
       const int n = d.kids_n[base + node];
       kids_seen += n;
       int mv;
-      const int ci = select_child(d, base, off, n, to_move, mc.PUCT, lane, true, &mv);
+      const int ci = select_child(d, base, off, n, to_move, mc.PUCT, lane, true, depth == 1, fkb, &mv);   // the root of the descent (node == 0), as the uniform loop counter
       if (ci < 0) { kind = LEAF_NULL; break; }
       const int child = off + ci;
       // what Apply does to the scalars the descent reads (apply_move): mover, Passes(), move count
@@ -1090,8 +1113,10 @@ __global__ __launch_bounds__(64) void k_expand(Dev d, GameCfg c, MctsCfg mc, Inf
 // pi(a) ~ N(a)^(1/ttau), on every searched ply whose root has a visited child — a ply that chose Pass or Resign included.
 // Only the row and the number of rows differ: the move, the sort, the RNG draws, the trees and cachedPolicies are the same.
 // d.cap_kind (agz_arena_set_playout_cap, handed in only while that setting is on): a game whose ply was a FAST search records no row.
+// pk >= 0: agz_arena_set_forced_playouts with prune on (forced.hpp) — the AGZ_TARGET_VISITS row is built from the pruned playouts n'
+// instead of the visits N; negative (the setting off, prune off, every other launch site): the row as above.
 __global__ __launch_bounds__(64) void k_end_move(Dev d, GameCfg c, MctsCfg mc, int record, int restart, const int32_t* forced,
-                                                 int search_only, int tkind, float ttau) {
+                                                 int search_only, int tkind, float ttau, float pk) {
   __shared__ Sh s;
   __shared__ uint32_t cv[CELLS_PAD];   // child visits
   __shared__ int16_t ckn[CELLS_PAD];   // child kids_n
@@ -1230,9 +1255,33 @@ __global__ __launch_bounds__(64) void k_end_move(Dev d, GameCfg c, MctsCfg mc, i
     const bool by_visits = tkind == AGZ_TARGET_VISITS;   // (a forced move has n == 0 and record == 0)
     float tot = 0.f;
     uint32_t nmax = 0;
+    const uint32_t* tv = cv;   // what the visits row is built from
     if (by_visits) {   // Nmax over the root's children, still in LDS in their pre-sort order (the row does not depend on the order)
       for (int i = lane; i < n; i += WAVE) nmax = cv[i] > nmax ? cv[i] : nmax;
       for (int o = 32; o > 0; o >>= 1) { uint32_t v = __shfl_xor(nmax, o, 64); nmax = v > nmax ? v : nmax; }
+      if (pk >= 0.f && nmax > 0) {   // pruned target (forced.hpp): n' from cv / s.touch / s.fscore, one child per lane slot, into rankv (free since the sort)
+        uint32_t sn = 0, pvr = 0;    // c*: the largest N, ties to the smallest move; pv: the sum of N
+        int sm = 0x7fffffff, si = -1;
+        for (int i = lane; i < n; i += WAVE) {
+          pvr += cv[i];
+          if (si < 0 || forced::star_before(cv[i], s.fmove[i], sn, sm)) { sn = cv[i]; sm = s.fmove[i]; si = i; }
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+          pvr += __shfl_xor(pvr, o, 64);
+          const uint32_t on = __shfl_xor(sn, o, 64);
+          const int om = __shfl_xor(sm, o, 64), oi = __shfl_xor(si, o, 64);
+          if (oi >= 0 && (si < 0 || forced::star_before(on, om, sn, sm))) { sn = on; sm = om; si = oi; }
+        }
+        const float num = sqrt_cr((float)pvr);
+        const uint32_t T = pvr - (uint32_t)n;
+        const float ustar = forced::U(forced::evaluate(__int_as_float(s.touch[si]), sn, player), s.fscore[si], mc.PUCT, num, sn);
+        for (int i = lane; i < n; i += WAVE)
+          rankv[i] = (int32_t)(i == si ? sn - 1u
+                                       : forced::pruned_playouts(cv[i], __int_as_float(s.touch[i]), s.fscore[i], player, mc.PUCT, num, (double)pk, T, ustar));
+        __syncthreads();             // (pk and nmax are the same in every lane: the whole workgroup is here)
+        tv = reinterpret_cast<const uint32_t*>(rankv);
+        nmax = sn - 1u;              // n'_c* = n_c* is the largest n'; 0: no row
+      }
     } else {
       for (int q = 0; q < pcn; q++) {
         int mv = d.pc_move[(size_t)t * d.moves_stride + q];
@@ -1253,7 +1302,7 @@ __global__ __launch_bounds__(64) void k_end_move(Dev d, GameCfg c, MctsCfg mc, i
 #pragma unroll
           for (int k = 0; k < PER_LANE; k++) {
             const int i = lane + k * WAVE;
-            w[k] = i < n ? target::weight(cv[i], nmax, tau) : 0;
+            w[k] = i < n ? target::weight(tv[i], nmax, tau) : 0;
             S += w[k];
           }
           for (int o = 32; o > 0; o >>= 1) {
@@ -1501,6 +1550,12 @@ struct agz_arena {
   int last_cap_batch = 0, last_cap_games = 0;     // network batch / still-searching games of the last step if it was a tail step, else 0
   Dev cap_dev() const { Dev x = d; if (cap.on) x.cap_kind = cap_b.kind; return x; }   // what k_root_noise and k_end_move get
   int cap_clear();                                // counts = 0, every kind = -1 (reset / load)
+  // agz_arena_set_forced_playouts (forced.hpp); the caller's configuration, not in a checkpoint.  It rides on kernel arguments: sel_fk is
+  // 0 and prune_k negative while it is off, and the step's kernels see the playout cap's kinds only while both settings are on
+  agz_forced_conf forced{2.0f, 0, 1, 0};
+  float sel_fk() const { return forced.on ? forced.k : 0.f; }                                       // what k_select / k_select_paths get
+  float prune_k() const { return forced.on && forced.prune ? forced.k : -1.f; }                     // what k_end_move gets
+  Dev sel_dev(const Dev& x0) const { Dev x = x0; if (sel_fk() > 0.f && cap.on) x.cap_kind = cap_b.kind; return x; }
   bool restart = false;  // continuous self-play: finished games restart immediately
   int moves_done = 0;
   // AGZ_INF_CALLBACK (mcts.Inferencer as a host function, mcts/mcts.go:15-18): the callee, its policy width, page-locked staging
@@ -1812,7 +1867,7 @@ int agz_arena::nn_step_split() {
     // held skew: queue 0 in turn starts behind queue 1's mid-tower event of the previous step
     if (k == 1 && (first || hold)) AGZ_HIP_TRY(hipStreamWaitEvent(q[1], ctx->ev_mid[0], 0));
     if (k == 0 && hold && !first) AGZ_HIP_TRY(hipStreamWaitEvent(q[0], ctx->ev_mid[1], 0));
-    hipLaunchKernelGGL(k_select, dim3(h), dim3(64), 0, q[k], d, gc, mc, act, act, 0, 1, k * h);
+    hipLaunchKernelGGL(k_select, dim3(h), dim3(64), 0, q[k], sel_dev(d), gc, mc, act, act, 0, 1, k * h, sel_fk());
     r = n->forward_half(G, k, q[k], d_policy[0], d_value[0], (k == 0 && (first || hold)) || (k == 1 && hold) ? ctx->ev_mid[k] : nullptr);
     if (r != AGZ_OK) { ctx->open2 = true; ctx->open_owner = this; ctx->join(); return r; }
     hipLaunchKernelGGL(k_expand, dim3(h), dim3(64), 0, q[k], d, gc, mc, inf, 0, 1, k * h);
@@ -1853,10 +1908,10 @@ int agz_arena::nn_step(int prep, int nl, int cap_i0) {
   {
     ProfScope ps(ctx, AGZ_PROF_SELECT);
     if (split_lanes) {
-      hipLaunchKernelGGL(k_select_paths, dim3(G), dim3(64), 0, ctx->stream, ds, gc, mc, prep, nl);
+      hipLaunchKernelGGL(k_select_paths, dim3(G), dim3(64), 0, ctx->stream, sel_dev(ds), gc, mc, prep, nl, sel_fk());
       hipLaunchKernelGGL(k_leaf, dim3(G * nl), dim3(64), 0, ctx->stream, ds, gc, mc, act0, act1, prep, nl);
     } else {
-      hipLaunchKernelGGL(k_select, dim3(G), dim3(64), 0, ctx->stream, ds, gc, mc, act0, act1, prep, nl, 0);
+      hipLaunchKernelGGL(k_select, dim3(G), dim3(64), 0, ctx->stream, sel_dev(ds), gc, mc, act0, act1, prep, nl, 0, sel_fk());
     }
   }
   // prepareRoot evaluates the network only for a root without children (search.go:392-408).  With tree reuse that is the rare
@@ -2348,6 +2403,69 @@ int agz_playout_cap_of(uint64_t seed, uint64_t key, int32_t ply, float p_full, i
   *kind = cap::kind_of(seed, key, ply, cap::threshold(p_full));
   return AGZ_OK;
 }
+// Forced playouts and policy-target pruning (BUILD EXTENSION, DESIGN.md §2 forced-playouts; forced.hpp holds the definitions): the
+// setting lives in the arena and rides on the arguments of k_select / k_select_paths / k_end_move: no buffer, no launch, no read-back.
+// Not part of an arena checkpoint.
+static bool forced_k_ok(float k) { return k >= 0.f && k <= 64.f; }   // (NaN fails every comparison)
+int agz_arena_set_forced_playouts(agz_arena* a, const agz_forced_conf* conf) {
+  AGZ_REQUIRE(a, AGZ_E_INVALID, "arena is NULL");
+  AGZ_REQUIRE(conf && (conf->on == 0 || conf->on == 1) && (conf->prune == 0 || conf->prune == 1) && forced_k_ok(conf->k) && conf->reserved == 0, AGZ_E_INVALID,
+              "agz_arena_set_forced_playouts: on and prune in {0,1}, 0 <= k <= 64, reserved == 0 (on %d, prune %d, k %g, reserved %d)", conf ? conf->on : -1,
+              conf ? conf->prune : -1, conf ? (double)conf->k : 0.0, conf ? conf->reserved : -1);
+  AGZ_REQUIRE(!a->in_move, AGZ_E_STATE, "agz_arena_set_forced_playouts: a search is in progress");
+  a->forced = *conf;
+  return AGZ_OK;
+}
+int agz_arena_get_forced_playouts(agz_arena* a, agz_forced_conf* out) {
+  AGZ_REQUIRE(a && out, AGZ_E_INVALID, "agz_arena_get_forced_playouts: NULL argument");
+  *out = a->forced;
+  return AGZ_OK;
+}
+// The same definitions without a context or a device.
+static int forced_block_ok(const char* fn, const uint32_t* visits, int n, int player, float puct, float k) {
+  AGZ_REQUIRE(n >= 1 && n <= forced::MAX_N && (player == AGZ_BLACK || player == AGZ_WHITE) && puct > 0.f && puct <= 1.f && forced_k_ok(k), AGZ_E_INVALID,
+              "%s: 1 <= n <= %d, player Black or White, 0 < puct <= 1, 0 <= k <= 64 (n %d, player %d, puct %g, k %g)", fn, forced::MAX_N, n, player, (double)puct,
+              (double)k);
+  uint64_t pv = 0;
+  for (int i = 0; i < n; i++) {
+    AGZ_REQUIRE(visits[i] >= 1, AGZ_E_INVALID, "%s: visits[%d] = 0 (a child is created with one visit)", fn, i);
+    pv += visits[i];
+  }
+  AGZ_REQUIRE(pv <= 0xFFFFFFFFull, AGZ_E_INVALID, "%s: the visits sum to more than 2^32 - 1", fn);
+  return AGZ_OK;
+}
+int agz_root_select_of(const uint32_t* visits, const float* black_scores, const float* priors, const uint8_t* marks, int n, int player, float puct, float k,
+                       int* index, int* forced) {
+  AGZ_REQUIRE(visits && black_scores && priors && index && forced, AGZ_E_INVALID, "agz_root_select_of: NULL argument");
+  { int r = forced_block_ok("agz_root_select_of", visits, n, player, puct, k); if (r != AGZ_OK) return r; }
+  int f = 0;
+  const int idx = forced::select_of(visits, black_scores, priors, marks, n, player, puct, k, &f);
+  *index = idx; *forced = f;
+  return AGZ_OK;
+}
+int agz_pruned_target_of(const int32_t* moves, const uint32_t* visits, const float* black_scores, const float* priors, int n, int action_space, int player,
+                         float puct, float k, float temperature, uint32_t* pruned_playouts, float* row) {
+  AGZ_REQUIRE(moves && visits && black_scores && priors && row, AGZ_E_INVALID, "agz_pruned_target_of: NULL argument");
+  { int r = forced_block_ok("agz_pruned_target_of", visits, n, player, puct, k); if (r != AGZ_OK) return r; }
+  AGZ_REQUIRE(action_space >= 1 && action_space <= forced::MAX_N && target_tau_ok(temperature), AGZ_E_INVALID,
+              "agz_pruned_target_of: 1 <= action_space <= %d, temperature finite and > 0 (action_space %d, temperature %g)", forced::MAX_N, action_space,
+              (double)temperature);
+  std::vector<uint8_t> seen((size_t)action_space + 1, 0);
+  uint32_t nmax = 0;
+  for (int i = 0; i < n; i++) {
+    const int mv = moves[i];
+    AGZ_REQUIRE(mv == AGZ_PASS || (mv >= 0 && mv < action_space), AGZ_E_INVALID, "agz_pruned_target_of: moves[%d] = %d is neither in [0, %d) nor AGZ_PASS", i, mv, action_space);
+    uint8_t& mark = seen[(size_t)target::index_of(mv, action_space)];
+    AGZ_REQUIRE(!mark, AGZ_E_INVALID, "agz_pruned_target_of: move %d appears twice", mv);
+    mark = 1;
+    nmax = std::max(nmax, visits[i]);
+  }
+  AGZ_REQUIRE(nmax >= 2, AGZ_E_INVALID, "agz_pruned_target_of: the most visited child has no playout, there is no target");
+  std::vector<uint32_t> scratch((size_t)n);
+  forced::pruned_row_of(moves, visits, black_scores, priors, n, action_space, player, puct, k, (double)temperature, scratch.data(), pruned_playouts, row);
+  return AGZ_OK;
+}
+
 int agz_arena_set_cap_compact(agz_arena* a, int on) {
   AGZ_REQUIRE(a, AGZ_E_INVALID, "arena is NULL");
   a->cap_compact = on != 0;
@@ -2492,7 +2610,7 @@ int agz_arena_end_move(agz_arena* a, int record) {
   {
     ProfScope ps(a->ctx, AGZ_PROF_MOVE);
     hipLaunchKernelGGL(k_end_move, dim3(a->G), dim3(64), 0, a->ctx->stream, a->cap_dev(), a->gc, a->mc, record, a->restart ? 1 : 0, (const int32_t*)nullptr, 0,
-                       a->target.kind, a->target.temperature);
+                       a->target.kind, a->target.temperature, a->prune_k());
   }
   AGZ_HIP_TRY(hipGetLastError());
   a->in_move = false;
@@ -2510,7 +2628,7 @@ int agz_arena_apply_moves(agz_arena* a, const int32_t* moves) {
   AGZ_HIP_TRY(hipMemcpyAsync(&before, a->d.counters + CNT_ILLEGAL, 8, hipMemcpyDeviceToHost, s));
   AGZ_HIP_TRY(hipMemcpyAsync(a->d_forced, moves, (size_t)a->G * sizeof(int32_t), hipMemcpyHostToDevice, s));
   AGZ_HIP_TRY(hipStreamSynchronize(s));   // `moves` is the caller's buffer
-  hipLaunchKernelGGL(k_end_move, dim3(a->G), dim3(64), 0, s, a->d, a->gc, a->mc, 0, 0, (const int32_t*)a->d_forced, 0, a->target.kind, a->target.temperature);
+  hipLaunchKernelGGL(k_end_move, dim3(a->G), dim3(64), 0, s, a->d, a->gc, a->mc, 0, 0, (const int32_t*)a->d_forced, 0, a->target.kind, a->target.temperature, -1.f);
   AGZ_HIP_TRY(hipGetLastError());
   AGZ_HIP_TRY(hipMemcpyAsync(&after, a->d.counters + CNT_ILLEGAL, 8, hipMemcpyDeviceToHost, s));
   AGZ_HIP_TRY(hipStreamSynchronize(s));
@@ -2784,7 +2902,7 @@ int agz_arena_random_moves(agz_arena* a, const int32_t* n_moves, uint64_t seed) 
   AGZ_HIP_TRY(hipStreamSynchronize(s));   // `n_moves` is the caller's buffer
   for (int i = 0; i < most; i++) {
     hipLaunchKernelGGL(k_random_pick, dim3(a->G), dim3(64), 0, s, a->d, a->gc, a->d_remaining, (unsigned long long)seed, a->d_forced);
-    hipLaunchKernelGGL(k_end_move, dim3(a->G), dim3(64), 0, s, a->d, a->gc, a->mc, 0, 0, (const int32_t*)a->d_forced, 0, a->target.kind, a->target.temperature);
+    hipLaunchKernelGGL(k_end_move, dim3(a->G), dim3(64), 0, s, a->d, a->gc, a->mc, 0, 0, (const int32_t*)a->d_forced, 0, a->target.kind, a->target.temperature, -1.f);
   }
   AGZ_HIP_TRY(hipGetLastError());
   AGZ_HIP_TRY(hipStreamSynchronize(s));
@@ -3248,7 +3366,7 @@ int agz_mcts_search(agz_mcts* m, int player, int32_t* best) {
   }
   {
     ProfScope ps(a->ctx, AGZ_PROF_MOVE);
-    hipLaunchKernelGGL(k_end_move, dim3(1), dim3(64), 0, s, a->d, a->gc, a->mc, 0, 0, (const int32_t*)nullptr, 1, AGZ_TARGET_REFERENCE, 1.0f);
+    hipLaunchKernelGGL(k_end_move, dim3(1), dim3(64), 0, s, a->d, a->gc, a->mc, 0, 0, (const int32_t*)nullptr, 1, AGZ_TARGET_REFERENCE, 1.0f, -1.f);
   }
   a->in_move = false;
   AGZ_HIP_TRY(hipGetLastError());

@@ -218,6 +218,12 @@ struct Arena {
     const agz_playout_cap_conf conf = {p_full, fast_budget, on ? 1 : 0, 0, seed};
     agz::check(agz_arena_set_playout_cap(h, &conf), "SetPlayoutCap");
   }
+  // build extension: forced playouts at the root with coefficient k and, with prune and AGZ_TARGET_VISITS, the pruned policy target
+  // (agz_arena_set_forced_playouts); default off.  Not in a checkpoint: set it again after Load.
+  void SetForcedPlayouts(float k, bool prune = true, bool on = true) {
+    const agz_forced_conf conf = {k, on ? 1 : 0, prune ? 1 : 0, 0};
+    agz::check(agz_arena_set_forced_playouts(h, &conf), "SetForcedPlayouts");
+  }
   void Opponent(const std::vector<int32_t>& moves) { agz::check(agz_arena_apply_moves(h, moves.data()), "opponent move"); }
   // Checkpoint of the running arena between two moves, and the continuation from one (agz_arena_save / agz_arena_load): games, trees, RNG
   // states, counters, examples.  The agents, the lanes and the pool policy are not in the file: set them again as they were.
@@ -324,6 +330,12 @@ struct Config {
   // PolicyTarget, neither field is in a SaveRun file (AGZRUN01 unchanged): a resumed run plays under the Config its AZ was constructed with
   int PlayoutCapFastBudget = 0;
   float PlayoutCapFull = 0.25f;
+  // build extension: forced playouts of the SELF-PLAY arena (Arena::SetForcedPlayouts): ForcedPlayoutsK = 0 (default) means off, otherwise
+  // a root child with n playouts and prior P is selected while n^2 < K P T (T the playouts below the root); ForcedPrune takes the forced
+  // playouts of a move that turned out bad back out of the PolicyTarget = AGZ_TARGET_VISITS row.  With the playout cap only full plies
+  // force.  The evaluation arena searches without them.  Neither field is in a SaveRun file (AGZRUN01 unchanged)
+  float ForcedPlayoutsK = 0.f;
+  bool ForcedPrune = true;
   // build extension: train from a replay window instead of one epoch's examples.  ReplayWindow = rows the window keeps across epochs; 0
   // (default) = off, AZ.Learn exactly as the reference has it.  ReplaySteps = minibatches per epoch; 0 = (live rows / BatchSize) * nniters.
   // ReplaySymmetric = every sampled row under one of the eight board symmetries, chosen per draw; the materialising augmenters
@@ -409,6 +421,7 @@ struct AZ {
         if (conf.RootNoiseEps > 0.f) sp.SetRootNoise(conf.RootNoiseEps, conf.RootNoiseAlpha);
         if (conf.PolicyTarget != AGZ_TARGET_REFERENCE) sp.SetPolicyTarget(conf.PolicyTarget, conf.TargetTemperature);
         if (conf.PlayoutCapFastBudget > 0) sp.SetPlayoutCap(conf.PlayoutCapFull, conf.PlayoutCapFastBudget, seed + 1000 * epoch + 2);
+        if (conf.ForcedPlayoutsK > 0.f) sp.SetForcedPlayouts(conf.ForcedPlayoutsK, conf.ForcedPrune);
         sp.PlayOnDevice(true);                                            // episodes x SelfPlay(), agogo.go:110-114
         ex.Append(sp);                                                     // device to device, episode after episode
       }

@@ -593,6 +593,32 @@ func (a *BatchedArena) SetPlayoutCap(pFull float32, fastBudget int, seed uint64,
 	return lastErr(C.agz_arena_set_playout_cap(a.h, &conf))
 }
 
+// SetForcedPlayouts turns forced playouts at the root on or off (agz_arena_set_forced_playouts): while on, a root child with n playouts
+// and prior P is selected as long as n*n < k*P*T, T being the playouts below the root (0 <= k <= 64); with prune and AGZ_TARGET_VISITS
+// the recorded row is built from the pruned playouts, which takes the forced playouts of a move that turned out bad back out.  With the
+// playout cap only full plies force.  Off by default; between moves.  The setting is not part of a checkpoint: set it again after Load.
+func (a *BatchedArena) SetForcedPlayouts(k float32, prune bool, on bool) error {
+	defer a.ctx.enter()()
+	conf := C.agz_forced_conf{k: C.float(k)}
+	if on {
+		conf.on = 1
+	}
+	if prune {
+		conf.prune = 1
+	}
+	return lastErr(C.agz_arena_set_forced_playouts(a.h, &conf))
+}
+
+// ForcedPlayouts returns the arena's forced-playout setting (agz_arena_get_forced_playouts).
+func (a *BatchedArena) ForcedPlayouts() (k float32, prune bool, on bool, err error) {
+	defer a.ctx.enter()()
+	var conf C.agz_forced_conf
+	if err = lastErr(C.agz_arena_get_forced_playouts(a.h, &conf)); err != nil {
+		return 0, false, false, err
+	}
+	return float32(conf.k), conf.prune != 0, conf.on != 0, nil
+}
+
 // Save writes a checkpoint of the running arena — games, both trees of every game, RNG states, counters, recorded examples — between two
 // moves (agz_arena_save).  The file replaces `path` only once it is complete.
 func (a *BatchedArena) Save(path string) error {

@@ -659,6 +659,55 @@ int agz_arena_playout_cap_counts(agz_arena* arena, int64_t* full_plies, int64_t*
 /* The same definition without a context or a device: the kind of ply `ply` of the slot with key `key`.  AGZ_E_INVALID unless ply >= 0,
  * 0 <= p_full <= 1 and kind != NULL. */
 int agz_playout_cap_of(uint64_t seed, uint64_t key, int32_t ply, float p_full, int32_t* kind);
+/* BUILD EXTENSION (no mcts.Config field; DESIGN.md §2 forced-playouts): KataGo's forced playouts and policy-target pruning at the root.
+ * Opt-in, default off; off (or never called) is everything as without this call, bit for bit and launch for launch: no allocation, no
+ * read-back, no load in the step's kernels (the setting rides on kernel arguments that leave one uniform branch not taken).
+ * The definitions (one copy, csrc/forced.hpp; IEEE float and double operations rounded once, contraction off, integers).  For the
+ * children i = 0..n-1 of a root as they stand in its child block:
+ *   N_i, n_i   the stored visits (>= 1: a child is created with one visit) and the playouts n_i = N_i - 1
+ *   B_i, P_i   the stored score sum and the stored prior (root noise, if on, is already in it)
+ *   pv, T      the sum of N_i and the sum of n_i (= pv - n)
+ *   q_i        Evaluate(B_i, N_i, player): B_i / N_i, and 1 - that for White, in float
+ *   U(i, m)    fadd(q_i, fmul(fmul(PUCT, P_i), fdiv(sqrt((float)pv), fadd(1.0f, (float)m)))), the square root correctly rounded;
+ *              U(i, N_i) is the value Node.Select maximises
+ *   rhs_i      ((double)k * (double)P_i) * (double)T
+ * Forced selection, at the root of every descent (below the root nothing changes): child i is forced iff n_i >= 1 and
+ * (double)(n_i + mark_i) * (double)(n_i + mark_i) < rhs_i, mark_i being the child's stored virtual-loss mark in a lane round
+ * (agz_arena_set_parallel) and 0 in the sequential search.  A forced child's value is +INFINITY, so Select's argmax and its tie rule
+ * (the first maximum) pick the forced child with the lowest block index.  k = 0 forces nothing.  While the playout cap is on only FULL
+ * plies force; a FAST ply searches as without this setting.
+ * Pruned target, used when on, prune and AGZ_TARGET_VISITS all hold; only the recorded row changes (the move, the sort,
+ * randomizeChildren, cachedPolicies and the trees are the same):
+ *   c*         the child with the largest N_i, ties to the smallest move as an int (AGZ_PASS = -1 first);  U* = U(c*, N_c*)
+ *   F_i        the largest integer f >= 0 with (double)f * (double)f <= rhs_i
+ *   n'_i       c*: n_i.  n_i == 0: 0.  Otherwise N'_i = the smallest m in [N_i - min(F_i, n_i), N_i] with U(i, m) < U* (N_i if
+ *              U(i, N_i) >= U*), with q_i, pv and U* held fixed; n'_i = N'_i - 1, and n'_i = 0 if N'_i < N_i and n'_i == 1 (a child
+ *              reduced to a single playout is pruned outright)
+ *   row        the AGZ_TARGET_VISITS definition applied to n' instead of N (weights from n'_i and max n' = n_c*, the temperature of
+ *              agz_arena_set_policy_target); n_c* == 0: no row
+ * With k = 0 the row is the playout-count target pi ~ (N - 1)^(1/tau): only the one visit every child is created with is removed.
+ * With prune = 0 the row is the AGZ_TARGET_VISITS row of the forced search.  Under AGZ_TARGET_REFERENCE prune has no effect.
+ * Nothing is added to an arena checkpoint (AGZARN01 unchanged): re-apply the setting after agz_arena_load and the continuation is bit
+ * for bit.  The single-tree agz_mcts_* handle is not covered.
+ * AGZ_E_INVALID, with the setting unchanged, unless on and prune are 0 or 1, k is finite with 0 <= k <= 64 and reserved == 0;
+ * AGZ_E_STATE inside a move. */
+typedef struct agz_forced_conf { float k; int32_t on; int32_t prune; int32_t reserved; } agz_forced_conf; /* 16 bytes; defaults 2.0f, 0, 1, 0 */
+int agz_arena_set_forced_playouts(agz_arena* arena, const agz_forced_conf* conf);
+int agz_arena_get_forced_playouts(agz_arena* arena, agz_forced_conf* out);
+/* The same definitions without a context or a device.  agz_root_select_of: the block index Node.Select returns at a root with the forced
+ * rule (*index; -1 if no value compares greater than -INFINITY) and whether that child was forced (*forced).  marks == NULL is the
+ * sequential search (no mark, and no virtual-loss term); with marks White's view adds 3.0 to the score sum of a marked child, as a lane
+ * round does.  k = 0 is plain Node.Select.  agz_pruned_target_of: the pruned playouts n' (pruned_playouts, [n], may be NULL) and the row
+ * ([action_space + 1], Pass last) of a root.  Both refuse with AGZ_E_INVALID, leaving every output untouched: a NULL pointer (other than
+ * marks / pruned_playouts), n outside [1, 4096], a player that is neither AGZ_BLACK nor AGZ_WHITE, puct outside (0, 1], k outside
+ * [0, 64], a visit count of 0 and visits that sum past 2^32 - 1; agz_pruned_target_of also an action_space outside [1, 4096], a move that
+ * is neither in [0, action_space) nor AGZ_PASS, a move given twice, a temperature that is not finite and > 0, and a root whose most
+ * visited child has no playout (there is no row). */
+int agz_root_select_of(const uint32_t* visits, const float* black_scores, const float* priors, const uint8_t* marks /* may be NULL */,
+                       int n, int player, float puct, float k, int* index, int* forced);
+int agz_pruned_target_of(const int32_t* moves, const uint32_t* visits, const float* black_scores, const float* priors, int n,
+                         int action_space, int player, float puct, float k, float temperature,
+                         uint32_t* pruned_playouts /* may be NULL, [n] */, float* row /* [action_space + 1] */);
 int agz_arena_begin_move(agz_arena* arena);
 int agz_arena_simulate(agz_arena* arena, int k);
 int agz_arena_end_move(agz_arena* arena, int record);
