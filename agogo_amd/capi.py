@@ -17,6 +17,7 @@ ENC_TWOPLANE, ENC_WQ = 0, 1
 INF_NET, INF_DUMMY, INF_SCRIPT, INF_HASH, INF_UNIFORM, INF_CALLBACK = 0, 1, 2, 3, 4, 5
 BN_DEGENERATE_EPS, BN_RUNNING, BN_IDENTITY = 0, 1, 2
 COMPUTE_F32_MFMA, COMPUTE_BF16X3, COMPUTE_FP16X2, COMPUTE_WINO, COMPUTE_AUTO, COMPUTE_WINO_H2 = 0, 1, 2, 3, 4, 5
+COMPUTE_BF16 = 6     # one bf16 product per multiply: NOT fp32-grade (agz.h)
 COMPUTE_FORCE = 0x100
 LOSS_REFERENCE, LOSS_ALPHAZERO = 0, 1   # agz_trainer_set_loss
 # agz_debug.h, agz_trainer_last_paths: the kernel a trainer layer's last step took (0 = none launched)
@@ -34,6 +35,7 @@ NPATH_BLK_F32_411, NPATH_BLK_F32_221, NPATH_BLK_F32_222 = 1, 2, 3
 NPATH_BLK_F32_411_SPLITK, NPATH_BLK_F32_221_SPLITK, NPATH_BLK_F32_222_SPLITK = 4, 5, 6
 NPATH_BLK_X3, NPATH_BLK_H2W, NPATH_BLK_H2, NPATH_BLK_WINO = 7, 8, 9, 10
 NPATH_BLK_WINO_H2_3K, NPATH_BLK_WINO_H2_3K_WIDE, NPATH_BLK_WINO_H2_CHAINED, NPATH_BLK_LAT_H2 = 11, 12, 13, 14
+NPATH_BLK_BF16 = 15
 NPATH_HEADS_ONE, NPATH_HEADS_SPREAD, NPATH_HEADS_SPREAD_NB4 = 1, 2, 3
 PROF_CONV, PROF_HEADS, PROF_SELECT, PROF_EXPAND, PROF_MOVE, PROF_CONV_INIT = 0, 1, 2, 3, 4, 5
 PROF_WINO_IN, PROF_WINO_GEMM, PROF_WINO_OUT = 6, 7, 8
@@ -347,6 +349,7 @@ def lib():
     sig("agz_net_wino_h2_last_rows", i32, vp, C.POINTER(C.c_int), C.POINTER(C.c_int))
     sig("agz_net_last_paths", i32, vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int))
     sig("agz_net_tower_out", i32, vp, i32, pf)
+    sig("agz_net_block_forward", i32, vp, i32, pf, i32, pf)
     sig("agz_net_min_same_batch", i32, vp, i32, i32, C.POINTER(C.c_int))
     sig("agz_arena_set_prep_compact", i32, vp, i32)
     sig("agz_arena_set_split", i32, vp, i32)
@@ -585,6 +588,15 @@ class Net:
         t = np.zeros((int(B), c.K, c.Height, c.Width), dtype=np.float32)
         _check(lib().agz_net_tower_out(self.h, int(B), _pf(t)), "agz_net_tower_out")
         return t
+
+    def block_forward(self, layer, x):
+        """agz_debug.h: dual block `layer` alone in the current compute mode (COMPUTE_BF16): x [B, K, H, W] float32 -> [B, K, H, W]"""
+        c = self.conf
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        assert x.ndim == 4 and x.shape[1:] == (c.K, c.Height, c.Width), x.shape
+        y = np.zeros_like(x)
+        _check(lib().agz_net_block_forward(self.h, int(layer), _pf(x), x.shape[0], _pf(y)), "agz_net_block_forward")
+        return y
 
     def min_same_batch(self, n, G):
         """agz_debug.h: the smallest batch >= n whose per-board outputs equal those of a G-board batch bit for bit"""

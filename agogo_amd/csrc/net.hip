@@ -300,6 +300,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_mfma_kernel(ConvArgs a) {
 }
 
 #include "conv_x3.hpp"
+#include "conv_bf16.hpp"
 #include "conv_wino.hpp"
 #include "conv_h2.hpp"
 #include "conv_wino_h2.hpp"
@@ -662,6 +663,7 @@ void agz_net::free_device() {
   for (auto& p : d_ep_dual) f(p);
   for (auto& p : d_w3_dual) if (p) { hipFree(p); p = nullptr; }
   for (auto& p : d_w2_dual) if (p) { hipFree(p); p = nullptr; }
+  free_wq();
   if (d_amax) { hipFree(d_amax); d_amax = nullptr; }
   amax_cap = 0;
   for (auto& p : d_u3_dual) if (p) { hipFree(p); p = nullptr; }
@@ -983,6 +985,81 @@ int agz::conv3x3_raw_wino_h2(agz_ctx* ctx, const float* x, const float* w, float
   return AGZ_OK;
 }
 
+// ---- AGZ_COMPUTE_BF16 (conv_bf16.hpp): rows per workgroup, the weight image, one block's launch
+// fp32 -> bf16, round to nearest even; NaN stays a (quiet) NaN — what v_cvt_pk_bf16_f32 does to the activations
+static unsigned short bf16_rne(float v) {
+  uint32_t u; memcpy(&u, &v, 4);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40u);
+  return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+
+// The most GEMM rows (a multiple of 32, at most the kernel's 384) one workgroup can own on an H x W board so that the haloed slice of
+// every run of that many rows — its board lines and one more on either side — stays inside the staged image; 0 if not even 32 do
+static int bf16_rows_tile(int H, int W) {
+  const int HW = H * W, Wp = W + 2;
+  for (int R = BF16_ROWS; R >= 32; R -= 32) {
+    bool ok = true;
+    for (int m0 = 0; m0 < HW && ok; m0 += R) {
+      const int mend = std::min(m0 + R, HW);
+      ok = ((mend - 1) / W - m0 / W + 3) * Wp <= BF16_SP_MAX;
+    }
+    if (ok) return R;
+  }
+  return 0;
+}
+
+// wq[n_tile][chunk][tap] = the [128 columns][64 channels] tile of conv3x3_bf16_dual_kernel in LDS byte order: column nn (< 64: channel
+// 64 n_tile + nn of branch a, else of branch b), 16-byte unit u at 128 nn + 16 (u ^ ((nn >> 1) & 7))
+int agz_net::build_bf16_weights() {
+  const int K = conf.K, L = conf.SharedLayers;
+  AGZ_REQUIRE(K % 64 == 0 && L > 0 && bf16_rows > 0, AGZ_E_UNSUPPORTED, "agz_net: AGZ_COMPUTE_BF16 needs K a multiple of 64 and SharedLayers > 0");
+  const int n_ntiles = 2 * Kp / 128, ncc = Kp / 64;
+  const size_t elems = (size_t)n_ntiles * ncc * 9 * (BF16_B_STAGE / 2);
+  // the kernel walks one layer's image with 32-bit byte offsets
+  AGZ_REQUIRE(elems * 2 < ((size_t)1 << 32), AGZ_E_UNSUPPORTED, "agz_net: K %d too wide for the bf16 weight image", K);
+  AGZ_HIP_TRY(hipSetDevice(ctx->device));
+  free_wq();
+  d_wq_dual.assign(L, nullptr);
+  std::vector<unsigned short> wq(elems);
+  size_t pi = 3;   // parameters: init conv (w, gamma, beta), then per block a: (w, gamma, beta), b: (w, gamma, beta)
+  for (int l = 0; l < L; l++, pi += 6) {
+    const std::vector<float>& wa = params[pi].v;
+    const std::vector<float>& wb = params[pi + 3].v;
+    for (int nt = 0; nt < n_ntiles; nt++)
+      for (int cc = 0; cc < ncc; cc++)
+        for (int t = 0; t < 9; t++) {
+          unsigned short* img = &wq[(((size_t)nt * ncc + cc) * 9 + t) * (BF16_B_STAGE / 2)];
+          for (int nn = 0; nn < 128; nn++) {
+            const std::vector<float>& w = nn < 64 ? wa : wb;
+            const int o = nt * 64 + (nn & 63);
+            for (int c = 0; c < 64; c++) {
+              const int u = c >> 3, ci = cc * 64 + c;
+              img[nn * 64 + ((u ^ ((nn >> 1) & 7)) << 3) + (c & 7)] = bf16_rne(w[((size_t)o * K + ci) * 9 + t]);
+            }
+          }
+        }
+    AGZ_HIP_TRY(hipMalloc(&d_wq_dual[l], elems * 2));
+    AGZ_HIP_TRY(hipMemcpyAsync(d_wq_dual[l], wq.data(), elems * 2, hipMemcpyHostToDevice, ctx->stream));
+    AGZ_HIP_TRY(hipStreamSynchronize(ctx->stream));
+  }
+  return AGZ_OK;
+}
+
+int agz_net::bf16_block(int l, int B, const float* x, float* y, hipStream_t st) {
+  AGZ_REQUIRE((int)d_wq_dual.size() == conf.SharedLayers && l >= 0 && l < conf.SharedLayers && d_wq_dual[l], AGZ_E_STATE, "agz_net: bf16 weights not built");
+  // inside a board the kernel uses 32-bit byte offsets (the board itself is a 64-bit base)
+  AGZ_REQUIRE((size_t)Hp * Wp * Kp * sizeof(float) < ((size_t)1 << 32) && (size_t)HW * Kp * sizeof(float4) < ((size_t)1 << 32), AGZ_E_UNSUPPORTED,
+              "agz_net: board %d x %d with %d channels too large for the bf16 block's 32-bit offsets", H, W, Kp);
+  Bf16Args q{};
+  q.x = x; q.y = y; q.ep = reinterpret_cast<const f32x4*>(d_ep_dual[l]); q.wq = d_wq_dual[l];
+  q.HW = HW; q.W = W; q.Wp = Wp; q.HpWp = Hp * Wp; q.Kp = Kp;
+  q.n_ntiles = 2 * Kp / 128; q.rows_tile = bf16_rows; q.m_per_board = ceil_div(HW, bf16_rows); q.ncc = Kp / 64;
+  const size_t grid = (size_t)B * q.m_per_board * q.n_ntiles;
+  AGZ_REQUIRE(grid < ((size_t)1 << 31), AGZ_E_UNSUPPORTED, "agz_net: batch %d too large for the bf16 block's grid", B);
+  hipLaunchKernelGGL(conv3x3_bf16_dual_kernel, dim3((unsigned)grid), dim3(256), 0, st, q);
+  return AGZ_OK;
+}
+
 // Winograd-domain weights of every dual block (conv_wino.hpp): columns [0,Kp) branch a, [Kp,2Kp) branch b, natural order
 int agz_net::build_wino_weights() {
   AGZ_REQUIRE(cfg == 0, AGZ_E_UNSUPPORTED, "agz_net: the Winograd path needs K a multiple of 64");
@@ -1133,6 +1210,10 @@ agz_net::FwdPlan agz_net::fwd_plan(int B) const {
   p.forced_split = compute_force && cfg == 0 && conf.SharedLayers > 0 &&
                    (this->compute_mode == AGZ_COMPUTE_WINO_H2 || this->compute_mode == AGZ_COMPUTE_WINO ||
                     this->compute_mode == AGZ_COMPUTE_BF16X3 || this->compute_mode == AGZ_COMPUTE_FP16X2);
+  // AGZ_COMPUTE_BF16 is its own arithmetic (one bf16 product): its block runs at EVERY batch size, FORCE or not — no latency regime,
+  // no split-K fp32 fallback (agz_net_set_compute_mode has checked cfg == 0 and SharedLayers > 0)
+  const bool bf16 = this->compute_mode == AGZ_COMPUTE_BF16;
+  p.forced_split = p.forced_split || bf16;
   p.latency = p.small && !p.forced_split;          // split-K convolutions
   const int spread_max = 64;
   // (wide towers: the spread form also wins at 512 boards — 0.17 vs 0.35 ms at 19x19 / K=256, profiles/r02/init_heads_ab.log)
@@ -1141,7 +1222,7 @@ agz_net::FwdPlan agz_net::fwd_plan(int B) const {
   // the split kernels only pay once the 128-row tiles fill the chip (Connect-4, K=64, 256 games: 84 tiles -> the fp32
   // half-tile kernel is faster: 187 vs 162 / 158 games/s measured)
   // (the split kernels use 32-bit BYTE offsets: activation tensor below 4 GiB)
-  p.split_ok = cfg == 0 && !p.latency && (!p.half_dual || compute_force) && conf.SharedLayers > 0 &&
+  p.split_ok = cfg == 0 && !p.latency && (!p.half_dual || compute_force || bf16) && conf.SharedLayers > 0 &&
                (size_t)B * Hp * Wp * Kp * sizeof(float) < ((size_t)1 << 32);
   // the three-kernel Winograd fp16x2 block picks its GEMM tile by how many workgroups the batch gives (forward_packed)
   {
@@ -1154,8 +1235,14 @@ agz_net::FwdPlan agz_net::fwd_plan(int B) const {
 int agz_net::min_same_batch(int n, int G) const {
   if (n >= G) return G;
   const FwdPlan want = fwd_plan(G);
+  // AGZ_COMPUTE_BF16: the block kernel is the same at every batch; what still follows the batch is the input convolution where it is
+  // not the bf16x3 kernel (K % 128 != 0: whole or half fp32 tiles) and the form of the heads
+  const bool bf16 = compute_mode == AGZ_COMPUTE_BF16;
   auto same = [&](int B) {
     const FwdPlan q = fwd_plan(B);
+    if (bf16)
+      return q.split_ok == want.split_ok && (Kp % 128 == 0 || q.half_init == want.half_init) && q.heads_spread == want.heads_spread &&
+             q.heads_nb == want.heads_nb;
     return q.half_init == want.half_init && q.half_dual == want.half_dual && q.small == want.small && q.forced_split == want.forced_split &&
            q.latency == want.latency && q.heads_spread == want.heads_spread && q.split_ok == want.split_ok && q.heads_nb == want.heads_nb && q.wino_wide == want.wino_wide;
   };
@@ -1356,7 +1443,9 @@ int agz_net::forward_packed(int B, float* policy_dev, float* value_dev) {
   const bool use_h2 = split_ok && compute_mode == AGZ_COMPUTE_FP16X2;
   const bool wino_ok = split_ok && compute_mode == AGZ_COMPUTE_WINO;
   const bool wino_h2_ok = split_ok && compute_mode == AGZ_COMPUTE_WINO_H2;
-  if (wino_h2_ok && d_ep_init_h2) a.ep = d_ep_init_h2;   // the tower takes its input pre-scaled by block 0's t_in (net.hpp)
+  // (no fallback to another precision: the mode's input convolution addresses the batch with 32-bit byte offsets)
+  AGZ_REQUIRE(compute_mode != AGZ_COMPUTE_BF16 || split_ok, AGZ_E_UNSUPPORTED, "agz_net: batch %d too large for AGZ_COMPUTE_BF16 (activations above 4 GiB)", B);
+  if (wino_h2_ok && d_ep_init_h2) a.ep = d_ep_init_h2;  // the tower takes its input pre-scaled by block 0's t_in (net.hpp)
   if (use_h2 && (size_t)B > amax_cap) {
     AGZ_HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (d_amax) hipFree(d_amax);
@@ -1522,6 +1611,12 @@ int agz_net::forward_packed(int B, float* policy_dev, float* value_dev) {
       }
       rc = AGZ_OK;
     }
+    else if (compute_mode == AGZ_COMPUTE_BF16) {
+      // one bf16 product per multiply (conv_bf16.hpp), at every batch size: a workgroup per (board, 128-column tile)
+      ProfScope ps(ctx, AGZ_PROF_CONV);
+      rc = bf16_block(l, B, cur, nxt, ctx->stream);
+      path_block = AGZ_NPATH_BLK_BF16;
+    }
     else if (split_ok && compute_mode == AGZ_COMPUTE_BF16X3) {
       a.n_ntiles = ceil_div(a.Ntot, 128); a.n_mtiles = ceil_div(a.M, 128);
       a.splits = 1; a.per = 0; a.ws = nullptr; a.raw = 0;
@@ -1620,6 +1715,7 @@ int agz_net_create(agz_ctx* ctx, const agz_net_conf* c, agz_net** out) {
   n->H = c->Height; n->W = c->Width; n->HW = n->H * n->W; n->Hp = n->H + 2; n->Wp = n->W + 2;
   n->Kp = round_up(c->K, 32);
   n->cfg = (n->Kp % 64 == 0) ? 0 : 1;
+  n->bf16_rows = bf16_rows_tile(n->H, n->W);
   int K = c->K, F = c->Features, H = n->H, W = n->W, hw = n->HW, B = c->BatchSize;
   auto conv = [&](const std::string& nm, int o, int i, int k) {
     n->params.push_back(Param{"Filter" + nm, std::vector<float>((size_t)o * i * k * k, 0.f), {o, i, k, k}, 0});
@@ -1944,6 +2040,8 @@ int agz_net_commit(agz_net* n) {
   for (auto& p : n->d_ep_h2) if (p) hipFree(p);
   n->d_ep_h2.clear();
   if (n->d_ep_init_h2) { hipFree(n->d_ep_init_h2); n->d_ep_init_h2 = nullptr; }
+  n->free_wq();
+  if (n->compute_mode == AGZ_COMPUTE_BF16) return n->build_bf16_weights();
   if (n->compute_mode == AGZ_COMPUTE_WINO && n->cfg == 0) return n->build_wino_weights();
   if ((n->compute_mode == AGZ_COMPUTE_WINO_H2 || n->compute_mode == AGZ_COMPUTE_AUTO) && n->cfg == 0) return n->build_wino_h2_weights();
   return AGZ_OK;
@@ -1991,6 +2089,37 @@ int agz_net_tower_out(agz_net* n, int B, float* host) {
       for (int y = 0; y < H; y++)
         for (int x = 0; x < W; x++)
           host[(((size_t)b * K + k) * H + y) * W + x] = pad[(((size_t)b * Hp + y + 1) * Wp + x + 1) * Kp + k];
+  return AGZ_OK;
+}
+
+int agz_net_block_forward(agz_net* n, int layer, const float* x_host, int B, float* y_host) {
+  AGZ_REQUIRE(n && x_host && y_host && B >= 1, AGZ_E_INVALID, "agz_net_block_forward: bad argument");
+  AGZ_REQUIRE(n->committed, AGZ_E_STATE, "agz_net_block_forward: commit the net first");
+  AGZ_REQUIRE(layer >= 0 && layer < n->conf.SharedLayers, AGZ_E_INVALID, "agz_net_block_forward: layer %d of %d", layer, n->conf.SharedLayers);
+  AGZ_REQUIRE(n->compute_mode == AGZ_COMPUTE_BF16, AGZ_E_UNSUPPORTED, "agz_net_block_forward: only AGZ_COMPUTE_BF16 runs a block alone");
+  AGZ_HIP_TRY(hipSetDevice(n->ctx->device));
+  int rc = n->ensure_batch(B);
+  if (rc != AGZ_OK) return rc;
+  const int H = n->H, W = n->W, Hp = n->Hp, Wp = n->Wp, Kp = n->Kp, K = n->conf.K;
+  hipStream_t s = n->ctx->stream;
+  std::vector<float> pad((size_t)B * Hp * Wp * Kp, 0.f);
+  for (int b = 0; b < B; b++)
+    for (int k = 0; k < K; k++)
+      for (int y = 0; y < H; y++)
+        for (int x = 0; x < W; x++)
+          pad[(((size_t)b * Hp + y + 1) * Wp + x + 1) * Kp + k] = x_host[(((size_t)b * K + k) * H + y) * W + x];
+  AGZ_HIP_TRY(hipMemcpyAsync(n->d_actA, pad.data(), pad.size() * sizeof(float), hipMemcpyHostToDevice, s));
+  rc = n->bf16_block(layer, B, n->d_actA, n->d_actB, s);
+  if (rc != AGZ_OK) return rc;
+  AGZ_HIP_TRY(hipGetLastError());
+  AGZ_HIP_TRY(hipMemcpyAsync(pad.data(), n->d_actB, pad.size() * sizeof(float), hipMemcpyDeviceToHost, s));
+  AGZ_HIP_TRY(hipStreamSynchronize(s));
+  n->last_tower = nullptr; n->last_tower_B = 0;   // (the activation buffers no longer hold a forward's tower)
+  for (int b = 0; b < B; b++)
+    for (int k = 0; k < K; k++)
+      for (int y = 0; y < H; y++)
+        for (int x = 0; x < W; x++)
+          y_host[(((size_t)b * K + k) * H + y) * W + x] = pad[(((size_t)b * Hp + y + 1) * Wp + x + 1) * Kp + k];
   return AGZ_OK;
 }
 
@@ -2050,8 +2179,19 @@ int agz_net_set_compute_mode(agz_net* n, int mode) {
   AGZ_REQUIRE(n, AGZ_E_INVALID, "agz_net_set_compute_mode: NULL net");
   const int base = mode & ~AGZ_COMPUTE_FORCE;
   AGZ_REQUIRE(base == AGZ_COMPUTE_F32_MFMA || base == AGZ_COMPUTE_BF16X3 || base == AGZ_COMPUTE_FP16X2 || base == AGZ_COMPUTE_WINO || base == AGZ_COMPUTE_AUTO ||
-                  base == AGZ_COMPUTE_WINO_H2,
+                  base == AGZ_COMPUTE_WINO_H2 || base == AGZ_COMPUTE_BF16,
               AGZ_E_INVALID, "agz_net_set_compute_mode: unknown mode %d", mode);
+  if (base == AGZ_COMPUTE_BF16) {
+    // its own arithmetic, so no other kernel may stand in for it: refuse (and keep the net's mode) where the bf16 block cannot run
+    AGZ_REQUIRE(n->conf.K % 64 == 0 && n->conf.SharedLayers > 0, AGZ_E_UNSUPPORTED,
+                "agz_net_set_compute_mode: AGZ_COMPUTE_BF16 needs K a multiple of 64 and SharedLayers > 0 (K = %d, SharedLayers = %d)", n->conf.K, n->conf.SharedLayers);
+    AGZ_REQUIRE(n->bf16_rows > 0, AGZ_E_UNSUPPORTED, "agz_net_set_compute_mode: AGZ_COMPUTE_BF16: three haloed lines of a %d-wide board exceed the %d staged pixels",
+                n->W, BF16_SP_MAX);
+    if (n->committed && n->d_wq_dual.empty()) {
+      const int rb = n->build_bf16_weights();
+      if (rb != AGZ_OK) return rb;
+    }
+  }
   n->compute_mode = base;
   n->compute_force = (mode & AGZ_COMPUTE_FORCE) != 0;
   if (base == AGZ_COMPUTE_WINO && n->committed && n->cfg == 0 && n->d_u3_dual.empty()) return n->build_wino_weights();

@@ -72,6 +72,11 @@ struct agz_net {
   std::vector<float*> d_ep_dual;  // per layer float4 {sa,ta,sb,tb} [HW][Kp]
   std::vector<unsigned short*> d_w3_dual;  // per layer bf16x3 image [Kp/16][9][3][2*Kp][16] (cfg 0 only), conv_x3.hpp
   std::vector<_Float16*> d_w2_dual;        // per layer fp16x2 image [Kp/32][9][2][2*Kp][32] (cfg 0 only), conv_h2.hpp
+  std::vector<unsigned short*> d_wq_dual;  // per layer single-product bf16 image [2*Kp/128][Kp/64][9][16 KB LDS tile] (AGZ_COMPUTE_BF16), conv_bf16.hpp
+  int bf16_rows = 0;                       // GEMM rows of one workgroup of that kernel on this board (bf16_rows_tile; 0: the board does not fit)
+  void free_wq() { for (auto& p : d_wq_dual) if (p) hipFree(p); d_wq_dual.clear(); }
+  int build_bf16_weights();                // (re)builds d_wq_dual from the host parameters, every value rounded once to bf16 (RNE)
+  int bf16_block(int l, int B, const float* x, float* y, hipStream_t st);   // dual block l of B boards, padded NHWC -> padded NHWC
   std::vector<float> w_unscale;            // per layer 2^-eb of the fp16x2 weight scale
   std::vector<unsigned short*> d_u3_dual;  // per layer Winograd-domain bf16x3 image [36][Kp/16][3][2*Kp][16] (AGZ_COMPUTE_WINO), conv_wino.hpp
   std::vector<_Float16*> d_u2_dual;        // per layer Winograd-domain fp16x2 image [36][Kp/32][2][2*Kp][32] (AGZ_COMPUTE_WINO_H2), conv_wino_h2.hpp

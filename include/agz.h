@@ -169,7 +169,17 @@ int agz_net_set_tower_queues(agz_net* net, int queues);
 #define AGZ_COMPUTE_WINO_H2 5 /* Winograd F(5x5,3x3) / F(4x4,3x3) (whichever needs fewer rows for the board) with FP16X2 products in the transform domain: the input transform writes the
                             * operand already split into two fp16 pieces (scaled per board by a power of two from a proven bound,
                             * overflow impossible), three fp16 MFMAs per product — half the matrix instructions of AGZ_COMPUTE_WINO */
-#define AGZ_COMPUTE_FORCE 0x100 /* OR-ed in: take the split kernel even below the chip-filling threshold (tests) */
+#define AGZ_COMPUTE_BF16 6 /* ONE bf16 product per multiply — NOT fp32-grade, does not meet the oracle tolerance of the modes above; opt-in, for
+                            * self-play in volume (`bf16-tower`).  The arithmetic of the dual blocks, all of it: every filter
+                            * value is rounded once to bfloat16 (round to nearest even) when the weight image is built; every input activation
+                            * of a block is rounded the same way on its way into LDS (NaN / Inf: whatever RNE gives, nothing special-cased);
+                            * products are exact in fp32, accumulation is the MFMA's fp32, the BN / ReLU / add epilogue is the fp32 one of the
+                            * other modes; activations stay fp32 in memory; the input convolution and the heads keep the split modes' kernels.
+                            * The block runs at EVERY batch size, with or without AGZ_COMPUTE_FORCE: no latency regime, no split-K fallback,
+                            * and a board's tower output is bit-identical whatever the batch and wherever the board sits in it (batch-1 speed
+                            * is not a goal of this mode).  Nets with K a multiple of 64 and SharedLayers > 0; any other net: AGZ_E_UNSUPPORTED,
+                            * the net keeps its mode — there is no fallback to another precision.  conv_bf16.hpp */
+#define AGZ_COMPUTE_FORCE 0x100/* OR-ed in: take the split kernel even below the chip-filling threshold (tests) */
 int agz_net_set_compute_mode(agz_net* net, int mode);
 /* Checkpoint of the learnables in Model() order (+ BN statistics).  The reference gob-encodes G.Values
  * (AZ.Save / Dual.GobEncode, agogo.go:175-209, dualnet/dual.go:180-206); gob is Go-only, so this is a documented

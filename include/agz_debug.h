@@ -190,7 +190,8 @@ int agz_trainer_last_planes(agz_trainer* t, int layer, int* fused, uint32_t* est
 #define AGZ_NPATH_BLK_WINO_H2_3K_WIDE 12  /* ... 128 x 256 GEMM tile */
 #define AGZ_NPATH_BLK_WINO_H2_CHAINED 13  /* chained Winograd fp16x2 block (conv_wino_h2c.hpp) */
 #define AGZ_NPATH_BLK_LAT_H2 14           /* conv_lat_h2_launch: latency regime, one launch per block */
-#define AGZ_NPATH_HEADS_ONE 1             /* heads_kernel: one workgroup per board */
+#define AGZ_NPATH_BLK_BF16 15             /* conv3x3_bf16_dual_kernel: one bf16 product per multiply (AGZ_COMPUTE_BF16, conv_bf16.hpp) */
+#define AGZ_NPATH_HEADS_ONE 1            /* heads_kernel: one workgroup per board */
 #define AGZ_NPATH_HEADS_SPREAD 2          /* heads_feat / heads_fc / heads_out */
 #define AGZ_NPATH_HEADS_SPREAD_NB4 3      /* ... with heads_fc_nb_kernel<4> (from 32 boards) */
 int agz_net_last_paths(agz_net* net, int* input_conv, int* block, int* heads);
@@ -199,6 +200,12 @@ int agz_net_last_paths(agz_net* net, int* input_conv, int* block, int* heads);
  * from the padded NHWC device layout [B][Hp][Wp][Kp] to host[B][K][H][W].  Synchronises and copies; launches nothing.  AGZ_E_STATE before
  * the first forward and after a split step (forward_half), which clears the record. */
 int agz_net_tower_out(agz_net* net, int B, float* host);
+
+/* Tests: dual block `layer` (0 .. SharedLayers - 1) of a committed net ALONE, in the net's current compute mode, on the given input:
+ * x_host [B][K][H][W] is packed into the padded NHWC device layout on the host, the block's kernel runs once, y_host [B][K][H][W] is
+ * unpacked from its output.  Available for AGZ_COMPUTE_BF16 (AGZ_E_UNSUPPORTED in every other mode).  Uses the net's activation buffers:
+ * agz_net_tower_out has nothing to read afterwards until the next forward. */
+int agz_net_block_forward(agz_net* net, int layer, const float* x_host, int B, float* y_host);
 
 /* The smallest batch >= n that runs the kernels of a batch of G boards on this net in its current compute mode (agz_net::min_same_batch, what
  * prepareRoot's packed forward uses): per board the outputs of such a batch are those of the G-board batch bit for bit.  The parity tests
