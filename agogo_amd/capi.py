@@ -18,6 +18,7 @@ INF_NET, INF_DUMMY, INF_SCRIPT, INF_HASH, INF_UNIFORM, INF_CALLBACK = 0, 1, 2, 3
 BN_DEGENERATE_EPS, BN_RUNNING, BN_IDENTITY = 0, 1, 2
 COMPUTE_F32_MFMA, COMPUTE_BF16X3, COMPUTE_FP16X2, COMPUTE_WINO, COMPUTE_AUTO, COMPUTE_WINO_H2 = 0, 1, 2, 3, 4, 5
 COMPUTE_BF16 = 6     # one bf16 product per multiply: NOT fp32-grade (agz.h)
+COMPUTE_BF16_ACT = 7 # COMPUTE_BF16's arithmetic, bit for bit, with bf16 activations between blocks (agz.h)
 COMPUTE_FORCE = 0x100
 LOSS_REFERENCE, LOSS_ALPHAZERO = 0, 1   # agz_trainer_set_loss
 # agz_debug.h, agz_trainer_last_paths: the kernel a trainer layer's last step took (0 = none launched)
@@ -35,7 +36,7 @@ NPATH_BLK_F32_411, NPATH_BLK_F32_221, NPATH_BLK_F32_222 = 1, 2, 3
 NPATH_BLK_F32_411_SPLITK, NPATH_BLK_F32_221_SPLITK, NPATH_BLK_F32_222_SPLITK = 4, 5, 6
 NPATH_BLK_X3, NPATH_BLK_H2W, NPATH_BLK_H2, NPATH_BLK_WINO = 7, 8, 9, 10
 NPATH_BLK_WINO_H2_3K, NPATH_BLK_WINO_H2_3K_WIDE, NPATH_BLK_WINO_H2_CHAINED, NPATH_BLK_LAT_H2 = 11, 12, 13, 14
-NPATH_BLK_BF16 = 15
+NPATH_BLK_BF16, NPATH_BLK_BF16_ACT = 15, 16
 NPATH_HEADS_ONE, NPATH_HEADS_SPREAD, NPATH_HEADS_SPREAD_NB4 = 1, 2, 3
 PROF_CONV, PROF_HEADS, PROF_SELECT, PROF_EXPAND, PROF_MOVE, PROF_CONV_INIT = 0, 1, 2, 3, 4, 5
 PROF_WINO_IN, PROF_WINO_GEMM, PROF_WINO_OUT = 6, 7, 8

@@ -301,6 +301,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_mfma_kernel(ConvArgs a) {
 
 #include "conv_x3.hpp"
 #include "conv_bf16.hpp"
+#include "conv_bf16a.hpp"
 #include "conv_wino.hpp"
 #include "conv_h2.hpp"
 #include "conv_wino_h2.hpp"
@@ -682,17 +683,34 @@ void agz_net::free_device() {
   d_w_dual.clear(); d_ep_dual.clear(); d_w3_dual.clear(); d_w2_dual.clear(); d_u3_dual.clear();
   f(d_head_conv); f(d_head_bn); f(d_Wp); f(d_bp); f(d_W1); f(d_b1); f(d_W2); f(d_b2);
   f(d_act_in); f(d_actA); f(d_actB); f(d_planes); f(d_policy); f(d_value); f(d_ws); f(d_hs);
+  free_bf16_act();
   ws_cap = 0; hs_cap = 0;
   max_batch = 0;
 }
 
+// The bf16 activation pair of AGZ_COMPUTE_BF16_ACT, for as many boards as the fp32 pair holds: zeroed once, the kernels write interiors
+// only, so the zero halo persists as in the fp32 pair.  Nets in another mode, or with fewer than two blocks, never pay for it.
+int agz_net::ensure_bf16_act() {
+  if (compute_mode != AGZ_COMPUTE_BF16_ACT || conf.SharedLayers < 2 || bf16_act_cap >= max_batch) return AGZ_OK;
+  AGZ_HIP_TRY(hipStreamSynchronize(ctx->stream));
+  free_bf16_act();
+  const size_t bytes = (size_t)max_batch * Hp * Wp * Kp * sizeof(unsigned short);
+  AGZ_HIP_TRY(hipMalloc(&d_acthA, bytes));
+  AGZ_HIP_TRY(hipMalloc(&d_acthB, bytes));
+  AGZ_HIP_TRY(hipMemsetAsync(d_acthA, 0, bytes, ctx->stream));
+  AGZ_HIP_TRY(hipMemsetAsync(d_acthB, 0, bytes, ctx->stream));
+  bf16_act_cap = max_batch;
+  return AGZ_OK;
+}
+
 int agz_net::ensure_batch(int B) {
-  if (B <= max_batch) return AGZ_OK;
+  if (B <= max_batch) return ensure_bf16_act();
   // the conv kernels index activations with 32-bit element offsets (and GEMM rows with int)
   AGZ_REQUIRE((size_t)B * Hp * Wp * (size_t)std::max(Kp, Fp) < ((size_t)1 << 31), AGZ_E_UNSUPPORTED,
               "agz_net: batch %d too large for 32-bit activation offsets (%d x %d board, %d channels)", B, H, W, Kp);
   auto f = [](float*& p) { if (p) { hipFree(p); p = nullptr; } };
   f(d_act_in); f(d_actA); f(d_actB); f(d_planes); f(d_policy); f(d_value);
+  free_bf16_act();
   size_t px = (size_t)B * Hp * Wp;
   AGZ_HIP_TRY(hipMalloc(&d_act_in, px * Fp * sizeof(float)));
   AGZ_HIP_TRY(hipMalloc(&d_actA, px * Kp * sizeof(float)));
@@ -705,7 +723,7 @@ int agz_net::ensure_batch(int B) {
   AGZ_HIP_TRY(hipMemsetAsync(d_actA, 0, px * Kp * sizeof(float), ctx->stream));
   AGZ_HIP_TRY(hipMemsetAsync(d_actB, 0, px * Kp * sizeof(float), ctx->stream));
   max_batch = B;
-  return AGZ_OK;
+  return ensure_bf16_act();
 }
 
 // Small batches (tournament-style Agent.Search with one tree = batch 1: 361 rows -> 12 tiles on 256 CUs) get split-K:
@@ -1060,6 +1078,29 @@ int agz_net::bf16_block(int l, int B, const float* x, float* y, hipStream_t st) 
   return AGZ_OK;
 }
 
+// AGZ_COMPUTE_BF16_ACT (conv_bf16a.hpp), towers of two or more blocks: block 0 reads the fp32 x and writes bf16, the blocks between read and
+// write bf16 (ping-pong: block l writes buffer l & 1), the last block writes the fp32 y the heads read
+int agz_net::bf16a_block(int l, int B, const float* x, float* y, hipStream_t st) {
+  const int L = conf.SharedLayers;
+  AGZ_REQUIRE((int)d_wq_dual.size() == L && L >= 2 && l >= 0 && l < L && d_wq_dual[l], AGZ_E_STATE, "agz_net: bf16 weights not built");
+  AGZ_REQUIRE(d_acthA && d_acthB && bf16_act_cap >= B, AGZ_E_STATE, "agz_net: bf16 activation buffers not allocated for %d boards", B);
+  // inside a board the kernel uses 32-bit byte offsets (the board itself is a 64-bit base): the fp32 ends as in bf16_block, the bf16 buffers half
+  AGZ_REQUIRE((size_t)Hp * Wp * Kp * sizeof(float) < ((size_t)1 << 32) && (size_t)HW * Kp * sizeof(float4) < ((size_t)1 << 32), AGZ_E_UNSUPPORTED,
+              "agz_net: board %d x %d with %d channels too large for the bf16 block's 32-bit offsets", H, W, Kp);
+  unsigned short* const hb[2] = {d_acthA, d_acthB};
+  Bf16aArgs q{};
+  q.x = x; q.y = y; q.xh = l > 0 ? hb[(l - 1) & 1] : nullptr; q.yh = l + 1 < L ? hb[l & 1] : nullptr;
+  q.ep = reinterpret_cast<const f32x4*>(d_ep_dual[l]); q.wq = d_wq_dual[l];
+  q.HW = HW; q.W = W; q.Wp = Wp; q.HpWp = Hp * Wp; q.Kp = Kp;
+  q.n_ntiles = 2 * Kp / 128; q.rows_tile = bf16_rows; q.m_per_board = ceil_div(HW, bf16_rows); q.ncc = Kp / 64;
+  const size_t grid = (size_t)B * q.m_per_board * q.n_ntiles;
+  AGZ_REQUIRE(grid < ((size_t)1 << 31), AGZ_E_UNSUPPORTED, "agz_net: batch %d too large for the bf16 block's grid", B);
+  if (l == 0) hipLaunchKernelGGL((conv3x3_bf16a_dual_kernel<false, true>), dim3((unsigned)grid), dim3(256), 0, st, q);
+  else if (l + 1 < L) hipLaunchKernelGGL((conv3x3_bf16a_dual_kernel<true, true>), dim3((unsigned)grid), dim3(256), 0, st, q);
+  else hipLaunchKernelGGL((conv3x3_bf16a_dual_kernel<true, false>), dim3((unsigned)grid), dim3(256), 0, st, q);
+  return AGZ_OK;
+}
+
 // Winograd-domain weights of every dual block (conv_wino.hpp): columns [0,Kp) branch a, [Kp,2Kp) branch b, natural order
 int agz_net::build_wino_weights() {
   AGZ_REQUIRE(cfg == 0, AGZ_E_UNSUPPORTED, "agz_net: the Winograd path needs K a multiple of 64");
@@ -1212,7 +1253,7 @@ agz_net::FwdPlan agz_net::fwd_plan(int B) const {
                     this->compute_mode == AGZ_COMPUTE_BF16X3 || this->compute_mode == AGZ_COMPUTE_FP16X2);
   // AGZ_COMPUTE_BF16 is its own arithmetic (one bf16 product): its block runs at EVERY batch size, FORCE or not — no latency regime,
   // no split-K fp32 fallback (agz_net_set_compute_mode has checked cfg == 0 and SharedLayers > 0)
-  const bool bf16 = this->compute_mode == AGZ_COMPUTE_BF16;
+  const bool bf16 = bf16_mode();                   // (AGZ_COMPUTE_BF16_ACT: the same schedule)
   p.forced_split = p.forced_split || bf16;
   p.latency = p.small && !p.forced_split;          // split-K convolutions
   const int spread_max = 64;
@@ -1237,7 +1278,7 @@ int agz_net::min_same_batch(int n, int G) const {
   const FwdPlan want = fwd_plan(G);
   // AGZ_COMPUTE_BF16: the block kernel is the same at every batch; what still follows the batch is the input convolution where it is
   // not the bf16x3 kernel (K % 128 != 0: whole or half fp32 tiles) and the form of the heads
-  const bool bf16 = compute_mode == AGZ_COMPUTE_BF16;
+  const bool bf16 = bf16_mode();
   auto same = [&](int B) {
     const FwdPlan q = fwd_plan(B);
     if (bf16)
@@ -1444,7 +1485,11 @@ int agz_net::forward_packed(int B, float* policy_dev, float* value_dev) {
   const bool wino_ok = split_ok && compute_mode == AGZ_COMPUTE_WINO;
   const bool wino_h2_ok = split_ok && compute_mode == AGZ_COMPUTE_WINO_H2;
   // (no fallback to another precision: the mode's input convolution addresses the batch with 32-bit byte offsets)
-  AGZ_REQUIRE(compute_mode != AGZ_COMPUTE_BF16 || split_ok, AGZ_E_UNSUPPORTED, "agz_net: batch %d too large for AGZ_COMPUTE_BF16 (activations above 4 GiB)", B);
+  AGZ_REQUIRE(!bf16_mode() || split_ok, AGZ_E_UNSUPPORTED, "agz_net: batch %d too large for AGZ_COMPUTE_BF16 (activations above 4 GiB)", B);
+  if (compute_mode == AGZ_COMPUTE_BF16_ACT) {   // (callers that sized the batch before the mode was set)
+    const int rh = ensure_bf16_act();
+    if (rh != AGZ_OK) return rh;
+  }
   if (wino_h2_ok && d_ep_init_h2) a.ep = d_ep_init_h2;  // the tower takes its input pre-scaled by block 0's t_in (net.hpp)
   if (use_h2 && (size_t)B > amax_cap) {
     AGZ_HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -1611,8 +1656,15 @@ int agz_net::forward_packed(int B, float* policy_dev, float* value_dev) {
       }
       rc = AGZ_OK;
     }
-    else if (compute_mode == AGZ_COMPUTE_BF16) {
+    else if (compute_mode == AGZ_COMPUTE_BF16_ACT && conf.SharedLayers >= 2) {
+      // the same arithmetic with bf16 activations between blocks (conv_bf16a.hpp): only block 0 reads cur, only the last block writes nxt
+      ProfScope ps(ctx, AGZ_PROF_CONV);
+      rc = bf16a_block(l, B, cur, nxt, ctx->stream);
+      path_block = AGZ_NPATH_BLK_BF16_ACT;
+    }
+    else if (bf16_mode()) {
       // one bf16 product per multiply (conv_bf16.hpp), at every batch size: a workgroup per (board, 128-column tile)
+      // (AGZ_COMPUTE_BF16_ACT with a single block: nothing travels between blocks)
       ProfScope ps(ctx, AGZ_PROF_CONV);
       rc = bf16_block(l, B, cur, nxt, ctx->stream);
       path_block = AGZ_NPATH_BLK_BF16;
@@ -2041,7 +2093,7 @@ int agz_net_commit(agz_net* n) {
   n->d_ep_h2.clear();
   if (n->d_ep_init_h2) { hipFree(n->d_ep_init_h2); n->d_ep_init_h2 = nullptr; }
   n->free_wq();
-  if (n->compute_mode == AGZ_COMPUTE_BF16) return n->build_bf16_weights();
+  if (n->bf16_mode()) return n->build_bf16_weights();
   if (n->compute_mode == AGZ_COMPUTE_WINO && n->cfg == 0) return n->build_wino_weights();
   if ((n->compute_mode == AGZ_COMPUTE_WINO_H2 || n->compute_mode == AGZ_COMPUTE_AUTO) && n->cfg == 0) return n->build_wino_h2_weights();
   return AGZ_OK;
@@ -2179,9 +2231,9 @@ int agz_net_set_compute_mode(agz_net* n, int mode) {
   AGZ_REQUIRE(n, AGZ_E_INVALID, "agz_net_set_compute_mode: NULL net");
   const int base = mode & ~AGZ_COMPUTE_FORCE;
   AGZ_REQUIRE(base == AGZ_COMPUTE_F32_MFMA || base == AGZ_COMPUTE_BF16X3 || base == AGZ_COMPUTE_FP16X2 || base == AGZ_COMPUTE_WINO || base == AGZ_COMPUTE_AUTO ||
-                  base == AGZ_COMPUTE_WINO_H2 || base == AGZ_COMPUTE_BF16,
+                  base == AGZ_COMPUTE_WINO_H2 || base == AGZ_COMPUTE_BF16 || base == AGZ_COMPUTE_BF16_ACT,
               AGZ_E_INVALID, "agz_net_set_compute_mode: unknown mode %d", mode);
-  if (base == AGZ_COMPUTE_BF16) {
+  if (base == AGZ_COMPUTE_BF16 || base == AGZ_COMPUTE_BF16_ACT) {   // (the second: the same arithmetic and weight image, bf16 activations between blocks)
     // its own arithmetic, so no other kernel may stand in for it: refuse (and keep the net's mode) where the bf16 block cannot run
     AGZ_REQUIRE(n->conf.K % 64 == 0 && n->conf.SharedLayers > 0, AGZ_E_UNSUPPORTED,
                 "agz_net_set_compute_mode: AGZ_COMPUTE_BF16 needs K a multiple of 64 and SharedLayers > 0 (K = %d, SharedLayers = %d)", n->conf.K, n->conf.SharedLayers);

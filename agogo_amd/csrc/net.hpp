@@ -77,6 +77,14 @@ struct agz_net {
   void free_wq() { for (auto& p : d_wq_dual) if (p) hipFree(p); d_wq_dual.clear(); }
   int build_bf16_weights();                // (re)builds d_wq_dual from the host parameters, every value rounded once to bf16 (RNE)
   int bf16_block(int l, int B, const float* x, float* y, hipStream_t st);   // dual block l of B boards, padded NHWC -> padded NHWC
+  // AGZ_COMPUTE_BF16_ACT (conv_bf16a.hpp): the same arithmetic and weight image, the activations between blocks as bf16
+  bool bf16_mode() const { return compute_mode == AGZ_COMPUTE_BF16 || compute_mode == AGZ_COMPUTE_BF16_ACT; }
+  unsigned short* d_acthA = nullptr;       // bf16 ping-pong pair [bf16_act_cap][Hp][Wp][Kp], zero halo; only nets in that mode with two or more blocks
+  unsigned short* d_acthB = nullptr;
+  int bf16_act_cap = 0;                    // boards the pair holds
+  void free_bf16_act() { if (d_acthA) hipFree(d_acthA); if (d_acthB) hipFree(d_acthB); d_acthA = d_acthB = nullptr; bf16_act_cap = 0; }
+  int ensure_bf16_act();                   // the pair for max_batch boards if the mode wants it (ensure_batch; forward_packed after a mode switch)
+  int bf16a_block(int l, int B, const float* x, float* y, hipStream_t st);   // block l of the tower: fp32 x in (block 0), fp32 y out (the last block), bf16 between
   std::vector<float> w_unscale;            // per layer 2^-eb of the fp16x2 weight scale
   std::vector<unsigned short*> d_u3_dual;  // per layer Winograd-domain bf16x3 image [36][Kp/16][3][2*Kp][16] (AGZ_COMPUTE_WINO), conv_wino.hpp
   std::vector<_Float16*> d_u2_dual;        // per layer Winograd-domain fp16x2 image [36][Kp/32][2][2*Kp][32] (AGZ_COMPUTE_WINO_H2), conv_wino_h2.hpp

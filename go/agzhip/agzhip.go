@@ -118,6 +118,7 @@ const (
 	ComputeWino    = C.AGZ_COMPUTE_WINO   // opt-in: Winograd F(4x4,3x3) with bf16x3 products, ~1.9x BF16X3 at self-play batch sizes
 	ComputeWinoH2  = C.AGZ_COMPUTE_WINO_H2 // Winograd F(5x5,3x3) / F(4x4,3x3) with range-managed fp16x2 products: the fastest at self-play batch sizes
 	ComputeBF16    = C.AGZ_COMPUTE_BF16   // opt-in, NOT fp32-grade: one bf16 product per multiply (operands rounded once, RNE), fp32 accumulation; every batch size
+	ComputeBF16Act = C.AGZ_COMPUTE_BF16_ACT // opt-in: ComputeBF16's arithmetic, bit for bit, with the activations between blocks kept as bf16 in device memory
 	ComputeForce   = C.AGZ_COMPUTE_FORCE  // flag: keep the mode's tower at every batch size
 )
 

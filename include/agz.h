@@ -179,6 +179,14 @@ int agz_net_set_tower_queues(agz_net* net, int queues);
                             * and a board's tower output is bit-identical whatever the batch and wherever the board sits in it (batch-1 speed
                             * is not a goal of this mode).  Nets with K a multiple of 64 and SharedLayers > 0; any other net: AGZ_E_UNSUPPORTED,
                             * the net keeps its mode — there is no fallback to another precision.  conv_bf16.hpp */
+#define AGZ_COMPUTE_BF16_ACT 7 /* The arithmetic of AGZ_COMPUTE_BF16, with results identical to it bit for bit, and the activations between blocks kept
+                            * as bfloat16 in device memory: a block's output is rounded once (the same round to nearest even) in the epilogue of
+                            * the block that produces it instead of on its way into the LDS of the block that reads it — the same values, half the
+                            * bytes, and both operands go global -> LDS by DMA.  The first block reads the input convolution's fp32 output, the
+                            * last block writes the fp32 tensor the heads read; a net of one block runs AGZ_COMPUTE_BF16's kernel.  Same nets,
+                            * same refusals (AGZ_E_UNSUPPORTED, the net keeps its mode), every batch size, with or without AGZ_COMPUTE_FORCE;
+                            * two more activation buffers of half the fp32 pair's size.  Opt-in; AGZ_COMPUTE_AUTO never picks it.
+                            * conv_bf16a.hpp, DESIGN.md section 4g */
 #define AGZ_COMPUTE_FORCE 0x100/* OR-ed in: take the split kernel even below the chip-filling threshold (tests) */
 int agz_net_set_compute_mode(agz_net* net, int mode);
 /* Checkpoint of the learnables in Model() order (+ BN statistics).  The reference gob-encodes G.Values

@@ -191,6 +191,7 @@ int agz_trainer_last_planes(agz_trainer* t, int layer, int* fused, uint32_t* est
 #define AGZ_NPATH_BLK_WINO_H2_CHAINED 13  /* chained Winograd fp16x2 block (conv_wino_h2c.hpp) */
 #define AGZ_NPATH_BLK_LAT_H2 14           /* conv_lat_h2_launch: latency regime, one launch per block */
 #define AGZ_NPATH_BLK_BF16 15             /* conv3x3_bf16_dual_kernel: one bf16 product per multiply (AGZ_COMPUTE_BF16, conv_bf16.hpp) */
+#define AGZ_NPATH_BLK_BF16_ACT 16         /* conv3x3_bf16a_dual_kernel: at least one block read or wrote bf16 activations (AGZ_COMPUTE_BF16_ACT, conv_bf16a.hpp) */
 #define AGZ_NPATH_HEADS_ONE 1            /* heads_kernel: one workgroup per board */
 #define AGZ_NPATH_HEADS_SPREAD 2          /* heads_feat / heads_fc / heads_out */
 #define AGZ_NPATH_HEADS_SPREAD_NB4 3      /* ... with heads_fc_nb_kernel<4> (from 32 boards) */
