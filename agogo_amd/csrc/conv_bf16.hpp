@@ -40,7 +40,7 @@
 //                        n-tiles of a board are adjacent workgroups of one XCD, so three of the four reads are L2 hits),
 //                        weights 2048 x 576 KB = 1.21 GB, epilogue parameters 2048 x 361 x 64 x 16 B = 0.76 GB
 //   registers            DESIGN.md section 4f quotes the compiler's resource-usage remarks
-// Batch-1 speed is out of scope: one board is four workgroups on 256 CUs.
+// Batch-1 speed is out of scope here: one board is four workgroups on 256 CUs (the small-batch form of the bf16-activation tower: conv_bf16s.hpp).
 #pragma once
 // (included by net.hip INSIDE namespace agz, after conv_x3.hpp: bf16x8_t, u32x4_t, f32x16)
 

@@ -54,6 +54,16 @@ struct Bf16aArgs {
   int n_ntiles, m_per_board, rows_tile, ncc;
 };
 
+// the epilogue of one output element, e = {sa, ta, sb, tb}: relu(relu(bn a) + relu(bn b)) in fp32 (shared with conv_bf16s.hpp)
+BF16A_FN __device__ __forceinline__ float bf16_dual_ep(float xa, float xb, f32x4 e) {
+  float va = xa * e.x + e.y;
+  float vb = xb * e.z + e.w;
+  va = va > 0.f ? va : 0.f;
+  vb = vb > 0.f ? vb : 0.f;
+  const float t = va + vb;
+  return t > 0.f ? t : 0.f;
+}
+
 constexpr int BF16A_ROUNDS = BF16_SP_MAX * 8 / 256;   // DMA rounds of a whole activation stage: 14
 static_assert(BF16A_ROUNDS * 256 == BF16_SP_MAX * 8 && BF16A_ROUNDS <= 18, "a stage is a whole number of rounds, at most two per tap");
 
@@ -289,14 +299,7 @@ BF16A_FN __global__ __launch_bounds__(256, 1) void conv3x3_bf16a_dual_kernel(Bf1
         const int m = m0 + wid * 96 + lr;
         float s[2];
 #pragma unroll
-        for (int j = 0; j < 2; j++) {
-          float va = acc[i][j][0][r] * e[rr][j].x + e[rr][j].y;
-          float vb = acc[i][j][1][r] * e[rr][j].z + e[rr][j].w;
-          va = va > 0.f ? va : 0.f;
-          vb = vb > 0.f ? vb : 0.f;
-          const float t = va + vb;
-          s[j] = t > 0.f ? t : 0.f;
-        }
+        for (int j = 0; j < 2; j++) s[j] = bf16_dual_ep(acc[i][j][0][r], acc[i][j][1][r], e[rr][j]);
         if (OUT_BF16) {
           // rows past the end are staged too (their own rows of the wave's region) and never stored
           const unsigned pk = bf16_pack2(s[0], s[1]);                   // channels lane & 31 and 32 + (lane & 31)

@@ -302,6 +302,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_mfma_kernel(ConvArgs a) {
 #include "conv_x3.hpp"
 #include "conv_bf16.hpp"
 #include "conv_bf16a.hpp"
+#include "conv_bf16s.hpp"
 #include "conv_wino.hpp"
 #include "conv_h2.hpp"
 #include "conv_wino_h2.hpp"
@@ -1101,6 +1102,48 @@ int agz_net::bf16a_block(int l, int B, const float* x, float* y, hipStream_t st)
   return AGZ_OK;
 }
 
+// The small-batch form (conv_bf16s.hpp), one decision per forward.  Policy: off, or AUTO with a coarse grid that already has a workgroup
+// per CU -> 0.  Then the largest RB of {4, 2, 1} whose haloed slices fit the stage (measured: four waves that share a weight tile beat
+// more and smaller workgroups even at one board, profiles/bf16_small.md); a board whose RB = 1 slice does not fit (very wide) keeps
+// conv_bf16a.hpp's kernel.
+int agz_net::bf16s_rb(int B) const {
+  if (bf16_small == AGZ_BF16_SMALL_OFF || compute_mode != AGZ_COMPUTE_BF16_ACT || conf.SharedLayers < 2 || bf16_rows <= 0) return 0;
+  auto fits = [&](int rb) {
+    for (int m0 = 0; m0 < HW; m0 += 32 * rb)
+      if (((std::min(m0 + 32 * rb, HW) - 1) / W - m0 / W + 3) * Wp > BF16S_SP_MAX) return false;
+    return true;
+  };
+  if (!fits(1)) return 0;
+  const size_t cus = (size_t)ctx->num_cus;
+  if (bf16_small == AGZ_BF16_SMALL_AUTO && (size_t)B * ceil_div(HW, bf16_rows) * (2 * Kp / 128) >= cus) return 0;
+  int rb = bf16_small_rb && fits(bf16_small_rb) ? bf16_small_rb : fits(4) ? 4 : fits(2) ? 2 : 1;
+  // AUTO: not past the two rounds of resident workgroups (two per CU) up to which the form was measured ahead
+  if (bf16_small == AGZ_BF16_SMALL_AUTO && (size_t)B * ceil_div(ceil_div(HW, 32), rb) * (Kp / 32) > 4 * cus) return 0;
+  return rb;
+}
+
+int agz_net::bf16s_block(int l, int B, const float* x, float* y, hipStream_t st) {
+  const int L = conf.SharedLayers, rb = bf16s_rb(B);
+  AGZ_REQUIRE(rb > 0, AGZ_E_STATE, "agz_net: the small-batch bf16 block does not apply to this net or batch");
+  AGZ_REQUIRE((int)d_wq_dual.size() == L && l >= 0 && l < L && d_wq_dual[l], AGZ_E_STATE, "agz_net: bf16 weights not built");
+  AGZ_REQUIRE(d_acthA && d_acthB && bf16_act_cap >= B, AGZ_E_STATE, "agz_net: bf16 activation buffers not allocated for %d boards", B);
+  // the 32-bit byte offsets inside a board of bf16a_block
+  AGZ_REQUIRE((size_t)Hp * Wp * Kp * sizeof(float) < ((size_t)1 << 32) && (size_t)HW * Kp * sizeof(float4) < ((size_t)1 << 32), AGZ_E_UNSUPPORTED,
+              "agz_net: board %d x %d with %d channels too large for the bf16 block's 32-bit offsets", H, W, Kp);
+  unsigned short* const hb[2] = {d_acthA, d_acthB};
+  Bf16aArgs q{};
+  q.x = x; q.y = y; q.xh = l > 0 ? hb[(l - 1) & 1] : nullptr; q.yh = l + 1 < L ? hb[l & 1] : nullptr;
+  q.ep = reinterpret_cast<const f32x4*>(d_ep_dual[l]); q.wq = d_wq_dual[l];
+  q.HW = HW; q.W = W; q.Wp = Wp; q.HpWp = Hp * Wp; q.Kp = Kp;
+  q.n_ntiles = Kp / 32; q.rows_tile = 32 * rb; q.m_per_board = ceil_div(HW, 32 * rb); q.ncc = Kp / 64;
+  const size_t grid = (size_t)B * q.m_per_board * q.n_ntiles;
+  AGZ_REQUIRE(grid < ((size_t)1 << 31), AGZ_E_UNSUPPORTED, "agz_net: batch %d too large for the bf16 block's grid", B);
+  if (l == 0) hipLaunchKernelGGL((conv3x3_bf16s_dual_kernel<false, true>), dim3((unsigned)grid), dim3(64 * rb), 0, st, q);
+  else if (l + 1 < L) hipLaunchKernelGGL((conv3x3_bf16s_dual_kernel<true, true>), dim3((unsigned)grid), dim3(64 * rb), 0, st, q);
+  else hipLaunchKernelGGL((conv3x3_bf16s_dual_kernel<true, false>), dim3((unsigned)grid), dim3(64 * rb), 0, st, q);
+  return AGZ_OK;
+}
+
 // Winograd-domain weights of every dual block (conv_wino.hpp): columns [0,Kp) branch a, [Kp,2Kp) branch b, natural order
 int agz_net::build_wino_weights() {
   AGZ_REQUIRE(cfg == 0, AGZ_E_UNSUPPORTED, "agz_net: the Winograd path needs K a multiple of 64");
@@ -1658,9 +1701,11 @@ int agz_net::forward_packed(int B, float* policy_dev, float* value_dev) {
     }
     else if (compute_mode == AGZ_COMPUTE_BF16_ACT && conf.SharedLayers >= 2) {
       // the same arithmetic with bf16 activations between blocks (conv_bf16a.hpp): only block 0 reads cur, only the last block writes nxt
+      // (bf16s_rb depends on the net and B alone: every block of a forward takes the same form, conv_bf16s.hpp's below a full chip)
+      const bool small = bf16s_rb(B) > 0;
       ProfScope ps(ctx, AGZ_PROF_CONV);
-      rc = bf16a_block(l, B, cur, nxt, ctx->stream);
-      path_block = AGZ_NPATH_BLK_BF16_ACT;
+      rc = small ? bf16s_block(l, B, cur, nxt, ctx->stream) : bf16a_block(l, B, cur, nxt, ctx->stream);
+      path_block = small ? AGZ_NPATH_BLK_BF16_ACT_SMALL : AGZ_NPATH_BLK_BF16_ACT;
     }
     else if (bf16_mode()) {
       // one bf16 product per multiply (conv_bf16.hpp), at every batch size: a workgroup per (board, 128-column tile)
@@ -2248,6 +2293,26 @@ int agz_net_set_compute_mode(agz_net* n, int mode) {
   n->compute_force = (mode & AGZ_COMPUTE_FORCE) != 0;
   if (base == AGZ_COMPUTE_WINO && n->committed && n->cfg == 0 && n->d_u3_dual.empty()) return n->build_wino_weights();
   if ((base == AGZ_COMPUTE_WINO_H2 || base == AGZ_COMPUTE_AUTO) && n->committed && n->cfg == 0 && n->d_u2_dual.empty()) return n->build_wino_h2_weights();
+  return AGZ_OK;
+}
+
+int agz_net_set_bf16_small_batch(agz_net* n, int policy) {
+  AGZ_REQUIRE(n, AGZ_E_INVALID, "agz_net_set_bf16_small_batch: NULL net");
+  AGZ_REQUIRE(policy == AGZ_BF16_SMALL_OFF || policy == AGZ_BF16_SMALL_AUTO || policy == AGZ_BF16_SMALL_ALWAYS, AGZ_E_INVALID,
+              "agz_net_set_bf16_small_batch: unknown policy %d", policy);
+  n->bf16_small = policy;
+  return AGZ_OK;
+}
+
+int agz_net_get_bf16_small_batch(const agz_net* n, int* policy) {
+  AGZ_REQUIRE(n && policy, AGZ_E_INVALID, "agz_net_get_bf16_small_batch: NULL argument");
+  *policy = n->bf16_small;
+  return AGZ_OK;
+}
+
+int agz_net_debug_set_bf16_small_rb(agz_net* n, int rb) {
+  AGZ_REQUIRE(n && (rb == 0 || rb == 1 || rb == 2 || rb == 4), AGZ_E_INVALID, "agz_net_debug_set_bf16_small_rb: rb must be 0, 1, 2 or 4");
+  n->bf16_small_rb = rb;
   return AGZ_OK;
 }
 

@@ -85,6 +85,11 @@ struct agz_net {
   void free_bf16_act() { if (d_acthA) hipFree(d_acthA); if (d_acthB) hipFree(d_acthB); d_acthA = d_acthB = nullptr; bf16_act_cap = 0; }
   int ensure_bf16_act();                   // the pair for max_batch boards if the mode wants it (ensure_batch; forward_packed after a mode switch)
   int bf16a_block(int l, int B, const float* x, float* y, hipStream_t st);   // block l of the tower: fp32 x in (block 0), fp32 y out (the last block), bf16 between
+  // the small-batch form of that block (conv_bf16s.hpp): one board over many workgroups, the same bits
+  int bf16_small = 0;                      // agz_net_set_bf16_small_batch: AGZ_BF16_SMALL_*
+  int bf16_small_rb = 0;                   // agz_net_debug_set_bf16_small_rb: 0 the launcher's rule, 1 / 2 / 4 forced where it fits
+  int bf16s_rb(int B) const;               // row blocks per workgroup a forward of B boards runs the small form with; 0: it keeps bf16a_block
+  int bf16s_block(int l, int B, const float* x, float* y, hipStream_t st);   // bf16a_block's contract and buffers
   std::vector<float> w_unscale;            // per layer 2^-eb of the fp16x2 weight scale
   std::vector<unsigned short*> d_u3_dual;  // per layer Winograd-domain bf16x3 image [36][Kp/16][3][2*Kp][16] (AGZ_COMPUTE_WINO), conv_wino.hpp
   std::vector<_Float16*> d_u2_dual;        // per layer Winograd-domain fp16x2 image [36][Kp/32][2][2*Kp][32] (AGZ_COMPUTE_WINO_H2), conv_wino_h2.hpp

@@ -122,6 +122,28 @@ const (
 	ComputeForce   = C.AGZ_COMPUTE_FORCE  // flag: keep the mode's tower at every batch size
 )
 
+// SetBF16SmallBatch selects when ComputeBF16Act runs its small-batch kernel (one board split over many workgroups, the same
+// results bit for bit): BF16SmallOff (default), BF16SmallAuto (batches that leave the whole-board kernel short of a workgroup
+// per CU) or BF16SmallAlways.  Inert in every other mode and on nets of one block.
+func (n *Net) SetBF16SmallBatch(policy int) error {
+	defer n.ctx.enter()()
+	return lastErr(C.agz_net_set_bf16_small_batch(n.h, C.int(policy)))
+}
+
+// BF16SmallBatch returns the policy SetBF16SmallBatch set.
+func (n *Net) BF16SmallBatch() (int, error) {
+	defer n.ctx.enter()()
+	var p C.int
+	err := lastErr(C.agz_net_get_bf16_small_batch(n.h, &p))
+	return int(p), err
+}
+
+const (
+	BF16SmallOff    = C.AGZ_BF16_SMALL_OFF
+	BF16SmallAuto   = C.AGZ_BF16_SMALL_AUTO
+	BF16SmallAlways = C.AGZ_BF16_SMALL_ALWAYS
+)
+
 func (n *Net) Close() error { defer n.ctx.enter()(); C.agz_net_destroy(n.h); n.h = nil; return nil }
 
 // Inferencer implements agogo.Inferer over a Net (the batch-1 path; the batched path is BatchedArena).  The board, policy and

@@ -189,6 +189,23 @@ int agz_net_set_tower_queues(agz_net* net, int queues);
                             * conv_bf16a.hpp, DESIGN.md section 4g */
 #define AGZ_COMPUTE_FORCE 0x100/* OR-ed in: take the split kernel even below the chip-filling threshold (tests) */
 int agz_net_set_compute_mode(agz_net* net, int mode);
+/* Small batches under AGZ_COMPUTE_BF16_ACT.  That mode's kernel gives a whole board to one workgroup per 128 filters: one board is four
+ * workgroups, and every launch of up to 64 boards costs what a single workgroup costs.  The small-batch form (conv_bf16s.hpp, DESIGN.md
+ * section 4h) splits a board over many workgroups — 32-row blocks x 64-column tiles, 96 tiles per 19x19 / K=256 board — with the SAME
+ * declared arithmetic and the SAME results bit for bit (K is never split, every output element is one accumulator summed in the same
+ * order), so agz_net_min_same_batch, the arena's packing and the promise that a board's result does not depend on its batch are untouched;
+ * no device memory of its own.  Policy: AGZ_BF16_SMALL_OFF (default: every launch as before), AGZ_BF16_SMALL_AUTO (the small form when
+ * the batch gives the whole-board kernel fewer workgroups than the chip has CUs and the small form at most four per CU, two rounds of
+ * resident workgroups: 1 to 42 boards at 19x19 / K=256, where it was measured 2.1x to 1.02x faster per block),
+ * AGZ_BF16_SMALL_ALWAYS (wherever the board fits the form's LDS stage; a board too wide for it keeps the whole-board kernel).  One
+ * decision per forward.  Has an effect only under AGZ_COMPUTE_BF16_ACT on nets of two or more blocks; otherwise it is stored and inert.
+ * Measured: profiles/bf16_small.md (one board: 0.87 ms per 40-block forward against 1.89; the fp32-grade latency regime of the other
+ * modes is still faster at ONE board). */
+#define AGZ_BF16_SMALL_OFF 0
+#define AGZ_BF16_SMALL_AUTO 1
+#define AGZ_BF16_SMALL_ALWAYS 2
+int agz_net_set_bf16_small_batch(agz_net* net, int policy);
+int agz_net_get_bf16_small_batch(const agz_net* net, int* policy);
 /* Checkpoint of the learnables in Model() order (+ BN statistics).  The reference gob-encodes G.Values
  * (AZ.Save / Dual.GobEncode, agogo.go:175-209, dualnet/dual.go:180-206); gob is Go-only, so this is a documented
  * flat format: "AGZNET01", agz_net_conf, n_params, then per parameter {uint64 n, float32[n]}, then per BN op
