@@ -20,6 +20,7 @@ COMPUTE_F32_MFMA, COMPUTE_BF16X3, COMPUTE_FP16X2, COMPUTE_WINO, COMPUTE_AUTO, CO
 COMPUTE_BF16 = 6     # one bf16 product per multiply: NOT fp32-grade (agz.h)
 COMPUTE_BF16_ACT = 7 # COMPUTE_BF16's arithmetic, bit for bit, with bf16 activations between blocks (agz.h)
 BF16_SMALL_OFF, BF16_SMALL_AUTO, BF16_SMALL_ALWAYS = 0, 1, 2   # agz_net_set_bf16_small_batch
+BF16_PACKED_OFF, BF16_PACKED_AUTO, BF16_PACKED_ALWAYS = 0, 1, 2   # agz_net_set_bf16_packed_boards
 COMPUTE_FORCE = 0x100
 LOSS_REFERENCE, LOSS_ALPHAZERO = 0, 1   # agz_trainer_set_loss
 # agz_debug.h, agz_trainer_last_paths: the kernel a trainer layer's last step took (0 = none launched)
@@ -39,6 +40,7 @@ NPATH_BLK_X3, NPATH_BLK_H2W, NPATH_BLK_H2, NPATH_BLK_WINO = 7, 8, 9, 10
 NPATH_BLK_WINO_H2_3K, NPATH_BLK_WINO_H2_3K_WIDE, NPATH_BLK_WINO_H2_CHAINED, NPATH_BLK_LAT_H2 = 11, 12, 13, 14
 NPATH_BLK_BF16, NPATH_BLK_BF16_ACT = 15, 16
 NPATH_BLK_BF16_ACT_SMALL = 17   # COMPUTE_BF16_ACT's small-batch form (agz_net_set_bf16_small_batch)
+NPATH_BLK_BF16_ACT_PACKED = 18  # COMPUTE_BF16_ACT's packed-boards form (agz_net_set_bf16_packed_boards)
 NPATH_HEADS_ONE, NPATH_HEADS_SPREAD, NPATH_HEADS_SPREAD_NB4 = 1, 2, 3
 PROF_CONV, PROF_HEADS, PROF_SELECT, PROF_EXPAND, PROF_MOVE, PROF_CONV_INIT = 0, 1, 2, 3, 4, 5
 PROF_WINO_IN, PROF_WINO_GEMM, PROF_WINO_OUT = 6, 7, 8
@@ -213,6 +215,9 @@ def lib():
     sig("agz_net_set_compute_mode", i32, vp, i32)
     sig("agz_net_set_bf16_small_batch", i32, vp, i32)
     sig("agz_net_get_bf16_small_batch", i32, vp, C.POINTER(C.c_int))
+    sig("agz_net_set_bf16_packed_boards", i32, vp, i32)
+    sig("agz_net_get_bf16_packed_boards", i32, vp, C.POINTER(C.c_int))
+    sig("agz_bf16_packed_boards_of", i32, i32, i32)
     sig("agz_net_flops_per_eval", f64, vp)
     sig("agz_net_save", i32, vp, C.c_char_p)
     sig("agz_net_load", i32, vp, C.c_char_p)
@@ -352,6 +357,7 @@ def lib():
     sig("agz_net_set_wino_h2_form", i32, vp, i32)
     sig("agz_net_set_wino_h2_gemm", i32, vp, i32)
     sig("agz_net_debug_set_bf16_small_rb", i32, vp, i32)
+    sig("agz_net_debug_set_bf16_packed_g", i32, vp, i32)
     sig("agz_net_wino_h2_last_rows", i32, vp, C.POINTER(C.c_int), C.POINTER(C.c_int))
     sig("agz_net_last_paths", i32, vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int))
     sig("agz_net_tower_out", i32, vp, i32, pf)
@@ -573,6 +579,19 @@ class Net:
     def debug_set_bf16_small_rb(self, rb):
         """agz_debug.h: row blocks per workgroup of the small-batch bf16 block, 0 = the launcher's rule, 1 / 2 / 4 forced where it fits"""
         _check(lib().agz_net_debug_set_bf16_small_rb(self.h, int(rb)), "agz_net_debug_set_bf16_small_rb")
+
+    def set_bf16_packed_boards(self, policy):
+        """agz.h: BF16_PACKED_OFF / AUTO / ALWAYS — COMPUTE_BF16_ACT's kernel with several small boards per workgroup, the same bits"""
+        _check(lib().agz_net_set_bf16_packed_boards(self.h, int(policy)), "agz_net_set_bf16_packed_boards")
+
+    def get_bf16_packed_boards(self):
+        p = C.c_int(0)
+        _check(lib().agz_net_get_bf16_packed_boards(self.h, C.byref(p)), "agz_net_get_bf16_packed_boards")
+        return p.value
+
+    def debug_set_bf16_packed_g(self, g):
+        """agz_debug.h: boards per workgroup of the packed-boards bf16 block, 0 = the launcher's rule, 2 .. bf16_packed_boards_of forced"""
+        _check(lib().agz_net_debug_set_bf16_packed_g(self.h, int(g)), "agz_net_debug_set_bf16_packed_g")
 
     def set_latency_mode(self, on=True):
         _check(lib().agz_net_set_latency_mode(self.h, int(on)), "agz_net_set_latency_mode")

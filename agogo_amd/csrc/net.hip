@@ -303,6 +303,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_mfma_kernel(ConvArgs a) {
 #include "conv_bf16.hpp"
 #include "conv_bf16a.hpp"
 #include "conv_bf16s.hpp"
+#include "conv_bf16p.hpp"
 #include "conv_wino.hpp"
 #include "conv_h2.hpp"
 #include "conv_wino_h2.hpp"
@@ -1144,6 +1145,42 @@ int agz_net::bf16s_block(int l, int B, const float* x, float* y, hipStream_t st)
   return AGZ_OK;
 }
 
+// The packed-boards form (conv_bf16p.hpp), one decision per forward, asked only where bf16s_rb(B) == 0.  Boards per workgroup: the debug
+// value where it fits, else the largest (agz_bf16_packed_boards_of).  AUTO: only where the whole-board grid exceeds the CU count — below
+// that a launch already costs one workgroup's time and packing gains nothing.
+static unsigned bf16p_magic(int d) { return (1u << 20) / (unsigned)d + 1u; }
+
+int agz_net::bf16p_g(int B) const {
+  if (bf16_packed == AGZ_BF16_PACKED_OFF || compute_mode != AGZ_COMPUTE_BF16_ACT || conf.SharedLayers < 2 || bf16_rows <= 0) return 0;
+  const int G = agz_bf16_packed_boards_of(H, W);
+  if (G < 2 || bf16s_rb(B) > 0) return 0;
+  if (bf16_packed == AGZ_BF16_PACKED_AUTO && (size_t)B * (2 * Kp / 128) <= (size_t)ctx->num_cus) return 0;
+  return bf16_packed_g >= 2 && bf16_packed_g <= G ? bf16_packed_g : G;
+}
+
+int agz_net::bf16p_block(int l, int B, const float* x, float* y, hipStream_t st) {
+  const int L = conf.SharedLayers, G = bf16p_g(B);
+  AGZ_REQUIRE(G >= 2 && G * HW <= BF16_ROWS && G * Hp * Wp <= BF16P_SP_MAX, AGZ_E_STATE, "agz_net: the packed-boards bf16 block does not apply to this net or batch");
+  AGZ_REQUIRE((int)d_wq_dual.size() == L && l >= 0 && l < L && d_wq_dual[l], AGZ_E_STATE, "agz_net: bf16 weights not built");
+  AGZ_REQUIRE(d_acthA && d_acthB && bf16_act_cap >= B, AGZ_E_STATE, "agz_net: bf16 activation buffers not allocated for %d boards", B);
+  // the 32-bit byte offsets of bf16a_block, here inside a group of G boards (the group itself is a 64-bit base)
+  AGZ_REQUIRE((size_t)G * Hp * Wp * Kp * sizeof(float) < ((size_t)1 << 32) && (size_t)HW * Kp * sizeof(float4) < ((size_t)1 << 32), AGZ_E_UNSUPPORTED,
+              "agz_net: %d boards of %d x %d with %d channels too large for the bf16 block's 32-bit offsets", G, H, W, Kp);
+  unsigned short* const hb[2] = {d_acthA, d_acthB};
+  Bf16pArgs q{};
+  q.x = x; q.y = y; q.xh = l > 0 ? hb[(l - 1) & 1] : nullptr; q.yh = l + 1 < L ? hb[l & 1] : nullptr;
+  q.ep = reinterpret_cast<const f32x4*>(d_ep_dual[l]); q.wq = d_wq_dual[l];
+  q.B = B; q.G = G; q.HW = HW; q.W = W; q.Wp = Wp; q.HpWp = Hp * Wp; q.Kp = Kp;
+  q.n_ntiles = 2 * Kp / 128; q.ncc = Kp / 64;
+  q.mg_hw = bf16p_magic(HW); q.mg_w = bf16p_magic(W); q.mg_hpwp = bf16p_magic(Hp * Wp); q.mg_wp = bf16p_magic(Wp);
+  const size_t grid = (size_t)ceil_div(B, G) * q.n_ntiles;
+  AGZ_REQUIRE(grid < ((size_t)1 << 31), AGZ_E_UNSUPPORTED, "agz_net: batch %d too large for the bf16 block's grid", B);
+  if (l == 0) hipLaunchKernelGGL((conv3x3_bf16p_dual_kernel<false, true>), dim3((unsigned)grid), dim3(256), 0, st, q);
+  else if (l + 1 < L) hipLaunchKernelGGL((conv3x3_bf16p_dual_kernel<true, true>), dim3((unsigned)grid), dim3(256), 0, st, q);
+  else hipLaunchKernelGGL((conv3x3_bf16p_dual_kernel<true, false>), dim3((unsigned)grid), dim3(256), 0, st, q);
+  return AGZ_OK;
+}
+
 // Winograd-domain weights of every dual block (conv_wino.hpp): columns [0,Kp) branch a, [Kp,2Kp) branch b, natural order
 int agz_net::build_wino_weights() {
   AGZ_REQUIRE(cfg == 0, AGZ_E_UNSUPPORTED, "agz_net: the Winograd path needs K a multiple of 64");
@@ -1702,10 +1739,11 @@ int agz_net::forward_packed(int B, float* policy_dev, float* value_dev) {
     else if (compute_mode == AGZ_COMPUTE_BF16_ACT && conf.SharedLayers >= 2) {
       // the same arithmetic with bf16 activations between blocks (conv_bf16a.hpp): only block 0 reads cur, only the last block writes nxt
       // (bf16s_rb depends on the net and B alone: every block of a forward takes the same form, conv_bf16s.hpp's below a full chip)
-      const bool small = bf16s_rb(B) > 0;
+      // (the packed-boards form, conv_bf16p.hpp, is asked second and only for small boards: bf16p_g is 0 wherever the small form applies)
+      const bool small = bf16s_rb(B) > 0, packed = !small && bf16p_g(B) > 0;
       ProfScope ps(ctx, AGZ_PROF_CONV);
-      rc = small ? bf16s_block(l, B, cur, nxt, ctx->stream) : bf16a_block(l, B, cur, nxt, ctx->stream);
-      path_block = small ? AGZ_NPATH_BLK_BF16_ACT_SMALL : AGZ_NPATH_BLK_BF16_ACT;
+      rc = small ? bf16s_block(l, B, cur, nxt, ctx->stream) : packed ? bf16p_block(l, B, cur, nxt, ctx->stream) : bf16a_block(l, B, cur, nxt, ctx->stream);
+      path_block = small ? AGZ_NPATH_BLK_BF16_ACT_SMALL : packed ? AGZ_NPATH_BLK_BF16_ACT_PACKED : AGZ_NPATH_BLK_BF16_ACT;
     }
     else if (bf16_mode()) {
       // one bf16 product per multiply (conv_bf16.hpp), at every batch size: a workgroup per (board, 128-column tile)
@@ -2313,6 +2351,32 @@ int agz_net_get_bf16_small_batch(const agz_net* n, int* policy) {
 int agz_net_debug_set_bf16_small_rb(agz_net* n, int rb) {
   AGZ_REQUIRE(n && (rb == 0 || rb == 1 || rb == 2 || rb == 4), AGZ_E_INVALID, "agz_net_debug_set_bf16_small_rb: rb must be 0, 1, 2 or 4");
   n->bf16_small_rb = rb;
+  return AGZ_OK;
+}
+
+int agz_bf16_packed_boards_of(int H, int W) {
+  if (H < 1 || W < 1) return 0;
+  const long long hw = (long long)H * W, hpwp = ((long long)H + 2) * ((long long)W + 2);
+  return (int)std::min((long long)BF16_ROWS / hw, (long long)BF16P_SP_MAX / hpwp);
+}
+
+int agz_net_set_bf16_packed_boards(agz_net* n, int policy) {
+  AGZ_REQUIRE(n, AGZ_E_INVALID, "agz_net_set_bf16_packed_boards: NULL net");
+  AGZ_REQUIRE(policy == AGZ_BF16_PACKED_OFF || policy == AGZ_BF16_PACKED_AUTO || policy == AGZ_BF16_PACKED_ALWAYS, AGZ_E_INVALID,
+              "agz_net_set_bf16_packed_boards: unknown policy %d", policy);
+  n->bf16_packed = policy;
+  return AGZ_OK;
+}
+
+int agz_net_get_bf16_packed_boards(const agz_net* n, int* policy) {
+  AGZ_REQUIRE(n && policy, AGZ_E_INVALID, "agz_net_get_bf16_packed_boards: NULL argument");
+  *policy = n->bf16_packed;
+  return AGZ_OK;
+}
+
+int agz_net_debug_set_bf16_packed_g(agz_net* n, int g) {
+  AGZ_REQUIRE(n && (g == 0 || g >= 2), AGZ_E_INVALID, "agz_net_debug_set_bf16_packed_g: g must be 0 or at least 2");
+  n->bf16_packed_g = g;
   return AGZ_OK;
 }
 

@@ -90,6 +90,11 @@ struct agz_net {
   int bf16_small_rb = 0;                   // agz_net_debug_set_bf16_small_rb: 0 the launcher's rule, 1 / 2 / 4 forced where it fits
   int bf16s_rb(int B) const;               // row blocks per workgroup a forward of B boards runs the small form with; 0: it keeps bf16a_block
   int bf16s_block(int l, int B, const float* x, float* y, hipStream_t st);   // bf16a_block's contract and buffers
+  // the packed-boards form of that block (conv_bf16p.hpp): several small boards per workgroup, the same bits
+  int bf16_packed = 0;                     // agz_net_set_bf16_packed_boards: AGZ_BF16_PACKED_*
+  int bf16_packed_g = 0;                   // agz_net_debug_set_bf16_packed_g: 0 the launcher's rule, 2 .. G forced
+  int bf16p_g(int B) const;                // boards per workgroup a forward of B boards runs the packed form with; 0: it keeps bf16s_block / bf16a_block
+  int bf16p_block(int l, int B, const float* x, float* y, hipStream_t st);   // bf16a_block's contract and buffers
   std::vector<float> w_unscale;            // per layer 2^-eb of the fp16x2 weight scale
   std::vector<unsigned short*> d_u3_dual;  // per layer Winograd-domain bf16x3 image [36][Kp/16][3][2*Kp][16] (AGZ_COMPUTE_WINO), conv_wino.hpp
   std::vector<_Float16*> d_u2_dual;        // per layer Winograd-domain fp16x2 image [36][Kp/32][2][2*Kp][32] (AGZ_COMPUTE_WINO_H2), conv_wino_h2.hpp

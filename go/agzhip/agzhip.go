@@ -144,6 +144,31 @@ const (
 	BF16SmallAlways = C.AGZ_BF16_SMALL_ALWAYS
 )
 
+// SetBF16PackedBoards selects when ComputeBF16Act gives a workgroup several small boards instead of one (BF16PackedBoardsOf of
+// them; the same results bit for bit): BF16PackedOff (default), BF16PackedAuto (batches whose whole-board grid exceeds the chip's
+// compute units) or BF16PackedAlways.  Inert in every other mode, on nets of one block and on boards that pack fewer than two.
+func (n *Net) SetBF16PackedBoards(policy int) error {
+	defer n.ctx.enter()()
+	return lastErr(C.agz_net_set_bf16_packed_boards(n.h, C.int(policy)))
+}
+
+// BF16PackedBoards returns the policy SetBF16PackedBoards set.
+func (n *Net) BF16PackedBoards() (int, error) {
+	defer n.ctx.enter()()
+	var p C.int
+	err := lastErr(C.agz_net_get_bf16_packed_boards(n.h, &p))
+	return int(p), err
+}
+
+// BF16PackedBoardsOf returns the boards per workgroup of the packed form on an h x w board (below 2: the form does not exist).
+func BF16PackedBoardsOf(h, w int) int { return int(C.agz_bf16_packed_boards_of(C.int(h), C.int(w))) }
+
+const (
+	BF16PackedOff    = C.AGZ_BF16_PACKED_OFF
+	BF16PackedAuto   = C.AGZ_BF16_PACKED_AUTO
+	BF16PackedAlways = C.AGZ_BF16_PACKED_ALWAYS
+)
+
 func (n *Net) Close() error { defer n.ctx.enter()(); C.agz_net_destroy(n.h); n.h = nil; return nil }
 
 // Inferencer implements agogo.Inferer over a Net (the batch-1 path; the batched path is BatchedArena).  The board, policy and

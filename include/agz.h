@@ -206,6 +206,25 @@ int agz_net_set_compute_mode(agz_net* net, int mode);
 #define AGZ_BF16_SMALL_ALWAYS 2
 int agz_net_set_bf16_small_batch(agz_net* net, int policy);
 int agz_net_get_bf16_small_batch(const agz_net* net, int* policy);
+/* Small BOARDS under AGZ_COMPUTE_BF16_ACT.  That mode's kernel gives a workgroup one board and 384 GEMM rows: on a 9x9 board 81 of them
+ * are live, on Connect-4 42, on tic-tac-toe 9, and the rest are multiplied all the same.  The packed-boards form (conv_bf16p.hpp, DESIGN.md
+ * section 4i) gives a workgroup G consecutive boards, G = agz_bf16_packed_boards_of(H, W) — as many as fit its 384 rows and its LDS stage
+ * of 496 haloed pixels: 19 at 3x3, 6 at 7x6, 4 at 9x9, 2 at 13x13 — with the SAME declared arithmetic and the SAME results bit for bit (K
+ * is never split, every output element is one accumulator summed in the same order), so agz_net_min_same_batch, the arena's packing and
+ * the promise that a board's result does not depend on its batch are untouched; no device memory of its own.  Policy:
+ * AGZ_BF16_PACKED_OFF (default: every launch as before), AGZ_BF16_PACKED_AUTO (the packed form when the whole-board grid, boards x
+ * 128-filter tiles, exceeds the chip's CU count; see profiles/bf16_packed.md for what was measured), AGZ_BF16_PACKED_ALWAYS (every batch).
+ * One decision per forward; the small-batch form above is asked first, the packed form only where that one does not apply.  Has an effect
+ * only under AGZ_COMPUTE_BF16_ACT on nets of two or more blocks whose board has G >= 2; otherwise it is stored and inert: such nets keep
+ * their kernel, nothing is refused and no other precision stands in. */
+#define AGZ_BF16_PACKED_OFF 0
+#define AGZ_BF16_PACKED_AUTO 1
+#define AGZ_BF16_PACKED_ALWAYS 2
+int agz_net_set_bf16_packed_boards(agz_net* net, int policy);
+int agz_net_get_bf16_packed_boards(const agz_net* net, int* policy);
+/* Boards per workgroup of the packed form on an H x W board: min(384 / (H W), 496 / ((H + 2) (W + 2))).  Below 2 (19x19: 1) the form
+ * does not exist for the board.  Host arithmetic only: needs no device and no net. */
+int agz_bf16_packed_boards_of(int H, int W);
 /* Checkpoint of the learnables in Model() order (+ BN statistics).  The reference gob-encodes G.Values
  * (AZ.Save / Dual.GobEncode, agogo.go:175-209, dualnet/dual.go:180-206); gob is Go-only, so this is a documented
  * flat format: "AGZNET01", agz_net_conf, n_params, then per parameter {uint64 n, float32[n]}, then per BN op

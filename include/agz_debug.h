@@ -193,7 +193,8 @@ int agz_trainer_last_planes(agz_trainer* t, int layer, int* fused, uint32_t* est
 #define AGZ_NPATH_BLK_BF16 15             /* conv3x3_bf16_dual_kernel: one bf16 product per multiply (AGZ_COMPUTE_BF16, conv_bf16.hpp) */
 #define AGZ_NPATH_BLK_BF16_ACT 16         /* conv3x3_bf16a_dual_kernel: at least one block read or wrote bf16 activations (AGZ_COMPUTE_BF16_ACT, conv_bf16a.hpp) */
 #define AGZ_NPATH_BLK_BF16_ACT_SMALL 17   /* conv3x3_bf16s_dual_kernel: that mode's small-batch form (agz_net_set_bf16_small_batch, conv_bf16s.hpp) */
-#define AGZ_NPATH_HEADS_ONE 1           /* heads_kernel: one workgroup per board */
+#define AGZ_NPATH_BLK_BF16_ACT_PACKED 18  /* conv3x3_bf16p_dual_kernel: that mode's packed-boards form (agz_net_set_bf16_packed_boards, conv_bf16p.hpp) */
+#define AGZ_NPATH_HEADS_ONE 1          /* heads_kernel: one workgroup per board */
 #define AGZ_NPATH_HEADS_SPREAD 2          /* heads_feat / heads_fc / heads_out */
 #define AGZ_NPATH_HEADS_SPREAD_NB4 3      /* ... with heads_fc_nb_kernel<4> (from 32 boards) */
 int agz_net_last_paths(agz_net* net, int* input_conv, int* block, int* heads);
@@ -202,6 +203,11 @@ int agz_net_last_paths(agz_net* net, int* input_conv, int* block, int* heads);
  * the launcher's rule — the largest of 4, 2, 1 whose slices fit the LDS stage; 1 / 2 / 4: that value wherever its slices fit the stage,
  * so that tests and measurements reach every form.  Results are bit-identical. */
 int agz_net_debug_set_bf16_small_rb(agz_net* net, int rb);
+
+/* Tests: boards per workgroup of the packed-boards bf16 block (agz_net_set_bf16_packed_boards, conv_bf16p.hpp).  0 (default): the launcher's
+ * rule, agz_bf16_packed_boards_of(H, W); 2 .. that value: so many, so that tests and measurements reach tail groups and partly filled
+ * stages (a larger value keeps the rule).  1 and negative values: AGZ_E_INVALID.  Results are bit-identical. */
+int agz_net_debug_set_bf16_packed_g(agz_net* net, int g);
 
 /* Tests: the tensor the heads of the last agz_net_infer / agz_net_infer_dev of B boards read — the tower's output — unpacked on the host
  * from the padded NHWC device layout [B][Hp][Wp][Kp] to host[B][K][H][W].  Synchronises and copies; launches nothing.  AGZ_E_STATE before
