@@ -19,6 +19,7 @@ BN_DEGENERATE_EPS, BN_RUNNING, BN_IDENTITY = 0, 1, 2
 COMPUTE_F32_MFMA, COMPUTE_BF16X3, COMPUTE_FP16X2, COMPUTE_WINO, COMPUTE_AUTO, COMPUTE_WINO_H2 = 0, 1, 2, 3, 4, 5
 COMPUTE_BF16 = 6     # one bf16 product per multiply: NOT fp32-grade (agz.h)
 COMPUTE_BF16_ACT = 7 # COMPUTE_BF16's arithmetic, bit for bit, with bf16 activations between blocks (agz.h)
+COMPUTE_FP16 = 8     # COMPUTE_BF16_ACT's kernels and paths on IEEE half: per-filter weight scales, activations clamped to +-65504 (agz.h)
 BF16_SMALL_OFF, BF16_SMALL_AUTO, BF16_SMALL_ALWAYS = 0, 1, 2   # agz_net_set_bf16_small_batch
 BF16_PACKED_OFF, BF16_PACKED_AUTO, BF16_PACKED_ALWAYS = 0, 1, 2   # agz_net_set_bf16_packed_boards
 COMPUTE_FORCE = 0x100
@@ -41,6 +42,7 @@ NPATH_BLK_WINO_H2_3K, NPATH_BLK_WINO_H2_3K_WIDE, NPATH_BLK_WINO_H2_CHAINED, NPAT
 NPATH_BLK_BF16, NPATH_BLK_BF16_ACT = 15, 16
 NPATH_BLK_BF16_ACT_SMALL = 17   # COMPUTE_BF16_ACT's small-batch form (agz_net_set_bf16_small_batch)
 NPATH_BLK_BF16_ACT_PACKED = 18  # COMPUTE_BF16_ACT's packed-boards form (agz_net_set_bf16_packed_boards)
+NPATH_BLK_FP16, NPATH_BLK_FP16_ACT, NPATH_BLK_FP16_ACT_SMALL, NPATH_BLK_FP16_ACT_PACKED = 19, 20, 21, 22   # COMPUTE_FP16: the same four kernels on half
 NPATH_HEADS_ONE, NPATH_HEADS_SPREAD, NPATH_HEADS_SPREAD_NB4 = 1, 2, 3
 PROF_CONV, PROF_HEADS, PROF_SELECT, PROF_EXPAND, PROF_MOVE, PROF_CONV_INIT = 0, 1, 2, 3, 4, 5
 PROF_WINO_IN, PROF_WINO_GEMM, PROF_WINO_OUT = 6, 7, 8
@@ -568,7 +570,7 @@ class Net:
         _check(lib().agz_net_set_compute_mode(self.h, int(mode)), "agz_net_set_compute_mode")
 
     def set_bf16_small_batch(self, policy):
-        """agz.h: BF16_SMALL_OFF / AUTO / ALWAYS — COMPUTE_BF16_ACT's small-batch kernel, the same bits"""
+        """agz.h: BF16_SMALL_OFF / AUTO / ALWAYS — the small-batch kernel of COMPUTE_BF16_ACT and COMPUTE_FP16, the same bits"""
         _check(lib().agz_net_set_bf16_small_batch(self.h, int(policy)), "agz_net_set_bf16_small_batch")
 
     def get_bf16_small_batch(self):
@@ -581,7 +583,7 @@ class Net:
         _check(lib().agz_net_debug_set_bf16_small_rb(self.h, int(rb)), "agz_net_debug_set_bf16_small_rb")
 
     def set_bf16_packed_boards(self, policy):
-        """agz.h: BF16_PACKED_OFF / AUTO / ALWAYS — COMPUTE_BF16_ACT's kernel with several small boards per workgroup, the same bits"""
+        """agz.h: BF16_PACKED_OFF / AUTO / ALWAYS — the kernel of COMPUTE_BF16_ACT and COMPUTE_FP16 with several small boards per workgroup, the same bits"""
         _check(lib().agz_net_set_bf16_packed_boards(self.h, int(policy)), "agz_net_set_bf16_packed_boards")
 
     def get_bf16_packed_boards(self):
@@ -628,7 +630,7 @@ class Net:
         return t
 
     def block_forward(self, layer, x):
-        """agz_debug.h: dual block `layer` alone in the current compute mode (COMPUTE_BF16): x [B, K, H, W] float32 -> [B, K, H, W]"""
+        """agz_debug.h: dual block `layer` alone in the current compute mode (COMPUTE_BF16 or COMPUTE_FP16): x [B, K, H, W] float32 -> [B, K, H, W]"""
         c = self.conf
         x = np.ascontiguousarray(x, dtype=np.float32)
         assert x.ndim == 4 and x.shape[1:] == (c.K, c.Height, c.Width), x.shape

@@ -41,6 +41,15 @@
 //                        weights 2048 x 576 KB = 1.21 GB, epilogue parameters 2048 x 361 x 64 x 16 B = 0.76 GB
 //   registers            DESIGN.md section 4f quotes the compiler's resource-usage remarks
 // Batch-1 speed is out of scope here: one board is four workgroups on 256 CUs (the small-batch form of the bf16-activation tower: conv_bf16s.hpp).
+//
+// Element type.  The kernel is a template over the 16-bit element E of its two operands: Bf16El (the arithmetic above) or Fp16El
+// (AGZ_COMPUTE_FP16, DESIGN.md section 2 `fp16-tower`, section 4j: IEEE half, every activation clamped to [-65504, 65504] and rounded
+// to nearest even, every filter rounded at its own power-of-two scale by agz_net::build_fp16_weights, which folds the scale back into the
+// epilogue image the kernel is handed as `ep`).  Three things differ under E: the pack-and-round helper (E::pack2), the MFMA (E::mfma:
+// v_mfma_f32_32x32x16_f16 runs at the bf16 instruction's rate on the same operand registers) and the fragment vector type (E::frag).
+// The element is 16 bits either way, so everything else above carries over byte for byte — the LDS images and their swizzle, the bank
+// argument, the XCD order, the accumulation order, the byte model — and the Bf16El instantiation compiles to the code the
+// untemplated kernel compiled to.
 #pragma once
 // (included by net.hip INSIDE namespace agz, after conv_x3.hpp: bf16x8_t, u32x4_t, f32x16)
 
@@ -58,7 +67,7 @@ struct Bf16Args {
   const float* x;            // padded NHWC [B][Hp][Wp][Kp]
   float* y;
   const f32x4* ep;           // {sa, ta, sb, tb} [HW][Kp]
-  const unsigned short* wq;  // agz_net::build_bf16_weights image
+  const unsigned short* wq;  // agz_net::build_bf16_weights image (Fp16El: build_fp16_weights, with its folded ep)
   int HW, W, Wp, HpWp, Kp;
   int n_ntiles, m_per_board, rows_tile, ncc;   // ncc = Kp / 64 channel chunks
 };
@@ -70,6 +79,32 @@ BF16_FN __device__ __forceinline__ unsigned bf16_pack2(float a, float b) {
   bf16_f2 v = {a, b};
   return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16_b2));
 }
+
+// two fp32 -> packed IEEE half pair, a in the low half: clamp to [-65504, 65504], then round to nearest even (the convert follows the
+// mode register's default, RNE; v_cvt_pkrtz would truncate).  The compares are false for a NaN, which so reaches the convert and stays a
+// NaN; +-Inf and every finite value past the half range become +-65504: no Inf ever comes out.  Subnormal halves are produced, not flushed.
+BF16_FN __device__ __forceinline__ unsigned fp16_pack2(float a, float b) {
+  typedef float fp16_f2 __attribute__((ext_vector_type(2)));
+  typedef _Float16 fp16_h2 __attribute__((ext_vector_type(2)));
+  a = a > 65504.f ? 65504.f : a;
+  a = a < -65504.f ? -65504.f : a;
+  b = b > 65504.f ? 65504.f : b;
+  b = b < -65504.f ? -65504.f : b;
+  fp16_f2 v = {a, b};
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, fp16_h2));
+}
+
+// The element types of the single-product tower (conv_bf16.hpp, conv_bf16a.hpp, conv_bf16s.hpp, conv_bf16p.hpp)
+struct Bf16El {
+  typedef bf16x8_t frag;
+  BF16_FN static __device__ __forceinline__ unsigned pack2(float a, float b) { return bf16_pack2(a, b); }
+  BF16_FN static __device__ __forceinline__ f32x16 mfma(frag A, frag B, f32x16 C) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, B, C, 0, 0, 0); }
+};
+struct Fp16El {
+  typedef _Float16 frag __attribute__((ext_vector_type(8)));
+  BF16_FN static __device__ __forceinline__ unsigned pack2(float a, float b) { return fp16_pack2(a, b); }
+  BF16_FN static __device__ __forceinline__ f32x16 mfma(frag A, frag B, f32x16 C) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(A, B, C, 0, 0, 0); }
+};
 
 // __syncthreads() spelled out (the library's is a function without the attribute: it would stay a call)
 BF16_FN __device__ __forceinline__ void bf16_sync() {
@@ -87,7 +122,9 @@ BF16_FN __device__ __forceinline__ void bf16_unit(int idx, int pbase, int Wp, in
   loff = (unsigned)q * 128u + (unsigned)((u ^ (((p - 2 * line) >> 1) & 7)) << 4);
 }
 
+template <typename E>
 BF16_FN __global__ __launch_bounds__(256, 1) void conv3x3_bf16_dual_kernel(Bf16Args a) {
+  typedef typename E::frag frag_t;
   __shared__ __attribute__((aligned(16))) unsigned char lds[2 * BF16_A_STAGE + 2 * BF16_B_STAGE];
   unsigned char* const ldsA = lds;
   unsigned char* const ldsB = lds + 2 * BF16_A_STAGE;
@@ -151,8 +188,8 @@ BF16_FN __global__ __launch_bounds__(256, 1) void conv3x3_bf16_dual_kernel(Bf16A
 #define BF16_STORE_A(DST)                                                                        \
   _Pragma("unroll") for (int s_ = 0; s_ < 2; s_++)                                               \
     if (av[s_]) {                                                                                \
-      u32x4_t v_ = {bf16_pack2(ra[s_][0].x, ra[s_][0].y), bf16_pack2(ra[s_][0].z, ra[s_][0].w),  \
-                    bf16_pack2(ra[s_][1].x, ra[s_][1].y), bf16_pack2(ra[s_][1].z, ra[s_][1].w)}; \
+      u32x4_t v_ = {E::pack2(ra[s_][0].x, ra[s_][0].y), E::pack2(ra[s_][0].z, ra[s_][0].w),      \
+                    E::pack2(ra[s_][1].x, ra[s_][1].y), E::pack2(ra[s_][1].z, ra[s_][1].w)};     \
       *reinterpret_cast<u32x4_t*>((DST) + al[s_]) = v_;                                          \
     }
 #define BF16_LOAD_B(IT)                                                                          \
@@ -185,8 +222,8 @@ BF16_FN __global__ __launch_bounds__(256, 1) void conv3x3_bf16_dual_kernel(Bf16A
 #pragma unroll
     for (int t = 0; t < 9; t++)
       if (pv[t]) {
-        u32x4_t v = {bf16_pack2(pa[t][0].x, pa[t][0].y), bf16_pack2(pa[t][0].z, pa[t][0].w),
-                     bf16_pack2(pa[t][1].x, pa[t][1].y), bf16_pack2(pa[t][1].z, pa[t][1].w)};
+        u32x4_t v = {E::pack2(pa[t][0].x, pa[t][0].y), E::pack2(pa[t][0].z, pa[t][0].w),
+                     E::pack2(pa[t][1].x, pa[t][1].y), E::pack2(pa[t][1].z, pa[t][1].w)};
         *reinterpret_cast<u32x4_t*>(ldsA + pl[t]) = v;
       }
   }
@@ -214,18 +251,18 @@ BF16_FN __global__ __launch_bounds__(256, 1) void conv3x3_bf16_dual_kernel(Bf16A
 #pragma unroll
       for (int ks = 0; ks < 4; ks++) {
         const unsigned u = (unsigned)(2 * ks + half);
-        bf16x8_t A_[3], B_[4];
+        frag_t A_[3], B_[4];
 #pragma unroll
-        for (int i = 0; i < 3; i++) A_[i] = *reinterpret_cast<const bf16x8_t*>(Ac + aoff[i] + ((u ^ asw[i]) << 4));
+        for (int i = 0; i < 3; i++) A_[i] = *reinterpret_cast<const frag_t*>(Ac + aoff[i] + ((u ^ asw[i]) << 4));
 #pragma unroll
-        for (int jb = 0; jb < 4; jb++) B_[jb] = *reinterpret_cast<const bf16x8_t*>(Bc + jb * 4096 + brow + ((u ^ bsw) << 4));
+        for (int jb = 0; jb < 4; jb++) B_[jb] = *reinterpret_cast<const frag_t*>(Bc + jb * 4096 + brow + ((u ^ bsw) << 4));
 #pragma unroll
         for (int i = 0; i < 3; i++)
 #pragma unroll
           for (int j = 0; j < 2; j++)
 #pragma unroll
             for (int br = 0; br < 2; br++)
-              acc[i][j][br] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_[i], B_[br * 2 + j], acc[i][j][br], 0, 0, 0);
+              acc[i][j][br] = E::mfma(A_[i], B_[br * 2 + j], acc[i][j][br]);
       }
       // ... and go to the other stages behind them (last read a whole step / chunk ago, before the barrier that ended it)
       if (more_b) { BF16_STORE_B(ldsB + ((it + 1) & 1) * BF16_B_STAGE) }

@@ -37,6 +37,12 @@
 //   epilogue, !OUT_BF16   the last block stores fp32 as conv_bf16.hpp does: the heads read what they read in AGZ_COMPUTE_BF16.
 // Byte model (19x19, K=256, 512 boards, 2048 workgroups): activations L2 -> CU 2048 x 441 x 256 x 2 B = 0.46 GB (0.92 in conv_bf16.hpp),
 // stored 46 KB per workgroup (92); weights 1.21 GB and epilogue parameters 0.76 GB as before.
+//
+// Element type E (conv_bf16.hpp): Bf16El is everything above; Fp16El is AGZ_COMPUTE_FP16 (DESIGN.md section 2 `fp16-tower`, section 4j) —
+// where "bf16" stands above read "the 16-bit element", where v_cvt_pk_bf16_f32 stands read E::pack2 (half: clamp to +-65504, then RNE),
+// where the MFMA stands read E::mfma.  The activation pair holds halves, `ep` is the folded image of build_fp16_weights.  The element is
+// 16 bits either way: LDS images and swizzles, DMA address maps, the vmcnt / barrier discipline, the XCD order, the accumulation order and
+// the staged write-back are the same bytes and the same instructions, and the bank arguments above are not re-argued.
 #pragma once
 // (included by net.hip INSIDE namespace agz, after conv_bf16.hpp: BF16_*, Bf16Args' helpers bf16_pack2 / bf16_sync / bf16_unit)
 
@@ -67,8 +73,9 @@ BF16A_FN __device__ __forceinline__ float bf16_dual_ep(float xa, float xb, f32x4
 constexpr int BF16A_ROUNDS = BF16_SP_MAX * 8 / 256;   // DMA rounds of a whole activation stage: 14
 static_assert(BF16A_ROUNDS * 256 == BF16_SP_MAX * 8 && BF16A_ROUNDS <= 18, "a stage is a whole number of rounds, at most two per tap");
 
-template <bool IN_BF16, bool OUT_BF16>
+template <typename E, bool IN_BF16, bool OUT_BF16>
 BF16A_FN __global__ __launch_bounds__(256, 1) void conv3x3_bf16a_dual_kernel(Bf16aArgs a) {
+  typedef typename E::frag frag_t;
   // four objects, not one array: see `completion` above
   __shared__ __attribute__((aligned(16))) unsigned char ldsA0[BF16_A_STAGE];
   __shared__ __attribute__((aligned(16))) unsigned char ldsA1[BF16_A_STAGE];
@@ -137,8 +144,8 @@ BF16A_FN __global__ __launch_bounds__(256, 1) void conv3x3_bf16a_dual_kernel(Bf1
 #define BF16A_STORE_A(DST)                                                                       \
   _Pragma("unroll") for (int s_ = 0; s_ < 2; s_++)                                               \
     if (av[s_]) {                                                                                \
-      u32x4_t v_ = {bf16_pack2(ra[s_][0].x, ra[s_][0].y), bf16_pack2(ra[s_][0].z, ra[s_][0].w),  \
-                    bf16_pack2(ra[s_][1].x, ra[s_][1].y), bf16_pack2(ra[s_][1].z, ra[s_][1].w)}; \
+      u32x4_t v_ = {E::pack2(ra[s_][0].x, ra[s_][0].y), E::pack2(ra[s_][0].z, ra[s_][0].w),      \
+                    E::pack2(ra[s_][1].x, ra[s_][1].y), E::pack2(ra[s_][1].z, ra[s_][1].w)};     \
       *reinterpret_cast<u32x4_t*>((DST) + al[s_]) = v_;                                          \
     }
 // this wave's DMA has landed (vmcnt = 0; expcnt and lgkmcnt left alone), then every wave's: the barrier
@@ -194,8 +201,8 @@ BF16A_FN __global__ __launch_bounds__(256, 1) void conv3x3_bf16a_dual_kernel(Bf1
 #pragma unroll
       for (int t = 0; t < 9; t++)
         if (pv[t]) {
-          u32x4_t v = {bf16_pack2(pa[t][0].x, pa[t][0].y), bf16_pack2(pa[t][0].z, pa[t][0].w),
-                       bf16_pack2(pa[t][1].x, pa[t][1].y), bf16_pack2(pa[t][1].z, pa[t][1].w)};
+          u32x4_t v = {E::pack2(pa[t][0].x, pa[t][0].y), E::pack2(pa[t][0].z, pa[t][0].w),
+                       E::pack2(pa[t][1].x, pa[t][1].y), E::pack2(pa[t][1].z, pa[t][1].w)};
           *reinterpret_cast<u32x4_t*>(ldsA0 + pl[t]) = v;
         }
     }
@@ -208,9 +215,9 @@ BF16A_FN __global__ __launch_bounds__(256, 1) void conv3x3_bf16a_dual_kernel(Bf1
   {                                                                                                                       \
     const unsigned u_ = (unsigned)(2 * (KS) + half);                                                                      \
     _Pragma("unroll") for (int i = 0; i < 3; i++)                                                                         \
-      A_[S][i] = *reinterpret_cast<const bf16x8_t*>(Ac + aoff[i] + ((u_ ^ asw[i]) << 4));                                 \
+      A_[S][i] = *reinterpret_cast<const frag_t*>(Ac + aoff[i] + ((u_ ^ asw[i]) << 4));                                   \
     _Pragma("unroll") for (int jb = 0; jb < 4; jb++)                                                                      \
-      B_[S][jb] = *reinterpret_cast<const bf16x8_t*>(Bc + jb * 4096 + brow + ((u_ ^ bsw) << 4));                          \
+      B_[S][jb] = *reinterpret_cast<const frag_t*>(Bc + jb * 4096 + brow + ((u_ ^ bsw) << 4));                            \
   }
 #define BF16A_STEP(TAP, SB)                                                                                               \
   {                                                                                                                       \
@@ -235,14 +242,14 @@ BF16A_FN __global__ __launch_bounds__(256, 1) void conv3x3_bf16a_dual_kernel(Bf1
       aoff[i] = (unsigned)(prel[i] + tapoff) * 128u;                                                                      \
       asw[i] = (unsigned)((mrow[i] + tapsw) >> 1) & 7u;                                                                   \
     }                                                                                                                     \
-    bf16x8_t A_[2][3], B_[2][4];   /* two sets: step ks + 1's reads under step ks's MFMAs */                              \
+    frag_t A_[2][3], B_[2][4];   /* two sets: step ks + 1's reads under step ks's MFMAs */                                \
     BF16A_FRAGS(0, 0)                                                                                                     \
     _Pragma("unroll") for (int ks = 0; ks < 4; ks++) {                                                                    \
       if (ks < 3) BF16A_FRAGS((ks + 1) & 1, ks + 1)                                                                       \
       _Pragma("unroll") for (int i = 0; i < 3; i++)                                                                       \
         _Pragma("unroll") for (int j = 0; j < 2; j++)                                                                     \
           _Pragma("unroll") for (int br = 0; br < 2; br++)                                                                \
-            acc[i][j][br] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_[ks & 1][i], B_[ks & 1][br * 2 + j], acc[i][j][br], 0, 0, 0); \
+            acc[i][j][br] = E::mfma(A_[ks & 1][i], B_[ks & 1][br * 2 + j], acc[i][j][br]);                                \
     }                                                                                                                     \
     if (!IN_BF16 && more_a) { BF16A_STORE_A(An) }                                                                         \
     BF16A_STEP_END()                                                                                                      \
@@ -302,7 +309,7 @@ BF16A_FN __global__ __launch_bounds__(256, 1) void conv3x3_bf16a_dual_kernel(Bf1
         for (int j = 0; j < 2; j++) s[j] = bf16_dual_ep(acc[i][j][0][r], acc[i][j][1][r], e[rr][j]);
         if (OUT_BF16) {
           // rows past the end are staged too (their own rows of the wave's region) and never stored
-          const unsigned pk = bf16_pack2(s[0], s[1]);                   // channels lane & 31 and 32 + (lane & 31)
+          const unsigned pk = E::pack2(s[0], s[1]);                   // channels lane & 31 and 32 + (lane & 31)
           const unsigned g = (unsigned)((lr >> 2) & 1) << 2, c = (unsigned)(lane & 31);
           unsigned char* row = stg + lr * 128 + ((c & 7u) << 1);
           *reinterpret_cast<unsigned short*>(row + (((c >> 3) ^ g) << 4)) = (unsigned short)pk;

@@ -44,6 +44,10 @@
 // LDS: 2 x 496 x 128 + 2 x 16 KB = 159 744 B static, one workgroup per CU.
 // Output: conv_bf16a.hpp's — bf16 through the wave's own 12 KB of the dead stage A0 (4 x 12 KB <= 62 KB) and 16-byte stores, the last
 // block fp32 — each row to the interior of its own board b0 + g.
+//
+// Element type E (conv_bf16.hpp): Fp16El is the packed-boards form of AGZ_COMPUTE_FP16, equal bit for bit to that mode's whole-board
+// kernel by the argument above with E::mfma and E::pack2 in the places of the bf16 instructions.  The element is 16 bits either way: the
+// bank map across board boundaries, the staging, the completion rule and the write-back are the same bytes and the same instructions.
 #pragma once
 // (included by net.hip INSIDE namespace agz, after conv_bf16a.hpp: bf16a_lds_ptr_t, bf16_dual_ep, bf16_pack2 / bf16_sync, BF16_B_STAGE)
 
@@ -82,8 +86,9 @@ BF16P_FN __device__ __forceinline__ unsigned bf16p_f(unsigned q, const Bf16pArgs
   return ((q - g * (unsigned)(a.HpWp - a.HW) - 2u * pl) >> 1) & 7u;
 }
 
-template <bool IN_BF16, bool OUT_BF16>
+template <typename E, bool IN_BF16, bool OUT_BF16>
 BF16P_FN __global__ __launch_bounds__(256, 1) void conv3x3_bf16p_dual_kernel(Bf16pArgs a) {
+  typedef typename E::frag frag_t;
   // four objects, not one array: every LDS access names its stage at compile time (conv_bf16a.hpp, `completion`)
   __shared__ __attribute__((aligned(16))) unsigned char ldsA0[BF16P_A_STAGE];
   __shared__ __attribute__((aligned(16))) unsigned char ldsA1[BF16P_A_STAGE];
@@ -153,8 +158,8 @@ BF16P_FN __global__ __launch_bounds__(256, 1) void conv3x3_bf16p_dual_kernel(Bf1
 #define BF16P_STORE_A(DST)                                                                       \
   _Pragma("unroll") for (int s_ = 0; s_ < 2; s_++)                                               \
     if (av[s_]) {                                                                                \
-      u32x4_t v_ = {bf16_pack2(ra[s_][0].x, ra[s_][0].y), bf16_pack2(ra[s_][0].z, ra[s_][0].w),  \
-                    bf16_pack2(ra[s_][1].x, ra[s_][1].y), bf16_pack2(ra[s_][1].z, ra[s_][1].w)}; \
+      u32x4_t v_ = {E::pack2(ra[s_][0].x, ra[s_][0].y), E::pack2(ra[s_][0].z, ra[s_][0].w),      \
+                    E::pack2(ra[s_][1].x, ra[s_][1].y), E::pack2(ra[s_][1].z, ra[s_][1].w)};     \
       *reinterpret_cast<u32x4_t*>((DST) + al[s_]) = v_;                                          \
     }
 // this wave's DMA has landed (vmcnt = 0; expcnt and lgkmcnt left alone), then every wave's: the barrier
@@ -211,8 +216,8 @@ BF16P_FN __global__ __launch_bounds__(256, 1) void conv3x3_bf16p_dual_kernel(Bf1
 #pragma unroll
       for (int t = 0; t < 9; t++)
         if (pv[t]) {
-          u32x4_t v = {bf16_pack2(pa[t][0].x, pa[t][0].y), bf16_pack2(pa[t][0].z, pa[t][0].w),
-                       bf16_pack2(pa[t][1].x, pa[t][1].y), bf16_pack2(pa[t][1].z, pa[t][1].w)};
+          u32x4_t v = {E::pack2(pa[t][0].x, pa[t][0].y), E::pack2(pa[t][0].z, pa[t][0].w),
+                       E::pack2(pa[t][1].x, pa[t][1].y), E::pack2(pa[t][1].z, pa[t][1].w)};
           *reinterpret_cast<u32x4_t*>(ldsA0 + pl[t]) = v;
         }
     }
@@ -225,9 +230,9 @@ BF16P_FN __global__ __launch_bounds__(256, 1) void conv3x3_bf16p_dual_kernel(Bf1
   {                                                                                                                       \
     const unsigned u_ = (unsigned)(2 * (KS) + half);                                                                      \
     _Pragma("unroll") for (int i = 0; i < 3; i++)                                                                         \
-      A_[S][i] = *reinterpret_cast<const bf16x8_t*>(Ac + aoff[i] + ((u_ ^ asw[i]) << 4));                                 \
+      A_[S][i] = *reinterpret_cast<const frag_t*>(Ac + aoff[i] + ((u_ ^ asw[i]) << 4));                                   \
     _Pragma("unroll") for (int jb = 0; jb < 4; jb++)                                                                      \
-      B_[S][jb] = *reinterpret_cast<const bf16x8_t*>(Bc + jb * 4096 + brow + ((u_ ^ bsw) << 4));                          \
+      B_[S][jb] = *reinterpret_cast<const frag_t*>(Bc + jb * 4096 + brow + ((u_ ^ bsw) << 4));                            \
   }
 #define BF16P_STEP(TAP, SB)                                                                                               \
   {                                                                                                                       \
@@ -252,14 +257,14 @@ BF16P_FN __global__ __launch_bounds__(256, 1) void conv3x3_bf16p_dual_kernel(Bf1
       aoff[i] = (unsigned)(prel[i] + tapoff) * 128u;                                                                      \
       asw[i] = (unsigned)((mrow[i] + tapsw) >> 1) & 7u;                                                                   \
     }                                                                                                                     \
-    bf16x8_t A_[2][3], B_[2][4];   /* two sets: step ks + 1's reads under step ks's MFMAs */                              \
+    frag_t A_[2][3], B_[2][4];   /* two sets: step ks + 1's reads under step ks's MFMAs */                                \
     BF16P_FRAGS(0, 0)                                                                                                     \
     _Pragma("unroll") for (int ks = 0; ks < 4; ks++) {                                                                    \
       if (ks < 3) BF16P_FRAGS((ks + 1) & 1, ks + 1)                                                                       \
       _Pragma("unroll") for (int i = 0; i < 3; i++)                                                                       \
         _Pragma("unroll") for (int j = 0; j < 2; j++)                                                                     \
           _Pragma("unroll") for (int br = 0; br < 2; br++)                                                                \
-            acc[i][j][br] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_[ks & 1][i], B_[ks & 1][br * 2 + j], acc[i][j][br], 0, 0, 0); \
+            acc[i][j][br] = E::mfma(A_[ks & 1][i], B_[ks & 1][br * 2 + j], acc[i][j][br]);                                \
     }                                                                                                                     \
     if (!IN_BF16 && more_a) { BF16P_STORE_A(An) }                                                                         \
     BF16P_STEP_END()                                                                                                      \
@@ -322,7 +327,7 @@ BF16P_FN __global__ __launch_bounds__(256, 1) void conv3x3_bf16p_dual_kernel(Bf1
         for (int j = 0; j < 2; j++) s[j] = bf16_dual_ep(acc[i][j][0][r], acc[i][j][1][r], e[rr][j]);
         if (OUT_BF16) {
           // rows past the end are staged too (their own rows of the wave's region) and never stored
-          const unsigned pk = bf16_pack2(s[0], s[1]);                   // channels lane & 31 and 32 + (lane & 31)
+          const unsigned pk = E::pack2(s[0], s[1]);                   // channels lane & 31 and 32 + (lane & 31)
           const unsigned g = (unsigned)((lr >> 2) & 1) << 2, c = (unsigned)(lane & 31);
           unsigned char* row = stg + lr * 128 + ((c & 7u) << 1);
           *reinterpret_cast<unsigned short*>(row + (((c >> 3) ^ g) << 4)) = (unsigned short)pk;

@@ -32,6 +32,10 @@
 // past the board still takes its part of the DMA and the barriers).
 // Output: bf16 goes through the wave's own 2 KB of the dead stage A0 ([32 rows][32 channels]: a two-way conflict on 16 two-byte writes,
 // left alone) and leaves as 16-byte stores, a pixel's 32 channels = 64 contiguous bytes; the last block stores fp32 as conv_bf16.hpp does.
+//
+// Element type E (conv_bf16.hpp): Fp16El is the small-batch form of AGZ_COMPUTE_FP16, equal bit for bit to that mode's whole-board kernel
+// by the argument above with E::mfma and E::pack2 in the places of the bf16 instructions.  The element is 16 bits either way: the stages,
+// the DMA maps, the completion rule and the write-back are the same bytes and the same instructions.
 #pragma once
 // (included by net.hip INSIDE namespace agz, after conv_bf16a.hpp: Bf16aArgs, bf16a_lds_ptr_t, bf16_dual_ep, bf16_pack2 / bf16_sync / bf16_unit)
 
@@ -45,8 +49,9 @@ static_assert(2 * (BF16S_A_STAGE + BF16S_B_STAGE) <= 80 * 1024, "two workgroups 
 static_assert(9 * BF16S_TAP_ROUNDS * 64 >= BF16S_SP_MAX * 8, "nine taps of one wave bring a whole stage");
 
 // Bf16aArgs with the small form's split: n_ntiles = Kp / 32 column tiles, rows_tile = 32 RB, m_per_board = runs of a board
-template <bool IN_BF16, bool OUT_BF16>
+template <typename E, bool IN_BF16, bool OUT_BF16>
 BF16S_FN __global__ __launch_bounds__(256, 2) void conv3x3_bf16s_dual_kernel(Bf16aArgs a) {
+  typedef typename E::frag frag_t;
   __shared__ __attribute__((aligned(16))) unsigned char ldsA0[BF16S_A_STAGE];
   __shared__ __attribute__((aligned(16))) unsigned char ldsA1[BF16S_A_STAGE];
   __shared__ __attribute__((aligned(16))) unsigned char ldsB0[BF16S_B_STAGE];
@@ -117,8 +122,8 @@ BF16S_FN __global__ __launch_bounds__(256, 2) void conv3x3_bf16s_dual_kernel(Bf1
 #define BF16S_STORE_A(DST)                                                                       \
   _Pragma("unroll") for (int s_ = 0; s_ < BF16S_TAP_ROUNDS; s_++)                                \
     if (av[s_]) {                                                                                \
-      u32x4_t v_ = {bf16_pack2(ra[s_][0].x, ra[s_][0].y), bf16_pack2(ra[s_][0].z, ra[s_][0].w),  \
-                    bf16_pack2(ra[s_][1].x, ra[s_][1].y), bf16_pack2(ra[s_][1].z, ra[s_][1].w)}; \
+      u32x4_t v_ = {E::pack2(ra[s_][0].x, ra[s_][0].y), E::pack2(ra[s_][0].z, ra[s_][0].w),      \
+                    E::pack2(ra[s_][1].x, ra[s_][1].y), E::pack2(ra[s_][1].z, ra[s_][1].w)};     \
       *reinterpret_cast<u32x4_t*>((DST) + al[s_]) = v_;                                          \
     }
 // this wave's DMA has landed (vmcnt = 0; expcnt and lgkmcnt left alone), then every wave's: the barrier
@@ -158,9 +163,9 @@ BF16S_FN __global__ __launch_bounds__(256, 2) void conv3x3_bf16s_dual_kernel(Bf1
 #define BF16S_FRAGS(S, KS)                                                                                                \
   {                                                                                                                       \
     const unsigned u_ = (unsigned)(2 * (KS) + half);                                                                      \
-    A_[S] = *reinterpret_cast<const bf16x8_t*>(Ac + aoff + ((u_ ^ asw) << 4));                                            \
+    A_[S] = *reinterpret_cast<const frag_t*>(Ac + aoff + ((u_ ^ asw) << 4));                                              \
     _Pragma("unroll") for (int br = 0; br < 2; br++)                                                                      \
-      B_[S][br] = *reinterpret_cast<const bf16x8_t*>(Bc + br * 4096 + brow + ((u_ ^ bsw) << 4));                          \
+      B_[S][br] = *reinterpret_cast<const frag_t*>(Bc + br * 4096 + brow + ((u_ ^ bsw) << 4));                            \
   }
 #define BF16S_STEP(TAP, SB)                                                                                               \
   {                                                                                                                       \
@@ -180,12 +185,12 @@ BF16S_FN __global__ __launch_bounds__(256, 2) void conv3x3_bf16s_dual_kernel(Bf1
     const int ky = tap / 3, kx = tap - 3 * ky;                                                                            \
     const unsigned aoff = (unsigned)(prel + ky * a.Wp + kx) * 128u;                                                       \
     const unsigned asw = (unsigned)((mrow + kx + a.W * ky) >> 1) & 7u;                                                    \
-    bf16x8_t A_[2], B_[2][2];   /* two sets: step ks + 1's reads under step ks's MFMAs */                                 \
+    frag_t A_[2], B_[2][2];   /* two sets: step ks + 1's reads under step ks's MFMAs */                                   \
     BF16S_FRAGS(0, 0)                                                                                                     \
     _Pragma("unroll") for (int ks = 0; ks < 4; ks++) {                                                                    \
       if (ks < 3) BF16S_FRAGS((ks + 1) & 1, ks + 1)                                                                       \
       _Pragma("unroll") for (int br = 0; br < 2; br++)                                                                    \
-        acc[br] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_[ks & 1], B_[ks & 1][br], acc[br], 0, 0, 0);                  \
+        acc[br] = E::mfma(A_[ks & 1], B_[ks & 1][br], acc[br]);                                                           \
     }                                                                                                                     \
     if (!IN_BF16 && more_a) { BF16S_STORE_A(An) }                                                                         \
     BF16S_STEP_END()                                                                                                      \
@@ -242,7 +247,7 @@ BF16S_FN __global__ __launch_bounds__(256, 2) void conv3x3_bf16s_dual_kernel(Bf1
       if (OUT_BF16) {
         // rows past the end are staged too (their own rows of the wave's region) and never stored; rows r, r + 1 in one conversion
         if ((rr & 1) == 0) {
-          const unsigned pk = bf16_pack2(s[rr], s[rr + 1]);
+          const unsigned pk = E::pack2(s[rr], s[rr + 1]);
           unsigned char* p = stg + lr * 64 + ((lane & 31) << 1);
           *reinterpret_cast<unsigned short*>(p) = (unsigned short)pk;
           *reinterpret_cast<unsigned short*>(p + 64) = (unsigned short)(pk >> 16);

@@ -25,6 +25,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <type_traits>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -667,6 +668,7 @@ void agz_net::free_device() {
   for (auto& p : d_w3_dual) if (p) { hipFree(p); p = nullptr; }
   for (auto& p : d_w2_dual) if (p) { hipFree(p); p = nullptr; }
   free_wq();
+  free_wh();
   if (d_amax) { hipFree(d_amax); d_amax = nullptr; }
   amax_cap = 0;
   for (auto& p : d_u3_dual) if (p) { hipFree(p); p = nullptr; }
@@ -692,8 +694,10 @@ void agz_net::free_device() {
 
 // The bf16 activation pair of AGZ_COMPUTE_BF16_ACT, for as many boards as the fp32 pair holds: zeroed once, the kernels write interiors
 // only, so the zero halo persists as in the fp32 pair.  Nets in another mode, or with fewer than two blocks, never pay for it.
+// AGZ_COMPUTE_FP16 uses the same pair for its halves: every interior element is rewritten by each forward before it is read, and zero
+// is zero in both formats.
 int agz_net::ensure_bf16_act() {
-  if (compute_mode != AGZ_COMPUTE_BF16_ACT || conf.SharedLayers < 2 || bf16_act_cap >= max_batch) return AGZ_OK;
+  if (!act16_mode() || conf.SharedLayers < 2 || bf16_act_cap >= max_batch) return AGZ_OK;
   AGZ_HIP_TRY(hipStreamSynchronize(ctx->stream));
   free_bf16_act();
   const size_t bytes = (size_t)max_batch * Hp * Wp * Kp * sizeof(unsigned short);
@@ -1040,6 +1044,7 @@ int agz_net::build_bf16_weights() {
   AGZ_HIP_TRY(hipSetDevice(ctx->device));
   free_wq();
   d_wq_dual.assign(L, nullptr);
+  // (the fp16 images of another mode stay: commit frees both, a mode switch builds the one it lacks)
   std::vector<unsigned short> wq(elems);
   size_t pi = 3;   // parameters: init conv (w, gamma, beta), then per block a: (w, gamma, beta), b: (w, gamma, beta)
   for (int l = 0; l < L; l++, pi += 6) {
@@ -1065,18 +1070,126 @@ int agz_net::build_bf16_weights() {
   return AGZ_OK;
 }
 
+// ---- AGZ_COMPUTE_FP16: the same kernels with IEEE half as the element (`fp16-tower`)
+// fp32 -> half as fp16_pack2 (conv_bf16.hpp) does it: clamp to [-65504, 65504], then round to nearest even (ties to the even 10-bit
+// significand, subnormal halves produced, a carry out of the significand moves the exponent); NaN stays a quiet NaN with the top of its payload
+static unsigned short half_rne(float v) {
+  uint32_t u; memcpy(&u, &v, 4);
+  const unsigned short sign = (unsigned short)((u >> 16) & 0x8000u);
+  const uint32_t m = u & 0x7fffffffu;
+  if (m > 0x7f800000u) return (unsigned short)(sign | 0x7e00u | ((m >> 13) & 0x1ffu));
+  if (m >= 0x477fe000u) return (unsigned short)(sign | 0x7bffu);                  // |v| >= 65504 (Inf too): the clamp
+  if (m < 0x33000000u) return sign;                                               // |v| < 2^-25: below half of the least subnormal
+  if (m < 0x38800000u) {                                                          // |v| < 2^-14: a subnormal half, in units of 2^-24
+    const int sh = 126 - (int)(m >> 23);                                          // 14 .. 24 bits of the 24-bit significand go
+    const uint32_t sig = (m & 0x7fffffu) | 0x800000u, q = sig >> sh, rem = sig & ((1u << sh) - 1u), hf = 1u << (sh - 1);
+    return (unsigned short)(sign | (q + (rem > hf || (rem == hf && (q & 1u)) ? 1u : 0u)));
+  }
+  return (unsigned short)(sign | ((m - 0x38000000u + 0xfffu + ((m >> 13) & 1u)) >> 13));
+}
+
+// d_wh_dual[l]: build_bf16_weights' image order with rne_half(w 2^s_n), s_n the integer that puts the largest |w| of output filter n (its
+// K x 9 values) into [2^14, 2^15) — an exact scaling, so every weight is rounded to 11 significant bits at its filter's own scale and none
+// becomes a subnormal half because its filter is small.  d_ep_fp16[l]: d_ep_dual[l] with 2^-s_n folded into the filter's scale (sa for a
+// filter of branch a, sb for branch b) — exact while the folded scale is a normal fp32, so |s_n| shrinks until it is, at every pixel.
+int agz_net::build_fp16_weights() {
+  const int K = conf.K, L = conf.SharedLayers;
+  AGZ_REQUIRE(K % 64 == 0 && L > 0 && bf16_rows > 0, AGZ_E_UNSUPPORTED, "agz_net: AGZ_COMPUTE_FP16 needs K a multiple of 64 and SharedLayers > 0");
+  AGZ_REQUIRE((int)h_ep_dual.size() == L, AGZ_E_STATE, "agz_net: fp16 weights before commit");
+  const int n_ntiles = 2 * Kp / 128, ncc = Kp / 64;
+  const size_t elems = (size_t)n_ntiles * ncc * 9 * (BF16_B_STAGE / 2);
+  AGZ_REQUIRE(elems * 2 < ((size_t)1 << 32), AGZ_E_UNSUPPORTED, "agz_net: K %d too wide for the fp16 weight image", K);
+  AGZ_HIP_TRY(hipSetDevice(ctx->device));
+  free_wh();
+  d_wh_dual.assign(L, nullptr);
+  d_ep_fp16.assign(L, nullptr);
+  std::vector<unsigned short> wq(elems);
+  std::vector<int> sn(2 * (size_t)K);   // s_n: [branch][filter]
+  size_t pi = 3;   // parameters: as in build_bf16_weights
+  for (int l = 0; l < L; l++, pi += 6) {
+    std::vector<float> ep = h_ep_dual[l];
+    for (int br = 0; br < 2; br++) {
+      const std::vector<float>& w = params[pi + 3 * br].v;
+      for (int o = 0; o < K; o++) {
+        float mx = 0.f;
+        for (size_t i = (size_t)o * K * 9; i < (size_t)(o + 1) * K * 9; i++) mx = std::max(mx, fabsf(w[i]));
+        int s = 0;
+        if (mx > 0.f && std::isfinite(mx)) {
+          int e;
+          frexpf(mx, &e);   // mx = f 2^e, 0.5 <= f < 1: 2^14 <= mx 2^(15 - e) < 2^15
+          s = 15 - e;
+        }
+        auto folds = [&](int sh) {
+          for (int p = 0; p < HW; p++) {
+            const float sc = ep[((size_t)p * Kp + o) * 4 + 2 * br], f = ldexpf(sc, -sh);
+            if (sc != 0.f && std::isfinite(sc) && (!std::isfinite(f) || fabsf(f) < std::numeric_limits<float>::min())) return false;
+          }
+          return true;
+        };
+        while (s != 0 && !folds(s)) s += s > 0 ? -1 : 1;
+        sn[(size_t)br * K + o] = s;
+        for (int p = 0; p < HW; p++) {
+          float& sc = ep[((size_t)p * Kp + o) * 4 + 2 * br];
+          sc = ldexpf(sc, -s);
+        }
+      }
+    }
+    for (int nt = 0; nt < n_ntiles; nt++)
+      for (int cc = 0; cc < ncc; cc++)
+        for (int t = 0; t < 9; t++) {
+          unsigned short* img = &wq[(((size_t)nt * ncc + cc) * 9 + t) * (BF16_B_STAGE / 2)];
+          for (int nn = 0; nn < 128; nn++) {
+            const int br = nn >> 6, o = nt * 64 + (nn & 63);
+            const std::vector<float>& w = params[pi + 3 * br].v;
+            const int s = sn[(size_t)br * K + o];
+            for (int c = 0; c < 64; c++) {
+              const int u = c >> 3, ci = cc * 64 + c;
+              img[nn * 64 + ((u ^ ((nn >> 1) & 7)) << 3) + (c & 7)] = half_rne(ldexpf(w[((size_t)o * K + ci) * 9 + t], s));
+            }
+          }
+        }
+    AGZ_HIP_TRY(hipMalloc(&d_wh_dual[l], elems * 2));
+    AGZ_HIP_TRY(hipMalloc(&d_ep_fp16[l], ep.size() * sizeof(float)));
+    AGZ_HIP_TRY(hipMemcpyAsync(d_wh_dual[l], wq.data(), elems * 2, hipMemcpyHostToDevice, ctx->stream));
+    AGZ_HIP_TRY(hipMemcpyAsync(d_ep_fp16[l], ep.data(), ep.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    AGZ_HIP_TRY(hipStreamSynchronize(ctx->stream));
+  }
+  return AGZ_OK;
+}
+
+// the kernels of one launcher, by element type: Bf16El, or Fp16El under AGZ_COMPUTE_FP16
+template <typename E, typename Args>
+static void bf16a_launch(int l, int L, unsigned grid, hipStream_t st, const Args& q) {
+  if (l == 0) hipLaunchKernelGGL((conv3x3_bf16a_dual_kernel<E, false, true>), dim3(grid), dim3(256), 0, st, q);
+  else if (l + 1 < L) hipLaunchKernelGGL((conv3x3_bf16a_dual_kernel<E, true, true>), dim3(grid), dim3(256), 0, st, q);
+  else hipLaunchKernelGGL((conv3x3_bf16a_dual_kernel<E, true, false>), dim3(grid), dim3(256), 0, st, q);
+}
+template <typename E, typename Args>
+static void bf16s_launch(int l, int L, unsigned grid, int rb, hipStream_t st, const Args& q) {
+  if (l == 0) hipLaunchKernelGGL((conv3x3_bf16s_dual_kernel<E, false, true>), dim3(grid), dim3(64 * rb), 0, st, q);
+  else if (l + 1 < L) hipLaunchKernelGGL((conv3x3_bf16s_dual_kernel<E, true, true>), dim3(grid), dim3(64 * rb), 0, st, q);
+  else hipLaunchKernelGGL((conv3x3_bf16s_dual_kernel<E, true, false>), dim3(grid), dim3(64 * rb), 0, st, q);
+}
+template <typename E, typename Args>
+static void bf16p_launch(int l, int L, unsigned grid, hipStream_t st, const Args& q) {
+  if (l == 0) hipLaunchKernelGGL((conv3x3_bf16p_dual_kernel<E, false, true>), dim3(grid), dim3(256), 0, st, q);
+  else if (l + 1 < L) hipLaunchKernelGGL((conv3x3_bf16p_dual_kernel<E, true, true>), dim3(grid), dim3(256), 0, st, q);
+  else hipLaunchKernelGGL((conv3x3_bf16p_dual_kernel<E, true, false>), dim3(grid), dim3(256), 0, st, q);
+}
+
 int agz_net::bf16_block(int l, int B, const float* x, float* y, hipStream_t st) {
-  AGZ_REQUIRE((int)d_wq_dual.size() == conf.SharedLayers && l >= 0 && l < conf.SharedLayers && d_wq_dual[l], AGZ_E_STATE, "agz_net: bf16 weights not built");
+  AGZ_REQUIRE(wq16(l), AGZ_E_STATE, "agz_net: bf16 / fp16 weights not built");
   // inside a board the kernel uses 32-bit byte offsets (the board itself is a 64-bit base)
   AGZ_REQUIRE((size_t)Hp * Wp * Kp * sizeof(float) < ((size_t)1 << 32) && (size_t)HW * Kp * sizeof(float4) < ((size_t)1 << 32), AGZ_E_UNSUPPORTED,
               "agz_net: board %d x %d with %d channels too large for the bf16 block's 32-bit offsets", H, W, Kp);
   Bf16Args q{};
-  q.x = x; q.y = y; q.ep = reinterpret_cast<const f32x4*>(d_ep_dual[l]); q.wq = d_wq_dual[l];
+  q.x = x; q.y = y; q.ep = reinterpret_cast<const f32x4*>(ep16(l)); q.wq = wq16(l);
   q.HW = HW; q.W = W; q.Wp = Wp; q.HpWp = Hp * Wp; q.Kp = Kp;
   q.n_ntiles = 2 * Kp / 128; q.rows_tile = bf16_rows; q.m_per_board = ceil_div(HW, bf16_rows); q.ncc = Kp / 64;
   const size_t grid = (size_t)B * q.m_per_board * q.n_ntiles;
   AGZ_REQUIRE(grid < ((size_t)1 << 31), AGZ_E_UNSUPPORTED, "agz_net: batch %d too large for the bf16 block's grid", B);
-  hipLaunchKernelGGL(conv3x3_bf16_dual_kernel, dim3((unsigned)grid), dim3(256), 0, st, q);
+  if (fp16_mode()) hipLaunchKernelGGL(conv3x3_bf16_dual_kernel<Fp16El>, dim3((unsigned)grid), dim3(256), 0, st, q);
+  else hipLaunchKernelGGL(conv3x3_bf16_dual_kernel<Bf16El>, dim3((unsigned)grid), dim3(256), 0, st, q);
   return AGZ_OK;
 }
 
@@ -1084,7 +1197,7 @@ int agz_net::bf16_block(int l, int B, const float* x, float* y, hipStream_t st) 
 // write bf16 (ping-pong: block l writes buffer l & 1), the last block writes the fp32 y the heads read
 int agz_net::bf16a_block(int l, int B, const float* x, float* y, hipStream_t st) {
   const int L = conf.SharedLayers;
-  AGZ_REQUIRE((int)d_wq_dual.size() == L && L >= 2 && l >= 0 && l < L && d_wq_dual[l], AGZ_E_STATE, "agz_net: bf16 weights not built");
+  AGZ_REQUIRE(L >= 2 && wq16(l), AGZ_E_STATE, "agz_net: bf16 / fp16 weights not built");
   AGZ_REQUIRE(d_acthA && d_acthB && bf16_act_cap >= B, AGZ_E_STATE, "agz_net: bf16 activation buffers not allocated for %d boards", B);
   // inside a board the kernel uses 32-bit byte offsets (the board itself is a 64-bit base): the fp32 ends as in bf16_block, the bf16 buffers half
   AGZ_REQUIRE((size_t)Hp * Wp * Kp * sizeof(float) < ((size_t)1 << 32) && (size_t)HW * Kp * sizeof(float4) < ((size_t)1 << 32), AGZ_E_UNSUPPORTED,
@@ -1092,14 +1205,13 @@ int agz_net::bf16a_block(int l, int B, const float* x, float* y, hipStream_t st)
   unsigned short* const hb[2] = {d_acthA, d_acthB};
   Bf16aArgs q{};
   q.x = x; q.y = y; q.xh = l > 0 ? hb[(l - 1) & 1] : nullptr; q.yh = l + 1 < L ? hb[l & 1] : nullptr;
-  q.ep = reinterpret_cast<const f32x4*>(d_ep_dual[l]); q.wq = d_wq_dual[l];
+  q.ep = reinterpret_cast<const f32x4*>(ep16(l)); q.wq = wq16(l);
   q.HW = HW; q.W = W; q.Wp = Wp; q.HpWp = Hp * Wp; q.Kp = Kp;
   q.n_ntiles = 2 * Kp / 128; q.rows_tile = bf16_rows; q.m_per_board = ceil_div(HW, bf16_rows); q.ncc = Kp / 64;
   const size_t grid = (size_t)B * q.m_per_board * q.n_ntiles;
   AGZ_REQUIRE(grid < ((size_t)1 << 31), AGZ_E_UNSUPPORTED, "agz_net: batch %d too large for the bf16 block's grid", B);
-  if (l == 0) hipLaunchKernelGGL((conv3x3_bf16a_dual_kernel<false, true>), dim3((unsigned)grid), dim3(256), 0, st, q);
-  else if (l + 1 < L) hipLaunchKernelGGL((conv3x3_bf16a_dual_kernel<true, true>), dim3((unsigned)grid), dim3(256), 0, st, q);
-  else hipLaunchKernelGGL((conv3x3_bf16a_dual_kernel<true, false>), dim3((unsigned)grid), dim3(256), 0, st, q);
+  if (fp16_mode()) bf16a_launch<Fp16El>(l, L, (unsigned)grid, st, q);
+  else bf16a_launch<Bf16El>(l, L, (unsigned)grid, st, q);
   return AGZ_OK;
 }
 
@@ -1108,7 +1220,7 @@ int agz_net::bf16a_block(int l, int B, const float* x, float* y, hipStream_t st)
 // more and smaller workgroups even at one board, profiles/bf16_small.md); a board whose RB = 1 slice does not fit (very wide) keeps
 // conv_bf16a.hpp's kernel.
 int agz_net::bf16s_rb(int B) const {
-  if (bf16_small == AGZ_BF16_SMALL_OFF || compute_mode != AGZ_COMPUTE_BF16_ACT || conf.SharedLayers < 2 || bf16_rows <= 0) return 0;
+  if (bf16_small == AGZ_BF16_SMALL_OFF || !act16_mode() || conf.SharedLayers < 2 || bf16_rows <= 0) return 0;
   auto fits = [&](int rb) {
     for (int m0 = 0; m0 < HW; m0 += 32 * rb)
       if (((std::min(m0 + 32 * rb, HW) - 1) / W - m0 / W + 3) * Wp > BF16S_SP_MAX) return false;
@@ -1126,7 +1238,7 @@ int agz_net::bf16s_rb(int B) const {
 int agz_net::bf16s_block(int l, int B, const float* x, float* y, hipStream_t st) {
   const int L = conf.SharedLayers, rb = bf16s_rb(B);
   AGZ_REQUIRE(rb > 0, AGZ_E_STATE, "agz_net: the small-batch bf16 block does not apply to this net or batch");
-  AGZ_REQUIRE((int)d_wq_dual.size() == L && l >= 0 && l < L && d_wq_dual[l], AGZ_E_STATE, "agz_net: bf16 weights not built");
+  AGZ_REQUIRE(wq16(l), AGZ_E_STATE, "agz_net: bf16 / fp16 weights not built");
   AGZ_REQUIRE(d_acthA && d_acthB && bf16_act_cap >= B, AGZ_E_STATE, "agz_net: bf16 activation buffers not allocated for %d boards", B);
   // the 32-bit byte offsets inside a board of bf16a_block
   AGZ_REQUIRE((size_t)Hp * Wp * Kp * sizeof(float) < ((size_t)1 << 32) && (size_t)HW * Kp * sizeof(float4) < ((size_t)1 << 32), AGZ_E_UNSUPPORTED,
@@ -1134,14 +1246,13 @@ int agz_net::bf16s_block(int l, int B, const float* x, float* y, hipStream_t st)
   unsigned short* const hb[2] = {d_acthA, d_acthB};
   Bf16aArgs q{};
   q.x = x; q.y = y; q.xh = l > 0 ? hb[(l - 1) & 1] : nullptr; q.yh = l + 1 < L ? hb[l & 1] : nullptr;
-  q.ep = reinterpret_cast<const f32x4*>(d_ep_dual[l]); q.wq = d_wq_dual[l];
+  q.ep = reinterpret_cast<const f32x4*>(ep16(l)); q.wq = wq16(l);
   q.HW = HW; q.W = W; q.Wp = Wp; q.HpWp = Hp * Wp; q.Kp = Kp;
   q.n_ntiles = Kp / 32; q.rows_tile = 32 * rb; q.m_per_board = ceil_div(HW, 32 * rb); q.ncc = Kp / 64;
   const size_t grid = (size_t)B * q.m_per_board * q.n_ntiles;
   AGZ_REQUIRE(grid < ((size_t)1 << 31), AGZ_E_UNSUPPORTED, "agz_net: batch %d too large for the bf16 block's grid", B);
-  if (l == 0) hipLaunchKernelGGL((conv3x3_bf16s_dual_kernel<false, true>), dim3((unsigned)grid), dim3(64 * rb), 0, st, q);
-  else if (l + 1 < L) hipLaunchKernelGGL((conv3x3_bf16s_dual_kernel<true, true>), dim3((unsigned)grid), dim3(64 * rb), 0, st, q);
-  else hipLaunchKernelGGL((conv3x3_bf16s_dual_kernel<true, false>), dim3((unsigned)grid), dim3(64 * rb), 0, st, q);
+  if (fp16_mode()) bf16s_launch<Fp16El>(l, L, (unsigned)grid, rb, st, q);
+  else bf16s_launch<Bf16El>(l, L, (unsigned)grid, rb, st, q);
   return AGZ_OK;
 }
 
@@ -1151,7 +1262,7 @@ int agz_net::bf16s_block(int l, int B, const float* x, float* y, hipStream_t st)
 static unsigned bf16p_magic(int d) { return (1u << 20) / (unsigned)d + 1u; }
 
 int agz_net::bf16p_g(int B) const {
-  if (bf16_packed == AGZ_BF16_PACKED_OFF || compute_mode != AGZ_COMPUTE_BF16_ACT || conf.SharedLayers < 2 || bf16_rows <= 0) return 0;
+  if (bf16_packed == AGZ_BF16_PACKED_OFF || !act16_mode() || conf.SharedLayers < 2 || bf16_rows <= 0) return 0;
   const int G = agz_bf16_packed_boards_of(H, W);
   if (G < 2 || bf16s_rb(B) > 0) return 0;
   if (bf16_packed == AGZ_BF16_PACKED_AUTO && (size_t)B * (2 * Kp / 128) <= (size_t)ctx->num_cus) return 0;
@@ -1161,7 +1272,7 @@ int agz_net::bf16p_g(int B) const {
 int agz_net::bf16p_block(int l, int B, const float* x, float* y, hipStream_t st) {
   const int L = conf.SharedLayers, G = bf16p_g(B);
   AGZ_REQUIRE(G >= 2 && G * HW <= BF16_ROWS && G * Hp * Wp <= BF16P_SP_MAX, AGZ_E_STATE, "agz_net: the packed-boards bf16 block does not apply to this net or batch");
-  AGZ_REQUIRE((int)d_wq_dual.size() == L && l >= 0 && l < L && d_wq_dual[l], AGZ_E_STATE, "agz_net: bf16 weights not built");
+  AGZ_REQUIRE(wq16(l), AGZ_E_STATE, "agz_net: bf16 / fp16 weights not built");
   AGZ_REQUIRE(d_acthA && d_acthB && bf16_act_cap >= B, AGZ_E_STATE, "agz_net: bf16 activation buffers not allocated for %d boards", B);
   // the 32-bit byte offsets of bf16a_block, here inside a group of G boards (the group itself is a 64-bit base)
   AGZ_REQUIRE((size_t)G * Hp * Wp * Kp * sizeof(float) < ((size_t)1 << 32) && (size_t)HW * Kp * sizeof(float4) < ((size_t)1 << 32), AGZ_E_UNSUPPORTED,
@@ -1169,15 +1280,14 @@ int agz_net::bf16p_block(int l, int B, const float* x, float* y, hipStream_t st)
   unsigned short* const hb[2] = {d_acthA, d_acthB};
   Bf16pArgs q{};
   q.x = x; q.y = y; q.xh = l > 0 ? hb[(l - 1) & 1] : nullptr; q.yh = l + 1 < L ? hb[l & 1] : nullptr;
-  q.ep = reinterpret_cast<const f32x4*>(d_ep_dual[l]); q.wq = d_wq_dual[l];
+  q.ep = reinterpret_cast<const f32x4*>(ep16(l)); q.wq = wq16(l);
   q.B = B; q.G = G; q.HW = HW; q.W = W; q.Wp = Wp; q.HpWp = Hp * Wp; q.Kp = Kp;
   q.n_ntiles = 2 * Kp / 128; q.ncc = Kp / 64;
   q.mg_hw = bf16p_magic(HW); q.mg_w = bf16p_magic(W); q.mg_hpwp = bf16p_magic(Hp * Wp); q.mg_wp = bf16p_magic(Wp);
   const size_t grid = (size_t)ceil_div(B, G) * q.n_ntiles;
   AGZ_REQUIRE(grid < ((size_t)1 << 31), AGZ_E_UNSUPPORTED, "agz_net: batch %d too large for the bf16 block's grid", B);
-  if (l == 0) hipLaunchKernelGGL((conv3x3_bf16p_dual_kernel<false, true>), dim3((unsigned)grid), dim3(256), 0, st, q);
-  else if (l + 1 < L) hipLaunchKernelGGL((conv3x3_bf16p_dual_kernel<true, true>), dim3((unsigned)grid), dim3(256), 0, st, q);
-  else hipLaunchKernelGGL((conv3x3_bf16p_dual_kernel<true, false>), dim3((unsigned)grid), dim3(256), 0, st, q);
+  if (fp16_mode()) bf16p_launch<Fp16El>(l, L, (unsigned)grid, st, q);
+  else bf16p_launch<Bf16El>(l, L, (unsigned)grid, st, q);
   return AGZ_OK;
 }
 
@@ -1333,7 +1443,7 @@ agz_net::FwdPlan agz_net::fwd_plan(int B) const {
                     this->compute_mode == AGZ_COMPUTE_BF16X3 || this->compute_mode == AGZ_COMPUTE_FP16X2);
   // AGZ_COMPUTE_BF16 is its own arithmetic (one bf16 product): its block runs at EVERY batch size, FORCE or not — no latency regime,
   // no split-K fp32 fallback (agz_net_set_compute_mode has checked cfg == 0 and SharedLayers > 0)
-  const bool bf16 = bf16_mode();                   // (AGZ_COMPUTE_BF16_ACT: the same schedule)
+  const bool bf16 = tower16_mode();                // (AGZ_COMPUTE_BF16_ACT, AGZ_COMPUTE_FP16: the same schedule)
   p.forced_split = p.forced_split || bf16;
   p.latency = p.small && !p.forced_split;          // split-K convolutions
   const int spread_max = 64;
@@ -1358,7 +1468,7 @@ int agz_net::min_same_batch(int n, int G) const {
   const FwdPlan want = fwd_plan(G);
   // AGZ_COMPUTE_BF16: the block kernel is the same at every batch; what still follows the batch is the input convolution where it is
   // not the bf16x3 kernel (K % 128 != 0: whole or half fp32 tiles) and the form of the heads
-  const bool bf16 = bf16_mode();
+  const bool bf16 = tower16_mode();
   auto same = [&](int B) {
     const FwdPlan q = fwd_plan(B);
     if (bf16)
@@ -1565,8 +1675,8 @@ int agz_net::forward_packed(int B, float* policy_dev, float* value_dev) {
   const bool wino_ok = split_ok && compute_mode == AGZ_COMPUTE_WINO;
   const bool wino_h2_ok = split_ok && compute_mode == AGZ_COMPUTE_WINO_H2;
   // (no fallback to another precision: the mode's input convolution addresses the batch with 32-bit byte offsets)
-  AGZ_REQUIRE(!bf16_mode() || split_ok, AGZ_E_UNSUPPORTED, "agz_net: batch %d too large for AGZ_COMPUTE_BF16 (activations above 4 GiB)", B);
-  if (compute_mode == AGZ_COMPUTE_BF16_ACT) {   // (callers that sized the batch before the mode was set)
+  AGZ_REQUIRE(!tower16_mode() || split_ok, AGZ_E_UNSUPPORTED, "agz_net: batch %d too large for AGZ_COMPUTE_BF16 / AGZ_COMPUTE_FP16 (activations above 4 GiB)", B);
+  if (act16_mode()) {   // (callers that sized the batch before the mode was set)
     const int rh = ensure_bf16_act();
     if (rh != AGZ_OK) return rh;
   }
@@ -1736,21 +1846,23 @@ int agz_net::forward_packed(int B, float* policy_dev, float* value_dev) {
       }
       rc = AGZ_OK;
     }
-    else if (compute_mode == AGZ_COMPUTE_BF16_ACT && conf.SharedLayers >= 2) {
+    else if (act16_mode() && conf.SharedLayers >= 2) {
       // the same arithmetic with bf16 activations between blocks (conv_bf16a.hpp): only block 0 reads cur, only the last block writes nxt
       // (bf16s_rb depends on the net and B alone: every block of a forward takes the same form, conv_bf16s.hpp's below a full chip)
       // (the packed-boards form, conv_bf16p.hpp, is asked second and only for small boards: bf16p_g is 0 wherever the small form applies)
       const bool small = bf16s_rb(B) > 0, packed = !small && bf16p_g(B) > 0;
       ProfScope ps(ctx, AGZ_PROF_CONV);
       rc = small ? bf16s_block(l, B, cur, nxt, ctx->stream) : packed ? bf16p_block(l, B, cur, nxt, ctx->stream) : bf16a_block(l, B, cur, nxt, ctx->stream);
-      path_block = small ? AGZ_NPATH_BLK_BF16_ACT_SMALL : packed ? AGZ_NPATH_BLK_BF16_ACT_PACKED : AGZ_NPATH_BLK_BF16_ACT;
+      // (AGZ_COMPUTE_FP16: the same three launchers on the half instantiations and the folded epilogue image)
+      if (fp16_mode()) path_block = small ? AGZ_NPATH_BLK_FP16_ACT_SMALL : packed ? AGZ_NPATH_BLK_FP16_ACT_PACKED : AGZ_NPATH_BLK_FP16_ACT;
+      else path_block = small ? AGZ_NPATH_BLK_BF16_ACT_SMALL : packed ? AGZ_NPATH_BLK_BF16_ACT_PACKED : AGZ_NPATH_BLK_BF16_ACT;
     }
-    else if (bf16_mode()) {
+    else if (tower16_mode()) {
       // one bf16 product per multiply (conv_bf16.hpp), at every batch size: a workgroup per (board, 128-column tile)
       // (AGZ_COMPUTE_BF16_ACT with a single block: nothing travels between blocks)
       ProfScope ps(ctx, AGZ_PROF_CONV);
       rc = bf16_block(l, B, cur, nxt, ctx->stream);
-      path_block = AGZ_NPATH_BLK_BF16;
+      path_block = fp16_mode() ? AGZ_NPATH_BLK_FP16 : AGZ_NPATH_BLK_BF16;
     }
     else if (split_ok && compute_mode == AGZ_COMPUTE_BF16X3) {
       a.n_ntiles = ceil_div(a.Ntot, 128); a.n_mtiles = ceil_div(a.M, 128);
@@ -2176,7 +2288,9 @@ int agz_net_commit(agz_net* n) {
   n->d_ep_h2.clear();
   if (n->d_ep_init_h2) { hipFree(n->d_ep_init_h2); n->d_ep_init_h2 = nullptr; }
   n->free_wq();
+  n->free_wh();
   if (n->bf16_mode()) return n->build_bf16_weights();
+  if (n->fp16_mode()) return n->build_fp16_weights();
   if (n->compute_mode == AGZ_COMPUTE_WINO && n->cfg == 0) return n->build_wino_weights();
   if ((n->compute_mode == AGZ_COMPUTE_WINO_H2 || n->compute_mode == AGZ_COMPUTE_AUTO) && n->cfg == 0) return n->build_wino_h2_weights();
   return AGZ_OK;
@@ -2231,7 +2345,7 @@ int agz_net_block_forward(agz_net* n, int layer, const float* x_host, int B, flo
   AGZ_REQUIRE(n && x_host && y_host && B >= 1, AGZ_E_INVALID, "agz_net_block_forward: bad argument");
   AGZ_REQUIRE(n->committed, AGZ_E_STATE, "agz_net_block_forward: commit the net first");
   AGZ_REQUIRE(layer >= 0 && layer < n->conf.SharedLayers, AGZ_E_INVALID, "agz_net_block_forward: layer %d of %d", layer, n->conf.SharedLayers);
-  AGZ_REQUIRE(n->compute_mode == AGZ_COMPUTE_BF16, AGZ_E_UNSUPPORTED, "agz_net_block_forward: only AGZ_COMPUTE_BF16 runs a block alone");
+  AGZ_REQUIRE(n->compute_mode == AGZ_COMPUTE_BF16 || n->fp16_mode(), AGZ_E_UNSUPPORTED, "agz_net_block_forward: only AGZ_COMPUTE_BF16 and AGZ_COMPUTE_FP16 run a block alone");
   AGZ_HIP_TRY(hipSetDevice(n->ctx->device));
   int rc = n->ensure_batch(B);
   if (rc != AGZ_OK) return rc;
@@ -2314,16 +2428,17 @@ int agz_net_set_compute_mode(agz_net* n, int mode) {
   AGZ_REQUIRE(n, AGZ_E_INVALID, "agz_net_set_compute_mode: NULL net");
   const int base = mode & ~AGZ_COMPUTE_FORCE;
   AGZ_REQUIRE(base == AGZ_COMPUTE_F32_MFMA || base == AGZ_COMPUTE_BF16X3 || base == AGZ_COMPUTE_FP16X2 || base == AGZ_COMPUTE_WINO || base == AGZ_COMPUTE_AUTO ||
-                  base == AGZ_COMPUTE_WINO_H2 || base == AGZ_COMPUTE_BF16 || base == AGZ_COMPUTE_BF16_ACT,
+                  base == AGZ_COMPUTE_WINO_H2 || base == AGZ_COMPUTE_BF16 || base == AGZ_COMPUTE_BF16_ACT || base == AGZ_COMPUTE_FP16,
               AGZ_E_INVALID, "agz_net_set_compute_mode: unknown mode %d", mode);
-  if (base == AGZ_COMPUTE_BF16 || base == AGZ_COMPUTE_BF16_ACT) {   // (the second: the same arithmetic and weight image, bf16 activations between blocks)
+  if (base == AGZ_COMPUTE_BF16 || base == AGZ_COMPUTE_BF16_ACT || base == AGZ_COMPUTE_FP16) {
+    // (BF16_ACT: BF16's arithmetic and weight image, bf16 activations between blocks; FP16: BF16_ACT's kernels and paths on IEEE half, its own images)
     // its own arithmetic, so no other kernel may stand in for it: refuse (and keep the net's mode) where the bf16 block cannot run
     AGZ_REQUIRE(n->conf.K % 64 == 0 && n->conf.SharedLayers > 0, AGZ_E_UNSUPPORTED,
-                "agz_net_set_compute_mode: AGZ_COMPUTE_BF16 needs K a multiple of 64 and SharedLayers > 0 (K = %d, SharedLayers = %d)", n->conf.K, n->conf.SharedLayers);
-    AGZ_REQUIRE(n->bf16_rows > 0, AGZ_E_UNSUPPORTED, "agz_net_set_compute_mode: AGZ_COMPUTE_BF16: three haloed lines of a %d-wide board exceed the %d staged pixels",
+                "agz_net_set_compute_mode: AGZ_COMPUTE_BF16 / AGZ_COMPUTE_FP16 need K a multiple of 64 and SharedLayers > 0 (K = %d, SharedLayers = %d)", n->conf.K, n->conf.SharedLayers);
+    AGZ_REQUIRE(n->bf16_rows > 0, AGZ_E_UNSUPPORTED, "agz_net_set_compute_mode: AGZ_COMPUTE_BF16 / AGZ_COMPUTE_FP16: three haloed lines of a %d-wide board exceed the %d staged pixels",
                 n->W, BF16_SP_MAX);
-    if (n->committed && n->d_wq_dual.empty()) {
-      const int rb = n->build_bf16_weights();
+    if (n->committed && (base == AGZ_COMPUTE_FP16 ? n->d_wh_dual.empty() : n->d_wq_dual.empty())) {
+      const int rb = base == AGZ_COMPUTE_FP16 ? n->build_fp16_weights() : n->build_bf16_weights();
       if (rb != AGZ_OK) return rb;
     }
   }

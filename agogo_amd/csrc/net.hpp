@@ -79,7 +79,19 @@ struct agz_net {
   int bf16_block(int l, int B, const float* x, float* y, hipStream_t st);   // dual block l of B boards, padded NHWC -> padded NHWC
   // AGZ_COMPUTE_BF16_ACT (conv_bf16a.hpp): the same arithmetic and weight image, the activations between blocks as bf16
   bool bf16_mode() const { return compute_mode == AGZ_COMPUTE_BF16 || compute_mode == AGZ_COMPUTE_BF16_ACT; }
-  unsigned short* d_acthA = nullptr;       // bf16 ping-pong pair [bf16_act_cap][Hp][Wp][Kp], zero halo; only nets in that mode with two or more blocks
+  // AGZ_COMPUTE_FP16 (DESIGN.md section 2 `fp16-tower`): BF16_ACT's paths, buffers and policies with IEEE half as the element.  Its own
+  // weight image (every filter rounded at its own power-of-two scale) and its own epilogue image (d_ep_dual with the scale folded back)
+  std::vector<unsigned short*> d_wh_dual;  // per layer fp16 image, d_wq_dual's order: rne_half(w 2^s_n)
+  std::vector<float*> d_ep_fp16;           // per layer float4 {sa 2^-s_a(n), ta, sb 2^-s_b(n), tb} [HW][Kp]
+  void free_wh() { for (auto& p : d_wh_dual) if (p) hipFree(p); for (auto& p : d_ep_fp16) if (p) hipFree(p); d_wh_dual.clear(); d_ep_fp16.clear(); }
+  int build_fp16_weights();                // (re)builds both from the host parameters and h_ep_dual
+  bool fp16_mode() const { return compute_mode == AGZ_COMPUTE_FP16; }
+  bool tower16_mode() const { return bf16_mode() || fp16_mode(); }                              // one 16-bit product per multiply
+  bool act16_mode() const { return compute_mode == AGZ_COMPUTE_BF16_ACT || fp16_mode(); }     // 16-bit activations between blocks
+  // the images a block launcher of the current mode hands its kernel (nullptr: not built)
+  const unsigned short* wq16(int l) const { const auto& v = fp16_mode() ? d_wh_dual : d_wq_dual; return (int)v.size() == conf.SharedLayers && l >= 0 && l < conf.SharedLayers ? v[l] : nullptr; }
+  const float* ep16(int l) const { return fp16_mode() ? d_ep_fp16[l] : d_ep_dual[l]; }
+  unsigned short* d_acthA = nullptr;       // bf16 (AGZ_COMPUTE_FP16: half) ping-pong pair [bf16_act_cap][Hp][Wp][Kp], zero halo; only nets in that mode with two or more blocks
   unsigned short* d_acthB = nullptr;
   int bf16_act_cap = 0;                    // boards the pair holds
   void free_bf16_act() { if (d_acthA) hipFree(d_acthA); if (d_acthB) hipFree(d_acthB); d_acthA = d_acthB = nullptr; bf16_act_cap = 0; }

@@ -119,10 +119,11 @@ const (
 	ComputeWinoH2  = C.AGZ_COMPUTE_WINO_H2 // Winograd F(5x5,3x3) / F(4x4,3x3) with range-managed fp16x2 products: the fastest at self-play batch sizes
 	ComputeBF16    = C.AGZ_COMPUTE_BF16   // opt-in, NOT fp32-grade: one bf16 product per multiply (operands rounded once, RNE), fp32 accumulation; every batch size
 	ComputeBF16Act = C.AGZ_COMPUTE_BF16_ACT // opt-in: ComputeBF16's arithmetic, bit for bit, with the activations between blocks kept as bf16 in device memory
+	ComputeFP16    = C.AGZ_COMPUTE_FP16     // opt-in, NOT fp32-grade: ComputeBF16Act's kernels on IEEE half (11 significant bits): weights rounded at per-filter power-of-two scales, activations clamped to +-65504
 	ComputeForce   = C.AGZ_COMPUTE_FORCE  // flag: keep the mode's tower at every batch size
 )
 
-// SetBF16SmallBatch selects when ComputeBF16Act runs its small-batch kernel (one board split over many workgroups, the same
+// SetBF16SmallBatch selects when ComputeBF16Act (or ComputeFP16) runs its small-batch kernel (one board split over many workgroups, the same
 // results bit for bit): BF16SmallOff (default), BF16SmallAuto (batches that leave the whole-board kernel short of a workgroup
 // per CU) or BF16SmallAlways.  Inert in every other mode and on nets of one block.
 func (n *Net) SetBF16SmallBatch(policy int) error {
@@ -144,7 +145,7 @@ const (
 	BF16SmallAlways = C.AGZ_BF16_SMALL_ALWAYS
 )
 
-// SetBF16PackedBoards selects when ComputeBF16Act gives a workgroup several small boards instead of one (BF16PackedBoardsOf of
+// SetBF16PackedBoards selects when ComputeBF16Act (or ComputeFP16) gives a workgroup several small boards instead of one (BF16PackedBoardsOf of
 // them; the same results bit for bit): BF16PackedOff (default), BF16PackedAuto (batches whose whole-board grid exceeds the chip's
 // compute units) or BF16PackedAlways.  Inert in every other mode, on nets of one block and on boards that pack fewer than two.
 func (n *Net) SetBF16PackedBoards(policy int) error {

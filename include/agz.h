@@ -187,9 +187,25 @@ int agz_net_set_tower_queues(agz_net* net, int queues);
                             * same refusals (AGZ_E_UNSUPPORTED, the net keeps its mode), every batch size, with or without AGZ_COMPUTE_FORCE;
                             * two more activation buffers of half the fp32 pair's size.  Opt-in; AGZ_COMPUTE_AUTO never picks it.
                             * conv_bf16a.hpp, DESIGN.md section 4g */
+#define AGZ_COMPUTE_FP16 8 /* ONE IEEE-half product per multiply — NOT fp32-grade, but 11 significant bits per operand where AGZ_COMPUTE_BF16 has 8;
+                            * opt-in (`fp16-tower`; section 4j).  It takes every path AGZ_COMPUTE_BF16_ACT takes — the same
+                            * kernels instantiated on half, launch paths, batch sizes, buffers, small-batch and packed-boards policies, nets
+                            * accepted and refused (AGZ_E_UNSUPPORTED, the net keeps its mode); a net of one block runs conv_bf16.hpp's kernel.
+                            * The arithmetic of the dual blocks, all of it.  Weights: for output filter n of either branch, s_n is the integer
+                            * with 2^14 <= max|w_n| 2^s_n < 2^15 (the maximum over the filter's K x 9 values; an all-zero filter: 0); the image
+                            * holds rne_half(w 2^s_n) and 2^-s_n is folded into that filter's epilogue scale, exactly (|s_n| is reduced where
+                            * the folded scale would leave fp32's normal range): a weight is rounded to 11 significant bits at its filter's own
+                            * scale, and none becomes a subnormal half or is flushed because its filter is small.  Activations: every input
+                            * activation of a block is clamped to [-65504, 65504], then rounded to half, round to nearest even; NaN stays NaN;
+                            * no Inf comes from a finite value; not rescaled, so values below 2^-14 keep an absolute error under 2^-25.  The
+                            * rounding is done on the way into LDS for the fp32 input of block 0 (and of one-block nets) and in the producer's
+                            * epilogue for every later block, stored as half in AGZ_COMPUTE_BF16_ACT's 16-bit activation pair.  Products are
+                            * exact in fp32, accumulation is the MFMA's fp32, the BN / ReLU / add epilogue is the fp32 one of the other modes on
+                            * the folded scales; the last block writes fp32 for the heads; the input convolution and the heads are untouched.
+                            * A board's tower output is bit-identical whatever the batch, its place in it and the form.  AGZ_COMPUTE_AUTO never picks it. */
 #define AGZ_COMPUTE_FORCE 0x100/* OR-ed in: take the split kernel even below the chip-filling threshold (tests) */
 int agz_net_set_compute_mode(agz_net* net, int mode);
-/* Small batches under AGZ_COMPUTE_BF16_ACT.  That mode's kernel gives a whole board to one workgroup per 128 filters: one board is four
+/* Small batches under AGZ_COMPUTE_BF16_ACT and AGZ_COMPUTE_FP16 (the same kernel on IEEE half; read "either mode" below).  That mode's kernel gives a whole board to one workgroup per 128 filters: one board is four
  * workgroups, and every launch of up to 64 boards costs what a single workgroup costs.  The small-batch form (conv_bf16s.hpp, DESIGN.md
  * section 4h) splits a board over many workgroups — 32-row blocks x 64-column tiles, 96 tiles per 19x19 / K=256 board — with the SAME
  * declared arithmetic and the SAME results bit for bit (K is never split, every output element is one accumulator summed in the same
@@ -198,7 +214,7 @@ int agz_net_set_compute_mode(agz_net* net, int mode);
  * the batch gives the whole-board kernel fewer workgroups than the chip has CUs and the small form at most four per CU, two rounds of
  * resident workgroups: 1 to 42 boards at 19x19 / K=256, where it was measured 2.1x to 1.02x faster per block),
  * AGZ_BF16_SMALL_ALWAYS (wherever the board fits the form's LDS stage; a board too wide for it keeps the whole-board kernel).  One
- * decision per forward.  Has an effect only under AGZ_COMPUTE_BF16_ACT on nets of two or more blocks; otherwise it is stored and inert.
+ * decision per forward.  Has an effect only under AGZ_COMPUTE_BF16_ACT and AGZ_COMPUTE_FP16 on nets of two or more blocks; otherwise it is stored and inert.
  * Measured: profiles/bf16_small.md (one board: 0.87 ms per 40-block forward against 1.89; the fp32-grade latency regime of the other
  * modes is still faster at ONE board). */
 #define AGZ_BF16_SMALL_OFF 0
@@ -206,7 +222,7 @@ int agz_net_set_compute_mode(agz_net* net, int mode);
 #define AGZ_BF16_SMALL_ALWAYS 2
 int agz_net_set_bf16_small_batch(agz_net* net, int policy);
 int agz_net_get_bf16_small_batch(const agz_net* net, int* policy);
-/* Small BOARDS under AGZ_COMPUTE_BF16_ACT.  That mode's kernel gives a workgroup one board and 384 GEMM rows: on a 9x9 board 81 of them
+/* Small BOARDS under AGZ_COMPUTE_BF16_ACT and AGZ_COMPUTE_FP16 (the same kernel on IEEE half).  That mode's kernel gives a workgroup one board and 384 GEMM rows: on a 9x9 board 81 of them
  * are live, on Connect-4 42, on tic-tac-toe 9, and the rest are multiplied all the same.  The packed-boards form (conv_bf16p.hpp, DESIGN.md
  * section 4i) gives a workgroup G consecutive boards, G = agz_bf16_packed_boards_of(H, W) — as many as fit its 384 rows and its LDS stage
  * of 496 haloed pixels: 19 at 3x3, 6 at 7x6, 4 at 9x9, 2 at 13x13 — with the SAME declared arithmetic and the SAME results bit for bit (K
@@ -215,7 +231,7 @@ int agz_net_get_bf16_small_batch(const agz_net* net, int* policy);
  * AGZ_BF16_PACKED_OFF (default: every launch as before), AGZ_BF16_PACKED_AUTO (the packed form when the whole-board grid, boards x
  * 128-filter tiles, exceeds the chip's CU count; see profiles/bf16_packed.md for what was measured), AGZ_BF16_PACKED_ALWAYS (every batch).
  * One decision per forward; the small-batch form above is asked first, the packed form only where that one does not apply.  Has an effect
- * only under AGZ_COMPUTE_BF16_ACT on nets of two or more blocks whose board has G >= 2; otherwise it is stored and inert: such nets keep
+ * only under AGZ_COMPUTE_BF16_ACT and AGZ_COMPUTE_FP16 on nets of two or more blocks whose board has G >= 2; otherwise it is stored and inert: such nets keep
  * their kernel, nothing is refused and no other precision stands in. */
 #define AGZ_BF16_PACKED_OFF 0
 #define AGZ_BF16_PACKED_AUTO 1

@@ -194,6 +194,10 @@ int agz_trainer_last_planes(agz_trainer* t, int layer, int* fused, uint32_t* est
 #define AGZ_NPATH_BLK_BF16_ACT 16         /* conv3x3_bf16a_dual_kernel: at least one block read or wrote bf16 activations (AGZ_COMPUTE_BF16_ACT, conv_bf16a.hpp) */
 #define AGZ_NPATH_BLK_BF16_ACT_SMALL 17   /* conv3x3_bf16s_dual_kernel: that mode's small-batch form (agz_net_set_bf16_small_batch, conv_bf16s.hpp) */
 #define AGZ_NPATH_BLK_BF16_ACT_PACKED 18  /* conv3x3_bf16p_dual_kernel: that mode's packed-boards form (agz_net_set_bf16_packed_boards, conv_bf16p.hpp) */
+#define AGZ_NPATH_BLK_FP16 19             /* conv3x3_bf16_dual_kernel<Fp16El>: one half product per multiply (AGZ_COMPUTE_FP16 on a net of one block, agz_net_block_forward) */
+#define AGZ_NPATH_BLK_FP16_ACT 20         /* conv3x3_bf16a_dual_kernel<Fp16El, ..>: AGZ_COMPUTE_FP16, half activations between blocks */
+#define AGZ_NPATH_BLK_FP16_ACT_SMALL 21   /* conv3x3_bf16s_dual_kernel<Fp16El, ..>: that mode's small-batch form (agz_net_set_bf16_small_batch) */
+#define AGZ_NPATH_BLK_FP16_ACT_PACKED 22  /* conv3x3_bf16p_dual_kernel<Fp16El, ..>: that mode's packed-boards form (agz_net_set_bf16_packed_boards) */
 #define AGZ_NPATH_HEADS_ONE 1          /* heads_kernel: one workgroup per board */
 #define AGZ_NPATH_HEADS_SPREAD 2          /* heads_feat / heads_fc / heads_out */
 #define AGZ_NPATH_HEADS_SPREAD_NB4 3      /* ... with heads_fc_nb_kernel<4> (from 32 boards) */
@@ -216,7 +220,7 @@ int agz_net_tower_out(agz_net* net, int B, float* host);
 
 /* Tests: dual block `layer` (0 .. SharedLayers - 1) of a committed net ALONE, in the net's current compute mode, on the given input:
  * x_host [B][K][H][W] is packed into the padded NHWC device layout on the host, the block's kernel runs once, y_host [B][K][H][W] is
- * unpacked from its output.  Available for AGZ_COMPUTE_BF16 (AGZ_E_UNSUPPORTED in every other mode).  Uses the net's activation buffers:
+ * unpacked from its output.  Available for AGZ_COMPUTE_BF16 and AGZ_COMPUTE_FP16 (conv_bf16.hpp's kernel on either element; AGZ_E_UNSUPPORTED in every other mode).  Uses the net's activation buffers:
  * agz_net_tower_out has nothing to read afterwards until the next forward. */
 int agz_net_block_forward(agz_net* net, int layer, const float* x_host, int B, float* y_host);
 
