@@ -21,6 +21,7 @@ COMPUTE_BF16 = 6     # one bf16 product per multiply: NOT fp32-grade (agz.h)
 COMPUTE_BF16_ACT = 7 # COMPUTE_BF16's arithmetic, bit for bit, with bf16 activations between blocks (agz.h)
 COMPUTE_FP16 = 8     # COMPUTE_BF16_ACT's kernels and paths on IEEE half: per-filter weight scales, activations clamped to +-65504 (agz.h)
 BF16_SMALL_OFF, BF16_SMALL_AUTO, BF16_SMALL_ALWAYS = 0, 1, 2   # agz_net_set_bf16_small_batch
+BF16_SMALL_FEW_AUTO, BF16_SMALL_FEW_ALWAYS = 3, 4             # ... with the few-boards kernel (conv_bf16f.hpp) where it fits
 BF16_PACKED_OFF, BF16_PACKED_AUTO, BF16_PACKED_ALWAYS = 0, 1, 2   # agz_net_set_bf16_packed_boards
 COMPUTE_FORCE = 0x100
 LOSS_REFERENCE, LOSS_ALPHAZERO = 0, 1   # agz_trainer_set_loss
@@ -43,6 +44,7 @@ NPATH_BLK_BF16, NPATH_BLK_BF16_ACT = 15, 16
 NPATH_BLK_BF16_ACT_SMALL = 17   # COMPUTE_BF16_ACT's small-batch form (agz_net_set_bf16_small_batch)
 NPATH_BLK_BF16_ACT_PACKED = 18  # COMPUTE_BF16_ACT's packed-boards form (agz_net_set_bf16_packed_boards)
 NPATH_BLK_FP16, NPATH_BLK_FP16_ACT, NPATH_BLK_FP16_ACT_SMALL, NPATH_BLK_FP16_ACT_PACKED = 19, 20, 21, 22   # COMPUTE_FP16: the same four kernels on half
+NPATH_BLK_BF16_ACT_FEW, NPATH_BLK_FP16_ACT_FEW = 23, 24   # the few-boards form of either mode (BF16_SMALL_FEW_*)
 NPATH_HEADS_ONE, NPATH_HEADS_SPREAD, NPATH_HEADS_SPREAD_NB4 = 1, 2, 3
 PROF_CONV, PROF_HEADS, PROF_SELECT, PROF_EXPAND, PROF_MOVE, PROF_CONV_INIT = 0, 1, 2, 3, 4, 5
 PROF_WINO_IN, PROF_WINO_GEMM, PROF_WINO_OUT = 6, 7, 8
@@ -570,7 +572,7 @@ class Net:
         _check(lib().agz_net_set_compute_mode(self.h, int(mode)), "agz_net_set_compute_mode")
 
     def set_bf16_small_batch(self, policy):
-        """agz.h: BF16_SMALL_OFF / AUTO / ALWAYS — the small-batch kernel of COMPUTE_BF16_ACT and COMPUTE_FP16, the same bits"""
+        """agz.h: BF16_SMALL_OFF / AUTO / ALWAYS / FEW_AUTO / FEW_ALWAYS — the small-batch and few-boards kernels of COMPUTE_BF16_ACT and COMPUTE_FP16, the same bits"""
         _check(lib().agz_net_set_bf16_small_batch(self.h, int(policy)), "agz_net_set_bf16_small_batch")
 
     def get_bf16_small_batch(self):

@@ -304,6 +304,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_mfma_kernel(ConvArgs a) {
 #include "conv_bf16.hpp"
 #include "conv_bf16a.hpp"
 #include "conv_bf16s.hpp"
+#include "conv_bf16f.hpp"
 #include "conv_bf16p.hpp"
 #include "conv_wino.hpp"
 #include "conv_h2.hpp"
@@ -1170,6 +1171,18 @@ static void bf16s_launch(int l, int L, unsigned grid, int rb, hipStream_t st, co
   else if (l + 1 < L) hipLaunchKernelGGL((conv3x3_bf16s_dual_kernel<E, true, true>), dim3(grid), dim3(64 * rb), 0, st, q);
   else hipLaunchKernelGGL((conv3x3_bf16s_dual_kernel<E, true, false>), dim3(grid), dim3(64 * rb), 0, st, q);
 }
+template <typename E, int RB, typename Args>
+static void bf16f_launch_rb(int l, int L, unsigned grid, hipStream_t st, const Args& q) {
+  if (l == 0) hipLaunchKernelGGL((conv3x3_bf16f_dual_kernel<E, RB, false, true>), dim3(grid), dim3(128 * RB), 0, st, q);
+  else if (l + 1 < L) hipLaunchKernelGGL((conv3x3_bf16f_dual_kernel<E, RB, true, true>), dim3(grid), dim3(128 * RB), 0, st, q);
+  else hipLaunchKernelGGL((conv3x3_bf16f_dual_kernel<E, RB, true, false>), dim3(grid), dim3(128 * RB), 0, st, q);
+}
+template <typename E, typename Args>
+static void bf16f_launch(int l, int L, unsigned grid, int rb, hipStream_t st, const Args& q) {
+  if (rb == 4) bf16f_launch_rb<E, 4>(l, L, grid, st, q);
+  else if (rb == 2) bf16f_launch_rb<E, 2>(l, L, grid, st, q);
+  else bf16f_launch_rb<E, 1>(l, L, grid, st, q);
+}
 template <typename E, typename Args>
 static void bf16p_launch(int l, int L, unsigned grid, hipStream_t st, const Args& q) {
   if (l == 0) hipLaunchKernelGGL((conv3x3_bf16p_dual_kernel<E, false, true>), dim3(grid), dim3(256), 0, st, q);
@@ -1221,6 +1234,8 @@ int agz_net::bf16a_block(int l, int B, const float* x, float* y, hipStream_t st)
 // conv_bf16a.hpp's kernel.
 int agz_net::bf16s_rb(int B) const {
   if (bf16_small == AGZ_BF16_SMALL_OFF || !act16_mode() || conf.SharedLayers < 2 || bf16_rows <= 0) return 0;
+  // (the FEW policies are ALWAYS and AUTO here: this is what runs where bf16f_rb gives 0)
+  const bool auto_rule = bf16_small == AGZ_BF16_SMALL_AUTO || bf16_small == AGZ_BF16_SMALL_FEW_AUTO;
   auto fits = [&](int rb) {
     for (int m0 = 0; m0 < HW; m0 += 32 * rb)
       if (((std::min(m0 + 32 * rb, HW) - 1) / W - m0 / W + 3) * Wp > BF16S_SP_MAX) return false;
@@ -1228,11 +1243,51 @@ int agz_net::bf16s_rb(int B) const {
   };
   if (!fits(1)) return 0;
   const size_t cus = (size_t)ctx->num_cus;
-  if (bf16_small == AGZ_BF16_SMALL_AUTO && (size_t)B * ceil_div(HW, bf16_rows) * (2 * Kp / 128) >= cus) return 0;
+  if (auto_rule && (size_t)B * ceil_div(HW, bf16_rows) * (2 * Kp / 128) >= cus) return 0;
   int rb = bf16_small_rb && fits(bf16_small_rb) ? bf16_small_rb : fits(4) ? 4 : fits(2) ? 2 : 1;
   // AUTO: not past the two rounds of resident workgroups (two per CU) up to which the form was measured ahead
-  if (bf16_small == AGZ_BF16_SMALL_AUTO && (size_t)B * ceil_div(ceil_div(HW, 32), rb) * (Kp / 32) > 4 * cus) return 0;
+  if (auto_rule && (size_t)B * ceil_div(ceil_div(HW, 32), rb) * (Kp / 32) > 4 * cus) return 0;
   return rb;
+}
+
+// The few-boards form (conv_bf16f.hpp), one decision per forward, asked FIRST: AGZ_BF16_SMALL_FEW_ALWAYS wherever a run's resident slice
+// fits, AGZ_BF16_SMALL_FEW_AUTO where AUTO would take the small form AND the few-boards grid is at most BF16F_AUTO_ROUNDS workgroups per
+// CU (one is resident: the measured bound, profiles/bf16_few.md).  RB: the debug value where it fits, else the largest of {4, 2, 1} whose
+// slices fit; 0: the small form's rule takes over.
+constexpr int BF16F_AUTO_ROUNDS = 1;
+int agz_net::bf16f_rb(int B) const {
+  if ((bf16_small != AGZ_BF16_SMALL_FEW_ALWAYS && bf16_small != AGZ_BF16_SMALL_FEW_AUTO) || !act16_mode() || conf.SharedLayers < 2 || bf16_rows <= 0) return 0;
+  auto fits = [&](int rb) {
+    for (int m0 = 0; m0 < HW; m0 += 32 * rb)
+      if (((std::min(m0 + 32 * rb, HW) - 1) / W - m0 / W + 3) * Wp * (Kp / 64) > BF16F_SPC_MAX) return false;
+    return true;
+  };
+  if (!fits(1)) return 0;
+  const int rb = bf16_small_rb && fits(bf16_small_rb) ? bf16_small_rb : fits(4) ? 4 : fits(2) ? 2 : 1;
+  if (bf16_small == AGZ_BF16_SMALL_FEW_AUTO &&
+      (bf16s_rb(B) == 0 || (size_t)B * ceil_div(ceil_div(HW, 32), rb) * (Kp / 32) > (size_t)BF16F_AUTO_ROUNDS * ctx->num_cus)) return 0;
+  return rb;
+}
+
+int agz_net::bf16f_block(int l, int B, const float* x, float* y, hipStream_t st) {
+  const int L = conf.SharedLayers, rb = bf16f_rb(B);
+  AGZ_REQUIRE(rb > 0, AGZ_E_STATE, "agz_net: the few-boards bf16 block does not apply to this net or batch");
+  AGZ_REQUIRE(wq16(l), AGZ_E_STATE, "agz_net: bf16 / fp16 weights not built");
+  AGZ_REQUIRE(d_acthA && d_acthB && bf16_act_cap >= B, AGZ_E_STATE, "agz_net: bf16 activation buffers not allocated for %d boards", B);
+  // the 32-bit byte offsets inside a board of bf16a_block
+  AGZ_REQUIRE((size_t)Hp * Wp * Kp * sizeof(float) < ((size_t)1 << 32) && (size_t)HW * Kp * sizeof(float4) < ((size_t)1 << 32), AGZ_E_UNSUPPORTED,
+              "agz_net: board %d x %d with %d channels too large for the bf16 block's 32-bit offsets", H, W, Kp);
+  unsigned short* const hb[2] = {d_acthA, d_acthB};
+  Bf16aArgs q{};
+  q.x = x; q.y = y; q.xh = l > 0 ? hb[(l - 1) & 1] : nullptr; q.yh = l + 1 < L ? hb[l & 1] : nullptr;
+  q.ep = reinterpret_cast<const f32x4*>(ep16(l)); q.wq = wq16(l);
+  q.HW = HW; q.W = W; q.Wp = Wp; q.HpWp = Hp * Wp; q.Kp = Kp;
+  q.n_ntiles = Kp / 32; q.rows_tile = 32 * rb; q.m_per_board = ceil_div(HW, 32 * rb); q.ncc = Kp / 64;
+  const size_t grid = (size_t)B * q.m_per_board * q.n_ntiles;
+  AGZ_REQUIRE(grid < ((size_t)1 << 31), AGZ_E_UNSUPPORTED, "agz_net: batch %d too large for the bf16 block's grid", B);
+  if (fp16_mode()) bf16f_launch<Fp16El>(l, L, (unsigned)grid, rb, st, q);
+  else bf16f_launch<Bf16El>(l, L, (unsigned)grid, rb, st, q);
+  return AGZ_OK;
 }
 
 int agz_net::bf16s_block(int l, int B, const float* x, float* y, hipStream_t st) {
@@ -1256,7 +1311,7 @@ int agz_net::bf16s_block(int l, int B, const float* x, float* y, hipStream_t st)
   return AGZ_OK;
 }
 
-// The packed-boards form (conv_bf16p.hpp), one decision per forward, asked only where bf16s_rb(B) == 0.  Boards per workgroup: the debug
+// The packed-boards form (conv_bf16p.hpp), one decision per forward, asked only where bf16f_rb(B) == 0 and bf16s_rb(B) == 0.  Boards per workgroup: the debug
 // value where it fits, else the largest (agz_bf16_packed_boards_of).  AUTO: only where the whole-board grid exceeds the CU count — below
 // that a launch already costs one workgroup's time and packing gains nothing.
 static unsigned bf16p_magic(int d) { return (1u << 20) / (unsigned)d + 1u; }
@@ -1264,7 +1319,7 @@ static unsigned bf16p_magic(int d) { return (1u << 20) / (unsigned)d + 1u; }
 int agz_net::bf16p_g(int B) const {
   if (bf16_packed == AGZ_BF16_PACKED_OFF || !act16_mode() || conf.SharedLayers < 2 || bf16_rows <= 0) return 0;
   const int G = agz_bf16_packed_boards_of(H, W);
-  if (G < 2 || bf16s_rb(B) > 0) return 0;
+  if (G < 2 || bf16f_rb(B) > 0 || bf16s_rb(B) > 0) return 0;
   if (bf16_packed == AGZ_BF16_PACKED_AUTO && (size_t)B * (2 * Kp / 128) <= (size_t)ctx->num_cus) return 0;
   return bf16_packed_g >= 2 && bf16_packed_g <= G ? bf16_packed_g : G;
 }
@@ -1850,11 +1905,13 @@ int agz_net::forward_packed(int B, float* policy_dev, float* value_dev) {
       // the same arithmetic with bf16 activations between blocks (conv_bf16a.hpp): only block 0 reads cur, only the last block writes nxt
       // (bf16s_rb depends on the net and B alone: every block of a forward takes the same form, conv_bf16s.hpp's below a full chip)
       // (the packed-boards form, conv_bf16p.hpp, is asked second and only for small boards: bf16p_g is 0 wherever the small form applies)
-      const bool small = bf16s_rb(B) > 0, packed = !small && bf16p_g(B) > 0;
+      // (the few-boards form, conv_bf16f.hpp, is asked first: under the FEW policies only; where it gives 0 the two rules above stand)
+      const bool few = bf16f_rb(B) > 0, small = !few && bf16s_rb(B) > 0, packed = !few && !small && bf16p_g(B) > 0;
       ProfScope ps(ctx, AGZ_PROF_CONV);
-      rc = small ? bf16s_block(l, B, cur, nxt, ctx->stream) : packed ? bf16p_block(l, B, cur, nxt, ctx->stream) : bf16a_block(l, B, cur, nxt, ctx->stream);
+      rc = few ? bf16f_block(l, B, cur, nxt, ctx->stream) : small ? bf16s_block(l, B, cur, nxt, ctx->stream) : packed ? bf16p_block(l, B, cur, nxt, ctx->stream) : bf16a_block(l, B, cur, nxt, ctx->stream);
       // (AGZ_COMPUTE_FP16: the same three launchers on the half instantiations and the folded epilogue image)
-      if (fp16_mode()) path_block = small ? AGZ_NPATH_BLK_FP16_ACT_SMALL : packed ? AGZ_NPATH_BLK_FP16_ACT_PACKED : AGZ_NPATH_BLK_FP16_ACT;
+      if (few) path_block = fp16_mode() ? AGZ_NPATH_BLK_FP16_ACT_FEW : AGZ_NPATH_BLK_BF16_ACT_FEW;
+      else if (fp16_mode()) path_block = small ? AGZ_NPATH_BLK_FP16_ACT_SMALL : packed ? AGZ_NPATH_BLK_FP16_ACT_PACKED : AGZ_NPATH_BLK_FP16_ACT;
       else path_block = small ? AGZ_NPATH_BLK_BF16_ACT_SMALL : packed ? AGZ_NPATH_BLK_BF16_ACT_PACKED : AGZ_NPATH_BLK_BF16_ACT;
     }
     else if (tower16_mode()) {
@@ -2451,7 +2508,8 @@ int agz_net_set_compute_mode(agz_net* n, int mode) {
 
 int agz_net_set_bf16_small_batch(agz_net* n, int policy) {
   AGZ_REQUIRE(n, AGZ_E_INVALID, "agz_net_set_bf16_small_batch: NULL net");
-  AGZ_REQUIRE(policy == AGZ_BF16_SMALL_OFF || policy == AGZ_BF16_SMALL_AUTO || policy == AGZ_BF16_SMALL_ALWAYS, AGZ_E_INVALID,
+  AGZ_REQUIRE(policy == AGZ_BF16_SMALL_OFF || policy == AGZ_BF16_SMALL_AUTO || policy == AGZ_BF16_SMALL_ALWAYS ||
+              policy == AGZ_BF16_SMALL_FEW_AUTO || policy == AGZ_BF16_SMALL_FEW_ALWAYS, AGZ_E_INVALID,
               "agz_net_set_bf16_small_batch: unknown policy %d", policy);
   n->bf16_small = policy;
   return AGZ_OK;

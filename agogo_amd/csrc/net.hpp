@@ -102,6 +102,9 @@ struct agz_net {
   int bf16_small_rb = 0;                   // agz_net_debug_set_bf16_small_rb: 0 the launcher's rule, 1 / 2 / 4 forced where it fits
   int bf16s_rb(int B) const;               // row blocks per workgroup a forward of B boards runs the small form with; 0: it keeps bf16a_block
   int bf16s_block(int l, int B, const float* x, float* y, hipStream_t st);   // bf16a_block's contract and buffers
+  // the few-boards form of that block (conv_bf16f.hpp): resident slice, counted weight ring, the same bits; asked first, under the FEW policies
+  int bf16f_rb(int B) const;               // row blocks per workgroup a forward of B boards runs the few-boards form with; 0: bf16s_rb's rule
+  int bf16f_block(int l, int B, const float* x, float* y, hipStream_t st);   // bf16a_block's contract and buffers
   // the packed-boards form of that block (conv_bf16p.hpp): several small boards per workgroup, the same bits
   int bf16_packed = 0;                     // agz_net_set_bf16_packed_boards: AGZ_BF16_PACKED_*
   int bf16_packed_g = 0;                   // agz_net_debug_set_bf16_packed_g: 0 the launcher's rule, 2 .. G forced

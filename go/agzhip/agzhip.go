@@ -140,9 +140,11 @@ func (n *Net) BF16SmallBatch() (int, error) {
 }
 
 const (
-	BF16SmallOff    = C.AGZ_BF16_SMALL_OFF
-	BF16SmallAuto   = C.AGZ_BF16_SMALL_AUTO
-	BF16SmallAlways = C.AGZ_BF16_SMALL_ALWAYS
+	BF16SmallOff       = C.AGZ_BF16_SMALL_OFF
+	BF16SmallAuto      = C.AGZ_BF16_SMALL_AUTO
+	BF16SmallAlways    = C.AGZ_BF16_SMALL_ALWAYS
+	BF16SmallFewAuto   = C.AGZ_BF16_SMALL_FEW_AUTO
+	BF16SmallFewAlways = C.AGZ_BF16_SMALL_FEW_ALWAYS
 )
 
 // SetBF16PackedBoards selects when ComputeBF16Act (or ComputeFP16) gives a workgroup several small boards instead of one (BF16PackedBoardsOf of

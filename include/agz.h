@@ -216,10 +216,20 @@ int agz_net_set_compute_mode(agz_net* net, int mode);
  * AGZ_BF16_SMALL_ALWAYS (wherever the board fits the form's LDS stage; a board too wide for it keeps the whole-board kernel).  One
  * decision per forward.  Has an effect only under AGZ_COMPUTE_BF16_ACT and AGZ_COMPUTE_FP16 on nets of two or more blocks; otherwise it is stored and inert.
  * Measured: profiles/bf16_small.md (one board: 0.87 ms per 40-block forward against 1.89; the fp32-grade latency regime of the other
- * modes is still faster at ONE board). */
+ * modes is still faster at ONE board).
+ * The few-boards form (conv_bf16f.hpp) is a second kernel for the same job, built for ONE to a few boards: a wave
+ * owns one 32 x 32 accumulator tile (half the small form's MFMA chain), the run's haloed slice of all channels is resident in LDS and the
+ * weight tiles arrive through a six-stage ring with five steps of DMA in flight.  The SAME declared arithmetic and the SAME results bit
+ * for bit, by the same argument; no device memory of its own.  AGZ_BF16_SMALL_FEW_ALWAYS: the few-boards form wherever a run's slice fits
+ * its LDS (19x19: up to K = 512), elsewhere exactly AGZ_BF16_SMALL_ALWAYS.  AGZ_BF16_SMALL_FEW_AUTO: AGZ_BF16_SMALL_AUTO's decision, with
+ * the few-boards form in place of the small form while its grid is at most one workgroup per CU, the one
+ * round that is resident (1 to 10 boards at 19x19 / K=256).  Measured: profiles/bf16_few.md — 20.2 us per block against the small form's
+ * 22.3 at one board, 21.2 against 23.0 at 10, 36.1 against 24.7 at 11; the fp32-grade latency regime (11.4 us) is still faster at ONE board. */
 #define AGZ_BF16_SMALL_OFF 0
 #define AGZ_BF16_SMALL_AUTO 1
 #define AGZ_BF16_SMALL_ALWAYS 2
+#define AGZ_BF16_SMALL_FEW_AUTO 3
+#define AGZ_BF16_SMALL_FEW_ALWAYS 4
 int agz_net_set_bf16_small_batch(agz_net* net, int policy);
 int agz_net_get_bf16_small_batch(const agz_net* net, int* policy);
 /* Small BOARDS under AGZ_COMPUTE_BF16_ACT and AGZ_COMPUTE_FP16 (the same kernel on IEEE half).  That mode's kernel gives a workgroup one board and 384 GEMM rows: on a 9x9 board 81 of them

@@ -198,6 +198,8 @@ int agz_trainer_last_planes(agz_trainer* t, int layer, int* fused, uint32_t* est
 #define AGZ_NPATH_BLK_FP16_ACT 20         /* conv3x3_bf16a_dual_kernel<Fp16El, ..>: AGZ_COMPUTE_FP16, half activations between blocks */
 #define AGZ_NPATH_BLK_FP16_ACT_SMALL 21   /* conv3x3_bf16s_dual_kernel<Fp16El, ..>: that mode's small-batch form (agz_net_set_bf16_small_batch) */
 #define AGZ_NPATH_BLK_FP16_ACT_PACKED 22  /* conv3x3_bf16p_dual_kernel<Fp16El, ..>: that mode's packed-boards form (agz_net_set_bf16_packed_boards) */
+#define AGZ_NPATH_BLK_BF16_ACT_FEW 23     /* conv3x3_bf16f_dual_kernel: that mode's few-boards form (AGZ_BF16_SMALL_FEW_*, conv_bf16f.hpp) */
+#define AGZ_NPATH_BLK_FP16_ACT_FEW 24     /* conv3x3_bf16f_dual_kernel<Fp16El, ..>: AGZ_COMPUTE_FP16's few-boards form */
 #define AGZ_NPATH_HEADS_ONE 1          /* heads_kernel: one workgroup per board */
 #define AGZ_NPATH_HEADS_SPREAD 2          /* heads_feat / heads_fc / heads_out */
 #define AGZ_NPATH_HEADS_SPREAD_NB4 3      /* ... with heads_fc_nb_kernel<4> (from 32 boards) */
@@ -205,7 +207,8 @@ int agz_net_last_paths(agz_net* net, int* input_conv, int* block, int* heads);
 
 /* Tests: row blocks of 32 GEMM rows per workgroup of the small-batch bf16 block (agz_net_set_bf16_small_batch, conv_bf16s.hpp).  0 (default):
  * the launcher's rule — the largest of 4, 2, 1 whose slices fit the LDS stage; 1 / 2 / 4: that value wherever its slices fit the stage,
- * so that tests and measurements reach every form.  Results are bit-identical. */
+ * so that tests and measurements reach every form.  Results are bit-identical.  The few-boards form (conv_bf16f.hpp) takes the same
+ * value wherever its resident slices fit with it. */
 int agz_net_debug_set_bf16_small_rb(agz_net* net, int rb);
 
 /* Tests: boards per workgroup of the packed-boards bf16 block (agz_net_set_bf16_packed_boards, conv_bf16p.hpp).  0 (default): the launcher's
