@@ -26,9 +26,9 @@ BF16_PACKED_OFF, BF16_PACKED_AUTO, BF16_PACKED_ALWAYS = 0, 1, 2   # agz_net_set_
 COMPUTE_FORCE = 0x100
 LOSS_REFERENCE, LOSS_ALPHAZERO = 0, 1   # agz_trainer_set_loss
 # agz_debug.h, agz_trainer_last_paths: the kernel a trainer layer's last step took (0 = none launched)
-PATH_FWD_F32, PATH_FWD_BF16X3, PATH_FWD_H2W, PATH_FWD_H2DMA, PATH_FWD_H2DMA3 = 1, 2, 3, 4, 5
-PATH_WGRAD_F32, PATH_WGRAD_X3, PATH_WGRAD_H2, PATH_WGRAD_H2T3 = 1, 2, 3, 4
-PATH_DGRAD_RAW, PATH_DGRAD_X3, PATH_DGRAD_WINO_H2 = 1, 2, 3
+PATH_FWD_F32, PATH_FWD_BF16X3, PATH_FWD_H2W, PATH_FWD_H2DMA, PATH_FWD_H2DMA3, PATH_FWD_BF16T = 1, 2, 3, 4, 5, 6
+PATH_WGRAD_F32, PATH_WGRAD_X3, PATH_WGRAD_H2, PATH_WGRAD_H2T3, PATH_WGRAD_BF16T = 1, 2, 3, 4, 5
+PATH_DGRAD_RAW, PATH_DGRAD_X3, PATH_DGRAD_WINO_H2, PATH_DGRAD_BF16T = 1, 2, 3, 4
 PATH_BN2_SCALAR, PATH_BN2_V = 1, 2
 # agz_debug.h, agz_trainer_last_rows: the words of a tower layer's row plan, and of the heads' (layer SharedLayers + 1)
 ROWS_WGRAD_CHUNKS, ROWS_SINGLE_PASS, ROWS_APPLY_RPB, ROWS_BWD2_RPB = 0, 1, 2, 3
@@ -357,6 +357,7 @@ def lib():
     sig("agz_rotate_boards", i32, vp, pf, i32, i32, i32, pf)
     sig("agz_ctx_prof_set_stride", i32, vp, i32, i32)
     sig("agz_wino_stages", i32, vp, pf, pf, i32, i32, i32, i32, i32, pf, pf)
+    sig("agz_trainer_conv_bf16", i32, vp, i32, pf, pf, i32, i32, i32, i32, i32, pf)
     sig("agz_wino_h2_tile", i32, i32, i32)
     sig("agz_net_set_wino_h2_form", i32, vp, i32)
     sig("agz_net_set_wino_h2_gemm", i32, vp, i32)
@@ -1749,6 +1750,18 @@ def wino_stages(ctx, x, w):
     M = np.zeros((36, T, N), np.float32)
     _check(lib().agz_wino_stages(ctx.h, _pf(x), _pf(w), B, H, W, Cc, N, _pf(V), _pf(M)), "agz_wino_stages")
     return V, M
+
+
+def trainer_conv_bf16(ctx, which, a, b):
+    """tests: one GEMM of the trainer's COMPUTE_BF16 mode alone (agz_debug.h, agz_trainer_conv_bf16).  NHWC tensors, filters [Cout,Cin,3,3]:
+    which 0: a = x, b = filter -> z [B,H,W,Cout]; 1: a = dz, b = filter -> dx [B,H,W,Cin]; 2: a = dz, b = x -> dw [9,Cout,Cin]"""
+    a = np.ascontiguousarray(a, np.float32)
+    b = np.ascontiguousarray(b, np.float32)
+    B, H, W = a.shape[:3]
+    Cin, Cout = (b.shape[3], a.shape[3]) if which == 2 else (b.shape[1], b.shape[0])
+    out = np.zeros((9, Cout, Cin) if which == 2 else (B, H, W, Cin if which == 1 else Cout), np.float32)
+    _check(lib().agz_trainer_conv_bf16(ctx.h, int(which), _pf(a), _pf(b), B, H, W, Cin, Cout, _pf(out)), "agz_trainer_conv_bf16")
+    return out
 
 
 def rotate_boards(ctx, boards, m, n):

@@ -20,6 +20,9 @@
 //                         (conv_wino_h2.hpp), weight gradient = k_wgrad_h2t3 (hi / lo fp16 planes of both operands, LDS-DMA, three taps
 //                         per workgroup from one x image, ds_read_b64_tr_b16): 0.55 ms per layer alone, 0.48 of the fp16x2 MFMA roof;
 //                         every layer's weight images are built at the start of the step on the side stream (prep_weights)  42.5-43.3 ms
+//   AGZ_COMPUTE_BF16      NOT inside that tolerance (opt-in mixed precision, DESIGN.md section 2 `bf16-train`): the dual-block layers' three
+//                         GEMMs with ONE bf16 product per multiply on operands rounded once (train_bf16.hpp: k_round_bf16_planes / _weights,
+//                         k_conv_bf16t forward and data gradient, k_wgrad_bf16t); everything else as AGZ_COMPUTE_BF16X3      35.5 ms
 // BatchNorm statistics / apply / backward are bandwidth-bound elementwise + reduction kernels at ~5 TB/s (43 % of a layer's time: the
 // reference's batch-shaped gamma / beta fix their bytes); the heads run as wave-per-row reductions and LDS-tiled FC kernels (second form,
 // 0.35 ms per step); the batch-shaped gamma / beta take their SGD step inside k_bn_bwd1 on single-process steps; the weight gradient
@@ -2165,8 +2168,14 @@ __global__ __launch_bounds__(256, 2) void k_conv_h2dma3(ConvDmaArgs a) {
     }
 }
 
+#include "train_bf16.hpp"   // AGZ_COMPUTE_BF16: k_round_bf16_planes / _weights, k_conv_bf16t, k_wgrad_bf16t and their launchers
+
 struct TLayer {
   int Cin_p, Cout_p, nbr;
+  // AGZ_COMPUTE_BF16 (train_bf16.hpp; allocated when the mode is set, for the layers it takes): xb = the layer INPUT rounded to bf16 by the
+  // forward pass, read again by the weight gradient; wbf / wbt = the bf16 images of the filter and of its transposed, tap-flipped form,
+  // rebuilt every step from the fp32 master filter (fw_ready / bw_ready / ev_fw below say "built for this step" as they do for WINO_H2)
+  unsigned short *xb = nullptr, *wbf = nullptr, *wbt = nullptr;
   size_t o_wf, o_gamma, o_beta;   // offsets in the flat P / G buffers
   float *wt = nullptr, *z = nullptr, *out = nullptr, *mean = nullptr, *inv = nullptr;
   unsigned short *w3f = nullptr, *w3t = nullptr;   // bf16x3 images of the forward / transposed filter (AGZ_COMPUTE_BF16X3)
@@ -2208,6 +2217,17 @@ struct agz_trainer {
   // of 87 ms per G19 step, but its rounding — 2e-6 of the output rms against 2e-7 — flips a ReLU unit against the reference arithmetic on
   // every other data draw at K = 256 / 19x19, which moves that unit's gradients by percent: outside the stated tolerance, removed.)
   bool wino = false;
+  // AGZ_COMPUTE_BF16: one bf16 product per multiply in the three GEMMs of the dual-block layers (train_bf16.hpp; NOT fp32-grade: DESIGN.md
+  // section 2 `bf16-train`).  x3 is set with it: the input layer and whatever use_bf16t refuses run what AGZ_COMPUTE_BF16X3 runs.
+  // dzb: dz of the layer in hand rounded to bf16, once per layer, for its weight gradient and its data gradient.
+  bool bf16t = false;
+  unsigned short* dzb = nullptr;
+  bool use_bf16t(int l) const {
+    if (!bf16t || l < 1) return false;
+    const TLayer& ly = layers[l];
+    return ly.xb && conv_bf16t_fits(g, ly.Cin_p, ly.Cout_p) && conv_bf16t_fits(g, ly.Cout_p, ly.Cin_p) && wgrad_bf16t_fits(g, ly.Cout_p, ly.Cin_p) &&
+           (x3_force || (size_t)((g.M + 255) / 256) * ((ly.Cout_p + 127) / 128) >= (size_t)ctx->num_cus);
+  }
   WinoRawScratch wsc;
   // ... and the weight gradient with fp16x2 products: both operands split once per layer (k_wgrad_h2)
   unsigned *dz_h2 = nullptr, *x_h2 = nullptr;
@@ -2298,6 +2318,16 @@ struct agz_trainer {
   hipEvent_t ev_w0 = nullptr, ev_bw = nullptr;
   int side_stream();
   int prep_weights(bool fwd_only = false);
+  // AGZ_COMPUTE_BF16: layer ly's bf16 filter image for the forward convolution (wbf) or the data gradient (wbt), from the master filter
+  void weights_bf16t(TLayer& ly, hipStream_t st, bool transposed) {
+    const unsigned gr = (unsigned)(((size_t)9 * ly.Cout_p * ly.Cin_p / 8 + 255) / 256);
+    if (transposed) hipLaunchKernelGGL(k_round_bf16_weights<true>, dim3(gr), dim3(256), 0, st, P + ly.o_wf, ly.wbt, ly.Cout_p, ly.Cin_p);
+    else hipLaunchKernelGGL(k_round_bf16_weights<false>, dim3(gr), dim3(256), 0, st, P + ly.o_wf, ly.wbf, ly.Cout_p, ly.Cin_p);
+  }
+  void round_bf16t(const float* src, unsigned short* dst, size_t n, hipStream_t st) {
+    const unsigned gs = (unsigned)std::min<size_t>((n / 8 + 255) / 256, (size_t)ctx->num_cus * 8);
+    hipLaunchKernelGGL(k_round_bf16_planes, dim3(gs), dim3(256), 0, st, src, dst, n / 8);
+  }
   // solver options (agz_trainer_set_solver; all 0 = the vanilla step, which then runs the kernels it always ran) and the first-order state:
   // V, one flat buffer laid out exactly like P / G, exists only while momentum != 0 (allocated and zeroed when it is first set, released
   // when it is set back to 0): a trainer that never asks for momentum allocates nothing more
@@ -2415,12 +2445,26 @@ int agz_trainer::side_stream() {
 // idle until the backward pass: forward images first, in layer order with an event each, then the data gradient's with one event
 int agz_trainer::prep_weights(bool fwd_only) {
   for (auto& ly : layers) { ly.fw_ready = false; ly.bw_ready = false; }
-  if (!wino || !hoist_w || one_stream) return AGZ_OK;
+  if ((!wino && !bf16t) || !hoist_w || one_stream) return AGZ_OK;
   int r = side_stream();
   if (r != AGZ_OK) return r;
   hipStream_t s = ctx->stream, sw = wg_stream;
   AGZ_HIP_TRY(hipEventRecord(ev_w0, s));              // (the previous step's apply() and its readers of the images)
   AGZ_HIP_TRY(hipStreamWaitEvent(sw, ev_w0, 0));
+  if (bf16t) {   // AGZ_COMPUTE_BF16: the bf16 filter images, forward ones first with an event each, then the data gradient's with one event
+    for (int pass = 0; pass < (fwd_only ? 1 : 2); pass++)
+      for (int l = pass ? L : 1; pass ? l >= 1 : l <= L; l += pass ? -1 : 1) {
+        TLayer& ly = layers[l];
+        if (!use_bf16t(l)) continue;
+        weights_bf16t(ly, sw, pass != 0);
+        if (pass) { ly.bw_ready = true; continue; }
+        if (!ly.ev_fw) AGZ_HIP_TRY(hipEventCreateWithFlags(&ly.ev_fw, hipEventDisableTiming));
+        AGZ_HIP_TRY(hipEventRecord(ly.ev_fw, sw));
+        ly.fw_ready = true;
+      }
+    AGZ_HIP_TRY(hipEventRecord(ev_bw, sw));
+    return AGZ_OK;
+  }
   for (int l = 0; l <= L; l++) {
     TLayer& ly = layers[l];
     if (!dma_layer(l)) continue;
@@ -2465,7 +2509,15 @@ int agz_trainer::forward_backward_dev(const float* planes, const float* pi, cons
     int r;
     ly.x_planes = false;
     const size_t n_x_fwd = (size_t)B * g.Hp * g.Wp * ly.Cin_p;
-    if (dma_layer(l) && x_amax_ready[l]) {
+    if (use_bf16t(l)) {
+      // AGZ_COMPUTE_BF16: the layer input rounded once (kept for the weight gradient), the filter image of this step, one bf16 MFMA per product
+      round_bf16t(cur, ly.xb, n_x_fwd, s);
+      if (ly.fw_ready) AGZ_HIP_TRY(hipStreamWaitEvent(s, ly.ev_fw, 0));
+      else weights_bf16t(ly, s, false);
+      conv_bf16t_launch(s, ly.xb, ly.wbf, ly.z, g, ly.Cin_p, ly.Cout_p);
+      ly.path_fwd = AGZ_PATH_FWD_BF16T;
+      r = AGZ_OK;
+    } else if (dma_layer(l) && x_amax_ready[l]) {
       // planes of the layer input (its range word came out of the previous layer's BatchNorm pass, and so did the planes themselves
       // unless the range's exponent moved since the last step), then the DMA GEMM
       if (!ly.xh2) { r = alloc(&ly.xh2, 2 * n_x_fwd); if (r != AGZ_OK) return r; planes_fused[l] = 0; }
@@ -2671,7 +2723,7 @@ int agz_trainer::forward_backward_dev(const float* planes, const float* pi, cons
   // ---- tower backward
   { int r = side_stream(); if (r != AGZ_OK) return r; }
   hipStream_t sw = one_stream ? s : wg_stream;
-  if (wino && hoist_w && !one_stream) AGZ_HIP_TRY(hipStreamWaitEvent(s, ev_bw, 0));   // the data gradient's weight images (prep_weights; long done)
+  if ((wino || bf16t) && hoist_w && !one_stream) AGZ_HIP_TRY(hipStreamWaitEvent(s, ev_bw, 0));   // the data gradient's weight images (prep_weights; long done)
   for (int l = L; l >= 0; l--) {
     TLayer& ly = layers[l];
     int C = ly.Cout_p;
@@ -2739,6 +2791,10 @@ int agz_trainer::forward_backward_dev(const float* planes, const float* pi, cons
       hipLaunchKernelGGL(k_bn_bwd2, dim3(nblk((size_t)g.M * C)), dim3(256), 0, s, g, ly.z, ly.mean, ly.inv, dz, s1, s2, C, (float)m_glob());
       ly.path_bn2 = AGZ_PATH_BN2_SCALAR;
     }
+    // AGZ_COMPUTE_BF16: dz rounded once for this layer's weight gradient and data gradient (the previous layer's readers of dzb are done:
+    // its data gradient ran on this stream, its weight gradient recorded ev_split, waited for above)
+    const bool bt = use_bf16t(l);
+    if (bt) round_bf16t(dz, dzb, (size_t)B * g.Hp * g.Wp * C, s);
     // weight gradient (on its own stream from here)
     if (sw != s) { AGZ_HIP_TRY(hipEventRecord(ev_dz, s)); AGZ_HIP_TRY(hipStreamWaitEvent(sw, ev_dz, 0)); }
     bool split_recorded = false;
@@ -2751,7 +2807,13 @@ int agz_trainer::forward_backward_dev(const float* planes, const float* pi, cons
     const bool chip_full = x3_force || (size_t)wa.n_tiles * wa.c_tiles * 9 * chunks >= (size_t)ctx->num_cus;
     const bool off31 = (size_t)B * g.Hp * g.Wp * (size_t)std::max(C, ly.Cin_p) * 4 < ((size_t)1 << 31);   // byte offsets of the buffer loads
     ly.rows[AGZ_ROWS_WGRAD_CHUNKS] = chunks; ly.rows[AGZ_ROWS_SPLIT_BLOCKS] = 0; ly.rows[AGZ_ROWS_SPLIT_NEED] = 0;
-    if (wino && chip_full && off31 && C % 4 == 0 && ly.Cin_p % 4 == 0) {
+    if (bt) {
+      // one bf16 product per multiply from the two rounded planes (k_wgrad_bf16t): x as the forward pass rounded it, dz as rounded above
+      const size_t n8 = (size_t)B * g.Hp * g.Wp * C / 8;
+      ly.rows[AGZ_ROWS_SPLIT_BLOCKS] = (int)std::min<size_t>(nblk(n8), (size_t)ctx->num_cus * 8); ly.rows[AGZ_ROWS_SPLIT_NEED] = nblk(n8);
+      ly.rows[AGZ_ROWS_WGRAD_CHUNKS] = wgrad_bf16t_launch(sw, ctx->num_cus, dzb, ly.xb, wa.dw, g, C, ly.Cin_p, wg_pad_lds ? (size_t)40960 : 0);
+      ly.path_wgrad = AGZ_PATH_WGRAD_BF16T;
+    } else if (wino && chip_full && off31 && C % 4 == 0 && ly.Cin_p % 4 == 0) {
       // fp16x2 products: range + split pass over dz and x (once per layer, not once per tap workgroup), then the GEMM
       const size_t n_dz = (size_t)B * g.Hp * g.Wp * C, n_x = (size_t)B * g.Hp * g.Wp * ly.Cin_p;
       if (dz_h2_cap < n_dz) { if (dz_h2) hipFree(dz_h2); dz_h2 = nullptr; dz_h2_cap = 0; AGZ_HIP_TRY(hipMalloc(&dz_h2, n_dz * 4)); dz_h2_cap = n_dz; }
@@ -2800,7 +2862,12 @@ int agz_trainer::forward_backward_dev(const float* planes, const float* pi, cons
     if (sw != s && !split_recorded) AGZ_HIP_TRY(hipEventRecord(ev_split, sw));   // (kernels that read dz itself: after the weight gradient)
     // layer l's slice [filter | gamma | beta] is final once its weight gradient has run (sw: it started after this layer's BatchNorm backward)
     if (on_slice) { int r = on_slice(ly.o_wf, (l < L ? layers[l + 1].o_wf : o_hc) - ly.o_wf, sw); if (r != AGZ_OK) return r; }
-    if (l > 0) {  // data gradient: the forward GEMM with flipped/transposed weights over the [a|b] channels of dz
+    if (l > 0 && bt) {  // AGZ_COMPUTE_BF16: k_conv_bf16t on the rounded dz and the transposed, tap-flipped bf16 filter image
+      if (!ly.bw_ready) weights_bf16t(ly, s, true);
+      conv_bf16t_launch(s, dzb, ly.wbt, dnext, g, C, ly.Cin_p);
+      ly.path_dgrad = AGZ_PATH_DGRAD_BF16T;
+      std::swap(dcur, dnext);
+    } else if (l > 0) {  // data gradient: the forward GEMM with flipped/transposed weights over the [a|b] channels of dz
       if (!ly.bw_ready) hipLaunchKernelGGL(k_make_wt, dim3(nblk((size_t)9 * C * ly.Cin_p)), dim3(256), 0, s, P + ly.o_wf, ly.wt, C, ly.Cin_p);
       int r;
       if (use_wino(C, ly.Cin_p)) {
@@ -3465,19 +3532,110 @@ int agz_trainer_set_compute_mode(agz_trainer* t, int mode) {
   AGZ_REQUIRE(t, AGZ_E_INVALID, "trainer is NULL");
   const bool force = (mode & AGZ_COMPUTE_FORCE) != 0;
   mode &= ~AGZ_COMPUTE_FORCE;
-  AGZ_REQUIRE(mode == AGZ_COMPUTE_F32_MFMA || mode == AGZ_COMPUTE_BF16X3 || mode == AGZ_COMPUTE_WINO_H2, AGZ_E_INVALID, "agz_trainer_set_compute_mode: mode %d not available for training", mode);
+  AGZ_REQUIRE(mode == AGZ_COMPUTE_F32_MFMA || mode == AGZ_COMPUTE_BF16X3 || mode == AGZ_COMPUTE_WINO_H2 || mode == AGZ_COMPUTE_BF16, AGZ_E_INVALID,
+              "agz_trainer_set_compute_mode: mode %d not available for training", mode);
+  // AGZ_COMPUTE_BF16 is NOT fp32-grade: a net its kernels cannot take is refused (the trainer keeps the mode it had), never served another precision
+  AGZ_REQUIRE(mode != AGZ_COMPUTE_BF16 || (t->L > 0 && t->K % 64 == 0), AGZ_E_UNSUPPORTED,
+              "agz_trainer_set_compute_mode: AGZ_COMPUTE_BF16 needs K %% 64 == 0 and SharedLayers > 0 (K %d, SharedLayers %d)", t->K, t->L);
   AGZ_HIP_TRY(hipSetDevice(t->ctx->device));
+  if (mode == AGZ_COMPUTE_BF16) {   // the per-layer bf16 planes and filter images, and dz's plane at the widest layer (kept once allocated)
+    const size_t n_pix = (size_t)t->B * t->g.Hp * t->g.Wp;
+    size_t n_dz = 0;
+    for (int l = 1; l <= t->L; l++) {
+      TLayer& ly = t->layers[l];
+      n_dz = std::max(n_dz, n_pix * ly.Cout_p);
+      if (ly.xb) continue;
+      int r = t->alloc(&ly.xb, n_pix * ly.Cin_p);
+      if (r == AGZ_OK) r = t->alloc(&ly.wbf, (size_t)9 * ly.Cin_p * ly.Cout_p);
+      if (r == AGZ_OK) r = t->alloc(&ly.wbt, (size_t)9 * ly.Cin_p * ly.Cout_p);
+      if (r != AGZ_OK) return r;
+    }
+    if (!t->dzb) { int r = t->alloc(&t->dzb, n_dz); if (r != AGZ_OK) return r; }
+  }
   t->x3_force = force;
-  if (mode == AGZ_COMPUTE_BF16X3 || mode == AGZ_COMPUTE_WINO_H2)
+  if (mode == AGZ_COMPUTE_BF16X3 || mode == AGZ_COMPUTE_WINO_H2 || mode == AGZ_COMPUTE_BF16)
     for (auto& ly : t->layers)
       if (!ly.w3f) {
         int r = t->alloc(&ly.w3f, w3_elems(ly.Cout_p, ly.Cin_p));
         if (r == AGZ_OK) r = t->alloc(&ly.w3t, w3_elems(ly.Cin_p, ly.Cout_p));
         if (r != AGZ_OK) return r;
       }
-  t->x3 = mode == AGZ_COMPUTE_BF16X3 || mode == AGZ_COMPUTE_WINO_H2;
+  t->x3 = mode == AGZ_COMPUTE_BF16X3 || mode == AGZ_COMPUTE_WINO_H2 || mode == AGZ_COMPUTE_BF16;
   t->wino = mode == AGZ_COMPUTE_WINO_H2;
+  t->bf16t = mode == AGZ_COMPUTE_BF16;
   return AGZ_OK;
+}
+
+// agz_debug.h: one of AGZ_COMPUTE_BF16's three GEMMs on host data, through the rounding kernels and launchers the step uses
+int agz_trainer_conv_bf16(agz_ctx* ctx, int which, const float* a, const float* b, int B, int H, int W, int Cin, int Cout, float* out) {
+  AGZ_REQUIRE(ctx && a && b && out, AGZ_E_INVALID, "agz_trainer_conv_bf16: NULL argument");
+  AGZ_REQUIRE(which >= 0 && which <= 2 && B >= 1 && H >= 1 && W >= 1 && Cin >= 1 && Cout >= 1, AGZ_E_INVALID, "agz_trainer_conv_bf16: bad argument");
+  const TGeo g{B, H, W, H * W, H + 2, W + 2, B * H * W};
+  AGZ_REQUIRE(conv_bf16t_fits(g, Cin, Cout) && conv_bf16t_fits(g, Cout, Cin) && wgrad_bf16t_fits(g, Cout, Cin), AGZ_E_UNSUPPORTED,
+              "agz_trainer_conv_bf16: %dx%d, B %d, %d -> %d channels is outside the bf16 training kernels' limits", W, H, B, Cin, Cout);
+  AGZ_HIP_TRY(hipSetDevice(ctx->device));
+  const size_t n_pix = (size_t)B * g.Hp * g.Wp, nw = (size_t)9 * Cin * Cout;
+  const int Ca = which == 0 ? Cin : Cout;                      // channels of a; of the second activation tensor (x, which == 2): Cin
+  const int Co = which == 0 ? Cout : Cin;                      // channels of a convolution's result
+  auto pad = [&](const float* src, int C) {                    // [B][H][W][C] -> padded NHWC with a zero halo
+    std::vector<float> p(n_pix * C, 0.f);
+    for (int bb = 0; bb < B; bb++) for (int h = 0; h < H; h++)
+      memcpy(&p[(((size_t)bb * g.Hp + h + 1) * g.Wp + 1) * C], &src[((size_t)bb * H + h) * W * C], (size_t)W * C * sizeof(float));
+    return p;
+  };
+  const std::vector<float> ap = pad(a, Ca);
+  std::vector<float> bp;
+  if (which == 2) bp = pad(b, Cin);
+  else {                                                       // [Cout][Cin][3][3] -> the master filter's layout [tap][Cout][Cin]
+    bp.resize(nw);
+    for (int n = 0; n < Cout; n++) for (int c = 0; c < Cin; c++) for (int tap = 0; tap < 9; tap++)
+      bp[((size_t)tap * Cout + n) * Cin + c] = b[((size_t)n * Cin + c) * 9 + tap];
+  }
+  const size_t n_out = which == 2 ? nw : n_pix * Co;
+  float *da = nullptr, *db = nullptr, *dout = nullptr;
+  unsigned short *ha = nullptr, *hb = nullptr;
+  int rc = AGZ_OK;
+  if (hipMalloc(&da, ap.size() * 4) != hipSuccess || hipMalloc(&db, bp.size() * 4) != hipSuccess || hipMalloc(&dout, n_out * 4) != hipSuccess ||
+      hipMalloc(&ha, ap.size() * 2) != hipSuccess || hipMalloc(&hb, bp.size() * 2) != hipSuccess) {
+    set_error("agz_trainer_conv_bf16: out of device memory");
+    rc = AGZ_E_NOMEM;
+  } else {
+    hipStream_t s = ctx->stream;
+    bool ok = hipMemcpyAsync(da, ap.data(), ap.size() * 4, hipMemcpyHostToDevice, s) == hipSuccess &&
+              hipMemcpyAsync(db, bp.data(), bp.size() * 4, hipMemcpyHostToDevice, s) == hipSuccess &&
+              hipMemsetAsync(dout, 0, n_out * 4, s) == hipSuccess;
+    if (ok) {
+      auto round = [&](const float* src, unsigned short* dst, size_t n) {
+        const unsigned gs = (unsigned)std::min<size_t>((n / 8 + 255) / 256, (size_t)ctx->num_cus * 8);
+        hipLaunchKernelGGL(k_round_bf16_planes, dim3(gs), dim3(256), 0, s, src, dst, n / 8);
+      };
+      round(da, ha, ap.size());
+      const unsigned gr = (unsigned)((nw / 8 + 255) / 256);
+      if (which == 0) {
+        hipLaunchKernelGGL(k_round_bf16_weights<false>, dim3(gr), dim3(256), 0, s, db, hb, Cout, Cin);
+        conv_bf16t_launch(s, ha, hb, dout, g, Cin, Cout);
+      } else if (which == 1) {
+        hipLaunchKernelGGL(k_round_bf16_weights<true>, dim3(gr), dim3(256), 0, s, db, hb, Cout, Cin);
+        conv_bf16t_launch(s, ha, hb, dout, g, Cout, Cin);
+      } else {
+        round(db, hb, bp.size());
+        wgrad_bf16t_launch(s, ctx->num_cus, ha, hb, dout, g, Cout, Cin, 0);
+      }
+    }
+    std::vector<float> op(which == 2 ? 0 : n_out);
+    ok = ok && hipGetLastError() == hipSuccess &&
+         hipMemcpyAsync(which == 2 ? out : op.data(), dout, n_out * 4, hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+    if (!ok) { set_error("agz_trainer_conv_bf16: HIP failure: %s", hipGetErrorString(hipGetLastError())); rc = AGZ_E_HIP; }
+    else if (which != 2)
+      for (int bb = 0; bb < B; bb++) for (int h = 0; h < H; h++)
+        memcpy(&out[((size_t)bb * H + h) * W * Co], &op[(((size_t)bb * g.Hp + h + 1) * g.Wp + 1) * Co], (size_t)W * Co * sizeof(float));
+  }
+  if (da) hipFree(da);
+  if (db) hipFree(db);
+  if (dout) hipFree(dout);
+  if (ha) hipFree(ha);
+  if (hb) hipFree(hb);
+  return rc;
 }
 
 int agz_trainer_set_dma_forward(agz_trainer* t, int on) {

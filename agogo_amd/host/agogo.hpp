@@ -311,7 +311,8 @@ struct Config {
   // build extension: the arithmetic of the inference networks (agz_net_set_compute_mode) and, through it, of the trainer: AGZ_COMPUTE_F32_MFMA
   // (default), AGZ_COMPUTE_BF16X3, AGZ_COMPUTE_WINO (training then uses BF16X3), AGZ_COMPUTE_WINO_H2 / AGZ_COMPUTE_AUTO (the measured mode;
   // training takes the trainer's AGZ_COMPUTE_WINO_H2); AGZ_COMPUTE_BF16 / AGZ_COMPUTE_BF16_ACT (opt-in, not fp32-grade: the single-product bf16
-  // tower for self-play, the second with bf16 activations between blocks and the same results bit for bit; the trainer keeps its default);
+  // tower for self-play, the second with bf16 activations between blocks and the same results bit for bit; the trainer keeps its default — its own single-product mode, agz_trainer_set_compute_mode(AGZ_COMPUTE_BF16), is set on the
+  // trainer handle, never through this field);
   // AGZ_COMPUTE_FP16 (opt-in, not fp32-grade: BF16_ACT's kernels on IEEE half, 11 significant bits per operand; the trainer keeps its default)
   int ComputeMode = AGZ_COMPUTE_F32_MFMA;
   // build extension: the options of the solver dual.Train builds (agz_trainer_set_solver); all 0 (default) = the reference's vanilla solver.

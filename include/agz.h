@@ -375,7 +375,12 @@ int agz_trainer_set_moments(agz_trainer* t, int index, const float* m, const flo
  * meets the same gradient tolerance against the reference arithmetic — every gradient tensor within 2e-5 of its maximum, tested per
  * mode at the headline width (K = 256, 19x19) on several data draws — which is why the forward convolutions do NOT take the
  * Winograd path: its rounding (2e-6 of the output rms against 3e-7 for the direct forms) puts a pre-activation on the other side of
- * a ReLU than the reference on every other batch at that width. */
+ * a ReLU than the reference on every other batch at that width.
+ * AGZ_COMPUTE_BF16 (opt-in, also with | AGZ_COMPUTE_FORCE; every trainer kind) is NOT one of them and NOT fp32-grade: mixed-precision
+ * training — the three GEMMs of the dual-block layers with one bf16 product per multiply on operands rounded once to nearest even,
+ * fp32 accumulation; master weights, gradients, BatchNorm, heads, losses, solver state and checkpoints stay fp32; the input layer and
+ * layers outside the kernels' limits run what AGZ_COMPUTE_BF16X3 runs (`bf16-train`).  K % 64 == 0 and
+ * SharedLayers > 0, else AGZ_E_UNSUPPORTED and the trainer keeps the mode it had.  Every other mode: AGZ_E_INVALID. */
 int agz_trainer_set_compute_mode(agz_trainer* t, int mode);
 /* dual.Train(d, Xs, policies, values, batches, iterations) (dualnet/meta.go:16-54): lr 0.1 vanilla SGD, shuffleBatch
  * after every iteration (build RNG; Xs/policies/values are shuffled in place like the reference). */

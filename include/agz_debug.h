@@ -114,13 +114,16 @@ int agz_trainer_set_dma_forward(agz_trainer* t, int on);
 #define AGZ_PATH_FWD_H2W 3      /* conv3x3_raw_h2: conv3x3_h2w_kernel, activations split while staged */
 #define AGZ_PATH_FWD_H2DMA 4    /* k_conv_h2dma: DMA GEMM on pre-split planes, one tap per K step, 128 x 256 tile */
 #define AGZ_PATH_FWD_H2DMA3 5   /* k_conv_h2dma3: nine taps from one x image, 256 x 128 tile */
+#define AGZ_PATH_FWD_BF16T 6    /* k_conv_bf16t: AGZ_COMPUTE_BF16, one bf16 product per multiply (train_bf16.hpp) */
 #define AGZ_PATH_WGRAD_F32 1    /* k_wgrad */
 #define AGZ_PATH_WGRAD_X3 2     /* k_wgrad_x3 */
 #define AGZ_PATH_WGRAD_H2 3     /* k_wgrad_h2 */
 #define AGZ_PATH_WGRAD_H2T3 4   /* k_wgrad_h2t3: three taps per workgroup from hi / lo planes (boards >= 16 wide) */
+#define AGZ_PATH_WGRAD_BF16T 5  /* k_wgrad_bf16t: AGZ_COMPUTE_BF16, three taps per workgroup from one bf16 plane per operand (boards >= 3 wide) */
 #define AGZ_PATH_DGRAD_RAW 1    /* conv3x3_raw on the transposed filter */
 #define AGZ_PATH_DGRAD_X3 2     /* conv3x3_raw_x3 */
 #define AGZ_PATH_DGRAD_WINO_H2 3 /* conv3x3_raw_wino_h2 */
+#define AGZ_PATH_DGRAD_BF16T 4  /* k_conv_bf16t on the rounded dz and the transposed, tap-flipped bf16 filter image */
 #define AGZ_PATH_BN2_SCALAR 1   /* k_bn_bwd2 (the weight gradient then takes dz's range with k_absmax) */
 #define AGZ_PATH_BN2_V 2        /* k_bn_bwd2_v: vector form, writes dz's range itself */
 int agz_trainer_last_paths(agz_trainer* t, int layer, int* fwd, int* wgrad, int* dgrad, int* bn_bwd2);
@@ -167,6 +170,16 @@ int agz_trainer_last_rows(agz_trainer* t, int layer, int32_t out[8]);
  * Both words are zero for layers that never had them.  Synchronises and copies two words; launches nothing and has no effect on any
  * launch.  Lets a test see whether a layer kept or re-split its planes, which identical results cannot show. */
 int agz_trainer_last_planes(agz_trainer* t, int layer, int* fused, uint32_t* est_bits, uint32_t* range_bits);
+
+/* Tests: one of the three GEMMs of the trainer's AGZ_COMPUTE_BF16 mode (`bf16-train`) ALONE on host data, without a
+ * trainer.  Tensors are NHWC without halo, filters [Cout][Cin][3][3]:
+ *   which 0  forward          a = x  [B][H][W][Cin],  b = filter,             out = z  [B][H][W][Cout]
+ *   which 1  data gradient    a = dz [B][H][W][Cout], b = filter,             out = dx [B][H][W][Cin]
+ *   which 2  weight gradient  a = dz [B][H][W][Cout], b = x [B][H][W][Cin],   out = dw [9][Cout][Cin]
+ * Pads on the host, runs the SAME rounding kernels (k_round_bf16_planes / _weights) and the SAME launchers the step runs (as under
+ * AGZ_COMPUTE_FORCE: no chip-filling threshold), copies back.  AGZ_E_UNSUPPORTED for a geometry outside the kernels' limits (Cin, Cout
+ * multiples of 64, W >= 3, a 256-row tile's haloed pixel span <= 464). */
+int agz_trainer_conv_bf16(agz_ctx* ctx, int which, const float* a, const float* b, int B, int H, int W, int Cin, int Cout, float* out);
 
 /* Tests: which kernels the last whole-batch forward of a net (agz_net_infer / agz_net_infer_dev, the arena's joined step) launched for the
  * input convolution, the dual blocks and the heads.  Every value is written on the host at the very branch of agz_net::forward_packed that
